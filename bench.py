@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — frames/s of the MI355X-native cost-volume hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of 32 synthetic frames PER GPU (BASELINE.json configs[3]: batch_size = 32; the
 reference's multi-GPU mode is Lightning DDP, train.py:124,135, where batch_size is per process) - "scaling": "weak", the path shards over
@@ -10,7 +10,7 @@ independent frames with no data-path collective.  `--scaling strong` shards ONE 
 Inputs are generated once and are resident in HBM before the timed region.  `--gpus N` (N > 1) without a launcher starts its own
 ranks (python -m torch.distributed.run, one process per GPU, RCCL, 127.0.0.1 rendezvous) and forwards rank 0's line; under a launcher
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) it is one of the ranks.  There is no data-path collective; the only message
-is an all-gather of per-frame metric vectors after the timed region - at N = 1 through a 1-rank RCCL group.
+is an all-gather of per-frame metric vectors after the timed region (--full) - at N = 1 through a 1-rank RCCL group.
 
 Workloads
   hot_path        (default) matching backbone's layer1 map -> encoder head -> fused volume -> CVEncoder ->
@@ -22,7 +22,11 @@ Workloads
                   stand-in backbones inside the timed region
   module_swap     the same call through dropin.convert + the reference's own forward sequence (module by module)
 
-Prints ONE JSON line on rank 0 (see the driver contract) with extra objects:
+A plain run sets up, warms up, times exactly K steps, writes the last step's outputs with --dump-outputs DIR (DIR/<name>.npy, see
+_dump_outputs) and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of the K steps / K), config.
+Everything else needs --full (the 1-rank RCCL group at N = 1, the metric all-gather and the objects below).
+
+Prints ONE JSON line on rank 0 (see the driver contract); with --full, extra objects:
   roofline     — dominant kernel, algorithmic flops (bytes) per launch ÷ HIP-event-measured average launch
                  time vs the gfx950 peak
   warp_match   — the north-star kernel on its own (K=8, D=64, same per-GPU batch): achieved algorithmic GB/s
@@ -83,8 +87,8 @@ def parse(argv=None):
     ap.add_argument("--math", default=None, choices=["fp32", "f16x3"],
                     help="shorthand: sets --conv-math, and --mlp-math f16x3 when f16x3")
     ap.add_argument("--split-line", action="store_true",
-                    help="also time the opt-in split-precision (f16x3) kernels on the same inputs -> the `split_precision` object (frozen code path, "
-                         "never `value`; off by default since round 6)")
+                    help="with --full: also time the opt-in split-precision (f16x3) kernels on the same inputs -> the `split_precision` object (frozen "
+                         "code path, never `value`; off by default since round 6)")
     ap.add_argument("--no-split-line", action="store_true", help=argparse.SUPPRESS)  # round <= 5 spelling of the default
     ap.add_argument("--no-process-group", action="store_true",
                     help="--gpus 1 without a launcher: do NOT create the 1-rank RCCL group (the default creates it so that the N = 1 record "
@@ -100,7 +104,15 @@ def parse(argv=None):
     ap.add_argument("--rank-report", default=None, metavar="DIR",
                     help="every rank writes DIR/rank<r>.json (its shard, input checksum, device) — evidence for the N > 1 tests")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: 1-rank RCCL group at N = 1, metric all-gather, roofline / fv_mlp replays, parity, "
+                         "warp_match / temporal / extra / k8 objects, cpu_baseline (a plain run only sets up, warms up, times --steps steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0; "
+                         "arrays above an equal share of 60 MB are a fixed seeded sample of their flattened elements; DIR/manifest.json says which)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.math is not None:
         args.conv_math = args.math
         args.mlp_math = "f16x3" if args.math == "f16x3" else "fp32"
@@ -209,6 +221,10 @@ class WarpMatchDot:
         if pmc is not None and pmc.get("kernel") == self.dominant_kernel:
             out["traffic"], out["traffic_source"] = pmc["traffic_bytes_per_launch"], "profiles/pmc_traffic.json"
         return out
+
+    def outputs(self):
+        """what a caller of idh_cost_volume_dot_ex_fwd receives from the last step"""
+        return {"cost_volume": self.cost, "lowest_cost": self.lowest, "depth_planes": self.planes}
 
     def metrics(self):
         # per-frame vector that is all-gathered (stand-in for the reference's per-frame
@@ -357,6 +373,10 @@ class HotPathWorkload:
         self.out = self._forward()
         if ev is not None:
             ev[1].record()
+
+    def outputs(self):
+        """the tensors of the output dict the last step returned (None entries dropped)"""
+        return {k: v for k, v in self.out.items() if torch.is_tensor(v)}
 
     # roofline of the dominant kernel -------------------------------------------------------
     dominant_kernel = None  # set by conv_only_ms(): the conv kernel family with the most time per step, as rocprofv3 names it
@@ -776,6 +796,8 @@ class FusedForwardWorkload:
         if ev is not None:
             ev[1].record()
 
+    outputs = HotPathWorkload.outputs
+
     def metrics(self):
         o = self.out["pred_0"]
         return torch.stack([o.mean((1, 2, 3)), torch.sigmoid(o).mean((1, 2, 3))], 1)
@@ -813,6 +835,39 @@ def _reference_cpu(key):
                 "source": "profiles/cpu_reference.json (the reference's own code, build container; not measured in this run)"}
     except Exception:
         return None
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all arrays together (the cap is 64 MB)
+DUMP_SEED = 0
+
+
+def _dump_outputs(outs, path):
+    """--dump-outputs: one DIR/<name>.npy per output tensor, float64 kept, every other dtype as float32.  Smallest arrays first, each
+    gets at most an equal share of the budget left; a larger one is written as the elements at DUMP_SEED's randperm positions (sorted,
+    flattened, row-major): the same positions for the same shape in every run, so two builds compare element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    items = sorted(outs.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left, manifest = DUMP_BUDGET_BYTES, {}
+    for i, (name, t) in enumerate(items):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        esize = 8 if dt == torch.float64 else 4
+        cap = left // (len(items) - i) // esize
+        flat = t.detach().reshape(-1)
+        sampled = flat.numel() > cap
+        if sampled:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:cap].sort().values
+            a = flat[idx.to(flat.device)].to(dt).cpu().numpy()
+        else:
+            a = flat.to(dt).cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        manifest[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "written": str(a.dtype),
+                          "sample": {"elements": int(a.size), "of": int(flat.numel()), "seed": DUMP_SEED, "positions": "sorted randperm prefix"}
+                          if sampled else None}
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def _median(xs):
@@ -902,9 +957,9 @@ def main():
     # weak scaling (default): --batch frames per rank (every rank its own 32 ScanNet-shaped tuples, seed = rank); strong: ONE global batch sharded by frame
     counts = [args.batch] * world if args.scaling == "weak" else shard_counts(args.batch, world)
     args.batch = counts[rank]  # frames of THIS rank
-    # A process group always exists (a 1-rank RCCL group at N = 1 without a launcher: the N = 1 record then exercises the path's one
-    # collective, ncclAllGather, too) unless --no-process-group asks for the bare single process.
-    use_dist = under_launcher or not args.no_process_group
+    # Under a launcher a process group always exists.  With --full it exists at N = 1 too (a 1-rank RCCL group: the N = 1 record then
+    # exercises the path's one collective, ncclAllGather, too) unless --no-process-group asks for the bare single process.
+    use_dist = under_launcher or (args.full and not args.no_process_group)
     dist_error = None
     if use_dist:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -956,8 +1011,11 @@ def main():
 
     elapsed, per_step = timed(wl)
     kernel_ms = sum(per_step) / max(len(per_step), 1)
+    if args.dump_outputs and rank == 0:  # before anything else runs through the model: outputs may live in recycled plan buffers
+        with torch.inference_mode():
+            _dump_outputs(wl.outputs(), args.dump_outputs)
     parity = None
-    if wl.name == "hot_path" and not args.no_parity and rank == 0:
+    if wl.name == "hot_path" and args.full and not args.no_parity and rank == 0:
         with torch.inference_mode():
             parity = wl.parity()
     frames_per_step_total = sum(counts)
@@ -965,7 +1023,7 @@ def main():
     # Secondary line (same run, same inputs and weights): the hot path with the fp32-equivalent
     # split-precision kernels (f16x3 convs + MLPs).  `value` above stays the fp32-MFMA path.
     split = None
-    if wl.name == "hot_path" and args.conv_math == "fp32" and args.mlp_math == "fp32" and args.split_line:
+    if wl.name == "hot_path" and args.conv_math == "fp32" and args.mlp_math == "fp32" and args.split_line and args.full:
         a2 = copy.copy(args)
         a2.conv_math, a2.mlp_math = "f16x3", "f16x3"
         wl2 = HotPathWorkload(a2, device, rank)
@@ -979,16 +1037,19 @@ def main():
         del wl2
         torch.cuda.empty_cache()
 
-    # the path's only collective: all-gather of per-frame metric vectors (RCCL over xGMI)
+    # the path's only collective: all-gather of per-frame metric vectors (RCCL over xGMI); with --full, or with --rank-report, whose
+    # rank files record it
     from implicit_depth_amd.dist import all_gather_metrics
 
-    local_rows = wl.metrics().float().contiguous()
-    send = local_rows.cpu() if host_coll else local_rows
-    m = all_gather_metrics(send, counts=counts)
+    local_rows = m = None
+    if args.full or args.rank_report:
+        local_rows = wl.metrics().float().contiguous()
+        send = local_rows.cpu() if host_coll else local_rows
+        m = all_gather_metrics(send, counts=counts)
     # evidence of the collective: wall time of the metric all-gather (median of 20 after the first, which carries RCCL's lazy
     # communicator setup), the world size the process group itself reports, and one device record per rank gathered through it
     allgather_us = first_allgather_us = ranks_reported = devices = None
-    if use_dist:
+    if use_dist and args.full:
         def one_gather():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -1017,7 +1078,9 @@ def main():
                                                                       torch.nan_to_num(local_rows.cpu(), nan=-7.0)))}, f)
 
     if rank == 0:
-        if not hasattr(wl, "conv_only_ms") and wl.bound != "hbm":
+        if not args.full:
+            roof = None  # the roofline figures replay kernels of their own: --full
+        elif not hasattr(wl, "conv_only_ms") and wl.bound != "hbm":
             # call-shape workloads (fused_forward / module_swap): the kernels are the hot path's; its line carries the roofline
             roof = {"bound": "mfma", "achieved": None, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": None, "traffic": None,
                     "note": "same kernels as --workload hot_path, whose line prices the dominant one; this workload measures the call shape"}
@@ -1053,7 +1116,7 @@ def main():
         key = f"{wl.name}/{getattr(wl, 'volume', 'dot')}/b{wl.B}" if wl.name != "warp_match_dot" else f"{wl.name}/b{wl.B}"
         if getattr(wl, "conv_math", "fp32") != "fp32":
             key += "/" + wl.conv_math
-        pmc = _pmc_traffic(key)
+        pmc = _pmc_traffic(key) if roof is not None else None
         if pmc is not None and pmc.get("kernel") == wl.dominant_kernel and (wl.name != "warp_match_dot" or (wl.K, wl.D) == (8, 64)):
             roof["traffic"] = pmc["traffic_bytes_per_launch"]
             roof["traffic_source"] = "profiles/pmc_traffic.json"
@@ -1075,14 +1138,14 @@ def main():
             "data": "synthetic",
             "config": dict(wl.config(), global_batch=frames_per_step_total, parallelism=f"dp{world}: frames sharded over {world} rank(s), one process per GPU, weights replicated, no data-path collective"),
             "roofline": roof,
-            "gathered_metric_rows": int(m.shape[0]),
+            "gathered_metric_rows": int(m.shape[0]) if m is not None else None,
             # the process group behind the barriers / MAX all-reduce / metric all-gather of this run ("nccl" = RCCL)
             "dist_backend": (args.dist_backend if use_dist else None),
             "ranks": ranks_reported,
             "devices": devices,
             "allgather_us": allgather_us,
             "allgather_first_call_us": first_allgather_us,
-            "allgather_payload_bytes_per_rank": int(local_rows.numel() * 4),
+            "allgather_payload_bytes_per_rank": int(local_rows.numel() * 4) if local_rows is not None else None,
             "launcher": ("torch.distributed.run" if under_launcher else "none (single process" + (", 1-rank process group)" if use_dist else ")")),
         }
         if dist_error is not None:
@@ -1094,12 +1157,12 @@ def main():
                                            "the rate is NOT a multi-GPU measurement)")
         if split is not None:
             out["split_precision"] = split
-        if wl.name == "hot_path" and getattr(wl, "mlp_math", "fp32") == "fp32":
+        if wl.name == "hot_path" and args.full and getattr(wl, "mlp_math", "fp32") == "fp32":
             with torch.inference_mode():
                 fv = wl.fv_mlp_roofline()
             if fv is not None:
                 out["fv_mlp"] = fv
-        if wl.name == "hot_path" and not args.no_extras:
+        if wl.name == "hot_path" and args.full and not args.no_extras:
             # the north-star kernel on its own, same per-GPU batch (BASELINE.json configs[1]: K=8, D=64)
             a3 = copy.copy(args)
             a3.views, a3.planes = 8, 64
@@ -1186,7 +1249,7 @@ def main():
                              "note": "whole hot path with K = 8 source views (BASELINE.json's literal configuration); rank-0 rate x ranks"}
                 del w8
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = wl.cpu_baseline(args.cpu_seconds)
             if cb is not None:
                 out["cpu_baseline"] = cb

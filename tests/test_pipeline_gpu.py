@@ -239,7 +239,7 @@ def test_bench_n2_branch_on_one_gpu_over_gloo(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29613",
            os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "7", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--ranks-on-device", "0",
-           "--no-extras", "--no-split-line", "--no-cpu-baseline", "--rank-report", str(rep)]
+           "--full", "--no-extras", "--no-split-line", "--no-cpu-baseline", "--rank-report", str(rep)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -280,7 +280,7 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
 
     rep = tmp_path / "ranks"
     out, err = _bench_line(["--gpus", "2", "--batch", "5", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--ranks-on-device", "0",
-                            "--no-extras", "--no-cpu-baseline", "--no-parity", "--rank-report", str(rep)])
+                            "--full", "--no-extras", "--no-cpu-baseline", "--no-parity", "--rank-report", str(rep)])
     assert out["n_gpus"] == 2 and out["ranks"] == 2 and out["dist_backend"] == "gloo" and out["config"]["global_batch"] == 5 and out["scaling"] == "strong"
     assert out["gathered_metric_rows"] == 5 and out["allgather_us"] > 0 and out["launcher"].startswith("self")
     assert [d["rank"] for d in out["devices"]] == [0, 1] and [d["frames"] for d in out["devices"]] == [3, 2]
@@ -290,9 +290,40 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     assert "self-launch" in err
     # the default: weak scaling, --batch frames on EVERY rank (DDP semantics: batch_size per process)
     w, _ = _bench_line(["--gpus", "2", "--batch", "3", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--ranks-on-device", "0",
-                        "--no-extras", "--no-cpu-baseline", "--no-parity"])
+                        "--full", "--no-extras", "--no-cpu-baseline", "--no-parity"])
     assert w["scaling"] == "weak" and w["config"]["global_batch"] == 6 and w["config"]["per_gpu_batch"] == 3 and w["gathered_metric_rows"] == 6
     assert [d["frames"] for d in w["devices"]] == [3, 3]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and carries only the headline (no process group, roofline,
+    parity or extra objects: those need --full).  --dump-outputs writes the last timed step's outputs; a second run with the same
+    arguments has the same inputs, so the same outputs.  The warp+match volume (100 MB at B = 32) is written as a seeded sample."""
+    import json
+
+    import numpy as np
+
+    argv = ["--gpus", "1", "--batch", "2", "--steps", "3", "--warmup", "1"]
+    a, _ = _bench_line(argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(a) and a["unit"] == "frames/s" and a["dtype"] == "f32"
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["value"] > 0
+    assert a["dist_backend"] is None and a["roofline"] is None and a["gathered_metric_rows"] is None
+    assert not {"parity", "fv_mlp", "warp_match", "temporal", "extra", "k8", "cpu_baseline"} & set(a), sorted(a)
+    b, _ = _bench_line(argv + ["--dump-outputs", str(tmp_path / "b")])
+    man = json.load(open(tmp_path / "a" / "manifest.json"))
+    assert man["pred_0"]["shape"] == [2, 8, 192, 256] and man["pred_0"]["sample"] is None
+    for name in man:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == y.shape == tuple(man[name]["shape"]), name
+        if man[name]["dtype"] == "bool":
+            assert (x != y).mean() < 2e-3, name
+        else:
+            assert np.abs(x - y).max() <= 1e-4 * max(np.abs(x).max(), 1e-30), name
+    c, _ = _bench_line(["--gpus", "1", "--workload", "warp_match_dot", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c")])
+    assert c["steps"] == 2 and c["roofline"] is None
+    man = json.load(open(tmp_path / "c" / "manifest.json"))
+    assert man["cost_volume"]["shape"] == [32, 64, 96, 128] and man["cost_volume"]["sample"] is not None
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= 64 << 20
 
 
 def test_bench_refuses_more_gpus_than_the_box_has():
@@ -316,7 +347,7 @@ def test_bench_n1_runs_under_a_one_rank_rccl_group():
     within 3 % of the same run with --no-process-group (measured: < 1 %)."""
     import os
 
-    common = ["--gpus", "1", "--batch", "8", "--steps", "12", "--warmup", "3", "--no-extras", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--batch", "8", "--steps", "12", "--warmup", "3", "--full", "--no-extras", "--no-cpu-baseline"]
     a, _ = _bench_line(common)
     assert a["dist_backend"] == "nccl" and a["ranks"] == 1 and len(a["devices"]) == 1 and a["devices"][0]["frames"] == 8, a.get("dist_init_error")
     assert a["allgather_us"] > 0 and a["gathered_metric_rows"] == 8

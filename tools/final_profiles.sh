@@ -6,9 +6,9 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT/matrix
 cd $ROOT
-B="timeout 300 python bench.py --no-cpu-baseline --no-parity"
-echo "== default bench line"; timeout 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-echo "== rocprofv3 kernel stats: hot path"; ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_hot -o hot -- python $ROOT/bench.py --no-cpu-baseline --no-parity --no-extras --steps 30 --warmup 3 > $OUT/prof_hot.log 2>&1 )
+B="timeout 300 python bench.py --full --no-cpu-baseline --no-parity"
+echo "== default bench line"; timeout 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+echo "== rocprofv3 kernel stats: hot path"; ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_hot -o hot -- python $ROOT/bench.py --full --no-cpu-baseline --no-parity --no-extras --steps 30 --warmup 3 > $OUT/prof_hot.log 2>&1 )
 echo "== rocprofv3 kernel stats: warp_match_dot"; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_dot -o dot -- python $ROOT/bench.py --workload warp_match_dot --no-cpu-baseline --steps 50 --warmup 5 > $OUT/prof_dot.log 2>&1 )
 echo "== rocprofv3 kernel stats: temporal"; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_temporal -o t -- python $ROOT/bench.py --workload temporal --no-cpu-baseline --steps 48 --warmup 8 > $OUT/prof_temporal.log 2>&1 )
 echo "== PMC HBM traffic"; tools/pmc_bench.sh ${TAG}_hot --no-parity --no-extras > $OUT/pmc_hot.txt 2>&1; tools/pmc_bench.sh ${TAG}_dot --workload warp_match_dot > $OUT/pmc_dot_traffic.txt 2>&1

@@ -7,7 +7,7 @@ import os, sys, json, runpy, torch
 sys.path.insert(0, os.getcwd())
 from implicit_depth_amd import nhwc
 nhwc.BUFFER_REUSE = {reuse == '1'}
-sys.argv = ['bench.py', '--no-cpu-baseline', '--no-split-line', '--no-extras', '--batch', '{B}', '--steps', '20']
+sys.argv = ['bench.py', '--full', '--no-cpu-baseline', '--no-split-line', '--no-extras', '--batch', '{B}', '--steps', '20']
 try:
     runpy.run_path('bench.py', run_name='__main__')
 except SystemExit:

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -o p -- python $ROOT/bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" > $OUT/$C.log 2>&1
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -o p -- python $ROOT/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > $OUT/$C.log 2>&1
 done
 python $ROOT/tools/pmc_summarize.py $OUT; exit 0
 python - <<PY

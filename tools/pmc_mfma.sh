@@ -6,7 +6,7 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/pmc_mfma_$TAG
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq -o p -- python $ROOT/bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" > $OUT/sq.log 2>&1
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq -o p -- python $ROOT/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > $OUT/sq.log 2>&1
 python - <<PY
 import csv, glob, collections, json, re
 fs = glob.glob("$OUT/sq/**/*counter_collection.csv", recursive=True)
