@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IDH_LIB") or os.path.join(_HERE, "lib", "libidh.so")
 
 _lib = None
-MIN_ABI_VERSION = 105
+MIN_ABI_VERSION = 106
 
 f32p = C.c_void_p  # device pointers travel as integers
 
@@ -103,9 +103,9 @@ _SIGS = {
 
 
 def _all_sigs():
-    from . import net_abi  # (structs of include/idh_net.h live there; imported lazily: net_abi imports this module)
+    from . import model_abi, net_abi  # (structs of include/idh_net.h / idh_model.h live there; imported lazily: they import this module)
 
-    return {**_SIGS, **net_abi.SIGS}
+    return {**_SIGS, **net_abi.SIGS, **model_abi.SIGS}
 
 
 def declared_symbols():

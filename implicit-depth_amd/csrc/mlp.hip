@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "idh_common.h"
+#include "net_plan.h"
 #include "split_f16.h"
 
 namespace {
@@ -359,6 +360,9 @@ __global__ __launch_bounds__(256) void pack_mlp_weight_k(const float *__restrict
 // ---- temporal prior: warp the previous frame's occlusion prediction into the current view ----
 // reference experiment_modules/bd_model.py:395-410 (BackprojectDepth -> Project3D ->
 // grid_sample(mode="nearest", zeros, align_corners=False) -> invalid := -1)
+// kLogits: `prior` holds the previous frame's occlusion LOGITS and the sampled value goes through sigmoid (torch.sigmoid's 1 / (1 + exp(-x)),
+// inference.py:154's sigmoid_custom(x, 1.0)) on load - the device-side frame chain of idh_model_fwd, no separate sigmoid pass
+template <bool kLogits>
 __global__ __launch_bounds__(256) void sample_prior_k(const float *__restrict__ depth, const float *__restrict__ prior,
                                                       int Q, const float *__restrict__ cur_world_T_cam,
                                                       const float *__restrict__ prior_cam_T_world,
@@ -408,6 +412,7 @@ __global__ __launch_bounds__(256) void sample_prior_k(const float *__restrict__ 
         if (xr >= 0.f && xr <= Wf - 1.f && yr >= 0.f && yr <= Hf - 1.f) {
             const int q = p < Q ? p : Q - 1;
             val = prior[((size_t)b * Q + q) * N + (int)yr * W + (int)xr];
+            if (kLogits) val = 1.f / (1.f + expf(-val));
         }
         // (cam z > 0) is always true after the clamp — same quirk as the cost-volume mask
         out[((size_t)b * P + p) * N + pix] = (d > 0.f && z > 0.f) ? val : -1.f;
@@ -426,8 +431,18 @@ extern "C" int idh_sample_prior_fwd(const float *rendered_depth_bphw, const floa
         return IDH_EINVAL;
     int gx = idh_cdiv((long long)P * H * W, 256);
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(sample_prior_k, dim3(gx, B), dim3(256), 0, idh_stream(stream), rendered_depth_bphw, prior_pred_bqhw, Q,
+    hipLaunchKernelGGL(sample_prior_k<false>, dim3(gx, B), dim3(256), 0, idh_stream(stream), rendered_depth_bphw, prior_pred_bqhw, Q,
                        cur_world_T_cam_44, prior_cam_T_world_44, K_44, invK_44, P, H, W, out_bphw);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+// idh_sample_prior_fwd for one frame whose prior is the previous frame's logits (csrc/model.hip's frame chain; arguments checked there)
+int idh_internal::sample_prior_from_logits(const float *depth, const float *logits, int Q, const float *cur_world_T_cam, const float *prior_cam_T_world,
+                                           const float *K, const float *invK, int B, int P, int H, int W, float *out, hipStream_t st) {
+    int gx = idh_cdiv((long long)P * H * W, 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(sample_prior_k<true>, dim3(gx, B), dim3(256), 0, st, depth, logits, Q, cur_world_T_cam, prior_cam_T_world, K, invK, P, H, W, out);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "idh_common.h"
+#include "net_plan.h"
 #include "../../include/idh_net.h"
 #include "../../include/idh_ops.h"
 
@@ -32,6 +33,8 @@ constexpr double kProjChunkWeight = 0.5;  // PROJ_CHUNK_WEIGHT
 constexpr int kS2FirstMinBlocks = 512;    // S2_FIRST_MIN_BLOCKS
 constexpr int kTargetWaves = 2048, kMinWaves = 1024;
 constexpr int kTileWino = IDH_TILE_WINO, kTileWino4 = IDH_TILE_WINO4;
+constexpr bool kFuseHeadNorm = true;      // FUSE_HEAD_NORM (matching-encoder head: InstanceNorm + LeakyReLU applied by the 3x3 conv on load)
+constexpr bool kFuseHeadImport = true;    // FUSE_HEAD_IMPORT (... and its 1x1 conv reading the backbone's NCHW map in place)
 
 inline int ceil16(int v) { return (v + 15) & ~15; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -67,6 +70,14 @@ struct Meta {
 struct Src {
     View v;
     const idh_conv_params *cv;
+};
+
+// normalise-on-load of a conv's first source (idh_conv_src.norm): the statistics an IDH_OP_INSTNORM leaves in its workspace
+struct Norm {
+    const float *stats = nullptr;
+    int buf = -1;  // pseudo-buffer of the statistics (dependency tracking only)
+    int act = IDH_ACT_NONE;
+    float slope = 0.2f;
 };
 
 class Plan {
@@ -141,18 +152,19 @@ class Plan {
     static Region region(const View &v, bool pad16 = false) { return Region{v.buf, v.c0, v.c0 + (pad16 ? ceil16(v.C) : v.C)}; }
 
     // ---- kernel-family predicates (nhwc.py: wino_eligible, wino4_eligible, lds_eligible, s2_first_eligible) --------------------------------
-    bool wino_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo) const {
+    bool wino_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int pad_mode = IDH_PAD_ZEROS) const {
         const idh_conv_params &c0 = *srcs[0].cv;
-        if (c0.ks != 3 || c0.stride != 1 || cout % 32) return false;
+        if (c0.ks != 3 || c0.stride != 1 || pad_mode != IDH_PAD_ZEROS || cout % 32) return false;
         if (srcs.size() > 1 && (srcs[1].cv->ks != 1 || srcs[1].cv->stride != 1)) return false;
         const int ty = cdiv(Ho, 8), tx = cdiv(Wo, 32);
         if ((double)Ho * Wo < kWinoMinFill * (ty * 8) * (tx * 32)) return false;
         return (long long)n * ty * tx * (cout / 32) >= kWinoMinTiles;
     }
-    bool wino4_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int act, float slope, const View &out, const View *res) const {
+    bool wino4_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int act, float slope, const View &out, const View *res,
+                        int pad_mode = IDH_PAD_ZEROS) const {
         const idh_conv_params &c0 = *srcs[0].cv;
         const View &v0 = srcs[0].v;
-        if (c0.ks != 3 || c0.stride != 1 || cout % 64) return false;
+        if (c0.ks != 3 || c0.stride != 1 || pad_mode != IDH_PAD_ZEROS || cout % 64) return false;
         if (srcs.size() > 1 && (srcs.size() > 2 || srcs[1].cv->ks != 1 || srcs[1].cv->stride != 1)) return false;
         if ((act != IDH_ACT_NONE && act != IDH_ACT_LRELU && act != IDH_ACT_ELU) || (act == IDH_ACT_LRELU && !(slope >= 0.f && slope <= 1.f)) || c0.cin <= 16) return false;
         if ((long long)H(v0) * W(v0) * cs(v0) * 4 >= (1ll << 30)) return false;
@@ -167,21 +179,22 @@ class Plan {
         if ((double)Ho * Wo < kWino4MinFill * (ty * 8) * (tx * 32)) return false;
         return (long long)n * ty * tx * (cout / 64) >= kWino4MinTiles;
     }
-    static bool lds_eligible(const std::vector<Src> &srcs, int cout, int Wo) {
+    static bool lds_eligible(const std::vector<Src> &srcs, int cout, int Wo, int pad_mode = IDH_PAD_ZEROS) {
         const idh_conv_params &c0 = *srcs[0].cv;
         if (c0.ks != 3 || c0.stride != 1 || cout % 16 || Wo < 16) return false;
+        if (pad_mode != IDH_PAD_ZEROS && (pad_mode != IDH_PAD_REPLICATE || srcs.size() > 1)) return false;
         if (srcs.size() > 1) {
             const idh_conv_params &c1 = *srcs[1].cv;
-            const bool strided3 = c1.ks == 3 && c1.stride == 2 && cout % 32 == 0;
+            const bool strided3 = c1.ks == 3 && c1.stride == 2 && pad_mode == IDH_PAD_ZEROS && cout % 32 == 0;
             if (!strided3 && (c1.ks != 1 || c1.stride != 1)) return false;
         }
         return true;
     }
     static int lds_subtiles(int cout) { return cout % 64 == 0 ? 4 : (cout % 32 == 0 ? 2 : 1); }
-    static bool s2_first_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo) {
+    static bool s2_first_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int pad_mode = IDH_PAD_ZEROS) {
         if (srcs.size() != 1) return false;
         const idh_conv_params &c0 = *srcs[0].cv;
-        if (c0.ks != 3 || c0.stride != 2 || cout % 32 || Wo < 16) return false;
+        if (c0.ks != 3 || c0.stride != 2 || pad_mode != IDH_PAD_ZEROS || cout % 32 || Wo < 16) return false;
         return (long long)n * cdiv(Wo, 16) * cdiv(Ho, 4) * (cout / (16 * lds_subtiles(cout))) >= kS2FirstMinBlocks;
     }
     static void choose_lds_tile(int n, int Ho, int Wo, int cout, int chunks, int &code, int &split) {
@@ -243,7 +256,8 @@ class Plan {
     }
 
     // ---- ops (Plan.conv / upsample2 / import_nchw / export_nchw / head) ---------------------------------------------------------------------
-    View conv(const View &x, const idh_conv_params &cv, const View &out, int act, float slope, const View *res, const View *x2, const idh_conv_params *cv2) {
+    View conv(const View &x, const idh_conv_params &cv, const View &out, int act, float slope, const View *res, const View *x2, const idh_conv_params *cv2,
+              int pad_mode = IDH_PAD_ZEROS, const Norm *norm = nullptr) {
         if (err) return out;
         idh_op op;
         std::memset(&op, 0, sizeof op);
@@ -253,8 +267,8 @@ class Plan {
         if (x2) srcs.push_back({*x2, cv2});
         const int n = N(out), Ho = H(out), Wo = W(out), cout = cv.cout;
         if (out.C != cout) { err = IDH_EINVAL; return out; }
-        bool use_wino = wino_eligible(srcs, cout, n, Ho, Wo);
-        const bool use_wino4 = (!x2 || !res) && wino4_eligible(srcs, cout, n, Ho, Wo, act, slope, out, res);
+        bool use_wino = !norm && wino_eligible(srcs, cout, n, Ho, Wo, pad_mode);
+        const bool use_wino4 = !norm && (!x2 || !res) && wino4_eligible(srcs, cout, n, Ho, Wo, act, slope, out, res, pad_mode);
         if (use_wino4) use_wino = false;
         int steps = 0;
         for (size_t i = 0; i < srcs.size(); ++i) {
@@ -265,7 +279,7 @@ class Plan {
             const WLayout lay = (use_wino4 && i == 0) ? W_WINO4 : (use_wino && i == 0) ? W_WINO : W_DIRECT;
             idh_conv_src &s = op.src[i];
             s.in = ptr(v); s.w = packed(c, lay); s.cs = cs(v); s.H = H(v); s.W = W(v); s.Cin = v.C;
-            s.ks = c.ks; s.stride = c.stride; s.pad_mode = IDH_PAD_ZEROS;
+            s.ks = c.ks; s.stride = c.stride; s.pad_mode = pad_mode;
             steps += c.ks * c.ks * (ceil16(v.C) / 16);
         }
         op.bias = bias_of(cv, cv2);  // (always present in the blob - BasicBlock's convs all have one, layers.py:52-55; a NULL bias packs as zeros)
@@ -277,7 +291,7 @@ class Plan {
         int tm, tn, split;
         if (use_wino4) { tm = kTileWino4; tn = 0; split = 1; ++n_wino4; }
         else if (use_wino) { tm = kTileWino; tn = 0; split = 1; ++n_wino2; }
-        else if (lds_eligible(srcs, cout, Wo)) {
+        else if (lds_eligible(srcs, cout, Wo, pad_mode)) {
             double ch = 0;
             for (const Src &s : srcs) ch += (ceil16(s.v.C) / 16) * (s.cv->ks == 3 ? 1.0 : kProjChunkWeight);
             choose_lds_tile(n, Ho, Wo, cout, (int)ch, tm, split);
@@ -287,7 +301,7 @@ class Plan {
                 if (blocks64 < kNarrowTileBelow) tn = 2;
             }
             tn = tn == 4 ? 0 : tn;
-        } else if (s2_first_eligible(srcs, cout, n, Ho, Wo)) {
+        } else if (!norm && s2_first_eligible(srcs, cout, n, Ho, Wo, pad_mode)) {
             choose_lds_tile(n, Ho, Wo, cout, ceil16(x.C) / 16, tm, split);
             tn = lds_subtiles(cout);
             tn = tn == 4 ? 0 : tn;
@@ -295,10 +309,15 @@ class Plan {
             choose_tiles(M, cout, steps, tm, tn, split);
         }
         op.tile_m = tm; op.tile_n = tn; op.split_k = split;
+        if (norm) {  // (Plan.conv: the LDS-staged kernel with 16-channel tiles and one source only)
+            if ((tm != 8 && tm != 9) || tn != 1 || x2) { err = IDH_EINVAL; return out; }
+            op.src[0].norm = norm->stats; op.src[0].norm_act = norm->act; op.src[0].norm_slope = norm->slope;
+        }
         if (split > 1) op.ws = ws_alloc((size_t)split * M * ceil16(cout));
         ops.push_back(op);
         Meta m;
         if (res) m.reads.push_back(region(*res));
+        if (norm) m.reads.push_back(Region{norm->buf, 0, 1});
         for (const Src &s : srcs) m.reads.push_back(region(s.v, true));
         m.writes.push_back(region(out));
         meta.push_back(m);
@@ -359,6 +378,52 @@ class Plan {
         meta.push_back(Meta{{region(x)}, {}});
     }
 
+    // Plan.instance_norm: nn.InstanceNorm2d (no affine, eps 1e-5) [+ LeakyReLU]; out == nullptr: statistics only, for a normalise-on-load conv
+    Norm instance_norm(const View &x, const View *out, int act, float slope) {
+        Norm nm;
+        if (err) return nm;
+        if (x.C % 4 || 256 % (x.C / 4)) { err = IDH_EINVAL; return nm; }
+        const int nchunks = cdiv(H(x) * W(x), 1024);
+        float *w = ws_alloc((size_t)N(x) * (nchunks + 1) * 2 * x.C);
+        idh_op op;
+        std::memset(&op, 0, sizeof op);
+        op.kind = IDH_OP_INSTNORM; op.N = N(x);
+        idh_conv_src &s = op.src[0];
+        s.in = ptr(x); s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
+        op.act = act; op.slope = slope;
+        if (out) { op.out = ptr(*out); op.out_cs = cs(*out); }
+        op.ws = w;
+        ops.push_back(op);
+        Meta m{{region(x)}, {}};
+        if (out) {
+            m.writes.push_back(region(*out));
+        } else {
+            Buf b{};  // the statistics as a pseudo-buffer: a dependency between this op and the conv that reads them
+            b.base = w + (size_t)N(x) * nchunks * 2 * x.C; b.N = N(x); b.H = 1; b.W = 1; b.cs = 1; b.internal = false;
+            bufs.push_back(b);
+            nm.stats = b.base; nm.buf = (int)bufs.size() - 1;
+            m.writes.push_back(Region{nm.buf, 0, 1});
+        }
+        meta.push_back(m);
+        return nm;
+    }
+    static bool pointwise_nchw_eligible(const idh_conv_params &c) { return c.ks == 1 && c.stride == 1 && c.cin == 64 && c.cout == 128; }
+    // Plan.pointwise_nchw: 1x1 conv read straight from a dense (n, C, H, W) tensor into an NHWC view
+    void pointwise_nchw(const float *src, int n, int C, int H_, int W_, const idh_conv_params &cv, const View &out) {
+        if (err) return;
+        if (n != N(out) || H_ != H(out) || W_ != W(out) || C != cv.cin || out.C != cv.cout || !pointwise_nchw_eligible(cv)) { err = IDH_EINVAL; return; }
+        idh_op op;
+        std::memset(&op, 0, sizeof op);
+        op.kind = IDH_OP_POINTWISE_NCHW; op.N = n;
+        idh_conv_src &s = op.src[0];
+        s.in = mode_ == MODE_RUN ? src : reinterpret_cast<const float *>(uintptr_t(6) << 32);
+        s.w = packed(cv, W_DIRECT); s.H = H_; s.W = W_; s.Cin = C; s.ks = 1; s.stride = 1;
+        op.bias = bias_of(cv, nullptr);
+        op.out = ptr(out); op.out_cs = cs(out); op.Ho = H_; op.Wo = W_; op.Cout = cv.cout;
+        ops.push_back(op);
+        meta.push_back(Meta{{}, {region(out)}});
+    }
+
     // ---- BasicBlock (Plan.basic_block; reference layers.py:78-95) ------------------------------------------------------------------------------
     View basic_block(const View &x, const idh_block_params &blk, const View *out_opt = nullptr) {
         const int st = blk.conv1.stride;
@@ -394,18 +459,19 @@ class Plan {
         else if (op.kind == IDH_OP_UPSAMPLE2) { r[0] = 2; }
         else if (op.kind == IDH_OP_NCHW_TO_NHWC) { r[0] = 2; r[1] = 1; }
     }
-    void schedule() {
+    // (Plan.schedule_segments: ops [0, n_first) and the rest are levelled and ordered each on their own - the volume kernel runs between them)
+    void schedule(int n_first = 0) {
         const int n = (int)ops.size();
         std::vector<int> level(n, 0), order(n);
         for (int j = 0; j < n; ++j)
-            for (int i = 0; i < j; ++i)
+            for (int i = j < n_first ? 0 : n_first; i < j; ++i)
                 if (overlap(meta[i].writes, meta[j].reads) || overlap(meta[i].writes, meta[j].writes) || overlap(meta[i].reads, meta[j].writes))
                     level[j] = std::max(level[j], level[i] + 1);
-        std::vector<std::array<long long, 5>> key(n);
+        std::vector<std::array<long long, 6>> key(n);
         for (int k = 0; k < n; ++k) {
             long long r[3];
             launch_rank(ops[k], r);
-            key[k] = {level[k], r[0], r[1], r[2], k};
+            key[k] = {k < n_first ? 0 : 1, level[k], r[0], r[1], r[2], k};
             ops[k].group = r[0] < 3 ? level[k] + 1 : 0;
             order[k] = k;
         }
@@ -415,9 +481,9 @@ class Plan {
         ops.swap(o2);
     }
 
-    int finish(idh_net_sizes *sizes) {
+    int finish(idh_net_sizes *sizes, int n_first = 0) {
         if (err) return err;
-        schedule();
+        schedule(n_first);
         if (sizes) {
             sizes->workspace_floats = ws_off;
             sizes->weight_floats = blob_off;
@@ -428,14 +494,19 @@ class Plan {
         }
         if (mode_ == MODE_RUN) {
             if (ws_off > ws_cap_) return IDH_EWORKSPACE;
+            // padding channels first: nothing an op or before_run writes may be cleared afterwards
             for (const Buf &b : bufs)
                 if (b.internal && b.zero_fill && hipMemsetAsync(b.base, 0, b.floats * sizeof(float), st_) != hipSuccess) return IDH_ELAUNCH;
-            return idh_run_ops(ops.data(), (int)ops.size(), st_);
+            int rc = n_first ? idh_run_ops(ops.data(), n_first, st_) : IDH_OK;
+            if (rc == IDH_OK && before_run) rc = before_run(before_ctx);
+            return rc != IDH_OK ? rc : idh_run_ops(ops.data() + n_first, (int)ops.size() - n_first, st_);
         }
         return IDH_OK;
     }
 
     Mode mode() const { return mode_; }
+    int (*before_run)(void *) = nullptr;  // MODE_RUN: called after scheduling, before the pass is enqueued (the whole-model entry's volume)
+    void *before_ctx = nullptr;
 
   private:
     Mode mode_;
@@ -484,18 +555,19 @@ int build_basic_block(Plan &p, const idh_block_params *blk, int N, const idh_ten
 }
 
 // CVEncoder.forward (networks.py:208-215): x = ds_conv_i(x); x = cat([x, img_feats[i]]); x = conv_i(x)
-int build_cvencoder(Plan &p, const idh_block_params *blocks, int num_blocks, int N, const idh_tensor *cost, const idh_tensor *img, const idh_tensor *outs) {
+// outs == NULL: level i's output stays a plan buffer (levels[i]), as in one HotPath plan
+int cvencoder_body(Plan &p, const idh_block_params *blocks, int num_blocks, int N, View x, const idh_tensor *img, const idh_tensor *outs,
+                   std::vector<View> *levels) {
     const bool run = p.mode() == MODE_RUN;
-    if (!blocks || num_blocks <= 0 || num_blocks > 8 || N <= 0 || !tensor_ok(cost, run) || !img || !outs) return IDH_EINVAL;
-    View x = input_view(p, *cost, N);
     for (int i = 0; i < num_blocks; ++i) {
         const idh_block_params &ds = blocks[3 * i], &c0 = blocks[3 * i + 1], &c1 = blocks[3 * i + 2];
-        if (!tensor_ok(&img[i], run) || !tensor_ok(&outs[i], run)) return IDH_EINVAL;
+        if (!tensor_ok(&img[i], run) || (outs && !tensor_ok(&outs[i], run))) return IDH_EINVAL;
         const int st = ds.conv1.stride;
         if (st != 1 && st != 2) return IDH_EINVAL;
         const int Ho = (p.H(x) + 2 - 3) / st + 1, Wo = (p.W(x) + 2 - 3) / st + 1;
         const int cout = ds.conv1.cout, cimg = img[i].C;
-        if (img[i].H != Ho || img[i].W != Wo || c0.conv1.cin != cout + cimg || outs[i].C != c1.conv1.cout || outs[i].H != Ho || outs[i].W != Wo) return IDH_EINVAL;
+        if (img[i].H != Ho || img[i].W != Wo || c0.conv1.cin != cout + cimg) return IDH_EINVAL;
+        if (outs && (outs[i].C != c1.conv1.cout || outs[i].H != Ho || outs[i].W != Wo)) return IDH_EINVAL;
         const View cat = p.buffer(N, Ho, Wo, cout + cimg);
         const View left = Plan::slice(cat, 0, cout);
         p.basic_block(x, ds, &left);
@@ -503,26 +575,30 @@ int build_cvencoder(Plan &p, const idh_block_params *blocks, int num_blocks, int
         if (img[i].layout == IDH_LAYOUT_NCHW) p.import_nchw(img[i].ptr, N, cimg, Ho, Wo, right);
         else return IDH_EUNSUPPORTED;  // (an NHWC image-feature map would need a copy op into the concat slice: the reference hands NCHW)
         View y = p.basic_block(cat, c0);
-        const View o = output_view(p, outs[i], N);
-        y = p.basic_block(y, c1, &o);
-        output_done(p, outs[i], y);
+        if (outs) {
+            const View o = output_view(p, outs[i], N);
+            y = p.basic_block(y, c1, &o);
+            output_done(p, outs[i], y);
+        } else {
+            y = p.basic_block(y, c1);
+        }
+        if (levels) levels->push_back(y);
         x = y;
         if (p.err) return p.err;
     }
     return p.err;
 }
 
-// BDDecoderPP / DepthDecoderPP.forward (networks.py:64-84, 163-183)
-int build_unetpp(Plan &p, const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
-                 const idh_tensor *fouts, float *const *log_depth, float *const *depth) {
+int build_cvencoder(Plan &p, const idh_block_params *blocks, int num_blocks, int N, const idh_tensor *cost, const idh_tensor *img, const idh_tensor *outs) {
     const bool run = p.mode() == MODE_RUN;
-    if (!blocks || n_blocks != IDH_UNETPP_BLOCKS || N <= 0 || !feats) return IDH_EINVAL;
-    std::vector<View> prev;
-    for (int i = 0; i < 5; ++i) {
-        if (!tensor_ok(&feats[i], run)) return IDH_EINVAL;
-        if (i && (feats[i].H * 2 != feats[i - 1].H || feats[i].W * 2 != feats[i - 1].W)) return IDH_EINVAL;  // pyramid levels differ by exactly x2
-        prev.push_back(input_view(p, feats[i], N));
-    }
+    if (!blocks || num_blocks <= 0 || num_blocks > 8 || N <= 0 || !tensor_ok(cost, run) || !img || !outs) return IDH_EINVAL;
+    return cvencoder_body(p, blocks, num_blocks, N, input_view(p, *cost, N), img, outs, nullptr);
+}
+
+// BDDecoderPP / DepthDecoderPP.forward (networks.py:64-84, 163-183) over the five input views; *feat0 (optional): the top-left result
+int unetpp_body(Plan &p, const idh_block_params *blocks, const idh_conv_params *heads, int N, std::vector<View> prev, const idh_tensor *fouts,
+                float *const *log_depth, float *const *depth, View *feat0) {
+    const bool run = p.mode() == MODE_RUN;
     const idh_block_params *out_blk[4] = {nullptr, &blocks[46], &blocks[47], &blocks[48]};
     auto want = [&](int i) { return fouts && fouts[i].C > 0; };  // (C == 0 skips a level; decided by the shape alone so that sizes / pack / fwd agree)
     std::vector<View> outputs;
@@ -587,10 +663,117 @@ int build_unetpp(Plan &p, const idh_block_params *blocks, int n_blocks, const id
             p.head(final_v[i], heads[i], run ? log_depth[i] : nullptr, (run && depth) ? depth[i] : nullptr);
         }
     }
+    if (feat0) *feat0 = final_v[0];
     return p.err;
 }
 
+int build_unetpp(Plan &p, const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
+                 const idh_tensor *fouts, float *const *log_depth, float *const *depth) {
+    const bool run = p.mode() == MODE_RUN;
+    if (!blocks || n_blocks != IDH_UNETPP_BLOCKS || N <= 0 || !feats) return IDH_EINVAL;
+    std::vector<View> prev;
+    for (int i = 0; i < 5; ++i) {
+        if (!tensor_ok(&feats[i], run)) return IDH_EINVAL;
+        if (i && (feats[i].H * 2 != feats[i - 1].H || feats[i].W * 2 != feats[i - 1].W)) return IDH_EINVAL;  // pyramid levels differ by exactly x2
+        prev.push_back(input_view(p, feats[i], N));
+    }
+    return unetpp_body(p, blocks, heads, N, prev, fouts, log_depth, depth, nullptr);
+}
+
+// FNV-1a over what decides a pass's arithmetic and memory layout: each op's kind, shapes and kernel choice
+uint64_t layout_hash(const std::vector<idh_op> &ops) {
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](long long v) {
+        for (int i = 0; i < 8; ++i) { h ^= (uint64_t)((v >> (8 * i)) & 0xff); h *= 1099511628211ull; }
+    };
+    for (const idh_op &op : ops) {
+        mix(op.kind); mix(op.N); mix(op.Ho); mix(op.Wo); mix(op.Cout); mix(op.tile_m); mix(op.tile_n); mix(op.split_k); mix(op.act); mix(op.group);
+        for (const idh_conv_src &s : op.src) { mix(s.Cin); mix(s.H); mix(s.W); mix(s.cs); mix(s.ks); mix(s.stride); mix(s.pad_mode); mix(s.norm != nullptr); }
+    }
+    return h;
+}
+
 }  // namespace
+
+// The conv stage of one HotPath plan (pipeline.py HotPath._plan): the volume buffer, the layout import of pyramid level 0, the CVEncoder
+// (importing levels 1..4 into its concat slices) and the UNet++ decoder over [level 0 | CVEncoder outputs], all in one op list.
+int idh_internal::conv_stage(int mode, ConvStage *s, float *ws, size_t ws_cap, float *blob, hipStream_t st, int (*before_ops)(void *), void *ctx) {
+    const Mode m = mode == STAGE_SIZES ? MODE_SIZES : mode == STAGE_PACK ? MODE_PACK : MODE_RUN;
+    if (!s || !s->enc || s->n_enc != 4 || !s->dec || s->N <= 0 || s->H <= 0 || s->W <= 0 || s->D <= 0) return IDH_EINVAL;
+    Plan p(m, ws, ws_cap, blob, st);
+    s->match = nullptr;
+    s->n_head_ops = 0;
+    if (s->head_mode) {
+        // nhwc.build_matching_head over all N (K+1) images at once (HotPath._plan): 1x1 conv, InstanceNorm + LeakyReLU, 3x3 conv (replicate
+        // padding), InstanceNorm; output = ONE (N, K+1, H, W, C) buffer the volume kernel addresses with batch strides
+        if (!s->head || s->K <= 0 || (s->head_mode != 1 && s->head_mode != 2)) return IDH_EINVAL;
+        const idh_conv_params &c1 = s->head[0], &c2 = s->head[1];
+        const int M = s->N * (s->K + 1), H = s->H, W = s->W;
+        if (c1.ks != 1 || c1.stride != 1 || c2.ks != 3 || c2.stride != 1 || c2.cin != c1.cout) return IDH_EINVAL;
+        if (m == MODE_RUN && (!s->layer1 || ((uintptr_t)s->layer1 & 15))) return IDH_EINVAL;
+        const View h = p.buffer(M, H, W, c1.cout);
+        if (s->head_mode == 1 && kFuseHeadImport && Plan::pointwise_nchw_eligible(c1)) {
+            p.pointwise_nchw(s->layer1, M, c1.cin, H, W, c1, h);  // the 1x1 conv reads the NCHW map in place
+        } else {
+            View x;
+            if (s->head_mode == 1) {
+                x = p.buffer(M, H, W, c1.cin);
+                p.import_nchw(s->layer1, M, c1.cin, H, W, x);
+            } else {  // channels-last producer: the conv reads the caller's tensor in place
+                const idh_tensor t{const_cast<float *>(s->layer1), IDH_LAYOUT_NHWC, c1.cin, H, W, c1.cin};
+                if (!tensor_ok(&t, m == MODE_RUN)) return IDH_EINVAL;
+                x = p.external(t, M);
+            }
+            p.conv(x, c1, h, IDH_ACT_NONE, 0.2f, nullptr, nullptr, nullptr);
+        }
+        const View y = p.buffer(M, H, W, c2.cout);
+        const std::vector<Src> s2{{h, &c2}};
+        if (kFuseHeadNorm && h.C % 16 == 0 && Plan::lds_subtiles(c2.cout) == 1 && Plan::lds_eligible(s2, c2.cout, W, IDH_PAD_REPLICATE)) {
+            const Norm nm = p.instance_norm(h, nullptr, IDH_ACT_NONE, 0.2f);
+            Norm on = nm;
+            on.act = IDH_ACT_LRELU; on.slope = 0.2f;
+            p.conv(h, c2, y, IDH_ACT_NONE, 0.2f, nullptr, nullptr, nullptr, IDH_PAD_REPLICATE, &on);
+        } else {
+            const View hn = p.buffer(M, H, W, c1.cout);
+            p.instance_norm(h, &hn, IDH_ACT_LRELU, 0.2f);
+            p.conv(hn, c2, y, IDH_ACT_NONE, 0.2f, nullptr, nullptr, nullptr, IDH_PAD_REPLICATE);
+        }
+        const View mo = p.buffer(M, H, W, c2.cout);
+        p.instance_norm(y, &mo, IDH_ACT_NONE, 0.2f);
+        if (p.err) return p.err;
+        if (p.cs(mo) != mo.C) return IDH_EUNSUPPORTED;  // (the volume kernels read dense (N, K+1, H, W, C) features)
+        s->match = p.ptr(mo);
+        s->n_head_ops = (int)p.ops.size();
+    }
+    const View cv_in = p.buffer(s->N, s->H, s->W, s->D);
+    for (int i = 0; i < 5; ++i)
+        if (s->img[i].layout != IDH_LAYOUT_NCHW || !tensor_ok(&s->img[i], m == MODE_RUN)) return IDH_EINVAL;
+    const View v0 = input_view(p, s->img[0], s->N);
+    std::vector<View> levels{v0};
+    int rc = cvencoder_body(p, s->enc, s->n_enc, s->N, cv_in, &s->img[1], nullptr, &levels);
+    if (rc != IDH_OK) return rc;
+    for (int i = 1; i < 5; ++i)
+        if (p.H(levels[i]) * 2 != p.H(levels[i - 1]) || p.W(levels[i]) * 2 != p.W(levels[i - 1])) return IDH_EINVAL;
+    View f0;
+    rc = unetpp_body(p, s->dec, s->heads, s->N, levels, nullptr, s->log_depth, s->depth, &f0);
+    if (rc != IDH_OK) return rc;
+    s->cv_in = p.ptr(cv_in);
+    s->cv_cs = p.cs(cv_in);
+    s->feat0 = p.ptr(f0);
+    s->feat0_cs = p.cs(f0); s->feat0_C = f0.C; s->feat0_H = p.H(f0); s->feat0_W = p.W(f0);
+    for (int i = 0; i < 5; ++i) { s->level_H[i] = p.H(levels[i]); s->level_W[i] = p.W(levels[i]); }
+    p.before_run = before_ops;
+    p.before_ctx = ctx;
+    idh_net_sizes sz{};
+    if (m == MODE_PACK) return p.err;
+    rc = p.finish(m == MODE_SIZES ? &sz : nullptr, s->n_head_ops);
+    if (rc != IDH_OK) return rc;
+    if (m == MODE_SIZES) {
+        s->ws_floats = sz.workspace_floats; s->weight_floats = sz.weight_floats; s->ops = sz.ops; s->launches = sz.launches;
+        s->layout_hash = layout_hash(p.ops);
+    }
+    return IDH_OK;
+}
 
 extern "C" int idh_basic_block_sizes(const idh_block_params *blk, int N, const idh_tensor *x, const idh_tensor *out, idh_net_sizes *sizes) {
     if (!sizes) return IDH_EINVAL;
