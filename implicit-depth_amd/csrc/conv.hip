@@ -34,6 +34,8 @@
 
 using namespace idh_conv;
 
+int idh_stem_op(const idh_op &op, hipStream_t st, bool launch);  // csrc/stem.hip (IDH_OP_STEM)
+
 namespace {
 
 // Zero page: out-of-image taps (zero padding) read from here instead of being predicated,
@@ -1833,6 +1835,12 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 if (s.Cin == 64) IDH_LAUNCH((pointwise_up_k<4, 4>), dim3(grid), dim3(256), 16 * 64 * sizeof(f32x4), st, pa);
                 else IDH_LAUNCH((pointwise_up_k<8, 8>), dim3(grid), dim3(256), 32 * 128 * sizeof(f32x4), st, pa);
                 IDH_CHECK_LAUNCH();
+                break;
+            }
+            case IDH_OP_STEM: {
+                const int rc = idh_stem_op(op, st, !t_dry_run);
+                if (rc != IDH_OK) return rc;
+                if (t_dry_run) ++t_launches;
                 break;
             }
             case IDH_OP_COPY: {

@@ -161,7 +161,7 @@ class Plan {
         return (long long)n * ty * tx * (cout / 32) >= kWinoMinTiles;
     }
     bool wino4_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int act, float slope, const View &out, const View *res,
-                        int pad_mode = IDH_PAD_ZEROS) const {
+                        int pad_mode = IDH_PAD_ZEROS, bool any_size = false) const {
         const idh_conv_params &c0 = *srcs[0].cv;
         const View &v0 = srcs[0].v;
         if (c0.ks != 3 || c0.stride != 1 || pad_mode != IDH_PAD_ZEROS || cout % 64) return false;
@@ -175,6 +175,7 @@ class Plan {
             if ((long long)H(v1) * W(v1) * cs(v1) * 4 >= (1ll << 31) || (long long)((srcs[1].cv->cin + 15) / 16) * 4 * ceil16(cout) * 64 >= (1ll << 31)) return false;
         }
         if ((long long)((c0.cin + 15) / 16) * 4 * ceil16(cout) * 36 * 16 * 4 >= (1ll << 31)) return false;
+        if (any_size) return true;  // (nhwc.wino4_eligible any_size: the stem's layer1, batch-size-independent rounding)
         const int ty = cdiv(Ho, 8), tx = cdiv(Wo, 32);
         if ((double)Ho * Wo < kWino4MinFill * (ty * 8) * (tx * 32)) return false;
         return (long long)n * ty * tx * (cout / 64) >= kWino4MinTiles;
@@ -257,7 +258,7 @@ class Plan {
 
     // ---- ops (Plan.conv / upsample2 / import_nchw / export_nchw / head) ---------------------------------------------------------------------
     View conv(const View &x, const idh_conv_params &cv, const View &out, int act, float slope, const View *res, const View *x2, const idh_conv_params *cv2,
-              int pad_mode = IDH_PAD_ZEROS, const Norm *norm = nullptr) {
+              int pad_mode = IDH_PAD_ZEROS, const Norm *norm = nullptr, bool wino4_any_size = false) {
         if (err) return out;
         idh_op op;
         std::memset(&op, 0, sizeof op);
@@ -268,7 +269,7 @@ class Plan {
         const int n = N(out), Ho = H(out), Wo = W(out), cout = cv.cout;
         if (out.C != cout) { err = IDH_EINVAL; return out; }
         bool use_wino = !norm && wino_eligible(srcs, cout, n, Ho, Wo, pad_mode);
-        const bool use_wino4 = !norm && (!x2 || !res) && wino4_eligible(srcs, cout, n, Ho, Wo, act, slope, out, res, pad_mode);
+        const bool use_wino4 = !norm && (!x2 || !res) && wino4_eligible(srcs, cout, n, Ho, Wo, act, slope, out, res, pad_mode, wino4_any_size);
         if (use_wino4) use_wino = false;
         int steps = 0;
         for (size_t i = 0; i < srcs.size(); ++i) {
@@ -424,6 +425,21 @@ class Plan {
         meta.push_back(Meta{{}, {region(out)}});
     }
 
+    // ---- the fused ResNet18 stem pass (Plan.stem): N dense NCHW images -> NHWC 64-channel view
+    void stem(const float *images, int n, int h, int w, const float *blob, const View &out) {
+        if (err) return;
+        idh_op op;
+        std::memset(&op, 0, sizeof op);
+        op.kind = IDH_OP_STEM; op.N = n;
+        idh_conv_src &s = op.src[0];
+        s.in = mode_ == MODE_RUN ? images : reinterpret_cast<const float *>(uintptr_t(3) << 32);
+        s.w = blob; s.H = h; s.W = w; s.Cin = 3;
+        s.up_C = n; s.up_cs[0] = 3 * h * w; s.up_cs[1] = n * 3 * h * w;  // (Plan.stem: one group of N dense images)
+        op.out = ptr(out); op.out_cs = cs(out); op.Ho = H(out); op.Wo = W(out); op.Cout = 64;
+        ops.push_back(op);
+        meta.push_back(Meta{{}, {region(out)}});
+    }
+
     // ---- BasicBlock (Plan.basic_block; reference layers.py:78-95) ------------------------------------------------------------------------------
     View basic_block(const View &x, const idh_block_params &blk, const View *out_opt = nullptr) {
         const int st = blk.conv1.stride;
@@ -505,6 +521,7 @@ class Plan {
     }
 
     Mode mode() const { return mode_; }
+    hipStream_t stream() const { return st_; }
     int (*before_run)(void *) = nullptr;  // MODE_RUN: called after scheduling, before the pass is enqueued (the whole-model entry's volume)
     void *before_ctx = nullptr;
 
@@ -551,6 +568,49 @@ int build_basic_block(Plan &p, const idh_block_params *blk, int N, const idh_ten
     const View o = output_view(p, *out, N);
     p.basic_block(xin, *blk, &o);
     output_done(p, *out, o);
+    return p.err;
+}
+
+// nhwc.build_matching_stem: stem pass, then layer1 = 2 x (conv1 + ReLU, conv2 + identity + ReLU), BatchNorms folded into the blob by *_pack
+int build_matching_stem(Plan &p, const idh_stem_params *sp, int N, const idh_tensor *img, const idh_tensor *out) {
+    const bool run = p.mode() == MODE_RUN;
+    if (!sp || N <= 0 || !img || img->layout != IDH_LAYOUT_NCHW || img->C != 3 || img->H < 8 || img->W < 8 || (run && !img->ptr)) return IDH_EINVAL;
+    const int Ho = ((img->H + 1) / 2) / 2, Wo = ((img->W + 1) / 2) / 2;
+    if ((long long)N * 3 * img->H * img->W >= (1ll << 31) || !tensor_ok(out, run, false) || out->C != 64 || out->H != Ho || out->W != Wo)
+        return (long long)N * 3 * img->H * img->W >= (1ll << 31) ? IDH_EUNSUPPORTED : IDH_EINVAL;
+    // blob: [stem weights][4 x (folded OIHW 64x64x3x3, folded bias 64)][what the four convs pack from them]
+    float *stem_w = p.blob_alloc(idh_stem_weight_floats());
+    idh_conv_params convs[4];
+    for (int i = 0; i < 4; ++i) {
+        float *fw = p.blob_alloc(64 * 64 * 9), *fb = p.blob_alloc(64);
+        convs[i] = idh_conv_params{fw, fb, 64, 64, 3, 1};
+    }
+    if (p.mode() == MODE_PACK) {
+        auto bn_ok = [](const idh_bn_params &b) { return b.weight && b.bias && b.running_mean && b.running_var && b.eps >= 0.f; };
+        if (!sp->conv1_weight || !bn_ok(sp->bn1)) return IDH_EINVAL;
+        for (int i = 0; i < 4; ++i)
+            if (!sp->layer1_conv[i] || !bn_ok(sp->layer1_bn[i])) return IDH_EINVAL;
+        int rc = idh_pack_stem_weight(sp->conv1_weight, sp->bn1.weight, sp->bn1.bias, sp->bn1.running_mean, sp->bn1.running_var, sp->bn1.eps, stem_w,
+                                      p.stream());
+        for (int i = 0; i < 4 && rc == IDH_OK; ++i) {
+            const idh_bn_params &b = sp->layer1_bn[i];
+            rc = idh_fold_conv_bn(sp->layer1_conv[i], 64, 64 * 9, b.weight, b.bias, b.running_mean, b.running_var, b.eps, const_cast<float *>(convs[i].weight),
+                                  const_cast<float *>(convs[i].bias), p.stream());
+        }
+        if (rc != IDH_OK) return rc;
+    }
+    View x = p.buffer(N, Ho, Wo, 64);
+    p.stem(img->ptr, N, img->H, img->W, stem_w, x);
+    for (int b = 0; b < 2; ++b) {
+        const View h = p.buffer(N, Ho, Wo, 64);
+        p.conv(x, convs[2 * b], h, IDH_ACT_LRELU, 0.f, nullptr, nullptr, nullptr, IDH_PAD_ZEROS, nullptr, true);
+        const View y = b == 1 ? output_view(p, *out, N) : p.buffer(N, Ho, Wo, 64);
+        p.conv(h, convs[2 * b + 1], y, IDH_ACT_LRELU, 0.f, &x, nullptr, nullptr, IDH_PAD_ZEROS, nullptr, true);
+        p.release(h);
+        if (b == 0) p.release(x);
+        x = y;
+    }
+    output_done(p, *out, x);
     return p.err;
 }
 
@@ -837,5 +897,25 @@ extern "C" int idh_unetpp_fwd(const idh_block_params *blocks, int n_blocks, cons
     if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
     Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
     const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs);
+    return rc != IDH_OK ? rc : p.finish(nullptr);
+}
+
+extern "C" int idh_matching_stem_sizes(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, idh_net_sizes *sizes) {
+    if (!sizes) return IDH_EINVAL;
+    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
+    const int rc = build_matching_stem(p, params, N, images, out);
+    return rc != IDH_OK ? rc : p.finish(sizes);
+}
+extern "C" int idh_matching_stem_pack(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, float *blob, void *stream) {
+    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
+    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
+    const int rc = build_matching_stem(p, params, N, images, out);
+    return rc != IDH_OK ? rc : p.err;
+}
+extern "C" int idh_matching_stem_fwd(const idh_stem_params *params, const float *blob, int N, const idh_tensor *images, const idh_tensor *out, float *ws,
+                                     size_t ws_floats, void *stream) {
+    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
+    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
+    const int rc = build_matching_stem(p, params, N, images, out);
     return rc != IDH_OK ? rc : p.finish(nullptr);
 }

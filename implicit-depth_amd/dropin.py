@@ -86,10 +86,25 @@ def convert_binary_mlp(ref: nn.Module) -> nn.Module:
     return new.to(_device(ref))
 
 
-def convert(model: nn.Module, math: str = None) -> nn.Module:
+def _check_native_stem(model: nn.Module) -> None:
+    from . import _lib
+    from .backbone import stem_is_native_eligible
+
+    mm = getattr(model, "matching_model", None)
+    net_ = getattr(mm, "net", None)
+    if net_ is None or len(net_) != 10 or not stem_is_native_eligible(net_[:5]):
+        raise _lib.IdhError("native_matching_stem=True needs a ResnetMatchingEncoder whose net[:5] is the eval-mode resnet18(filter_size=4, "
+                            "pool_only=True) stem (backbone.stem_is_native_eligible)")
+
+
+def convert(model: nn.Module, math: str = None, native_matching_stem: bool = False) -> nn.Module:
     """In-place: replace ``cost_volume``, ``cost_volume_net``, ``depth_decoder`` and (BDModel)
     ``binary_mlp`` of a reference model.  Idempotent.  ``math``: None keeps the default (fp32 MFMA); "f16x3" selects the split-precision
-    kernels for this model's convs (and, for "f16x3", its MLP feature volume and BinaryMLP)."""
+    kernels for this model's convs (and, for "f16x3", its MLP feature volume and BinaryMLP).  ``native_matching_stem``: additionally check
+    that the matching encoder's ResNet18 stem can run on the native kernels (``IdhError`` if not); its modules and state dict are left
+    as they are."""
+    if native_matching_stem:
+        _check_native_stem(model)
     if not isinstance(model.cost_volume, cv.CostVolumeManager):
         model.cost_volume = convert_cost_volume(model.cost_volume)
     if not isinstance(model.cost_volume_net, net.CVEncoder):
@@ -112,9 +127,10 @@ def convert(model: nn.Module, math: str = None) -> nn.Module:
     return model
 
 
-def hot_path_of(model: nn.Module, min_depth: float = 0.25, max_depth: float = 5.0, math: str = None) -> HotPath:
-    """Fused pipeline sharing the (converted) modules of ``model``."""
-    convert(model, math)
+def hot_path_of(model: nn.Module, min_depth: float = 0.25, max_depth: float = 5.0, math: str = None, native_matching_stem: bool = False) -> HotPath:
+    """Fused pipeline sharing the (converted) modules of ``model``.  ``native_matching_stem``: see ``convert``; the caller then passes
+    ``matching_images`` to the pipeline."""
+    convert(model, math, native_matching_stem)
     o = getattr(model, "run_opts", None)
     if o is not None:
         min_depth, max_depth = o.min_matching_depth, o.max_matching_depth
@@ -127,18 +143,19 @@ def hot_path_of(model: nn.Module, min_depth: float = 0.25, max_depth: float = 5.
     return hot
 
 
-def fused_forward(model: nn.Module, math: str = None):
+def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool = False):
     """A replacement for ``BDModel.forward`` / ``DepthModel.forward`` at inference time (bd_model.py:175-311,
     depth_model.py:280-440): same arguments, same output dictionary, but everything between the third-party backbones
     and the outputs runs as ONE fused pass of ``HotPath`` (matching-encoder head, volume, CVEncoder, decoder, occlusion
     MLP / depth heads) instead of module by module.  The third-party image encoder and ResNet18 stem still run as the
-    model's own torch modules.  ``model.forward = fused_forward(model)`` installs it; the model's config / checkpoint
+    model's own torch modules - unless ``native_matching_stem`` is set: the stem (conv1 .. layer1, which must pass
+    ``backbone.stem_is_native_eligible``; ``IdhError`` otherwise) then runs on the gfx950 kernels inside the same pass, from the raw images.  ``model.forward = fused_forward(model)`` installs it; the model's config / checkpoint
     surface is untouched (the hot-path modules are converted in place and share their parameters with the pipeline).
     Side effects on the input dicts are the reference's: ``cur_data["prior_mask"]`` and, with ``bd_edge_regularision``,
     ``cur_data["edge_mask"]`` (computed by the reference's own ``get_edge_mask``, which must then be importable)."""
     from . import _lib
 
-    hot = hot_path_of(model, math=math)
+    hot = hot_path_of(model, math=math, native_matching_stem=native_matching_stem)
     is_bd = hasattr(model, "binary_mlp")
     opts = model.run_opts
     if getattr(opts, "matching_scale", 1) != 1:
@@ -160,7 +177,12 @@ def fused_forward(model: nn.Module, math: str = None):
             cur_feats = list(model.encoder(cur_image))  # third-party image encoder (strong image prior), bd_model.py:218
             kw = {}
             mc = msrc = None
-            if hot.matching_model is not None:
+            if native_matching_stem:
+                # the whole matching encoder (stem + layer1 + head) inside the pipeline, straight from the images; the batched and the
+                # image-by-image (unbatched_matching_encoder_forward) reference orders give the same per-image results here
+                _check_native_stem(model)
+                kw["matching_images"] = torch.cat([cur_image.unsqueeze(1), src_image], 1)
+            elif hot.matching_model is not None:
                 # third-party stem on frame b's current image followed by its K source images (bd_model.py:149-160);
                 # the encoder head runs inside the pipeline
                 frames = torch.cat([cur_image.unsqueeze(1), src_image], 1)

@@ -103,6 +103,32 @@ def unetpp_blocks(dec, keep: list):
     return (BlockParams * len(out))(*out), heads
 
 
+class BnParams(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("eps", C.c_float),
+                ("_r", C.c_int32)]
+
+
+class StemParams(C.Structure):
+    _fields_ = [("conv1_weight", C.c_void_p), ("bn1", BnParams), ("layer1_conv", C.c_void_p * 4), ("layer1_bn", BnParams * 4)]
+
+
+def stem_params(stem, keep: list) -> StemParams:
+    """conv1 / bn1 / layer1 of a ResNet18 matching stem (``encoder.net[:5]``, backbone.py) as an idh_stem_params; ``keep`` holds the
+    contiguous copies alive."""
+    def t(x):
+        x = x.detach().float().contiguous()
+        keep.append(x)
+        return x.data_ptr()
+
+    def bn(b):
+        return BnParams(t(b.weight), t(b.bias), t(b.running_mean), t(b.running_var), float(b.eps), 0)
+
+    mods = list(stem)
+    convs = [c for blk in mods[4] for c in (blk.conv1, blk.conv2)]
+    bns = [b for blk in mods[4] for b in (blk.bn1, blk.bn2)]
+    return StemParams(t(mods[0].weight), bn(mods[1]), (C.c_void_p * 4)(*[t(c.weight) for c in convs]), (BnParams * 4)(*[bn(b) for b in bns]))
+
+
 def _sigs():
     P = C.POINTER
     vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
@@ -116,6 +142,9 @@ def _sigs():
         "idh_unetpp_sizes": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), P(NetSizes)]),
         "idh_unetpp_pack": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), vp, vp]),
         "idh_unetpp_fwd": (i32, [P(BlockParams), i32, P(ConvParams), vp, i32, P(Tensor), P(Tensor), P(vp), P(vp), vp, sz, vp]),
+        "idh_matching_stem_sizes": (i32, [P(StemParams), i32, P(Tensor), P(Tensor), P(NetSizes)]),
+        "idh_matching_stem_pack": (i32, [P(StemParams), i32, P(Tensor), P(Tensor), vp, vp]),
+        "idh_matching_stem_fwd": (i32, [P(StemParams), vp, i32, P(Tensor), P(Tensor), vp, sz, vp]),
     }
 
 

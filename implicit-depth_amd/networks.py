@@ -144,17 +144,24 @@ class BinaryMLPNetwork(nn.Module):
 class ResnetMatchingEncoder(nn.Module):
     """Matching encoder (reference modules/networks.py:236-287).
 
-    ``net[0:5]`` — conv1/bn1/relu/maxpool/layer1 of antialiased_cnns.resnet18 — is third-party
-    code that is not part of the reference tree: the caller passes those five
-    modules in (or any stand-in with 64 output channels at 1/4 resolution) and they run as
-    ordinary torch modules.  The head ``net[5:10]`` (1x1 conv 64->128, InstanceNorm, LeakyReLU(0.2),
+    ``net[0:5]`` is conv1/bn1/relu/maxpool/layer1 of antialiased_cnns.resnet18.  With
+    ``backbone_modules=None`` the encoder builds that stem itself (backbone.py: same architecture and
+    state-dict keys, ``net.0.weight`` … ``net.4.1.bn2.*``, ``net.3.1.filt``) and the whole forward —
+    stem, layer1 and head — runs on the gfx950 kernels from the raw images (inference only: the stem's
+    BatchNorms must be in eval mode).  Passed-in ``backbone_modules`` (the third-party package's, or
+    any stand-in with 64 output channels at 1/4 resolution) run as ordinary torch modules, as before.
+    The head ``net[5:10]`` (1x1 conv 64->128, InstanceNorm, LeakyReLU(0.2),
     3x3 replicate-padded conv 128->C, InstanceNorm) runs on the gfx950 kernels and can hand its
     output over channels-last, which is the layout the cost-volume kernels consume.
     State-dict keys are the reference's (``net.5.weight`` … ``net.8.bias``)."""
 
-    def __init__(self, backbone_modules, num_ch_out: int = 16, backbone_channels: int = 64):
+    def __init__(self, backbone_modules=None, num_ch_out: int = 16, backbone_channels: int = 64):
         super().__init__()
-        _lib.watch_state_dict_loads(self)  # load_state_dict invalidates packed-weight caches of inference-mode parameters
+        self.native_stem = backbone_modules is None
+        if self.native_stem:
+            from .backbone import resnet18_stem
+
+            backbone_modules = resnet18_stem()
         backbone_modules = list(backbone_modules)
         if len(backbone_modules) != 5:
             raise ValueError("expected the 5 backbone modules conv1, bn1, relu, maxpool, layer1")
@@ -167,15 +174,22 @@ class ResnetMatchingEncoder(nn.Module):
             nn.Conv2d(128, num_ch_out, (3, 3), padding=1, padding_mode="replicate"),
             nn.InstanceNorm2d(num_ch_out),
         )
+        _lib.watch_state_dict_loads(self)  # load_state_dict invalidates packed-weight caches of inference-mode parameters
 
     def backbone(self, x):
+        if self.native_stem:
+            from .nhwc import matching_encoder_forward
+
+            return matching_encoder_forward(self, x, head=False)
         for i in range(5):
             x = self.net[i](x)
         return x
 
     def forward(self, input_image, channels_last: bool = False):
-        from .nhwc import matching_head_forward
+        from .nhwc import matching_encoder_forward, matching_head_forward
 
+        if self.native_stem:
+            return matching_encoder_forward(self, input_image, channels_last)
         return matching_head_forward(self, self.backbone(input_image), channels_last)
 
 

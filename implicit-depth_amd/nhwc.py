@@ -26,6 +26,7 @@ from . import _lib
 
 # --- ctypes mirrors of include/idh_ops.h -------------------------------------------------
 OP_CONV, OP_UPSAMPLE2, OP_IMPORT, OP_EXPORT, OP_SPLITK, OP_HEAD, OP_INSTNORM, OP_UPSAMPLE2_NEAREST, OP_COPY, OP_POINTWISE_NCHW, OP_POINTWISE_UP = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+OP_STEM = 12
 ACT_NONE, ACT_LRELU, ACT_ELU = 0, 1, 2
 PAD_ZEROS, PAD_REPLICATE = 0, 1
 
@@ -233,7 +234,7 @@ WINO4_MIN_TILES = 768  # (re-swept late in round 5, tools/perf_levels.py: 384 / 
 WINO4_MIN_FILL = 0.85
 
 
-def wino4_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int, act: int, out=None, res=None, slope: float = 0.2) -> bool:
+def wino4_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int, act: int, out=None, res=None, slope: float = 0.2, any_size: bool = False) -> bool:
     """Mirror of ``idh_conv::wino4_supported`` (csrc/conv_wino4.hip) plus the fill / tile-count rules.  ``out`` / ``res``: the views the op
     writes / adds - their per-image byte sizes (with the channel stride of a wider concat buffer) are 32-bit buffer ranges in the kernel, so a
     layer that exceeds them is planned onto F(2x2) / the direct kernels here instead of failing at run time with IDH_EUNSUPPORTED."""
@@ -257,6 +258,8 @@ def wino4_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int, act
             return False
     if ((c0.in_channels + 15) // 16) * 4 * (((cout + 15) // 16) * 16) * 36 * 16 * 4 >= 1 << 31:  # packed weights
         return False
+    if any_size:  # (the shape family alone: a caller that needs the same kernel - the same rounding - at every batch size)
+        return True
     ty, tx = -(-Ho // 8), -(-Wo // 32)
     if Ho * Wo < WINO4_MIN_FILL * (ty * 8) * (tx * 32):
         return False
@@ -486,9 +489,10 @@ class Plan:
 
     # ops -----------------------------------------------------------------------------
     def conv(self, x: View, conv: nn.Conv2d, out: View, act=ACT_NONE, slope=0.2, res: Optional[View] = None,
-             x2: Optional[View] = None, conv2: Optional[nn.Conv2d] = None, pad_mode=PAD_ZEROS, norm=None):
+             x2: Optional[View] = None, conv2: Optional[nn.Conv2d] = None, pad_mode=PAD_ZEROS, norm=None, wino4_any_size: bool = False):
         """``norm`` = (stats, act, slope): read ``x`` through act((x - mean) * rstd) with the (N, 2, C) statistics of
-        ``instance_norm(x, None)`` (``norm_on_load_eligible`` layers only)."""
+        ``instance_norm(x, None)`` (``norm_on_load_eligible`` layers only).  ``wino4_any_size``: an fp32 layer of the F(4x4) shape family runs on
+        conv3x3_wino4_k whatever its tile count (results then do not depend on the batch size)."""
         op = Op()
         op.kind = OP_CONV
         op.N = x.N
@@ -498,7 +502,7 @@ class Plan:
         use_wino = (WINOGRAD and self.math == "fp32" and norm is None and
                     wino_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode))
         use_wino4 = (WINOGRAD4 and self.math == "fp32" and norm is None and (x2 is None or res is None) and
-                     wino4_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode, act, out, res, slope))
+                     wino4_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode, act, out, res, slope, wino4_any_size))
         if use_wino4:
             use_wino = False
         for i, (v, cv) in enumerate(srcs):
@@ -701,6 +705,31 @@ class Plan:
             op.bias = bias.data_ptr()
         op.out, op.out_cs, op.Ho, op.Wo, op.Cout = out.ptr, out.cs, H, W, conv.out_channels
         self.flops += 2 * N * H * W * conv.out_channels * conv.in_channels
+        self.ops.append(op)
+        self.meta.append({"reads": [], "writes": [_region(out)]})
+        self._arr = None
+        return len(self.ops) - 1
+
+    def stem(self, shape, strides, blob: torch.Tensor, out: View) -> int:
+        """conv1 + folded BatchNorm + ReLU + MaxPool2d(2, 1) + BlurPool of the ResNet18 stem (IDH_OP_STEM, csrc/stem.hip) from N fp32 NCHW
+        images into an NHWC view of 64 channels.  ``shape`` = (N, 3, H, W); ``strides`` = (images per group, floats between the images of
+        a group, floats between groups) - a (B, K+1, 3, H, W) tensor is B groups of K+1; ``blob`` = ``idh_pack_stem_weight`` output.  The
+        image pointer is patched per call with ``set_in``; returns the op index."""
+        N, Cc, H, W = [int(v) for v in shape]
+        Ho, Wo = ((H + 1) // 2) // 2, ((W + 1) // 2) // 2
+        if Cc != 3 or H < 8 or W < 8 or (out.N, out.H, out.W, out.C) != (N, Ho, Wo, 64):
+            raise _lib.IdhError(f"stem: images {tuple(shape)} (3 channels, H, W >= 8) into a view of {(out.N, out.C, out.H, out.W)}")
+        group, img_stride, grp_stride = [int(v) for v in strides]
+        if max(img_stride, grp_stride) >= 1 << 31 or N % group:
+            raise _lib.IdhError("stem: image strides must fit in 32 bits and the groups divide the batch")
+        op = Op()
+        op.kind, op.N = OP_STEM, N
+        s = op.src[0]
+        s.w, s.H, s.W, s.Cin = blob.data_ptr(), H, W, 3
+        s.up_C, s.up_cs[0], s.up_cs[1] = group, img_stride, grp_stride
+        self.keep.append(blob)
+        op.out, op.out_cs, op.Ho, op.Wo, op.Cout = out.ptr, out.cs, Ho, Wo, 64
+        self.flops += 2 * N * ((H + 1) // 2) * ((W + 1) // 2) * 64 * 147
         self.ops.append(op)
         self.meta.append({"reads": [], "writes": [_region(out)]})
         self._arr = None
@@ -1237,6 +1266,146 @@ def matching_head_forward(enc, feat_nchw: torch.Tensor, channels_last: bool = Fa
         p.run()
         return y.dense().clone()
     out = torch.empty(y.N, y.C, y.H, y.W, device=x.device, dtype=torch.float32)
+    p.set_out(i_out, out)
+    p.run()
+    return out
+
+
+# --- the ResNet18 stem of the matching encoder (implicit-depth_amd/backbone.py) ---------------------------------------------------
+class FoldedStem:
+    """Eval-mode BatchNorms of the stem folded into its convolutions: ``blob`` (conv1 + bn1 for IDH_OP_STEM, idh_pack_stem_weight) and
+    four bias-carrying ``nn.Conv2d`` (layer1[b].conv1 + bn1, conv2 + bn2), which ``Plan.conv`` packs and caches like any other conv.
+    Folded on the device by ``idh_fold_conv_bn`` (the same arithmetic as the C entry idh_matching_stem_pack)."""
+
+    def __init__(self, stem, device):
+        L = _bind()
+        sp = _lib.stream_ptr()
+        conv1, bn1, layer1 = stem[0], stem[1], stem[4]
+        f = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        bn_args = lambda bn: [f(bn.weight), f(bn.bias), f(bn.running_mean), f(bn.running_var)]
+        self.blob = torch.empty(L.idh_stem_weight_floats(), device=device, dtype=torch.float32)
+        a = [f(conv1.weight)] + bn_args(bn1)
+        _lib.check(L.idh_pack_stem_weight(*[t.data_ptr() for t in a], float(bn1.eps), self.blob.data_ptr(), sp), "idh_pack_stem_weight")
+        self.convs = []
+        for blk in layer1:
+            for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
+                c = nn.Conv2d(conv.in_channels, conv.out_channels, 3, padding=1, bias=True).to(device)
+                c.requires_grad_(False)
+                w, b = torch.empty_like(c.weight), torch.empty_like(c.bias)
+                a = [f(conv.weight)] + bn_args(bn)
+                _lib.check(L.idh_fold_conv_bn(a[0].data_ptr(), conv.out_channels, conv.in_channels * 9, *[t.data_ptr() for t in a[1:]], float(bn.eps),
+                                              w.data_ptr(), b.data_ptr(), sp), "idh_fold_conv_bn")
+                c.weight.data, c.bias.data = w, b
+                self.convs.append(c)
+
+
+def stem_param_key(stem) -> ParamKey:
+    """Parameters AND buffers (BatchNorm running statistics) of the stem, with the BatchNorm eps values."""
+    from .backbone import stem_bns
+
+    mods = list(stem)
+    ts = [t for m in mods for t in list(m.parameters()) + list(m.buffers())]
+    return ParamKey(tuple((t.data_ptr(), _lib.param_version(t)) for t in ts) + tuple(float(bn.eps) for bn in stem_bns(mods)))
+
+
+def folded_stem(enc, device) -> FoldedStem:
+    """The encoder's FoldedStem, cached on it and rebuilt when a stem parameter or BatchNorm statistic changes (``load_state_dict``
+    bumps the epoch of inference-mode tensors, ``_lib.watch_state_dict_loads``)."""
+    stem = enc.net[:5]
+    require_native_stem(enc)
+    key = (stem_param_key(stem), str(device))
+    c = enc.__dict__.get("_idh_folded_stem")
+    if c is not None and c[0] == key:
+        return c[1]
+    fs = FoldedStem(stem, device)
+    enc.__dict__["_idh_folded_stem"] = (key, fs)
+    return fs
+
+
+def require_native_stem(enc) -> None:
+    from .backbone import stem_bns, stem_is_native_eligible
+
+    stem = list(enc.net[:5])
+    try:
+        bns = stem_bns(stem)
+    except (AttributeError, IndexError, TypeError):
+        bns = []
+    if any(isinstance(bn, nn.BatchNorm2d) and bn.training for bn in bns):
+        raise _lib.IdhError("the native matching stem is inference-only: a stem BatchNorm is in training mode (call .eval(); there is no CPU fallback)")
+    if not stem_is_native_eligible(stem):
+        raise _lib.IdhError("the matching encoder's net[:5] is not the resnet18(filter_size=4, pool_only=True) stem the native kernels compute "
+                            "(implicit-depth_amd/backbone.py: stem_is_native_eligible)")
+
+
+def image_strides(images: torch.Tensor):
+    """(images, (N, 3, H, W), (group, image stride, group stride)) for an (N, 3, H, W) or (B, K+1, 3, H, W) fp32 tensor whose images are
+    dense; any other layout is made contiguous first."""
+    if images.dim() not in (4, 5) or images.shape[-3] != 3:
+        raise _lib.IdhError(f"expected (N, 3, H, W) or (B, K+1, 3, H, W) images, got {tuple(images.shape)}")
+    H, W = images.shape[-2:]
+    if tuple(images.stride()[-3:]) != (H * W, W, 1):
+        images = images.contiguous()
+    if images.dim() == 4:
+        N = images.shape[0]
+        return images, (N, 3, H, W), (N, images.stride(0), N * images.stride(0))
+    B, K1 = images.shape[:2]
+    if B > 1 and K1 > 1 and images.stride(0) < K1 * images.stride(1):
+        images = images.contiguous()  # overlapping groups: not an addressing the kernel is meant for
+    return images, (B * K1, 3, H, W), (K1, images.stride(1), images.stride(0))
+
+
+def build_matching_stem(p: Plan, enc, images: torch.Tensor, out: Optional[View] = None):
+    """conv1 .. layer1 of the encoder's ResNet18 stem (backbone.py) on raw images: the fused IDH_OP_STEM pass, then layer1's two
+    BasicBlocks as four ``Plan.conv`` ops with the BatchNorms folded in (ReLU = LeakyReLU with slope 0; conv2 adds the block input in its
+    epilogue) - on conv3x3_wino4_k at every batch size (fp32 plans), so one image's layer1 map is bit-identical to the same image's in any batch.  ``images``: a tensor of the call's shape and strides (N, 3, H, W) or
+    (B, K+1, 3, H, W) (only its geometry is recorded; the pointer is patched per call with ``set_in``).  Returns (the layer1 map as an
+    NHWC view of 64 channels, the stem op's index)."""
+    fs = folded_stem(enc, p.device)
+    _, shape, strides = image_strides(images)
+    N, _, H, W = shape
+    Ho, Wo = ((H + 1) // 2) // 2, ((W + 1) // 2) // 2
+    x = p.buffer(N, Ho, Wo, 64)
+    i_img = p.stem(shape, strides, fs.blob, x)
+    for b in range(2):
+        c1, c2 = fs.convs[2 * b], fs.convs[2 * b + 1]
+        h = p.buffer(N, Ho, Wo, 64)
+        p.conv(x, c1, h, act=ACT_LRELU, slope=0.0, wino4_any_size=True)
+        y = out if (b == 1 and out is not None) else p.buffer(N, Ho, Wo, 64)
+        p.conv(h, c2, y, act=ACT_LRELU, slope=0.0, res=x, wino4_any_size=True)
+        p.release(h)
+        if b == 0:
+            p.release(x)
+        x = y
+    return x, i_img
+
+
+def matching_encoder_forward(enc, images: torch.Tensor, channels_last: bool = False, head: bool = True) -> torch.Tensor:
+    """ResnetMatchingEncoder.forward with a native stem: raw (N, 3, H, W) images -> stem -> layer1 -> head (``head=False``: the layer1
+    map) in one plan, NHWC throughout.  Returns NCHW, or with ``channels_last`` the (N, H, W, C) map (as ``matching_head_forward``)."""
+    require_native_stem(enc)
+    _lib.require_cuda_f32(images)
+    if images.dim() != 4:
+        raise _lib.IdhError(f"expected NCHW images, got shape {tuple(images.shape)}")
+    images, shape, strides = image_strides(images)
+    pk = stem_param_key(enc.net[:5]) + ((_param_key(enc.net[5]) + _param_key(enc.net[8])) if head else ParamKey())
+    key = ("stem", tuple(shape), strides, str(images.device), channels_last, head, pk)
+    cache = _plan_cache(enc)
+    ent = cache.get(key)
+    if ent is None:
+        p = Plan(images.device, math=math_of(enc))
+        y, i_in = build_matching_stem(p, enc, images)
+        if head:
+            y = build_matching_head(p, enc, y)
+        i_out = None if channels_last else p.export_nchw(y)
+        p.schedule()
+        ent = (p, i_in, i_out, y)
+        cache.put(key, ent)
+    p, i_in, i_out, y = ent
+    p.set_in(i_in, images)
+    if channels_last:
+        p.run()
+        return y.dense().clone()
+    out = torch.empty(y.N, y.C, y.H, y.W, device=images.device, dtype=torch.float32)
     p.set_out(i_out, out)
     p.run()
     return out

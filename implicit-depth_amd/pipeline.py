@@ -50,12 +50,19 @@ class HotPath(nn.Module):
         _lib.watch_state_dict_loads(self)
 
     # ------------------------------------------------------------------------------------
-    def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0):
+    def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
+              images: Optional[torch.Tensor] = None):
         """``head``: None = matching features come in finished (NCHW); "nchw" / "nhwc" = the plan starts at the
-        matching backbone's layer1 map (B*(K+1), head_ch, H, W) in that physical layout and runs the encoder head."""
-        key = (B, K, C, H, W, tuple(tuple(s) for s in enc_shapes), str(device), self.conv_math, head, head_ch,
+        matching backbone's layer1 map (B*(K+1), head_ch, H, W) in that physical layout and runs the encoder head;
+        "images" = the plan starts at the raw (B, K+1, 3, h, w) ``images`` and runs the native stem (nhwc.build_matching_stem) first."""
+        geom = None
+        if head == "images":
+            _, shape, strides = nhwc.image_strides(images)
+            geom = (tuple(shape), strides)
+        key = (B, K, C, H, W, tuple(tuple(s) for s in enc_shapes), str(device), self.conv_math, head, head_ch, geom,
                nhwc._param_key(self.cost_volume_net), nhwc._param_key(self.depth_decoder),
-               nhwc.ParamKey(nhwc._param_key(self.matching_model.net[5]) + nhwc._param_key(self.matching_model.net[8])) if head else None)
+               nhwc.ParamKey(nhwc._param_key(self.matching_model.net[5]) + nhwc._param_key(self.matching_model.net[8])) if head else None,
+               nhwc.stem_param_key(self.matching_model.net[:5]) if head == "images" else None)
         ent = self._plans.get(key)
         if ent is not None:
             return ent
@@ -74,7 +81,10 @@ class HotPath(nn.Module):
             # kernel addresses with batch strides.
             M = B * (K + 1)
             n0 = len(p.ops)
-            if head == "nchw" and nhwc.FUSE_HEAD_IMPORT and nhwc.Plan.pointwise_nchw_eligible(self.matching_model.net[5]):
+            if head == "images":  # stem + layer1 (one fused pass + four Winograd convs), then the head, all NHWC
+                x, ent["i_l1"] = nhwc.build_matching_stem(p, self.matching_model, images)
+                y = nhwc.build_matching_head(p, self.matching_model, x)
+            elif head == "nchw" and nhwc.FUSE_HEAD_IMPORT and nhwc.Plan.pointwise_nchw_eligible(self.matching_model.net[5]):
                 # the first 1x1 conv reads the backbone's NCHW map in place: no layout-import pass
                 y, ent["i_l1"] = nhwc.build_matching_head(p, self.matching_model, None, nchw_shape=(M, head_ch, H, W))
             elif head == "nchw":
@@ -115,7 +125,7 @@ class HotPath(nn.Module):
                 return_mask: bool = False, return_features: bool = False,
                 prior_inputs: Optional[Dict[str, torch.Tensor]] = None, infer_depth: bool = False,
                 matching_layer1: Optional[torch.Tensor] = None, return_matching_feats: bool = False,
-                frame_chain: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                frame_chain: Optional[Dict[str, torch.Tensor]] = None, matching_images: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """``matching_layer1`` (B, K+1, 64, H, W): output of the matching backbone (conv1..layer1 of the ResNet18,
         third-party, run by the caller) for frame b's current image followed by its K source images — the order
         reference bd_model.py:149-160 builds; contiguous or channels-last per image
@@ -132,11 +142,28 @@ class HotPath(nn.Module):
         separate calls would.  Keys: "world_T_cam_b44", "cam_T_world_b44" (B,4,4: the frames' poses), "K_s0_b44",
         "invK_s0_b44" (B,4,4), and the chain's start "prior_prediction" (1,1,H/2,W/2) + "prior_cam_T_world" (1,4,4) (or None
         for the first frame of a sequence).  Returns the usual dictionary with pred_0 of all B frames (the last one's
-        sigmoid and pose are the next call's chain start)."""
-        _lib.require_cuda_f32(matching_cur_feats, matching_src_feats, matching_layer1, src_cam_T_cur_cam, src_K, cur_invK, rendered_depth, prior, *cur_feats)
+        sigmoid and pose are the next call's chain start).
+        ``matching_images`` (B, K+1, 3, h, w): instead of ``matching_layer1``, the raw images in the same order; the matching encoder's
+        ResNet18 stem (conv1 .. layer1, backbone.py) then runs natively inside this call as well, the whole encoder in the same plan.
+        Needs a ``matching_model`` whose ``net[:5]`` passes ``backbone.stem_is_native_eligible`` (eval mode)."""
+        _lib.require_cuda_f32(matching_cur_feats, matching_src_feats, matching_layer1, matching_images, src_cam_T_cur_cam, src_K, cur_invK, rendered_depth, prior, *cur_feats)
         head = None
         head_ch = 0
-        if matching_layer1 is not None:
+        images = None
+        if matching_images is not None:
+            if matching_cur_feats is not None or matching_src_feats is not None or matching_layer1 is not None:
+                raise _lib.IdhError("pass one of finished matching features, matching_layer1 or matching_images")
+            if self.matching_model is None:
+                raise _lib.IdhError("matching_images needs HotPath(matching_model=...)")
+            if matching_images.dim() != 5 or matching_images.shape[2] != 3:
+                raise _lib.IdhError(f"matching_images must be (B, K+1, 3, H, W), got {tuple(matching_images.shape)}")
+            nhwc.require_native_stem(self.matching_model)
+            images, _, _ = nhwc.image_strides(matching_images)
+            B, K1, _, h_img, w_img = images.shape
+            K, C, head, head_ch = K1 - 1, self.matching_model.net[8].out_channels, "images", 64
+            H, W = ((h_img + 1) // 2) // 2, ((w_img + 1) // 2) // 2
+            l1 = images
+        elif matching_layer1 is not None:
             if matching_cur_feats is not None or matching_src_feats is not None:
                 raise _lib.IdhError("pass either finished matching features or matching_layer1, not both")
             if self.matching_model is None:
@@ -156,7 +183,7 @@ class HotPath(nn.Module):
             B, K, C, H, W = matching_src_feats.shape
         dev = src_K.device
         cur_feats = [f if f.is_contiguous() else f.contiguous() for f in cur_feats]
-        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch)
+        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch, images)
         p, st = ent["plan"], ent["state"]
         L = _lib.lib()
         sp = _lib.stream_ptr()

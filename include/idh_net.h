@@ -104,6 +104,33 @@ int idh_unetpp_fwd(const idh_block_params *blocks, int n_blocks, const idh_conv_
                    const idh_tensor *feats, const idh_tensor *feature_outs, float *const *log_depth_outs, float *const *depth_outs,
                    float *workspace, size_t workspace_floats, void *stream);
 
+/* ---- ResNet18 matching stem (implicit-depth_amd/backbone.py: conv1, bn1, relu, maxpool, layer1 of antialiased_cnns.resnet18(filter_size=4,
+ * pool_only=True), reference modules/networks.py:261-271) --------------------------------------------------------------------------------
+ * Raw images -> the 64-channel layer1 map at 1/4 resolution, inference only (eval-mode BatchNorms, folded into the convolutions by *_pack):
+ * one fused IDH_OP_STEM pass (conv1 7x7/2 + bn1 + ReLU + MaxPool2d(2, 1) + BlurPool; the blur filter is the fixed binomial
+ * outer([1,3,3,1], [1,3,3,1]) / 64 behind ReflectionPad2d((1, 2, 1, 2)) and is not a parameter), then layer1's two BasicBlocks as four 3x3
+ * convs with ReLU after conv1 and after conv2 + identity - the op list nhwc.build_matching_stem builds, so results are bit-identical to the
+ * Python path.  images: IDH_LAYOUT_NCHW, C = 3, dense (N, 3, H, W), H, W >= 8 (else IDH_EINVAL); out: C = 64, H = floor(ceil(H/2) / 2), W
+ * likewise, NHWC (in place, any channel stride) or NCHW.  An NHWC out with cs = 64 is what idh_model_fwd's IDH_MATCH_LAYER1_NHWC reads
+ * (N = B (K+1) images in the frame order of include/idh_model.h).  BatchNorm pointers: device memory, read by *_pack only. */
+typedef struct idh_bn_params {
+    const float *weight, *bias, *running_mean, *running_var; /* (64) each */
+    float eps;
+    int32_t _r;
+} idh_bn_params;
+
+typedef struct idh_stem_params {
+    const float *conv1_weight;      /* (64, 3, 7, 7) OIHW, no bias */
+    idh_bn_params bn1;
+    const float *layer1_conv[4];    /* layer1[0].conv1, layer1[0].conv2, layer1[1].conv1, layer1[1].conv2: (64, 64, 3, 3), no bias */
+    idh_bn_params layer1_bn[4];     /* layer1[0].bn1, layer1[0].bn2, layer1[1].bn1, layer1[1].bn2 */
+} idh_stem_params;
+
+int idh_matching_stem_sizes(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, idh_net_sizes *sizes);
+int idh_matching_stem_pack(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, float *weight_blob, void *stream);
+int idh_matching_stem_fwd(const idh_stem_params *params, const float *weight_blob, int N, const idh_tensor *images, const idh_tensor *out,
+                          float *workspace, size_t workspace_floats, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -44,6 +44,15 @@ enum {
                                  resolution because a 1x1 conv commutes with bilinear upsampling.  src[0] = x (N,H,W,Cin), w =
                                  idh_pack_conv_weight(Cout, Cin, 1); src[1].in / .cs / .H / .W = the (N,H/2,W/2,Cout) map; Cin == Cout in {64, 128},
                                  H and W even; other shapes: IDH_EUNSUPPORTED */
+    IDH_OP_STEM = 12,       /* ResNet18 stem of the matching encoder up to its anti-aliased max-pool (implicit-depth_amd/backbone.py: conv1 7x7/2 3->64
+                               with eval-mode BatchNorm folded in, ReLU, MaxPool2d(2, 1), BlurPool = ReflectionPad2d((1, 2, 1, 2)) + depthwise 4x4
+                               filter outer([1,3,3,1], [1,3,3,1]) / 64 at stride 2 - a fixed filter, not read from memory), one fused pass
+                               (csrc/stem.hip stem_conv7_pool_k).  src[0].in = image 0 of N dense fp32 (3, H, W) images, H, W >= 8;
+                               src[0].H / .W = H, W; src[0].Cin = 3; src[0].w = idh_pack_stem_weight output; images in groups (a (B, K+1, 3, H, W)
+                               view): src[0].up_C = images per group (0: one group of N), src[0].up_cs[0] = floats between consecutive images of a
+                               group (0: 3 H W), src[0].up_cs[1] = floats between groups (0: up_C times the image stride).  out = NHWC (N, Ho, Wo,
+                               out_cs), channels [0, 64) written, 16-byte aligned, out_cs >= 64 and a multiple of 4; Cout = 64; Ho = floor(ceil(H/2) / 2),
+                               Wo likewise.  bias / res / ws / act unused */
     IDH_OP_INSTNORM = 7     /* nn.InstanceNorm2d (no affine, eps 1e-5) [+ LeakyReLU] on NHWC; matching-encoder
                                head networks.py:279-283.  ws: N*(ceil(HW/1024)+1)*2*C floats (chunk partials + mean/rstd);
                                out == NULL: statistics only — float[N][2][C] at ws + N*ceil(HW/1024)*2*C, for a
@@ -157,6 +166,17 @@ int idh_pack_conv_weight_wino(const float *w_oihw, float *dst, int Cout, int Cin
 #define IDH_TILE_WINO4 13
 size_t idh_packed_wino4_weight_floats(int Cout, int Cin);
 int idh_pack_conv_weight_wino4(const float *w_oihw, float *dst, int Cout, int Cin, void *stream);
+
+/* IDH_OP_STEM weights: conv1 (64, 3, 7, 7) OIHW times bn_weight / sqrt(bn_var + eps) in the kernel's MFMA B-fragment order
+ * ([channel quarter 4][K-step 42][lane 64], taps kx padded 7 -> 8 with zeros), then the 64 folded biases bn_bias - bn_mean * bn_weight /
+ * sqrt(bn_var + eps).  All pointers device memory; dst holds idh_stem_weight_floats() floats. */
+size_t idh_stem_weight_floats(void);
+int idh_pack_stem_weight(const float *w_oihw, const float *bn_weight, const float *bn_bias, const float *bn_mean, const float *bn_var, float eps,
+                         float *dst, void *stream);
+/* Eval-mode BatchNorm folded into the conv before it: w_out[o][i] = w[o][i] * s[o], b_out[o] = bn_bias[o] - bn_mean[o] * s[o],
+ * s = bn_weight / sqrt(bn_var + eps) in fp32, i < per_out (= Cin * ks * ks).  The layer1 convs of the stem (BasicBlock conv + bn). */
+int idh_fold_conv_bn(const float *w, int cout, int per_out, const float *bn_weight, const float *bn_bias, const float *bn_mean,
+                     const float *bn_var, float eps, float *w_out, float *b_out, void *stream);
 
 /* sizeof(idh_op) as compiled into the library (bindings assert their mirror matches). */
 size_t idh_sizeof_op(void);
