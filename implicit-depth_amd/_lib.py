@@ -41,6 +41,24 @@ class VolumeOpts(C.Structure):
 CV_KERNEL_LANE, CV_KERNEL_QUAD, CV_KERNEL_WINDOW = 1, 2, 3  # IDH_CV_KERNEL_* of include/idh.h
 
 
+class EvalArgs(C.Structure):
+    """ctypes mirror of ``idh_eval_args`` (include/idh.h, fused per-frame test evaluation)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("prediction", C.c_void_p), ("pred_kind", C.c_int32), ("sampling", C.c_int32),
+                ("sigmoid_multiplier", C.c_float), ("surface_threshold", C.c_float), ("rendered_bphw", C.c_void_p), ("depth_b1hw", C.c_void_p),
+                ("gt_b1HW", C.c_void_p), ("thresholds", C.c_void_p), ("bins", C.c_void_p), ("T", C.c_int32), ("n_bins", C.c_int32),
+                ("tag_mask", C.c_int32), ("B", C.c_int32), ("P", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(EvalArgs)
+
+
+EVAL_PRED_LOGITS, EVAL_PRED_DEPTH = 0, 1  # IDH_EVAL_PRED_*
+EVAL_BILINEAR, EVAL_NEAREST = 0, 1  # IDH_EVAL_BILINEAR / IDH_EVAL_NEAREST
+EVAL_TAG_ALL, EVAL_TAG_SURFACE, EVAL_TAG_BOUNDARY = 1, 2, 4  # IDH_EVAL_TAG_*
+
+
 _SIGS = {
     "idh_version": (C.c_int, []),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
@@ -97,6 +115,11 @@ _SIGS = {
     "idh_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "idh_plane_iou_fwd": (C.c_int, [f32p, f32p, f32p, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "idh_depth_metrics_fwd": (C.c_int, [f32p, f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "idh_sizeof_eval_args": (C.c_size_t, []),
+    "idh_eval_frame_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "idh_eval_masks_fwd": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_void_p, C.c_void_p]),
+    "idh_eval_plane_scores_fwd": (C.c_int, [C.POINTER(EvalArgs), f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "idh_eval_depth_metrics_fwd": (C.c_int, [f32p, f32p] + [C.c_int] * 6 + [C.c_float, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -134,6 +157,8 @@ def lib():
         ver = h.idh_version()
         if ver < MIN_ABI_VERSION and not os.environ.get("IDH_LIB_ANY_ABI"):  # (IDH_LIB_ANY_ABI: A/B timing against a library built from an older tree)
             raise IdhError(f"{LIB_PATH} reports ABI version {ver}, this binding needs >= {MIN_ABI_VERSION}: rebuild with `python implicit-depth_amd/build.py --force`")
+        if h.idh_sizeof_eval_args() != C.sizeof(EvalArgs):
+            raise IdhError(f"{LIB_PATH}: sizeof(idh_eval_args) = {h.idh_sizeof_eval_args()} in the library, {C.sizeof(EvalArgs)} in this binding")
         if h.idh_sizeof_volume_opts() != C.sizeof(VolumeOpts):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_volume_opts) = {h.idh_sizeof_volume_opts()} in the library, {C.sizeof(VolumeOpts)} in this binding")
         _lib = h

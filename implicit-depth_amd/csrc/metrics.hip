@@ -11,11 +11,11 @@
 // metric family is one counting / summing pass plus a tiny finalise kernel.  IoU counts are integer
 // (exact, order independent); depth sums are accumulated per block and combined in a fixed order
 // in double, so results are deterministic.
-#include "idh_common.h"
+#include "metrics_common.h"
 
 namespace {
 
-constexpr int kMaxThr = 8;
+using idh_metrics::kMaxThr;
 
 struct IouArgs {
     const float *query;   // B,D,N
@@ -77,61 +77,30 @@ __global__ void iou_finalise_k(const unsigned *__restrict__ counts, int BD, int 
     if (i >= BD * T) return;
     const int bd = i / T, t = i - bd * T;
     const unsigned *c = counts + (size_t)bd * (2 + 2 * T);
-    const float nv = (float)c[0], nt = (float)c[1], np = (float)c[2 + t], ni = (float)c[2 + T + t];
-    const float pos = ni / (nt + np - ni);
-    const float nn_t = nv - nt, nn_p = nv - np, nn_i = nv - nt - np + ni;  // counts of the negated masks
-    const float neg = nn_i / (nn_t + nn_p - nn_i);
-    const float iou = 2.f * (pos * neg) / (pos + neg);
-    out[(size_t)i * 3 + 0] = iou;
-    out[(size_t)i * 3 + 1] = pos;
-    out[(size_t)i * 3 + 2] = neg;
+    idh_metrics::iou_from_counts(c[0], c[1], c[2 + t], c[2 + T + t], out + (size_t)i * 3);
 }
 
-constexpr int kDM = 12;  // abs_diff abs_rel sq_rel rmse rmse_log a5 a10 a25 a0 a1 a2 a3
-constexpr int kDmChunk = 4096;
+using idh_metrics::kDM;
+using idh_metrics::kDmChunk;
 
 __global__ __launch_bounds__(256) void depth_metrics_partial_k(const float *__restrict__ gt, const float *__restrict__ pred,
                                                                const unsigned char *__restrict__ valid, int N, int nchunks,
                                                                double *__restrict__ part) {  // part[b][chunk][13]
-    __shared__ double red[4][kDM + 1];
     const int b = blockIdx.y, chunk = blockIdx.x;
     const int i0 = chunk * kDmChunk, i1 = min(N, i0 + kDmChunk);
     double s[kDM + 1];
     for (int k = 0; k <= kDM; ++k) s[k] = 0.0;
     for (int i = i0 + threadIdx.x; i < i1; i += 256) {
         if (!valid[(size_t)b * N + i]) continue;
-        const float g = gt[(size_t)b * N + i], p = pred[(size_t)b * N + i];
-        const float d = g - p;
-        const float th = fmaxf(g / p, p / g);
-        const float lg = logf(g) - logf(p);
-        s[0] += fabsf(d); s[1] += fabsf(d) / g; s[2] += d * d / g; s[3] += d * d; s[4] += lg * lg;
-        s[5] += th < 1.05f; s[6] += th < 1.10f; s[7] += th < 1.25f; s[8] += th < 1.10f; s[9] += th < 1.25f;
-        s[10] += th < 1.25f * 1.25f; s[11] += th < 1.25f * 1.25f * 1.25f;
-        s[12] += 1.0;
+        idh_metrics::depth_metric_terms(gt[(size_t)b * N + i], pred[(size_t)b * N + i], s);
     }
-    for (int k = 0; k <= kDM; ++k) {
-        double v = s[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x <= kDM)
-        part[((size_t)b * nchunks + chunk) * (kDM + 1) + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    idh_metrics::depth_metric_block_store(s, part + ((size_t)b * nchunks + chunk) * (kDM + 1));
 }
 
 __global__ void depth_metrics_finalise_k(const double *__restrict__ part, int nchunks, int mult_a, float *__restrict__ out) {
     const int b = blockIdx.x, k = threadIdx.x;
     if (k >= kDM) return;
-    double s = 0.0, n = 0.0;
-    for (int c = 0; c < nchunks; ++c) {
-        s += part[((size_t)b * nchunks + c) * (kDM + 1) + k];
-        n += part[((size_t)b * nchunks + c) * (kDM + 1) + kDM];
-    }
-    double m = s / n;  // nanmean over the valid pixels (0/0 -> NaN like torch.nanmean of an all-NaN row)
-    if (k == 3 || k == 4) m = sqrt(m);
-    if (k >= 5 && mult_a) m *= 100.0;
-    out[(size_t)b * kDM + k] = (float)m;
+    out[(size_t)b * kDM + k] = idh_metrics::depth_metric_finalise(part, b, nchunks, k, mult_a);
 }
 
 }  // namespace

@@ -1,0 +1,178 @@
+"""Fused per-frame test evaluation (csrc/eval_frame.hip).
+
+Reference test_bd.py:185-318 and test_reg.py:189-268 turn a batch's model outputs into per-frame metric rows with
+surface / boundary masks, four F.interpolate calls up to the ground-truth resolution and three PlaneEvaluator calls,
+materialising several (B, P, H, W) tensors on the way.  ``bd_frame_scores`` / ``reg_frame_scores`` return the same
+score dict from one mask pass at model resolution and one counting pass at ground-truth resolution that samples the
+low-resolution inputs on the fly.  The dict goes through ``metrics.metric_rows`` unchanged (the payload of the metrics
+all-gather)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .metrics import DEPTH_METRIC_KEYS, PlaneEvaluator
+
+TAGS = (None, "surface", "boundary")  # order of the tag axis of plane_scores
+_ALL_TAGS = _lib.EVAL_TAG_ALL | _lib.EVAL_TAG_SURFACE | _lib.EVAL_TAG_BOUNDARY
+_PLANES = tuple(1.5 + x * 0.5 for x in range(8))  # the key names' depth planes (binary_metrics_utils.py:135, :233)
+_EV = PlaneEvaluator()
+
+
+def _check_planes(depth_b1hw, rendered_bphw):
+    _lib.require_cuda_f32(depth_b1hw, rendered_bphw)
+    if rendered_bphw.dim() != 4 or depth_b1hw.dim() != 4 or depth_b1hw.shape[1] != 1 or depth_b1hw.shape[0] != rendered_bphw.shape[0] \
+            or depth_b1hw.shape[2:] != rendered_bphw.shape[2:]:
+        raise _lib.IdhError(f"eval masks: depth {tuple(depth_b1hw.shape)} must be (B,1,h,w) of rendered {tuple(rendered_bphw.shape)}")
+
+
+def eval_masks(depth_b1hw: torch.Tensor, rendered_depth_bdhw: torch.Tensor, threshold: float = 0.05, surface=True, boundary=True, code=False):
+    """(surface, boundary, code): the two float masks of the reference functions and the uint8 per-pixel code (bit 0 surface,
+    bit 1 boundary); those not asked for are None.  One kernel for all."""
+    _check_planes(depth_b1hw, rendered_depth_bdhw)
+    B, P, h, w = rendered_depth_bdhw.shape
+    d, r = depth_b1hw.contiguous(), rendered_depth_bdhw.contiguous()
+    mk = lambda want, dt: torch.empty(B, P, h, w, device=r.device, dtype=dt) if want else None
+    s, b, c = mk(surface, torch.float32), mk(boundary, torch.float32), mk(code, torch.uint8)
+    _lib.check(_lib.lib().idh_eval_masks_fwd(d.data_ptr(), r.data_ptr(), B, P, h, w, float(threshold), _lib.ptr(s), _lib.ptr(b), _lib.ptr(c),
+                                             _lib.stream_ptr()), "idh_eval_masks_fwd")
+    return s, b, c
+
+
+def get_surface_mask(depth_b1hw, rendered_depth_bdhw, threshold=0.05):
+    """utils/binary_metrics_utils.py:35-39: (|depth - rendered| / depth < threshold) as a float (B, P, h, w) mask."""
+    return eval_masks(depth_b1hw, rendered_depth_bdhw, threshold, boundary=False)[0]
+
+
+def get_boundary_mask(depth_b1hw, rendered_depth_bdhw):
+    """utils/binary_metrics_utils.py:23-32: 7x7 dilation of the 3x3 occlusion edges of (rendered < depth), 0 where depth is NaN."""
+    return eval_masks(depth_b1hw, rendered_depth_bdhw, surface=False)[1]
+
+
+def _workspace(B, P, h, w, H, W, T, device):
+    n = _lib.lib().idh_eval_frame_workspace_bytes(B, P, h, w, H, W, T)
+    return torch.empty(max(n, 8), device=device, dtype=torch.uint8), n
+
+
+def plane_scores(prediction, rendered_bphw, gt_b1HW, depth_b1hw=None, *, regressed=False, nearest=False, sigmoid_multiplier=1.0,
+                 thresholds: Sequence[float] = (), bins: Optional[torch.Tensor] = None, bin_thresholds: Optional[torch.Tensor] = None,
+                 tag_mask=_ALL_TAGS, surface_threshold=0.05, return_counts=False):
+    """(B, 3, P, T, 3) = [iou, iou_pos, iou_neg] per (frame, tag in TAGS, query plane, threshold) after upsampling to gt's resolution.
+    ``prediction``: logits (B, P, h, w), or with ``regressed`` a depth (B, 1, h, w) compared with the query (T = 1).  ``bins`` /
+    ``bin_thresholds``: the Thresholder (T = 1).  With ``return_counts`` also the (B, 3, P, 2 + 2T) int32 counts
+    {valid, target, pred[T], inter[T]}."""
+    _lib.require_cuda_f32(prediction, rendered_bphw, gt_b1HW, depth_b1hw, bins, bin_thresholds)
+    B, P, h, w = rendered_bphw.shape
+    H, W = gt_b1HW.shape[-2:]
+    dev = rendered_bphw.device
+    if tuple(prediction.shape) != ((B, 1, h, w) if regressed else (B, P, h, w)) or tuple(gt_b1HW.shape) != (B, 1, H, W):
+        raise _lib.IdhError(f"plane_scores: shapes prediction {tuple(prediction.shape)}, rendered {tuple(rendered_bphw.shape)}, gt {tuple(gt_b1HW.shape)}")
+    if tag_mask & ~_lib.EVAL_TAG_ALL:
+        _check_planes(depth_b1hw, rendered_bphw)
+    if regressed:
+        thr, T = None, 1
+    elif bins is not None:
+        thr, T = bin_thresholds.contiguous(), 1
+        if thr.numel() != bins.numel():
+            raise _lib.IdhError("Thresholder needs one threshold per bin")
+        bins = bins.contiguous()
+    else:
+        thr, T = torch.tensor([float(t) for t in thresholds], device=dev, dtype=torch.float32), len(thresholds)
+    keep = [prediction.contiguous(), rendered_bphw.contiguous(), gt_b1HW.contiguous(), None if depth_b1hw is None else depth_b1hw.contiguous()]
+    a = _lib.EvalArgs()
+    a.prediction, a.rendered_bphw, a.gt_b1HW, a.depth_b1hw = [_lib.ptr(t) for t in keep]
+    a.pred_kind = _lib.EVAL_PRED_DEPTH if regressed else _lib.EVAL_PRED_LOGITS
+    a.sampling = _lib.EVAL_NEAREST if nearest else _lib.EVAL_BILINEAR
+    a.sigmoid_multiplier, a.surface_threshold = float(sigmoid_multiplier), float(surface_threshold)
+    a.thresholds, a.bins = _lib.ptr(thr), _lib.ptr(bins)
+    a.T, a.n_bins, a.tag_mask = T, 0 if bins is None or regressed else bins.numel(), tag_mask
+    a.B, a.P, a.h, a.w, a.H, a.W = B, P, h, w, H, W
+    out = torch.empty(B, len(TAGS), P, T, 3, device=dev)
+    counts = torch.empty(B, len(TAGS), P, 2 + 2 * T, device=dev, dtype=torch.int32) if return_counts else None
+    ws, nbytes = _workspace(B, P, h, w, H, W, T, dev)
+    _lib.check(_lib.lib().idh_eval_plane_scores_fwd(C.byref(a), out.data_ptr(), _lib.ptr(counts), ws.data_ptr(), nbytes, _lib.stream_ptr()),
+               "idh_eval_plane_scores_fwd")
+    return (out, counts) if return_counts else out
+
+
+def upsampled_depth_metrics(gt_b1HW, pred_b1hw, nearest=False, valid_above=0.5, mult_a=False) -> Dict[str, torch.Tensor]:
+    """compute_depth_metrics_batched(gt, F.interpolate(pred, gt's size, "nearest" / "bilinear"), gt > valid_above, mult_a)."""
+    _lib.require_cuda_f32(gt_b1HW, pred_b1hw)
+    B, _, H, W = gt_b1HW.shape
+    if pred_b1hw.dim() != 4 or pred_b1hw.shape[:2] != (B, 1) or gt_b1HW.shape[1] != 1:
+        raise _lib.IdhError(f"upsampled_depth_metrics: gt {tuple(gt_b1HW.shape)} and prediction {tuple(pred_b1hw.shape)} must be (B,1,.,.)")
+    h, w = pred_b1hw.shape[-2:]
+    g, p = gt_b1HW.contiguous(), pred_b1hw.contiguous()
+    out = torch.empty(B, len(DEPTH_METRIC_KEYS), device=g.device)
+    ws, nbytes = _workspace(B, 1, h, w, H, W, 1, g.device)
+    _lib.check(_lib.lib().idh_eval_depth_metrics_fwd(g.data_ptr(), p.data_ptr(), B, h, w, H, W, _lib.EVAL_NEAREST if nearest else _lib.EVAL_BILINEAR,
+                                                     float(valid_above), int(mult_a), out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr()),
+               "idh_eval_depth_metrics_fwd")
+    return {k: out[:, i] for i, k in enumerate(DEPTH_METRIC_KEYS)}
+
+
+def _keep(gt_b1HW, thresh):
+    return (gt_b1HW.flatten(1) > thresh).any(1)
+
+
+def _tag_scores(out, names, is_rendering):
+    scores: Dict[str, torch.Tensor] = {}
+    for i, tag in enumerate(TAGS):
+        scores.update(_EV._scores(out[:, i], names, is_rendering, tag, _PLANES))
+    return scores
+
+
+def _names(thresholder, evaluator_thresholds):
+    return [""] if thresholder is not None else [f"{float(t):.1f}_" for t in evaluator_thresholds]
+
+
+def bd_score_keys(P, thresholder=None, evaluator_thresholds=np.linspace(0.3, 0.7, 5), temporal_eval=False, binary_eval_depth=False):
+    """The keys, in order, of bd_frame_scores' dict for P query planes (no device work)."""
+    if binary_eval_depth:
+        return list(DEPTH_METRIC_KEYS)
+    names = _names(thresholder, evaluator_thresholds)
+    return list(_tag_scores(torch.zeros(1, len(TAGS), P, len(names), 3), names, temporal_eval))
+
+
+def reg_score_keys(P, regression_plane_eval=False, temporal_eval=False):
+    """The keys, in order, of reg_frame_scores' dict for P query planes (no device work)."""
+    if not regression_plane_eval:
+        return list(DEPTH_METRIC_KEYS)
+    return list(_tag_scores(torch.zeros(1, len(TAGS), P, 1, 3), [""], temporal_eval))
+
+
+def bd_frame_scores(outputs, cur_data, thresholder=None, evaluator_thresholds=np.linspace(0.3, 0.7, 5), bd_sigmoid_multiplier=1.0,
+                    temporal_eval=False, binary_eval_depth=False):
+    """test_bd.py:185-318 for one batch: ``(metrics_b_dict, keep_b)``.
+
+    ``outputs``: BDModel.forward's outputs as returned (``pred_0`` logits; ``search_depths`` with ``binary_eval_depth``);
+    ``cur_data``: ``depth_b1hw``, ``rendered_depth`` (B, P, h, w) and ``full_res_depth_b1hw``.  ``metrics_b_dict`` has the keys, in
+    order, and the values test_bd.py builds; ``keep_b`` (B,) bool is its per-frame test (:275, :323): the frames whose rows it keeps.
+    Neither argument is modified."""
+    gt = cur_data["full_res_depth_b1hw"]
+    if binary_eval_depth:
+        scores = upsampled_depth_metrics(gt, outputs["search_depths"], nearest=True, valid_above=0.5, mult_a=False)
+        return scores, _keep(gt, 0.5)
+    if thresholder is not None:
+        dev = gt.device
+        thr = dict(bins=thresholder.bins.to(dev).float(), bin_thresholds=thresholder.thresholds.to(dev).float())
+    else:
+        thr = dict(thresholds=[float(t) for t in evaluator_thresholds])
+    out = plane_scores(outputs["pred_0"], cur_data["rendered_depth"], gt, cur_data["depth_b1hw"], nearest=temporal_eval,
+                       sigmoid_multiplier=bd_sigmoid_multiplier, **thr)
+    return _tag_scores(out, _names(thresholder, evaluator_thresholds), temporal_eval), _keep(gt, 0.0)
+
+
+def reg_frame_scores(outputs, cur_data, regression_plane_eval=False, temporal_eval=False):
+    """test_reg.py:189-268 for one batch: ``(metrics_b_dict, keep_b)`` from DepthModel's ``depth_pred_s0_b1hw`` — the regressed-depth
+    plane IoU for the three families with ``regression_plane_eval``, else the depth metrics (mult_a=True) over gt > 0.5."""
+    gt = cur_data["full_res_depth_b1hw"]
+    pred = outputs["depth_pred_s0_b1hw"]
+    if regression_plane_eval:
+        out = plane_scores(pred, cur_data["rendered_depth"], gt, cur_data["depth_b1hw"], regressed=True, nearest=temporal_eval)
+        return _tag_scores(out, [""], temporal_eval), _keep(gt, 0.0)
+    return upsampled_depth_metrics(gt, pred, nearest=temporal_eval, valid_above=0.5, mult_a=True), _keep(gt, 0.5)

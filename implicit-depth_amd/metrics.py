@@ -84,6 +84,14 @@ class PlaneEvaluator:
                         bin_thresholds=thresholder.thresholds.to(dev).float())
         return self._scores(out, [""], is_rendering, tag, depth_planes)
 
+    def compute_regressed_depth_batch_scores(self, query_depth_bdhw, gt_depth_b1hw, prediction_b1hw, is_rendering=False, tag=None):
+        """utils/binary_metrics_utils.py:194-244: the plane IoU of a regressed depth, prediction = query < depth, over the same
+        valid pixels (csrc/eval_frame.hip at equal resolutions: its nearest sampling is then the identity)."""
+        from .evaluation import plane_scores
+
+        out = plane_scores(prediction_b1hw, query_depth_bdhw, gt_depth_b1hw, regressed=True, nearest=True, tag_mask=_lib.EVAL_TAG_ALL)
+        return self._scores(out[:, 0], [""], is_rendering, tag, tuple(1.5 + x * 0.5 for x in range(8)))
+
 
 def compute_depth_metrics_batched(gt_bN: torch.Tensor, pred_bN: torch.Tensor, valid_masks_bN: torch.Tensor, mult_a: bool = False) -> Dict[str, torch.Tensor]:
     _lib.require_cuda_f32(gt_bN, pred_bN)

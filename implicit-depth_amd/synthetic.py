@@ -250,3 +250,40 @@ def custom_depth_planes(B: int, D: int, H: int, W: int, seed: int = 0) -> torch.
     xs = torch.linspace(-1, 1, W).view(1, 1, 1, W)
     b = torch.arange(B, dtype=torch.float32).view(B, 1, 1, 1)
     return (base * (1.0 + 0.08 * xs - 0.05 * ys + 0.03 * b) + 0.01 * torch.sigmoid(randn((B, D, H, W), seed, "planes"))).contiguous()
+
+
+def smooth_field(shape, seed: int, tag: str = "", cells=(6, 8)) -> np.ndarray:
+    """A smooth (..., H, W) float64 field: the bilinear blend of a coarse (cells + 1) standard-normal grid.  Basic arithmetic
+    only, so every host computes the same bits (thresholded masks of it can then be compared bit for bit)."""
+    *lead, H, W = shape
+    ch, cw = cells
+    g = _rng(seed, tag).standard_normal(size=(*lead, ch + 1, cw + 1))
+    y = np.arange(H, dtype=np.float64) * (ch / max(H - 1, 1))
+    x = np.arange(W, dtype=np.float64) * (cw / max(W - 1, 1))
+    y0 = np.minimum(np.floor(y).astype(np.int64), ch - 1)
+    x0 = np.minimum(np.floor(x).astype(np.int64), cw - 1)
+    fy, fx = (y - y0)[:, None], (x - x0)[None, :]
+    Y, X = y0[:, None], x0[None, :]
+    return (1 - fy) * ((1 - fx) * g[..., Y, X] + fx * g[..., Y, X + 1]) + fy * ((1 - fx) * g[..., Y + 1, X] + fx * g[..., Y + 1, X + 1])
+
+
+def eval_frame_case(B: int, P: int, h: int, w: int, H: int, W: int, seed: int = 0):
+    """(outputs, cur_data) for one test batch of reference test_bd.py / test_reg.py's evaluation block (:185-318 / :189-268):
+    model-resolution ``depth_b1hw`` (with NaN and zero patches), ``rendered_depth`` (B, P, h, w) query planes 1.5..5 m with a
+    smooth relief, full-resolution ``full_res_depth_b1hw`` (with zero and NaN patches), and the outputs ``pred_0`` (logits),
+    ``search_depths`` and ``depth_pred_s0_b1hw``.  Basic float64 arithmetic, cast once to float32: identical on every host."""
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    depth = np.maximum(2.8 + 1.2 * smooth_field((B, 1, h, w), seed, "eval_depth"), 0.3)
+    depth[:, :, h // 4: h // 4 + 5, w // 3: w // 3 + 9] = np.nan
+    depth[:, :, -6:, :8] = 0.0
+    planes = 1.5 + (3.5 / max(P - 1, 1)) * np.arange(P, dtype=np.float64) if P > 1 else np.array([2.5])
+    rendered = planes.reshape(1, P, 1, 1) * (1.0 + 0.04 * smooth_field((B, P, h, w), seed, "eval_rendered"))
+    gt = np.maximum(2.8 + 1.2 * smooth_field((B, 1, H, W), seed, "eval_gt") + 0.02 * _rng(seed, "eval_gt_noise").standard_normal((B, 1, H, W)), 0.3)
+    gt[:, :, : H // 8, -(W // 6):] = 0.0
+    gt[:, :, H // 2: H // 2 + 7, W // 2: W // 2 + 11] = np.nan
+    logits = 2.0 * smooth_field((B, P, h, w), seed, "eval_logits", cells=(12, 16)) + 0.5 * _rng(seed, "eval_logits_noise").standard_normal((B, P, h, w))
+    search = np.maximum(2.8 + 1.2 * smooth_field((B, 1, h, w), seed, "eval_search") + 0.05 * _rng(seed, "eval_search_noise").standard_normal((B, 1, h, w)), 0.25)
+    dpred = np.maximum(2.8 + 1.2 * smooth_field((B, 1, h, w), seed, "eval_dpred") + 0.05 * _rng(seed, "eval_dpred_noise").standard_normal((B, 1, h, w)), 0.25)
+    outputs = {"pred_0": f32(logits), "search_depths": f32(search), "depth_pred_s0_b1hw": f32(dpred)}
+    cur = {"depth_b1hw": f32(depth), "rendered_depth": f32(rendered), "full_res_depth_b1hw": f32(gt)}
+    return outputs, cur

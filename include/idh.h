@@ -285,6 +285,62 @@ int idh_plane_iou_fwd(const float *query_depth_bdn, const float *gt_depth_b1n, c
 int idh_depth_metrics_fwd(const float *gt_bn, const float *pred_bn, const unsigned char *valid_bn, int B, int N,
                           int mult_a, float *out_b12, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- fused per-frame test evaluation ------------------------------------------------------------------------------------ */
+/* What reference test_bd.py:185-318 and test_reg.py:189-268 do between the model outputs at model resolution (h, w) and
+ * the per-frame metric rows at ground-truth resolution (H, W), without materialising any (B, P, H, W) tensor:
+ *   - get_surface_mask / get_boundary_mask (utils/binary_metrics_utils.py:23-39) at (h, w);
+ *   - sigmoid_custom(pred_0, bd_sigmoid_multiplier) (test_bd.py:225-227, modules/layers.py:138);
+ *   - F.interpolate of the prediction (bilinear, align_corners=False, or nearest), of the query planes and of the
+ *     surface- / boundary-masked query planes (nearest) up to (H, W) (test_bd.py:238-264, test_reg.py:189-233);
+ *   - PlaneEvaluator.compute_batch_scores(_test) (binary_metrics_utils.py:59-192) or compute_regressed_depth_batch_scores
+ *     (:194-244) for the untagged, "surface" and "boundary" families (test_bd.py:287-318, test_reg.py:235-261);
+ *   - compute_depth_metrics_batched (utils/metrics_utils.py:52-120) over an upsampled search_depths or regressed depth
+ *     (test_bd.py:266-285, test_reg.py:263-268).
+ * Upsampling reproduces PyTorch's legacy nearest (src = min(floor(dst * (float)in / out), in - 1)) and its bilinear
+ * source index / tap / lambda order.  IoU counts are integers. */
+#define IDH_EVAL_PRED_LOGITS 0 /* prediction = occlusion logits (B,P,h,w); positive when sigmoid(m * logit), upsampled, > threshold */
+#define IDH_EVAL_PRED_DEPTH 1  /* prediction = regressed depth (B,1,h,w); positive when query < upsampled depth (T = 1) */
+#define IDH_EVAL_BILINEAR 0
+#define IDH_EVAL_NEAREST 1      /* temporal_eval */
+#define IDH_EVAL_TAG_ALL 1      /* the untagged family (query > 0) */
+#define IDH_EVAL_TAG_SURFACE 2  /* query inside the surface mask */
+#define IDH_EVAL_TAG_BOUNDARY 4 /* query inside the boundary mask */
+
+/* Host struct, read during the call.  struct_size = sizeof(idh_eval_args) of the caller's header (must be >= the library's). */
+typedef struct idh_eval_args {
+    int64_t struct_size;
+    const float *prediction;    /* see pred_kind */
+    int32_t pred_kind;          /* IDH_EVAL_PRED_* */
+    int32_t sampling;           /* IDH_EVAL_BILINEAR / IDH_EVAL_NEAREST: how the prediction is upsampled */
+    float sigmoid_multiplier;   /* bd_sigmoid_multiplier (logits only) */
+    float surface_threshold;    /* get_surface_mask's threshold (0.05) */
+    const float *rendered_bphw; /* (B,P,h,w) query planes (cur_data["rendered_depth"]) */
+    const float *depth_b1hw;    /* (B,1,h,w) model-resolution depth (cur_data["depth_b1hw"]); NULL when tag_mask == IDH_EVAL_TAG_ALL */
+    const float *gt_b1HW;       /* (B,1,H,W) full-resolution ground truth */
+    const float *thresholds;    /* logits: T constant thresholds (bins == NULL) or n_bins per-bin thresholds; unused for depth */
+    const float *bins;          /* NULL, or the Thresholder's n_bins (<= 8) sorted bin edges (T must be 1) */
+    int32_t T;                  /* 1..8 */
+    int32_t n_bins;
+    int32_t tag_mask;           /* IDH_EVAL_TAG_* bits */
+    int32_t B, P, h, w, H, W;
+} idh_eval_args;
+
+/* sizeof(idh_eval_args) as compiled into the library. */
+size_t idh_sizeof_eval_args(void);
+/* Bytes of workspace (8-byte aligned) that idh_eval_plane_scores_fwd and idh_eval_depth_metrics_fwd need at most. */
+size_t idh_eval_frame_workspace_bytes(int B, int P, int h, int w, int H, int W, int T);
+/* Surface / boundary masks at model resolution: surface_out, boundary_out (B,P,h,w) 0/1 floats as the reference functions
+ * return them, code_out (B,P,h,w) bit 0 surface, bit 1 boundary.  Any output may be NULL, not all three.  No workspace. */
+int idh_eval_masks_fwd(const float *depth_b1hw, const float *rendered_bphw, int B, int P, int h, int w, float surface_threshold,
+                       float *surface_out, float *boundary_out, unsigned char *code_out, void *stream);
+/* out[b, tag, d, t, {iou, iou_pos, iou_neg}] (B,3,P,T,3) with tag 0 untagged, 1 surface, 2 boundary (families outside tag_mask are
+ * not counted: NaN); counts_out (B,3,P,2+2T) {valid, target, pred[T], inter[T]} or NULL (then they live in the workspace). */
+int idh_eval_plane_scores_fwd(const idh_eval_args *args, float *out, unsigned *counts_out, void *workspace, size_t workspace_bytes,
+                              void *stream);
+/* compute_depth_metrics_batched(gt, upsample(pred_b1hw), gt > valid_above, mult_a): out[b, 12] in the order of idh_depth_metrics_fwd. */
+int idh_eval_depth_metrics_fwd(const float *gt_b1HW, const float *pred_b1hw, int B, int h, int w, int H, int W, int sampling,
+                               float valid_above, int mult_a, float *out_b12, void *workspace, size_t workspace_bytes, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
