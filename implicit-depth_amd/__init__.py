@@ -6,3 +6,13 @@ for this path so they can be swapped into ``BDModel`` / ``DepthModel`` like the 
 own ``to_fast()`` precedent (reference ``test_bd.py:80-81``).
 """
 __version__ = "0.1.0"
+
+_EXPORTS = {"MeshDepthRasterizer": "raster", "load_ply": "raster", "TemporalEvaluator": "evaluation", "temporal_final_metrics": "evaluation"}
+
+
+def __getattr__(name):  # lazily: these modules import torch and bind the library
+    if name in _EXPORTS:
+        import importlib
+
+        return getattr(importlib.import_module("." + _EXPORTS[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -120,6 +120,10 @@ _SIGS = {
     "idh_eval_masks_fwd": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_void_p, C.c_void_p]),
     "idh_eval_plane_scores_fwd": (C.c_int, [C.POINTER(EvalArgs), f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "idh_eval_depth_metrics_fwd": (C.c_int, [f32p, f32p] + [C.c_int] * 6 + [C.c_float, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "idh_raster_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "idh_raster_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_void_p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "idh_vertex_predictions_fwd": (C.c_int, [f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, C.c_void_p]),
+    "idh_vertex_occlusion_changes_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,

@@ -176,3 +176,62 @@ def reg_frame_scores(outputs, cur_data, regression_plane_eval=False, temporal_ev
         out = plane_scores(pred, cur_data["rendered_depth"], gt, cur_data["depth_b1hw"], regressed=True, nearest=temporal_eval)
         return _tag_scores(out, [""], temporal_eval), _keep(gt, 0.0)
     return upsampled_depth_metrics(gt, pred, nearest=temporal_eval, valid_above=0.5, mult_a=True), _keep(gt, 0.5)
+
+
+class TemporalEvaluator:
+    """The reference's ``TemporalEvaluator`` (utils/binary_metrics_utils.py:247-280): over a window of frames, how often the occlusion
+    decision at a ground-truth vertex flips.  The renders and the vertex sampling are ``raster.MeshDepthRasterizer``'s kernels; the
+    flip count of GPU histories is csrc/raster.hip's integer count.  INTEGRATION.md §2e shows the loop of test_bd.py:157-236 with it."""
+
+    def __init__(self):
+        self.rasterizer = None
+        self.total_diffs = 0
+        self.total_verts = 0
+
+    def initialise_new_scene(self, gt_mesh_path=None, height=192, width=256, verts=None, faces=None, device="cuda"):
+        from .raster import MeshDepthRasterizer
+
+        self.rasterizer = MeshDepthRasterizer(height=height, width=width)
+        self.rasterizer.load_gt_mesh(gt_mesh_path, verts=verts, faces=faces, device=device)
+
+    def initialise_new_plane(self, depth_gt_b1hw, world_T_cam_b44):
+        self.rasterizer.create_plane_from_camera(world_T_cam_b44, distance=torch.nanquantile(depth_gt_b1hw, 0.75))
+        self.rasterizer.gt_vertex_predictions = []
+
+    @staticmethod
+    def mask_prediction_edges(prediction, edge_size=4):
+        """In place, as the reference: -1 on the ``edge_size`` border rows and columns (everywhere when the map is too small to
+        have an interior, which is what the reference's mask does)."""
+        H, W = prediction.shape[-2:]
+        if H <= 2 * edge_size or W <= 2 * edge_size:
+            prediction[...] = -1.0
+            return
+        prediction[..., :edge_size, :] = -1.0
+        prediction[..., -edge_size:, :] = -1.0
+        prediction[..., :, :edge_size] = -1.0
+        prediction[..., :, -edge_size:] = -1.0
+
+    def update_vertex_predictions(self, prediction, cam_T_world_b44, K_b44):
+        self.mask_prediction_edges(prediction)
+        self.rasterizer.update_gt_vertex_predictions(prediction, cam_T_world_b44, K_b44)
+
+    def compute_vertex_occlusion_changes(self):
+        predictions = torch.stack(self.rasterizer.gt_vertex_predictions).float()
+        if predictions.is_cuda:
+            from .raster import vertex_occlusion_changes
+
+            diffs = vertex_occlusion_changes(predictions)
+        else:  # host tensors (fixtures, tests): the reference's own statement (:274-279)
+            predictions = predictions.clone()
+            predictions[predictions == -1] = torch.nan
+            predictions[predictions > 0.5] = 1
+            predictions[predictions < 0.5] = 0
+            diffs = float(torch.nansum(torch.abs(predictions[1:] - predictions[:-1]).double()))
+        self.total_diffs += diffs
+        self.total_verts += predictions.shape[1]
+
+
+def temporal_final_metrics(total_diffs, eval_length, warmup, eval_frame_multiplier, n_scans, temporal_d=-1):
+    """The two entries test_bd.py:451-459 adds to the final metrics."""
+    return {f"total_diffs_d_{temporal_d:.1f}": total_diffs,
+            f"temporal_score_d_{temporal_d:.1f}": total_diffs / ((eval_length - warmup) * eval_frame_multiplier * n_scans)}

@@ -1,0 +1,246 @@
+"""Depth-only mesh rasterisation (csrc/raster.hip) with the surface of the reference's ``Pytorch3DRasterizer``
+(utils/binary_metrics_utils.py:283-388), which needs pytorch3d's CUDA kernels.
+
+``MeshDepthRasterizer`` renders the query plane of a ``temporal_eval`` window (test_bd.py:172-181) and the scene's ground-truth mesh
+(:362), and samples a prediction at every projected ground-truth vertex (:360-388).  ``load_ply`` reads the mesh.  Semantics of the render:
+include/idh_raster.h and DESIGN.md §4.8 — pixel (i, j) looks along the ray through (j + 0.5, i + 0.5), the nearest z > 0 wins, -1 where
+nothing is hit, triangles crossing z = 0 are drawn for their part in front of the camera."""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+PLANE_SIZE = 1024      # vertices per side of the query plane (binary_metrics_utils.py:306)
+PLANE_SPACING = 0.025  # metres between them
+DEPTH_TOLERANCE = 0.05  # a vertex is visible when the visibility render is within this of its depth (:381)
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_type(name, path):
+    try:
+        return _PLY_TYPES[name]
+    except KeyError:
+        raise ValueError(f"{path}: unknown PLY property type {name!r}") from None
+
+
+def load_ply(path) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(verts float32 (V,3), faces int64 (F,3)) of an ASCII or binary-little-endian PLY file, as pytorch3d.io.load_ply returns them
+    (binary_metrics_utils.py:299).  Extra vertex properties (ScanNet meshes carry uchar colours), scalar properties beside the face
+    list (e.g. ``uchar flags``) and extra scalar-only elements are skipped; the face list may have any integer count and index type.
+    Triangles only.  Not supported (ValueError): big-endian files, list properties outside the face element, more than one list per face."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []  # elements: [name, count, [(name, type) or (name, count type, index type)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], _ply_type(tok[2], path), _ply_type(tok[3], path)))
+            else:
+                elements[-1][2].append((tok[2], _ply_type(tok[1], path)))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii and binary_little_endian are)")
+    tokens = data[body:].split() if fmt == "ascii" else None
+    at = 0 if fmt == "ascii" else body
+    verts = faces = None
+    for name, count, props in elements:
+        lists = [p for p in props if len(p) == 3]
+        if lists and (name != "face" or len(lists) > 1):
+            raise ValueError(f"{path}: list properties are only supported as the one vertex list of the face element (element {name!r})")
+        # every row has a fixed width once the list is known to hold three indices: a structured dtype / a token matrix reads the block
+        fields, width = [], 0
+        for p in props:
+            if len(p) == 3:
+                fields += [("#n", "<" + p[1]), ("#i", "<" + p[2], (3,))]
+                width += 4
+            else:
+                fields.append((p[0], "<" + p[1]))
+                width += 1
+        if fmt == "ascii":
+            block = tokens[at:at + count * width]
+            at += count * width
+            if lists and count:
+                col = [len(q) == 3 for q in props].index(True)
+                if len(block) != count * width or any(int(t) != 3 for t in block[col::width]):
+                    raise ValueError(f"{path}: only triangle faces are supported")
+            rows = np.array(block, dtype=np.float64).reshape(count, width)
+            cols, j = {}, 0
+            for p in props:
+                if len(p) == 3:
+                    cols["#n"], cols["#i"] = rows[:, j], rows[:, j + 1:j + 4]
+                    j += 4
+                else:
+                    cols[p[0]] = rows[:, j]
+                    j += 1
+        else:
+            dt = np.dtype(fields)
+            if lists and count:
+                off = sum(np.dtype(f[1]).itemsize for f in fields[:[f[0] for f in fields].index("#n")])
+                first = int(np.frombuffer(data, dtype=dt.fields["#n"][0], count=1, offset=at + off)[0]) if at + dt.itemsize <= len(data) else -1
+                if first != 3 or at + count * dt.itemsize > len(data):
+                    raise ValueError(f"{path}: only triangle faces are supported")
+            rows = np.frombuffer(data, dtype=dt, count=count, offset=at)
+            at += count * dt.itemsize
+            cols = {f[0]: rows[f[0]] for f in fields}
+        if name == "vertex":
+            if not all(k in cols for k in "xyz"):
+                raise ValueError(f"{path}: vertex element without x, y, z")
+            verts = np.stack([np.asarray(cols[k], dtype=np.float32) for k in "xyz"], 1)
+        elif name == "face" and lists:
+            if (np.asarray(cols["#n"]) != 3).any():
+                raise ValueError(f"{path}: only triangle faces are supported")
+            faces = np.asarray(cols["#i"]).astype(np.int64).reshape(count, 3)
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    if faces is None:
+        faces = np.zeros((0, 3), np.int64)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError(f"{path}: face index outside the {len(verts)} vertices")
+    return torch.from_numpy(np.ascontiguousarray(verts)), torch.from_numpy(np.ascontiguousarray(faces))
+
+
+def plane_faces(size: int = PLANE_SIZE) -> torch.Tensor:
+    """The (2 (size-1)^2, 3) int64 faces of the size x size vertex grid in the order of the reference's double loop
+    (binary_metrics_utils.py:315-323): for idx = h * size + w, (idx, idx + size + 1, idx + size) then (idx, idx + 1, idx + 1 + size)."""
+    idx = (torch.arange(size - 1).view(-1, 1) * size + torch.arange(size - 1).view(1, -1)).reshape(-1, 1)
+    off = torch.tensor([[0, size + 1, size], [0, 1, size + 1]])
+    return (idx.view(-1, 1, 1) + off.view(1, 2, 3)).reshape(-1, 3)
+
+
+def plane_vertices(world_T_cam_b44: torch.Tensor, distance) -> torch.Tensor:
+    """(size^2, 3) vertices of the plane ``distance`` in front of the camera (binary_metrics_utils.py:306-314, :325), by the same
+    operations: the float32 grid, z scaled by ``distance``, one matmul with the pose."""
+    x = (torch.arange(PLANE_SIZE, dtype=torch.float64) - PLANE_SIZE // 2) * PLANE_SPACING
+    ys, xs = torch.meshgrid(x, x, indexing="ij")  # np.meshgrid(x, x): xs varies along the row
+    one = torch.ones_like(xs)
+    points_14N = torch.stack((xs, ys, one, one), 0).float().view(1, 4, -1).to(world_T_cam_b44.device)
+    points_14N[:, 2] *= distance
+    return torch.matmul(world_T_cam_b44, points_14N)[0, :3].T
+
+
+def _mesh(verts, faces, device=None):
+    v = torch.as_tensor(verts).float()
+    f = torch.as_tensor(faces)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or f.dtype.is_floating_point:
+        raise _lib.IdhError(f"mesh: vertices {tuple(v.shape)} must be (V,3) floats and faces {tuple(f.shape)} (F,3) integers")
+    if device is not None:
+        v, f = v.to(device), f.to(device)
+    return v.contiguous(), f.long().contiguous()
+
+
+def render_depth(verts, faces, cam_T_world_b44, K_b44, height, width) -> torch.Tensor:
+    """(B,1,height,width) depth of the mesh (``verts`` (V,3) float32, ``faces`` (F,3) integer, both on the GPU) in B cameras.  The kernel
+    reads int32 faces: pass them as int32 to render the same mesh repeatedly without a conversion per call (MeshDepthRasterizer does)."""
+    _lib.require_cuda_f32(verts, cam_T_world_b44, K_b44)
+    if cam_T_world_b44.dim() != 3 or tuple(cam_T_world_b44.shape[1:]) != (4, 4) or tuple(K_b44.shape) != tuple(cam_T_world_b44.shape):
+        raise _lib.IdhError(f"render_depth: cam_T_world {tuple(cam_T_world_b44.shape)} and K {tuple(K_b44.shape)} must both be (B,4,4)")
+    if not faces.is_cuda:
+        raise _lib.IdhError("render_depth: faces must be on the GPU; there is no CPU fallback")
+    B, V, F = cam_T_world_b44.shape[0], verts.shape[0], faces.shape[0]
+    f32 = faces.to(torch.int32).contiguous()  # no copy when they already are
+    v, T, K = verts.contiguous(), cam_T_world_b44.contiguous(), K_b44.contiguous()
+    out = torch.empty(B, 1, height, width, device=v.device)
+    nbytes = _lib.lib().idh_raster_workspace_bytes(B, V, F)
+    ws = torch.empty(max(nbytes, 256), device=v.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().idh_raster_depth_fwd(_lib.ptr(v) if V else None, V, _lib.ptr(f32) if F else None, F, T.data_ptr(), K.data_ptr(), B,
+                                               height, width, out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr()), "idh_raster_depth_fwd")
+    return out
+
+
+def vertex_predictions(verts, cam_T_world_b44, K_b44, pred_11hw, depth_11hw, tolerance=DEPTH_TOLERANCE) -> torch.Tensor:
+    """(V,) the prediction sampled at each projected vertex, -1 where the vertex is behind the camera, off the image, hidden
+    (``depth_11hw`` is the mesh's own render) or the prediction is not positive (binary_metrics_utils.py:364-386)."""
+    _lib.require_cuda_f32(verts, cam_T_world_b44, K_b44, pred_11hw, depth_11hw)
+    H, W = depth_11hw.shape[-2:]
+    if pred_11hw.numel() != H * W or depth_11hw.numel() != H * W or cam_T_world_b44.numel() != 16 or K_b44.numel() != 16:
+        raise _lib.IdhError(f"vertex_predictions: one camera and (1,1,H,W) maps (got prediction {tuple(pred_11hw.shape)}, depth "
+                            f"{tuple(depth_11hw.shape)}, cam_T_world {tuple(cam_T_world_b44.shape)})")
+    v, T, K, p, d = (t.contiguous() for t in (verts, cam_T_world_b44, K_b44, pred_11hw, depth_11hw))
+    out = torch.empty(v.shape[0], device=v.device)
+    _lib.check(_lib.lib().idh_vertex_predictions_fwd(v.data_ptr(), v.shape[0], T.data_ptr(), K.data_ptr(), p.data_ptr(), d.data_ptr(), H, W,
+                                                     float(tolerance), out.data_ptr(), _lib.stream_ptr()), "idh_vertex_predictions_fwd")
+    return out
+
+
+def vertex_occlusion_changes(history_tv: torch.Tensor) -> float:
+    """sum over vertices and consecutive frames of |p[t+1] - p[t]| after the reference's quantisation (-1 -> unknown, > 0.5 -> 1,
+    < 0.5 -> 0; binary_metrics_utils.py:273-279), counted on the GPU in integer units of 0.5.  Synchronises (it returns a host number,
+    as the reference does)."""
+    _lib.require_cuda_f32(history_tv)
+    if history_tv.dim() != 2:
+        raise _lib.IdhError(f"vertex_occlusion_changes: history {tuple(history_tv.shape)} must be (T,V)")
+    h = history_tv.contiguous()
+    out = torch.empty(1, device=h.device, dtype=torch.int64)
+    _lib.check(_lib.lib().idh_vertex_occlusion_changes_fwd(h.data_ptr(), h.shape[0], h.shape[1], out.data_ptr(), _lib.stream_ptr()),
+               "idh_vertex_occlusion_changes_fwd")
+    return 0.5 * int(out.item())
+
+
+class MeshDepthRasterizer:
+    """The reference's ``Pytorch3DRasterizer(height, width)``.  ``mesh`` / ``gt_mesh`` are ``(verts (V,3) float32, faces (F,3) int64)``
+    pairs in place of pytorch3d ``Meshes``.  The reference hard-codes 256 / 192 when it normalises the vertices' screen positions
+    (:370-371); the instance's width / height are used here, which is the same at its default size."""
+
+    def __init__(self, height: int = 192, width: int = 256):
+        self.height, self.width = int(height), int(width)
+        self.mesh: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self.faces: Optional[torch.Tensor] = None  # the plane's faces, built once
+        self.gt_mesh: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self.gt_vertex_predictions: List[torch.Tensor] = []
+        self._faces_i32 = self._gt_faces_i32 = None  # the kernel's int32 copies of faces / gt_mesh's faces, made once
+
+    def load_gt_mesh(self, gt_mesh_path=None, verts=None, faces=None, device="cuda"):
+        """The scene's ground-truth mesh from a PLY file (or from ``verts`` / ``faces`` directly)."""
+        if gt_mesh_path is not None:
+            verts, faces = load_ply(gt_mesh_path)
+        self.gt_mesh = _mesh(verts, faces, device)
+        self._gt_faces_i32 = self.gt_mesh[1].to(torch.int32)
+
+    def create_plane_from_camera(self, world_T_cam_b44, distance=2.5):
+        """The query plane: a 1024 x 1024 grid of 2.5 cm cells, fronto-parallel ``distance`` in front of the camera (the reference
+        calls this argument cam_T_world_b44 and passes world_T_cam_b44, test_bd.py:174-176).  On the device of the pose."""
+        vertices = plane_vertices(world_T_cam_b44, distance)
+        if self.faces is None or self.faces.device != vertices.device:
+            self.faces = plane_faces().to(vertices.device)
+            self._faces_i32 = self.faces.to(torch.int32)
+        self.mesh = (vertices.contiguous(), self.faces)
+
+    def __call__(self, cam_T_world_b44, K_b44):
+        if self.mesh is None:
+            raise ValueError("Mesh has not been initialised for rendering!")
+        return self.render_depth(cam_T_world_b44, K_b44)
+
+    def render_depth(self, cam_T_world_b44, K_b44, mesh=None):
+        """(B,1,height,width) depth of ``mesh`` (default: the plane) from the B cameras (binary_metrics_utils.py:336-358)."""
+        verts, faces = self.mesh if mesh is None else mesh
+        if faces is self.faces:
+            faces = self._faces_i32
+        elif self.gt_mesh is not None and faces is self.gt_mesh[1]:
+            faces = self._gt_faces_i32
+        return render_depth(verts, faces, cam_T_world_b44, K_b44, self.height, self.width)
+
+    def update_gt_vertex_predictions(self, pred, cam_T_world_b44, K_b44):
+        """Render the ground-truth mesh for visibility, sample ``pred`` (1,1,height,width) at its visible vertices and append the
+        (V,) result to ``gt_vertex_predictions`` (binary_metrics_utils.py:360-388)."""
+        if self.gt_mesh is None:
+            raise ValueError("The ground-truth mesh has not been loaded!")
+        rendered_depth = self.render_depth(cam_T_world_b44, K_b44, mesh=self.gt_mesh)
+        self.gt_vertex_predictions.append(vertex_predictions(self.gt_mesh[0], cam_T_world_b44, K_b44, pred, rendered_depth))

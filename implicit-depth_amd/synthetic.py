@@ -287,3 +287,126 @@ def eval_frame_case(B: int, P: int, h: int, w: int, H: int, W: int, seed: int = 
     outputs = {"pred_0": f32(logits), "search_depths": f32(search), "depth_pred_s0_b1hw": f32(dpred)}
     cur = {"depth_b1hw": f32(depth), "rendered_depth": f32(rendered), "full_res_depth_b1hw": f32(gt)}
     return outputs, cur
+
+
+# ---- temporal evaluation: meshes, cameras, vertex histories (raster.py, evaluation.TemporalEvaluator) ----------------------
+def pinhole(fx: float, fy: float, cx: float, cy: float) -> torch.Tensor:
+    K = torch.eye(4, dtype=torch.float64)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = fx, fy, cx, cy
+    return K
+
+
+def plane_pose(i: int) -> torch.Tensor:
+    """world_T_cam (1,4,4) float32 of the camera a query plane is created from (pose 0: the world frame)."""
+    T = _rot_y(0.2 * i)
+    T[0, 3], T[1, 3], T[2, 3] = 0.3 * i, -0.1 * i, 0.05 * i
+    return T.float()[None]
+
+
+def vertex_histories(T: int, V: int, seed: int = 0) -> torch.Tensor:
+    """(T,V) stacked per-frame vertex predictions as update_gt_vertex_predictions leaves them: probabilities, -1 where a vertex
+    was not seen, and a share of exact 0.5 / 0 / 1 values."""
+    r = _rng(seed, "vertex_hist")
+    p = r.random((T, V), dtype=np.float32)
+    kind = r.integers(0, 10, (T, V))
+    p[kind == 0] = -1.0
+    p[kind == 1] = 0.5
+    p[kind == 2] = 0.0
+    p[kind == 3] = 1.0
+    return torch.from_numpy(p)
+
+
+def _grid_faces(n: int, m: int, flip_every_other: bool = True) -> np.ndarray:
+    """Two triangles per cell of an (n+1) x (m+1) vertex grid; with ``flip_every_other`` the second of each pair is wound the other way."""
+    idx = (np.arange(n)[:, None] * (m + 1) + np.arange(m)[None, :]).reshape(-1)
+    a, b, c, d = idx, idx + 1, idx + m + 1, idx + m + 2
+    t1 = np.stack([a, d, c], 1)
+    t2 = np.stack([a, d, b] if flip_every_other else [a, b, d], 1)
+    return np.concatenate([t1, t2], 0).astype(np.int64)
+
+
+def raster_scene(height: int, width: int, seed: int = 0, cells: int = 64, K: torch.Tensor | None = None, span_x=(-0.1, 0.85), span_y=(-0.1, 1.1)):
+    """A mesh and two cameras for the rasteriser's tests: a noisy height field of ``cells`` x ``cells`` cells about 2.5 m in front of
+    camera 0 spanning ``span_x`` x ``span_y`` of the image (every second triangle wound the other way), three near-camera triangles spanning large parts of the image, triangles
+    that straddle z = 0, and triangles that must draw nothing (wholly behind, off screen, repeated index, collinear corners).
+    Returns verts (V,3) float32, faces (F,3) int64, cam_T_world (2,4,4) and K (2,4,4) float32."""
+    Km = (intrinsics(width, height) if K is None else K).double()
+    fx, fy, cx, cy = float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
+    r = _rng(seed, "raster_scene")
+    n = cells
+    gy, gx = np.meshgrid(np.linspace(*span_y, n + 1), np.linspace(*span_x, n + 1), indexing="ij")  # in image widths / heights; the default leaves the right partly empty
+    z = 2.5 + 0.3 * smooth_field((n + 1, n + 1), seed, "raster_relief") + 0.02 * r.standard_normal((n + 1, n + 1))
+    jit = 0.2 / n * (r.random((2, n + 1, n + 1)) - 0.5)
+    x = ((gx + jit[0]) * width - cx) / fx * z
+    y = ((gy + jit[1]) * height - cy) / fy * z
+    field = np.stack([x, y, z], -1).reshape(-1, 3)
+    faces = [_grid_faces(n, n)]
+    extra, ef = [], []
+
+    def tri(p, q, s):
+        base = len(field) + len(extra)
+        extra.extend([p, q, s])
+        ef.append([base, base + 1, base + 2])
+
+    ray = lambda u, v, zz: [(u * width - cx) / fx * zz, (v * height - cy) / fy * zz, zz]
+    # near-camera triangles over large parts of the image
+    tri(ray(-0.2, 0.03, 0.7), ray(0.93, 0.11, 0.9), ray(0.41, 0.62, 0.6))
+    tri(ray(0.07, 0.97, 0.8), ray(0.52, 0.35, 1.0), ray(1.3, 1.1, 0.75))
+    tri(ray(0.61, 0.04, 1.1), ray(0.97, 0.83, 0.65), ray(0.78, 0.9, 0.95))
+    # straddling z = 0: one corner behind, two corners behind
+    tri(ray(0.13, 0.71, 1.4), ray(0.37, 0.93, 1.2), [0.3, 0.2, -0.6])
+    tri(ray(0.88, 0.21, 1.3), [-0.4, 0.1, -0.3], [0.5, -0.6, -0.8])
+    tri([0.9, -0.7, 0.4], [1.2, 0.9, -0.2], ray(0.66, 0.47, 1.6))
+    # nothing to draw: wholly behind, off screen, collinear corners
+    tri([0.1, 0.1, -1.0], [0.5, 0.2, -2.0], [-0.3, 0.6, -1.5])
+    tri(ray(-2.0, 0.2, 2.0), ray(-1.5, 0.8, 2.0), ray(-1.2, 0.1, 2.2))
+    tri([0.0, 0.0, 1.0], [0.1, 0.1, 1.1], [0.2, 0.2, 1.2])
+    ef.append([5, 5, 9])  # repeated index
+    verts = np.concatenate([field, np.asarray(extra, dtype=np.float64)], 0)
+    faces = np.concatenate(faces + [np.asarray(ef, dtype=np.int64)], 0)
+    cam1 = _rot_y(0.15)
+    cam1[0, 3], cam1[1, 3], cam1[2, 3] = 0.2, -0.05, 0.1
+    cams = torch.stack([torch.eye(4, dtype=torch.float64), torch.linalg.inv(cam1)]).float()
+    return (torch.from_numpy(verts.astype(np.float32)), torch.from_numpy(faces), cams, Km.float().expand(2, 4, 4).contiguous())
+
+
+def track_trajectory(T: int = 6):
+    """cam_T_world (T,1,4,4) float32 of a camera that drifts and pans through a ``raster_scene``."""
+    out = []
+    for t in range(T):
+        w = _rot_y(0.02 * t)
+        w[0, 3], w[2, 3] = 0.03 * t, 0.01 * t
+        out.append(torch.linalg.inv(w).float()[None])
+    return torch.stack(out)
+
+
+def track_predictions(T: int, height: int, width: int, seed: int = 0) -> torch.Tensor:
+    """(T,1,1,height,width) float32 predictions in (0,1): a smooth function of pixel and frame whose 0.5 level set moves."""
+    a = smooth_field((1, 1, height, width), seed, "track_a")
+    b = smooth_field((1, 1, height, width), seed, "track_b")
+    frames = [0.5 + 0.45 * np.tanh(1.5 * (np.cos(0.9 * t) * a + np.sin(0.9 * t) * b)) for t in range(T)]
+    return torch.from_numpy(np.stack(frames).astype(np.float32))
+
+
+def static_vertex_scene(height: int, width: int, step: int = 4):
+    """A scene whose vertex sampling has no borderline case: a two-triangle tilted wall that fills the image of a camera at the world
+    origin, and unreferenced vertices on the rays of every ``step``-th pixel centre, placed on the wall, 3 cm and 20 cm behind it and
+    20 cm in front of it in turn.  Returns verts, faces, cam_T_world (1,4,4), K (1,4,4)."""
+    Km = intrinsics(width, height)
+    fx, fy, cx, cy = float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
+    wall = lambda dx, dy: 2.0 / (1.0 - 0.1 * dx + 0.05 * dy)  # z of the plane z = 2 + 0.1 x - 0.05 y along the ray (dx, dy, 1)
+    corners = []
+    for u, v in ((-7.3, -5.7), (width + 9.1, -6.4), (width + 8.2, height + 7.9), (-6.6, height + 5.3)):
+        dx, dy = (u - cx) / fx, (v - cy) / fy
+        zz = wall(dx, dy)
+        corners.append([dx * zz, dy * zz, zz])
+    pts, k = [], 0
+    for i in range(step // 2, height, step):
+        for j in range(step // 2, width, step):
+            dx, dy = (j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy
+            zz = wall(dx, dy) + (0.0, 0.03, 0.2, -0.2)[k % 4]
+            pts.append([dx * zz, dy * zz, zz])
+            k += 1
+    verts = torch.tensor(corners + pts, dtype=torch.float64).float()
+    faces = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int64)
+    return verts, faces, torch.eye(4)[None], Km.float()[None]

@@ -1,0 +1,75 @@
+/*
+ * idh_raster.h — depth-only mesh rasterisation and the vertex bookkeeping of the temporal evaluation (added without an ABI version change: nothing existing moved).
+ *
+ * Under --temporal_eval the reference (test_bd.py:109-116, 157-183, 214-236; utils/binary_metrics_utils.py:247-388) renders a
+ * 1024 x 1024-vertex plane and the scene's ground-truth mesh into every frame with pytorch3d's CUDA rasteriser, samples the
+ * prediction at every projected ground-truth vertex and counts how often a vertex's occlusion decision flips between frames.
+ * The three *_fwd entry points replace those three steps (idh_raster_workspace_bytes sizes the first one's workspace):
+ *
+ *   idh_raster_depth_fwd                 Pytorch3DRasterizer.render_depth                 binary_metrics_utils.py:336-358
+ *   idh_vertex_predictions_fwd           Pytorch3DRasterizer.update_gt_vertex_predictions binary_metrics_utils.py:360-388 (after its render)
+ *   idh_vertex_occlusion_changes_fwd     TemporalEvaluator.compute_vertex_occlusion_changes binary_metrics_utils.py:273-280
+ *
+ * Rasterisation semantics
+ *   - camera point X_c = R X_w + t from cam_T_world; OpenCV intrinsics fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2];
+ *   - pixel (row i, col j) samples the ray through image point (u, v) = (j + 0.5, i + 0.5): direction ((u - cx) / fx, (v - cy) / fy, 1)
+ *     (pytorch3d's convention behind cameras_from_opencv_projection: pixel centres at half-integers of the screen);
+ *   - the output is the smallest camera-space z > 0 over all triangles the ray hits (faces_per_pixel = 1, blur_radius = 0,
+ *     perspective-correct: the ray / triangle intersection depth), both windings, -1 where nothing is hit;
+ *   - the ray test runs in camera space, so a triangle that straddles z = 0 is drawn correctly for its z > 0 part (pytorch3d does not
+ *     clip such triangles; geometric correctness is the definition chosen here); triangles wholly at z <= 0 are skipped;
+ *   - an edge shared by two triangles is evaluated from its lower-numbered vertex in both, so the two see exactly negated values and
+ *     a pixel centre on the edge is covered by at least one of them (>= 0 is inside);
+ *   - zero-area triangles, faces with an index outside [0, V) and non-finite vertices contribute nothing.
+ * The z-buffer is resolved with a 32-bit unsigned atomic minimum on the float's bit pattern: the result does not depend on the order
+ * in which triangles arrive and is bit-reproducible from run to run.
+ *
+ * Conventions of include/idh.h: device pointers, dense fp32 (faces int32), caller-owned outputs and workspace, `stream` a hipStream_t,
+ * asynchronous, IDH_OK or a negative IDH_E* code.  Arguments are validated on the host before anything is launched.
+ */
+#ifndef IDH_RASTER_H_
+#define IDH_RASTER_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "idh.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+#if defined(__GNUC__) || defined(__clang__)
+#pragma GCC visibility push(default)
+#endif
+
+/* Bytes of workspace (256-byte aligned) idh_raster_depth_fwd needs for V vertices and F faces in B cameras: the camera-space and
+ * screen-space vertices (24 B per vertex and camera) and the queue of large triangles (4 B per face and camera).  0 for bad arguments. */
+size_t idh_raster_workspace_bytes(int B, int V, int F);
+
+/* verts_v3 (V,3) fp32 world space; faces_f3 (F,3) int32 (may be NULL when F == 0: every pixel is then -1);
+ * cam_T_world_b44, K_b44 (B,4,4) row-major; out_b1hw (B,1,H,W) also serves as the z-buffer.
+ * IDH_EINVAL: null pointer, B < 0, V < 0, F < 0, H <= 0, W <= 0, H * W >= 2^31; IDH_EWORKSPACE: workspace null, misaligned or short;
+ * IDH_EUNSUPPORTED: B > 65535 or B * H * W >= 2^31. */
+int idh_raster_depth_fwd(const float *verts_v3, int V, const int32_t *faces_f3, int F, const float *cam_T_world_b44,
+                         const float *K_b44, int B, int H, int W, float *out_b1hw, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+/* Per vertex: camera-space z and screen position (x_s, y_s) = (fx x / z + cx, fy y / z + cy); the nearest sample
+ * (grid_sample(mode="nearest", align_corners=False, zero padding): column nearbyint(x_s - 0.5), row nearbyint(y_s - 0.5), 0 outside)
+ * of pred_11hw and of the visibility render depth_11hw (both (1,1,H,W)); valid = depth_s > 0 && z > 0 && |z - depth_s| < depth_tolerance
+ * && pred_s > 0 (the reference's 0.05); out_v[v] = pred_s where valid, else -1.  One camera (4,4), as the reference's batch of 1. */
+int idh_vertex_predictions_fwd(const float *verts_v3, int V, const float *cam_T_world_44, const float *K_44, const float *pred_11hw,
+                               const float *depth_11hw, int H, int W, float depth_tolerance, float *out_v, void *stream);
+
+/* hist_tv (T,V): the stacked per-frame vertex predictions.  -1 and NaN are "unknown", > 0.5 -> 1, < 0.5 -> 0, exactly 0.5 stays 0.5;
+ * *half_units_out (one int64 on the device) = 2 * sum over t, v of |p[t+1,v] - p[t,v]| ignoring pairs with an unknown: the flips
+ * counted exactly in units of 0.5.  T < 2 or V == 0 gives 0. */
+int idh_vertex_occlusion_changes_fwd(const float *hist_tv, int T, int V, long long *half_units_out, void *stream);
+
+#if defined(__GNUC__) || defined(__clang__)
+#pragma GCC visibility pop
+#endif
+#ifdef __cplusplus
+}
+#endif
+#endif /* IDH_RASTER_H_ */
