@@ -59,6 +59,23 @@ EVAL_BILINEAR, EVAL_NEAREST = 0, 1  # IDH_EVAL_BILINEAR / IDH_EVAL_NEAREST
 EVAL_TAG_ALL, EVAL_TAG_SURFACE, EVAL_TAG_BOUNDARY = 1, 2, 4  # IDH_EVAL_TAG_*
 
 
+class CompositeArgs(C.Structure):
+    """ctypes mirror of ``idh_composite_args`` (include/idh_composite.h, AR compositing)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("image_bHW3", C.c_void_p), ("virtual_rgba_bHW4", C.c_void_p), ("map_b1hw", C.c_void_p),
+                ("virtual_depth_bHW", C.c_void_p), ("fade_b", C.c_void_p), ("out_bHW3", C.c_void_p), ("matte_out_bHW", C.c_void_p),
+                ("plane_distance", C.c_double), ("colour", C.c_double * 3), ("sigmoid_multiplier", C.c_float), ("mode", C.c_int32),
+                ("has_colour", C.c_int32), ("has_plane", C.c_int32), ("bgr", C.c_int32), ("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(CompositeArgs)
+
+
+COMPOSITE_MASK_LOGITS, COMPOSITE_MASK_PROB, COMPOSITE_DEPTH_SOFT, COMPOSITE_DEPTH_HARD = 0, 1, 2, 3  # IDH_COMPOSITE_*
+
+
 _SIGS = {
     "idh_version": (C.c_int, []),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
@@ -124,6 +141,9 @@ _SIGS = {
     "idh_raster_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_void_p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "idh_vertex_predictions_fwd": (C.c_int, [f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, C.c_void_p]),
     "idh_vertex_occlusion_changes_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "idh_sizeof_composite_args": (C.c_size_t, []),
+    "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
+    "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -163,6 +183,8 @@ def lib():
             raise IdhError(f"{LIB_PATH} reports ABI version {ver}, this binding needs >= {MIN_ABI_VERSION}: rebuild with `python implicit-depth_amd/build.py --force`")
         if h.idh_sizeof_eval_args() != C.sizeof(EvalArgs):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_eval_args) = {h.idh_sizeof_eval_args()} in the library, {C.sizeof(EvalArgs)} in this binding")
+        if h.idh_sizeof_composite_args() != C.sizeof(CompositeArgs):
+            raise IdhError(f"{LIB_PATH}: sizeof(idh_composite_args) = {h.idh_sizeof_composite_args()} in the library, {C.sizeof(CompositeArgs)} in this binding")
         if h.idh_sizeof_volume_opts() != C.sizeof(VolumeOpts):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_volume_opts) = {h.idh_sizeof_volume_opts()} in the library, {C.sizeof(VolumeOpts)} in this binding")
         _lib = h

@@ -289,6 +289,46 @@ def eval_frame_case(B: int, P: int, h: int, w: int, H: int, W: int, seed: int = 
     return outputs, cur
 
 
+def composite_case(B: int, h: int, w: int, H: int, W: int, seed: int = 0, render_hw: Tuple[int, int] | None = None):
+    """Inputs of the AR compositing path (reference inference/inference.py:117-128, inference/composite.py:75-143) for B frames with a
+    (h, w) model map and a (H, W) camera image.  Basic float64 arithmetic and PCG64 integers, cast once: identical on every host.
+      image          uint8 (B,H,W,3) camera image
+      rgba           uint8 (B,H,W,4) render of the asset: alpha exactly 0, exactly 255 and mixed regions
+      logits         float32 (B,1,h,w) smooth occlusion logits with saturated patches (+-40)
+      prob           float32 (B,1,h,w) occlusion probabilities clip(0.5 + 0.2 * logits, 0, 1): no transcendental, the same bits everywhere
+      depth          float32 (B,1,h,w) regressed depth around the asset's
+      virtual_depth  float32 (B,H,W) depth of the render, 0 where alpha is 0 (no asset)
+      render         float32 (B,1,Hr,Wr) full-resolution asset depth for the preparation step (Hr, Wr = render_hw, default (2h+2, 2w+6)):
+                     0 = no asset, with holes on every border and corner, isolated one-pixel holes and one 9 x 11 hole whose centre
+                     stays 0 after the 7x7 fill."""
+    u8 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    image = _rng(seed, "comp_image").integers(0, 256, size=(B, H, W, 3))
+    alpha = np.clip(np.floor(255.0 * (0.5 + 0.9 * smooth_field((B, H, W), seed, "comp_alpha", cells=(3, 4))) + 0.5), 0, 255)
+    alpha[:, : max(H // 6, 1), : max(W // 5, 1)] = 0
+    alpha[:, H // 2: H // 2 + max(H // 6, 1), W // 2: W // 2 + max(W // 5, 1)] = 255
+    rgba = np.concatenate([_rng(seed, "comp_rgb").integers(0, 256, size=(B, H, W, 3)), alpha[..., None]], -1)
+    # moderate amplitude: outside the two patches sigmoid(2.5 * logit) stays away from exactly 0 and 1, where a blend lands on an integer
+    logits = 1.2 * smooth_field((B, 1, h, w), seed, "comp_logits", cells=(4, 5)) + 0.3 * _rng(seed, "comp_logits_noise").standard_normal((B, 1, h, w))
+    ph, pw = max(h // 8, 1), max(w // 10, 1)
+    logits[:, :, h // 3: h // 3 + ph, w // 4: w // 4 + pw] = 40.0
+    logits[:, :, 2 * h // 3: 2 * h // 3 + ph, 2 * w // 3: 2 * w // 3 + pw] = -40.0
+    vdepth = 2.0 + 0.5 * smooth_field((B, H, W), seed, "comp_vdepth", cells=(3, 4))
+    vdepth[alpha == 0] = 0.0
+    depth = np.maximum(2.0 + 0.6 * smooth_field((B, 1, h, w), seed, "comp_depth", cells=(4, 5)) + 0.03 * _rng(seed, "comp_depth_noise").standard_normal((B, 1, h, w)), 0.25)
+    Hr, Wr = render_hw if render_hw is not None else (2 * h + 2, 2 * w + 6)
+    render = 1.5 + 0.5 * smooth_field((B, 1, Hr, Wr), seed, "comp_render", cells=(3, 4)) + 0.01 * _rng(seed, "comp_render_noise").standard_normal((B, 1, Hr, Wr))
+    render[smooth_field((B, 1, Hr, Wr), seed, "comp_render_holes", cells=(3, 4)) > 0.9] = 0.0
+    render[..., :2, :3] = render[..., :3, -2:] = render[..., -2:, :2] = render[..., -3:, -3:] = 0.0  # corners
+    render[..., 0, Wr // 2: Wr // 2 + 4] = render[..., -1, Wr // 3: Wr // 3 + 2] = 0.0  # top / bottom border
+    render[..., Hr // 2: Hr // 2 + 3, 0] = render[..., Hr // 3: Hr // 3 + 2, -1] = 0.0  # left / right border
+    ys, xs = _rng(seed, "comp_render_dots").integers(0, Hr, size=12), _rng(seed, "comp_render_dots_x").integers(0, Wr, size=12)
+    render[..., ys, xs] = 0.0  # isolated pixels
+    y0, x0 = (Hr - 9) // 2, (Wr - 11) // 2
+    render[..., y0: y0 + 9, x0: x0 + 11] = 0.0  # larger than the 7x7 window: the centre stays 0
+    return {"image": u8(image), "rgba": u8(rgba), "logits": f32(logits), "prob": f32(np.clip(0.5 + 0.2 * logits, 0.0, 1.0)), "depth": f32(depth), "virtual_depth": f32(vdepth), "render": f32(render)}
+
+
 # ---- temporal evaluation: meshes, cameras, vertex histories (raster.py, evaluation.TemporalEvaluator) ----------------------
 def pinhole(fx: float, fy: float, cx: float, cy: float) -> torch.Tensor:
     K = torch.eye(4, dtype=torch.float64)
