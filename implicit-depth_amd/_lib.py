@@ -76,6 +76,35 @@ class CompositeArgs(C.Structure):
 COMPOSITE_MASK_LOGITS, COMPOSITE_MASK_PROB, COMPOSITE_DEPTH_SOFT, COMPOSITE_DEPTH_HARD = 0, 1, 2, 3  # IDH_COMPOSITE_*
 
 
+class IngestColorArgs(C.Structure):
+    """ctypes mirror of ``idh_ingest_color_args`` (include/idh_ingest.h, frame ingest)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("frames_bHW3", C.c_void_p), ("x_bounds", C.c_void_p), ("x_taps", C.c_void_p), ("y_bounds", C.c_void_p),
+                ("y_taps", C.c_void_p), ("image_b3hw", C.c_void_p), ("resized_bhw3", C.c_void_p), ("filter", C.c_int32), ("normalize", C.c_int32),
+                ("B", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(IngestColorArgs)
+
+
+class IngestDepthArgs(C.Structure):
+    """ctypes mirror of ``idh_ingest_depth_args`` (include/idh_ingest.h)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_bHW", C.c_void_p), ("depth_b1hw", C.c_void_p), ("mask_b1hw", C.c_void_p),
+                ("mask_b_b1hw", C.c_void_p), ("full_depth_b1HW", C.c_void_p), ("full_mask_b1HW", C.c_void_p), ("full_mask_b_b1HW", C.c_void_p),
+                ("value_scale", C.c_float), ("min_valid", C.c_float), ("max_valid", C.c_float), ("B", C.c_int32), ("Hs", C.c_int32),
+                ("Ws", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(IngestDepthArgs)
+
+
+RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
+INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
+
+
 _SIGS = {
     "idh_version": (C.c_int, []),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
@@ -144,6 +173,12 @@ _SIGS = {
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
+    "idh_resize_coeffs_sizes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "idh_resize_coeffs_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "idh_sizeof_ingest_color_args": (C.c_size_t, []),
+    "idh_sizeof_ingest_depth_args": (C.c_size_t, []),
+    "idh_ingest_color_fwd": (C.c_int, [C.POINTER(IngestColorArgs), C.c_void_p]),
+    "idh_ingest_depth_fwd": (C.c_int, [C.POINTER(IngestDepthArgs), C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -185,6 +220,10 @@ def lib():
             raise IdhError(f"{LIB_PATH}: sizeof(idh_eval_args) = {h.idh_sizeof_eval_args()} in the library, {C.sizeof(EvalArgs)} in this binding")
         if h.idh_sizeof_composite_args() != C.sizeof(CompositeArgs):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_composite_args) = {h.idh_sizeof_composite_args()} in the library, {C.sizeof(CompositeArgs)} in this binding")
+        for what, got, mirror in (("idh_ingest_color_args", h.idh_sizeof_ingest_color_args(), IngestColorArgs),
+                                  ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs)):
+            if got != C.sizeof(mirror):
+                raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         if h.idh_sizeof_volume_opts() != C.sizeof(VolumeOpts):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_volume_opts) = {h.idh_sizeof_volume_opts()} in the library, {C.sizeof(VolumeOpts)} in this binding")
         _lib = h
