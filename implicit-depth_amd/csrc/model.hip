@@ -164,6 +164,7 @@ void stage_of(const idh_model_desc *d, int B, const idh_model_inputs *in, float 
     cs = ConvStage{};
     cs.enc = n->cv_blocks; cs.n_enc = 4; cs.dec = n->dec_blocks;
     cs.heads = d->kind == IDH_MODEL_DEPTH ? n->depth_heads : nullptr;
+    cs.scales = d->kind == IDH_MODEL_DEPTH ? IDH_SCALES_ALL : 0x1;  // the occlusion MLP reads scale 0 only; the 1x1 depth heads are outputs at all four
     cs.N = B; cs.H = d->H; cs.W = d->W; cs.D = d->D;
     int h = d->H, w = d->W;
     for (int i = 0; i < 4; ++i) {  // level i + 1 = CVEncoder level i's output size

@@ -19,6 +19,7 @@ struct ConvStage {
     int n_enc;                    // levels
     const idh_block_params *dec;  // IDH_UNETPP_BLOCKS decoder blocks (idh_unetpp_fwd order)
     const idh_conv_params *heads; // NULL (BDDecoderPP) or the four 1x1 heads (DepthDecoderPP)
+    unsigned scales;              // bit i: the decoder's output_i result is read (idh_unetpp_fwd_ex); IDH_SCALES_ALL with heads
     int N, H, W, D;               // the volume: (N, H, W, D) NHWC, written by the caller into cv_in before the ops run
     idh_tensor img[5];            // the image-encoder pyramid, IDH_LAYOUT_NCHW (level 0 feeds the decoder, 1..4 the CVEncoder)
     float *const *log_depth;      // heads: 4 dense (N,1,Hi,Wi) outputs (STAGE_RUN)

@@ -116,6 +116,7 @@ class Plan {
     // Dense NHWC buffer of the plan (Plan.buffer): channel counts that are not a multiple of 16 get zero padding channels
     View buffer(int n, int h, int w, int c) {
         const int cs_ = ceil16(c);
+        if (dry_) return phantom(n, h, w, c, cs_);
         if (cs_ == c) {
             auto it = free_.find(std::make_tuple(n, h, w, cs_));
             if (it != free_.end() && !it->second.empty()) {
@@ -129,6 +130,14 @@ class Plan {
         b.N = n; b.H = h; b.W = w; b.cs = cs_; b.internal = true; b.zero_fill = cs_ != c;
         b.floats = (size_t)n * h * w * cs_;
         b.base = ws_alloc(b.floats);
+        bufs.push_back(b);
+        return View{(int)bufs.size() - 1, 0, c};
+    }
+    // A view with a shape and no memory, for reserve_block: the kernel-family predicates see the dimensions, nothing is allocated or pooled
+    View phantom(int n, int h, int w, int c, int cs_) {
+        Buf b{};
+        b.N = n; b.H = h; b.W = w; b.cs = cs_; b.internal = false; b.zero_fill = false;
+        b.base = reinterpret_cast<float *>((uintptr_t(7) << 32) + ((uintptr_t)bufs.size() << 24));
         bufs.push_back(b);
         return View{(int)bufs.size() - 1, 0, c};
     }
@@ -290,8 +299,8 @@ class Plan {
         op.act = act; op.slope = slope;
         const long long M = (long long)n * Ho * Wo;
         int tm, tn, split;
-        if (use_wino4) { tm = kTileWino4; tn = 0; split = 1; ++n_wino4; }
-        else if (use_wino) { tm = kTileWino; tn = 0; split = 1; ++n_wino2; }
+        if (use_wino4) { tm = kTileWino4; tn = 0; split = 1; n_wino4 += !dry_; }
+        else if (use_wino) { tm = kTileWino; tn = 0; split = 1; n_wino2 += !dry_; }
         else if (lds_eligible(srcs, cout, Wo, pad_mode)) {
             double ch = 0;
             for (const Src &s : srcs) ch += (ceil16(s.v.C) / 16) * (s.cv->ks == 3 ? 1.0 : kProjChunkWeight);
@@ -314,6 +323,7 @@ class Plan {
             if ((tm != 8 && tm != 9) || tn != 1 || x2) { err = IDH_EINVAL; return out; }
             op.src[0].norm = norm->stats; op.src[0].norm_act = norm->act; op.src[0].norm_slope = norm->slope;
         }
+        if (dry_) return out;  // (reserve_block: the blob slots are taken, in the layout this conv's kernel reads; no op, no workspace)
         if (split > 1) op.ws = ws_alloc((size_t)split * M * ceil16(cout));
         ops.push_back(op);
         Meta m;
@@ -460,6 +470,21 @@ class Plan {
         return out;
     }
 
+    // The blob slots of a BasicBlock that this pass does not run (a decoder scale the caller does not read): the same packed() / bias_of()
+    // calls, with the same kernel selection, as basic_block(x, blk) would make - MODE_PACK fills them, so a blob serves every scale mask -
+    // and nothing else: no op, no buffer, no workspace.  out_cs: the pixel stride of the caller's NHWC output tensor (0: a plan buffer).
+    void reserve_block(const View &x, const idh_block_params &blk, int out_cs) {
+        dry_ = true;
+        if (out_cs) {
+            const int st = blk.conv1.stride == 2 ? 2 : 1;
+            const View o = phantom(N(x), (H(x) + 2 - 3) / st + 1, (W(x) + 2 - 3) / st + 1, blk.conv1.cout, out_cs);
+            basic_block(x, blk, &o);
+        } else {
+            basic_block(x, blk);
+        }
+        dry_ = false;
+    }
+
     // ---- Plan.schedule: dependency levels, launch order inside a level, group ids ----------------------------------------------------------
     static bool overlap(const std::vector<Region> &a, const std::vector<Region> &b) {
         for (const Region &x : a)
@@ -531,6 +556,7 @@ class Plan {
     size_t ws_cap_;
     float *blob_;
     hipStream_t st_;
+    bool dry_ = false;  // reserve_block
     std::map<std::tuple<int, int, int, int>, std::vector<int>> free_;
 };
 
@@ -656,11 +682,17 @@ int build_cvencoder(Plan &p, const idh_block_params *blocks, int num_blocks, int
 }
 
 // BDDecoderPP / DepthDecoderPP.forward (networks.py:64-84, 163-183) over the five input views; *feat0 (optional): the top-left result
+// scales (nhwc.build_decoder): bit i = the caller reads the output_i result.  A scale without its bit gets no output_i block - the grid node
+// X(i, 4-i) under it is built either way, the next column reads it.  keep_slots: such a block still takes its blob slots (reserve_block), so
+// that the blob layout, weight_floats and a packed blob do not depend on the mask.
 int unetpp_body(Plan &p, const idh_block_params *blocks, const idh_conv_params *heads, int N, std::vector<View> prev, const idh_tensor *fouts,
-                float *const *log_depth, float *const *depth, View *feat0) {
+                float *const *log_depth, float *const *depth, View *feat0, unsigned scales = IDH_SCALES_ALL, bool keep_slots = false) {
     const bool run = p.mode() == MODE_RUN;
+    if ((scales & ~(unsigned)IDH_SCALES_ALL) || (heads && scales != IDH_SCALES_ALL)) return IDH_EINVAL;  // (the 1x1 heads are outputs at every scale)
     const idh_block_params *out_blk[4] = {nullptr, &blocks[46], &blocks[47], &blocks[48]};
-    auto want = [&](int i) { return fouts && fouts[i].C > 0; };  // (C == 0 skips a level; decided by the shape alone so that sizes / pack / fwd agree)
+    auto sel = [&](int i) { return ((scales >> i) & 1u) != 0; };
+    auto given = [&](int i) { return fouts && fouts[i].C > 0; };  // (C == 0 skips a level; decided by the shape alone so that sizes / pack / fwd agree)
+    auto want = [&](int i) { return given(i) && sel(i); };
     std::vector<View> outputs;
     View final_v[4];
     int bi = 0;
@@ -677,6 +709,9 @@ int unetpp_body(Plan &p, const idh_block_params *blocks, const idh_conv_params *
             p.basic_block(xi, right, &s0);
             const View lo = p.basic_block(prev[i + 1], diag);
             if (p.H(lo) * 2 != p.H(xi) || p.W(lo) * 2 != p.W(xi)) return IDH_EINVAL;
+            // (liveness reuse) prev[i + 1] is X(i+1, 4-(i+1)), the last node of its row: up_conv and the output head read it in the column
+            // before, this diag_conv was its last reader
+            if (j > 1 && !has_up) p.release(prev[i + 1]);
             p.upsample2(lo, Plan::slice(cat, cout, cout));
             p.release(lo);  // (liveness reuse: the half-resolution map has no reader after its upsampling)
             if (has_up) {
@@ -704,7 +739,9 @@ int unetpp_body(Plan &p, const idh_block_params *blocks, const idh_conv_params *
             outputs.push_back(y);
             if (last) {  // the only (i, j) whose output_i result survives in the reference's dict
                 if (i == 0) final_v[0] = y;
-                else if (want(i)) {
+                else if (!sel(i)) {
+                    if (keep_slots && given(i)) p.reserve_block(y, *out_blk[i], fouts[i].layout == IDH_LAYOUT_NHWC ? fouts[i].cs : 0);
+                } else if (want(i)) {
                     if (!tensor_ok(&fouts[i], run) || fouts[i].C != out_blk[i]->conv1.cout) return IDH_EINVAL;
                     const View o = output_view(p, fouts[i], N);
                     final_v[i] = p.basic_block(y, *out_blk[i], &o);
@@ -728,7 +765,7 @@ int unetpp_body(Plan &p, const idh_block_params *blocks, const idh_conv_params *
 }
 
 int build_unetpp(Plan &p, const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
-                 const idh_tensor *fouts, float *const *log_depth, float *const *depth) {
+                 const idh_tensor *fouts, float *const *log_depth, float *const *depth, unsigned scales = IDH_SCALES_ALL) {
     const bool run = p.mode() == MODE_RUN;
     if (!blocks || n_blocks != IDH_UNETPP_BLOCKS || N <= 0 || !feats) return IDH_EINVAL;
     std::vector<View> prev;
@@ -737,7 +774,7 @@ int build_unetpp(Plan &p, const idh_block_params *blocks, int n_blocks, const id
         if (i && (feats[i].H * 2 != feats[i - 1].H || feats[i].W * 2 != feats[i - 1].W)) return IDH_EINVAL;  // pyramid levels differ by exactly x2
         prev.push_back(input_view(p, feats[i], N));
     }
-    return unetpp_body(p, blocks, heads, N, prev, fouts, log_depth, depth, nullptr);
+    return unetpp_body(p, blocks, heads, N, prev, fouts, log_depth, depth, nullptr, scales, true);
 }
 
 // FNV-1a over what decides a pass's arithmetic and memory layout: each op's kind, shapes and kernel choice
@@ -815,7 +852,7 @@ int idh_internal::conv_stage(int mode, ConvStage *s, float *ws, size_t ws_cap, f
     for (int i = 1; i < 5; ++i)
         if (p.H(levels[i]) * 2 != p.H(levels[i - 1]) || p.W(levels[i]) * 2 != p.W(levels[i - 1])) return IDH_EINVAL;
     View f0;
-    rc = unetpp_body(p, s->dec, s->heads, s->N, levels, nullptr, s->log_depth, s->depth, &f0);
+    rc = unetpp_body(p, s->dec, s->heads, s->N, levels, nullptr, s->log_depth, s->depth, &f0, s->scales);
     if (rc != IDH_OK) return rc;
     s->cv_in = p.ptr(cv_in);
     s->cv_cs = p.cs(cv_in);
@@ -898,6 +935,31 @@ extern "C" int idh_unetpp_fwd(const idh_block_params *blocks, int n_blocks, cons
     Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
     const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs);
     return rc != IDH_OK ? rc : p.finish(nullptr);
+}
+
+extern "C" int idh_unetpp_sizes_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
+                                   const idh_tensor *feature_outs, uint32_t scales, idh_net_sizes *sizes) {
+    if (!sizes) return IDH_EINVAL;
+    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
+    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales);
+    return rc != IDH_OK ? rc : p.finish(sizes);
+}
+extern "C" int idh_unetpp_pack_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
+                                  const idh_tensor *feature_outs, uint32_t scales, float *blob, void *stream) {
+    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
+    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
+    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales);
+    return rc != IDH_OK ? rc : p.err;
+}
+extern "C" int idh_unetpp_fwd_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, const float *blob, size_t weight_floats,
+                                 int N, const idh_tensor *feats, const idh_tensor *feature_outs, uint32_t scales, float *const *log_depth_outs,
+                                 float *const *depth_outs, float *ws, size_t ws_floats, void *stream) {
+    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
+    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
+    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs, scales);
+    if (rc != IDH_OK) return rc;
+    if (weight_floats != p.blob_off) return IDH_EINVAL;  // a blob sized for another (N, shapes, feature_outs): never read
+    return p.finish(nullptr);
 }
 
 extern "C" int idh_matching_stem_sizes(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, idh_net_sizes *sizes) {

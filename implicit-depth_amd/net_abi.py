@@ -18,6 +18,7 @@ from . import _lib
 
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
 UNETPP_BLOCKS = 49
+SCALES_ALL = 0xF  # IDH_SCALES_ALL
 
 
 class Tensor(C.Structure):
@@ -142,6 +143,9 @@ def _sigs():
         "idh_unetpp_sizes": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), P(NetSizes)]),
         "idh_unetpp_pack": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), vp, vp]),
         "idh_unetpp_fwd": (i32, [P(BlockParams), i32, P(ConvParams), vp, i32, P(Tensor), P(Tensor), P(vp), P(vp), vp, sz, vp]),
+        "idh_unetpp_sizes_ex": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), C.c_uint32, P(NetSizes)]),
+        "idh_unetpp_pack_ex": (i32, [P(BlockParams), i32, P(ConvParams), i32, P(Tensor), P(Tensor), C.c_uint32, vp, vp]),
+        "idh_unetpp_fwd_ex": (i32, [P(BlockParams), i32, P(ConvParams), vp, sz, i32, P(Tensor), P(Tensor), C.c_uint32, P(vp), P(vp), vp, sz, vp]),
         "idh_matching_stem_sizes": (i32, [P(StemParams), i32, P(Tensor), P(Tensor), P(NetSizes)]),
         "idh_matching_stem_pack": (i32, [P(StemParams), i32, P(Tensor), P(Tensor), vp, vp]),
         "idh_matching_stem_fwd": (i32, [P(StemParams), vp, i32, P(Tensor), P(Tensor), vp, sz, vp]),

@@ -1102,9 +1102,14 @@ def cv_encoder_forward_nchw(enc, x: torch.Tensor, img_feats: List[torch.Tensor])
 
 
 # --- UNet++ decoders (reference networks.py:20-84, 118-183) ------------------------------
-def build_decoder(p: Plan, dec, feats: List[View]):
+ALL_SCALES = 0b1111  # IDH_SCALES_ALL of include/idh_net.h: bit i = the caller reads the output_i result
+
+
+def build_decoder(p: Plan, dec, feats: List[View], scales: int = ALL_SCALES):
     """Adds the UNet++ grid to ``p``; returns {scale i: View of the surviving output_i result
-    (before the optional 1x1 depth head)}."""
+    (before the optional 1x1 depth head)} for the scales whose bit is set in ``scales``.  A scale that is not wanted gets no output_i
+    block (two 3x3 convs and two buffers each); the grid node X(i, 4-i) under it is built either way, the next column reads it.  Scale 0
+    (output_0[0] is nn.Identity: the grid's top-left node itself) is always returned."""
     prev = list(feats)
     outputs: List[View] = []
     final: Dict[int, View] = {}
@@ -1132,6 +1137,10 @@ def build_decoder(p: Plan, dec, feats: List[View]):
                 lo = p.basic_block(prev[i + 1], diag)
                 if (lo.H * 2, lo.W * 2) != (xi.H, xi.W):
                     raise _lib.IdhError("decoder pyramid levels must differ by exactly x2")
+                if j > 1 and not has_up:
+                    # (liveness reuse) prev[i + 1] is X(i+1, 4-(i+1)), the last node of its row: up_conv and the output head read it in the
+                    # column before, this diag_conv was its last reader
+                    p.release(prev[i + 1])
                 p.upsample2(lo, cat.slice(cout, cout))
                 lows = [lo]
                 # (liveness reuse) the half-resolution maps have no reader after their upsampling - unless the low-resolution projection
@@ -1158,7 +1167,10 @@ def build_decoder(p: Plan, dec, feats: List[View]):
             outputs.append(y)
             if j == 4 - i:  # the only (i,j) whose output_i result survives in the dict
                 head = dec.convs[f"output_{i}"]
-                final[i] = p.basic_block(y, head[0]) if not isinstance(head[0], nn.Identity) else y
+                if isinstance(head[0], nn.Identity):
+                    final[i] = y
+                elif (scales >> i) & 1:
+                    final[i] = p.basic_block(y, head[0])
         prev = outputs[::-1]
     return final
 
@@ -1442,11 +1454,12 @@ def build_skip_decoder(p: Plan, dec, feats: List[View]) -> Dict[int, View]:
     return final
 
 
-def build_any_decoder(p: Plan, dec, feats: List[View]) -> Dict[int, View]:
-    """UNet++ (BDDecoderPP / DepthDecoderPP) or skip decoder, by the structure of ``dec``."""
+def build_any_decoder(p: Plan, dec, feats: List[View], scales: int = ALL_SCALES) -> Dict[int, View]:
+    """UNet++ (BDDecoderPP / DepthDecoderPP) or skip decoder, by the structure of ``dec``.  ``scales``: see ``build_decoder`` (a skip
+    decoder's scales feed one another: it always builds all of them)."""
     if hasattr(dec, "block1"):
         return build_skip_decoder(p, dec, feats)
-    return build_decoder(p, dec, feats)
+    return build_decoder(p, dec, feats, scales)
 
 
 def build_regression_heads(p: Plan, dec, final: Dict[int, View]) -> Dict[int, "tuple"]:

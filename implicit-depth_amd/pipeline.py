@@ -50,16 +50,25 @@ class HotPath(nn.Module):
         _lib.watch_state_dict_loads(self)
 
     # ------------------------------------------------------------------------------------
+    def _scales(self, return_features: bool) -> int:
+        """The decoder scales a call reads (nhwc.build_decoder): the occlusion MLP takes scale 0 only, so a BDDecoderPP behind it builds
+        output_1..3 just for the callers that ask for the feature maps; depth / regression heads are outputs at every scale."""
+        dec = self.depth_decoder
+        if return_features or self.binary_mlp is None or getattr(dec, "depth_head", False) or hasattr(dec, "out1"):
+            return nhwc.ALL_SCALES
+        return 0b0001
+
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
-              images: Optional[torch.Tensor] = None):
-        """``head``: None = matching features come in finished (NCHW); "nchw" / "nhwc" = the plan starts at the
+              images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):
+        """``scales``: bit i = the plan builds the decoder's output_i result (part of the plan key: the full plan is built on first demand).
+        ``head``: None = matching features come in finished (NCHW); "nchw" / "nhwc" = the plan starts at the
         matching backbone's layer1 map (B*(K+1), head_ch, H, W) in that physical layout and runs the encoder head;
         "images" = the plan starts at the raw (B, K+1, 3, h, w) ``images`` and runs the native stem (nhwc.build_matching_stem) first."""
         geom = None
         if head == "images":
             _, shape, strides = nhwc.image_strides(images)
             geom = (tuple(shape), strides)
-        key = (B, K, C, H, W, tuple(tuple(s) for s in enc_shapes), str(device), self.conv_math, head, head_ch, geom,
+        key = (B, K, C, H, W, tuple(tuple(s) for s in enc_shapes), str(device), self.conv_math, head, head_ch, geom, scales,
                nhwc._param_key(self.cost_volume_net), nhwc._param_key(self.depth_decoder),
                nhwc.ParamKey(nhwc._param_key(self.matching_model.net[5]) + nhwc._param_key(self.matching_model.net[8])) if head else None,
                nhwc.stem_param_key(self.matching_model.net[:5]) if head == "images" else None)
@@ -106,7 +115,7 @@ class HotPath(nn.Module):
         i_enc = [p.import_nchw(enc_shapes[0], v0)]
         outs, i_img = nhwc.build_cv_encoder(p, self.cost_volume_net, cv_in, enc_shapes[1:])
         i_enc += i_img
-        final = nhwc.build_any_decoder(p, self.depth_decoder, [v0] + outs)
+        final = nhwc.build_any_decoder(p, self.depth_decoder, [v0] + outs, scales)
         ent.update(cv_in=cv_in, i_enc=i_enc, final=final)
         if getattr(self.depth_decoder, "depth_head", False):
             for i, v in final.items():
@@ -183,7 +192,7 @@ class HotPath(nn.Module):
             B, K, C, H, W = matching_src_feats.shape
         dev = src_K.device
         cur_feats = [f if f.is_contiguous() else f.contiguous() for f in cur_feats]
-        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch, images)
+        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch, images, self._scales(return_features))
         p, st = ent["plan"], ent["state"]
         L = _lib.lib()
         sp = _lib.stream_ptr()

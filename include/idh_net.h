@@ -104,6 +104,24 @@ int idh_unetpp_fwd(const idh_block_params *blocks, int n_blocks, const idh_conv_
                    const idh_tensor *feats, const idh_tensor *feature_outs, float *const *log_depth_outs, float *const *depth_outs,
                    float *workspace, size_t workspace_floats, void *stream);
 
+/* The same three calls with a scale mask: bit i of `scales` = the caller reads the output_i result.  A scale without its bit gets no output_i
+ * block (two 3x3 convs, their buffers and their weight reads; feature_outs[i].ptr may then be NULL) - the grid nodes under it are built
+ * either way, the next column reads them.  Scale 0 is the grid's top-left node itself (output_0[0] is nn.Identity): without bit 0 it is
+ * computed and not delivered.  heads != NULL needs IDH_SCALES_ALL (every 1x1 head is an output), anything else is IDH_EINVAL.
+ * The weight blob does NOT depend on the mask: the slots of a block that is not run stay where they are (and _pack_ex fills them), so
+ * weight_floats, and a packed blob, serve every mask over the same (N, feats, feature_outs) - a host packs once and alternates between masks.
+ * workspace_floats, ops and launches are those of the mask given.  idh_unetpp_fwd_ex also takes the blob's size and returns IDH_EINVAL
+ * before it launches anything when its own plan needs another: a blob packed for another N or other shapes is never read.
+ * idh_unetpp_sizes / _pack / _fwd are these calls with IDH_SCALES_ALL (and without the size check). */
+#define IDH_SCALES_ALL 0xF
+int idh_unetpp_sizes_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
+                        const idh_tensor *feature_outs, uint32_t scales, idh_net_sizes *sizes);
+int idh_unetpp_pack_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
+                       const idh_tensor *feature_outs, uint32_t scales, float *weight_blob, void *stream);
+int idh_unetpp_fwd_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, const float *weight_blob, size_t weight_floats,
+                      int N, const idh_tensor *feats, const idh_tensor *feature_outs, uint32_t scales, float *const *log_depth_outs,
+                      float *const *depth_outs, float *workspace, size_t workspace_floats, void *stream);
+
 /* ---- ResNet18 matching stem (implicit-depth_amd/backbone.py: conv1, bn1, relu, maxpool, layer1 of antialiased_cnns.resnet18(filter_size=4,
  * pool_only=True), reference modules/networks.py:261-271) --------------------------------------------------------------------------------
  * Raw images -> the 64-channel layer1 map at 1/4 resolution, inference only (eval-mode BatchNorms, folded into the convolutions by *_pack):
