@@ -1103,6 +1103,36 @@ __global__ __launch_bounds__(256) void argmax_planes_k(const float *__restrict__
 
 extern "C" size_t idh_feature_volume_workspace_bytes(int B) { return B <= 0 ? 0 : (size_t)B * kWsStrideReal * sizeof(float); }
 
+// plane groups: tasks are uniform in cost and run on 256 CUs x 8 persistent waves, so pick the
+// number of groups G (>= 4 planes per task, so the per-pixel pre-activation stays amortised) that
+// wastes the least of the last round: minimise ceil(tasks/slots)*slots/tasks, smallest G on ties.
+// The one place the choice is made: the launch below and the idh_feature_volume_plane_groups query both call it.
+// (G <= ceil(D / 4) alone let D = 5, 6 and 9 through with three planes per task: candidates below four planes are skipped.)
+static void fv_plane_groups(int B, int H, int W, int D, int *G_out, int *DP_out) {
+    const long long pix_tasks = (long long)B * (((long long)H * W + 15) / 16);
+    const long long slots = 256ll * 8;
+    int bestG = 1;
+    double bestWaste = 1e30;
+    for (int G = 1; G <= (D + 3) / 4; ++G) {
+        const int DP = (D + G - 1) / G;
+        const int Gr = (D + DP - 1) / DP;
+        if (Gr != G || (G > 1 && DP < 4)) continue;
+        // planes are not always divisible: cost of a task ~ DP (+1 for the pre-activation)
+        const long long tasks = pix_tasks * G;
+        const double rounds = (double)((tasks + slots - 1) / slots);
+        const double waste = rounds * slots * (DP + 1) / ((double)pix_tasks * (D + G));
+        if (waste < bestWaste - 1e-9) { bestWaste = waste; bestG = G; }
+    }
+    *G_out = bestG;
+    *DP_out = (D + bestG - 1) / bestG;
+}
+
+extern "C" int idh_feature_volume_plane_groups(int B, int H, int W, int D, int *groups, int *planes_per_group) {
+    if (B <= 0 || H <= 0 || W <= 0 || D <= 0 || D > 4096 || !groups || !planes_per_group) return IDH_EINVAL;
+    fv_plane_groups(B, H, W, D, groups, planes_per_group);
+    return IDH_OK;
+}
+
 static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                                const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
                                float dmin, float dmax, int B, int K, int C, int H, int W, int D,
@@ -1197,25 +1227,8 @@ static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, con
         }
     }
     a.tiles_per_img = (N + 15) / 16;
-    // plane groups: tasks are uniform in cost and run on 256 CUs x 8 persistent waves, so pick the
-    // number of groups G (>= 4 planes per task, so the per-pixel pre-activation stays amortised) that
-    // wastes the least of the last round: minimise ceil(tasks/slots)*slots/tasks, smallest G on ties.
+    fv_plane_groups(B, H, W, D, &a.G, &a.DP);  // (shared with idh_feature_volume_plane_groups)
     const long long pix_tasks = (long long)B * a.tiles_per_img;
-    const long long slots = 256ll * 8;
-    int bestG = 1;
-    double bestWaste = 1e30;
-    for (int G = 1; G <= (D + 3) / 4; ++G) {
-        const int DP = (D + G - 1) / G;
-        const int Gr = (D + DP - 1) / DP;
-        if (Gr != G) continue;
-        // planes are not always divisible: cost of a task ~ DP (+1 for the pre-activation)
-        const long long tasks = pix_tasks * G;
-        const double rounds = (double)((tasks + slots - 1) / slots);
-        const double waste = rounds * slots * (DP + 1) / ((double)pix_tasks * (D + G));
-        if (waste < bestWaste - 1e-9) { bestWaste = waste; bestG = G; }
-    }
-    a.G = bestG;
-    a.DP = (D + bestG - 1) / bestG;
     const long long ntasks = pix_tasks * a.G;
     int grid = (int)((ntasks + 7) / 8);
     if (grid > 256) grid = 256;  // persistent: one 512-thread workgroup per CU (LDS-resident weights)

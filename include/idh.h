@@ -158,6 +158,11 @@ const char *idh_cost_volume_dot_kernel_name(int B, int K, int H, int W, int D);
  * One frame's K source maps are addressed through a buffer descriptor: K*H*W*C*4 bytes must stay below 2 GiB (else IDH_EUNSUPPORTED).
  */
 size_t idh_feature_volume_workspace_bytes(int B);
+/* Host-only query (ABI >= 107): how idh_feature_volume*_fwd splits the D depth planes of this shape over tasks.  A task is one tile of 16
+ * pixels times one group of consecutive planes [g * planes_per_group, min(D, (g + 1) * planes_per_group)); `groups` of them cover D, the
+ * last one may be shorter.  The launch calls the same function, so the answer is the partition the kernels run (K, C and the math mode
+ * do not enter the choice).  IDH_EINVAL for non-positive sizes, D > 4096 or a NULL output pointer. */
+int idh_feature_volume_plane_groups(int B, int H, int W, int D, int *groups, int *planes_per_group);
 int idh_feature_volume_fwd(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                            const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
                            float dmin, float dmax, int B, int K, int C, int H, int W, int D,

@@ -130,6 +130,55 @@ def test_launch_grouping_decisions_without_a_gpu():
     assert count([bad]) == -1
 
 
+def _plane_groups(L, B, H, W, D):
+    import ctypes as C
+
+    g, dp = C.c_int(-1), C.c_int(-1)
+    rc = L.idh_feature_volume_plane_groups(B, H, W, D, C.byref(g), C.byref(dp))
+    return rc, g.value, dp.value
+
+
+def test_feature_volume_plane_partition_rule_without_a_gpu():
+    """idh_feature_volume_plane_groups answers with the function the launch calls (csrc/feature_volume.hip: fv_plane_groups).  Whatever the rule
+    prefers, the partition must cover D with exactly G non-empty groups, keep >= 4 planes per task once D allows it (the per-pixel
+    pre-activation is amortised over a task's planes) and never split fewer than 4 planes."""
+    from implicit_depth_amd import _lib
+
+    L = _lib.lib()
+    n = 0
+    for B in (1, 2, 3, 4, 6, 8, 32):
+        for H, W in ((1, 1), (8, 8), (9, 13), (24, 32), (48, 40), (47, 65), (96, 128), (192, 256)):
+            for D in (1, 2, 3, 4, 5, 7, 8, 9, 13, 16, 22, 27, 63, 64, 65, 96, 128, 4095, 4096):
+                rc, G, DP = _plane_groups(L, B, H, W, D)
+                assert rc == 0, (B, H, W, D)
+                assert G >= 1 and DP >= 1 and G * DP >= D and (G - 1) * DP < D, (B, H, W, D, G, DP)
+                if D >= 4:
+                    assert DP >= 4, (B, H, W, D, G, DP)
+                else:
+                    assert G == 1 and DP == D, (B, H, W, D, G, DP)
+                n += 1
+    assert n == 7 * 8 * 19
+
+
+def test_feature_volume_plane_partition_operating_points_and_errors():
+    """The partitions of the operating points README.md quotes (a retune of the rule shows up here as a diff), and the error code for
+    arguments the launch refuses too."""
+    from implicit_depth_amd import _lib
+
+    L = _lib.lib()
+    assert _plane_groups(L, 32, 96, 128, 64) == (0, 1, 64)
+    assert _plane_groups(L, 4, 96, 128, 64) == (0, 2, 32)
+    assert _plane_groups(L, 1, 96, 128, 64) == (0, 8, 8)
+    assert _plane_groups(L, 1, 96, 128, 96) == (0, 8, 12)
+    for bad in ((0, 96, 128, 64), (-1, 96, 128, 64), (1, 0, 128, 64), (1, 96, -3, 64), (1, 96, 128, 0), (1, 96, 128, 4097)):
+        assert _plane_groups(L, *bad) == (-1, -1, -1), bad  # IDH_EINVAL, outputs untouched
+    import ctypes as C
+
+    g = C.c_int(-1)
+    assert L.idh_feature_volume_plane_groups(1, 96, 128, 64, None, C.byref(g)) == -1
+    assert L.idh_feature_volume_plane_groups(1, 96, 128, 64, C.byref(g), None) == -1 and g.value == -1
+
+
 def test_hot_kernels_compile_without_scratch():
     """The stage loops of the F(4x4) conv kernel and the plane loop of the tuned feature-volume kernel must stay spill-free: a scratch reload in front
     of a batch of loads waits for every load in flight (profiles/r04-r05/experiments.md).  Compiles the two sources for gfx950 with
