@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IDH_LIB") or os.path.join(_HERE, "lib", "libidh.so")
 
 _lib = None
-MIN_ABI_VERSION = 107
+MIN_ABI_VERSION = 108
 
 f32p = C.c_void_p  # device pointers travel as integers
 
@@ -126,6 +126,7 @@ _SIGS = {
     "idh_sizeof_op": (C.c_size_t, []),
     "idh_run_ops": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "idh_count_launches": (C.c_int, [C.c_void_p, C.c_int]),
+    "idh_conv_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "idh_packed_mlp_weight_floats": (C.c_size_t, [C.c_int]),
     "idh_pack_mlp_weight": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "idh_binary_mlp_fwd": (C.c_int, [f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_float, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),

@@ -834,23 +834,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_group_k(const ReduceGroupAr
     d.out[m * d.out_cs + co] = act_apply(v, d.act, d.slope);
 }
 
-// split-K tail: out = act(sum_s ws[s] + bias + res)
-__global__ __launch_bounds__(256) void splitk_reduce_k(const float *__restrict__ ws, const float *__restrict__ bias,
-                                                       const float *__restrict__ res, float *__restrict__ out,
-                                                       int M, int Cout, int Cout_pad, int S, int res_cs, int out_cs,
-                                                       int act, float slope) {
-    const long long total = (long long)M * Cout;
-    for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total; t += gridDim.x * 256ll) {
-        const int co = (int)(t % Cout);
-        const long long m = t / Cout;
-        float v = 0.f;
-        for (int s = 0; s < S; ++s) v += ws[((size_t)s * M + m) * Cout_pad + co];
-        if (bias) v += bias[co];
-        if (res) v += res[m * res_cs + co];
-        out[m * out_cs + co] = act_apply(v, act, slope);
-    }
-}
-
 // OIHW -> [tap][ci/4][co][ci%4], zero padded
 __global__ __launch_bounds__(256) void pack_weight_k(const float *__restrict__ w, float *__restrict__ dst, int Cout,
                                                      int Cin, int ks, int Cin_pad, int Cout_pad) {
@@ -1882,6 +1865,23 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 return IDH_EINVAL;
         }
     }
+    return IDH_OK;
+}
+
+extern "C" int idh_conv_variant(const idh_op *op, int32_t out[8]) {
+    if (!op || !out || op->kind != IDH_OP_CONV) return IDH_EINVAL;
+    PreparedConv pc{};
+    const int rc = prep_conv(*op, pc);
+    if (rc != IDH_OK) return rc;
+    const bool lds = pc.lds_rows == 8 || pc.lds_rows == 4;
+    out[0] = pc.lds_rows;
+    out[1] = lds ? pc.nj : 0;
+    out[2] = lds ? 0 : pc.tm;
+    out[3] = lds ? 0 : pc.tn;
+    out[4] = pc.a.S;
+    out[5] = pc.up;
+    out[6] = pc.norm;
+    out[7] = pc.s2;
     return IDH_OK;
 }
 

@@ -30,7 +30,9 @@ enum {
                                under 32 GiB - else IDH_EUNSUPPORTED (no 64-bit-index variant is kept; split the batch) */
     IDH_OP_NCHW_TO_NHWC = 3,/* strided layout import: (N,C,H,W) -> NHWC slice                */
     IDH_OP_NHWC_TO_NCHW = 4,/* strided layout export: NHWC slice -> (N,C,H,W)                */
-    IDH_OP_SPLITK_REDUCE = 5,/* sum split-K partials + bias + residual + activation          */
+    IDH_OP_SPLITK_REDUCE = 5,/* RESERVED, never accepted: idh_run_ops / idh_count_launches answer IDH_EINVAL for it.  The sum of the
+                                split-K partials (+ bias + residual + activation) is implicit in an IDH_OP_CONV with split_k > 1, which
+                                launches its own reduce (one grid for all split members of a group); the number stays taken */
     IDH_OP_POINTWISE_HEAD = 6,/* 1x1 conv to 1 channel (DepthDecoderPP heads, networks.py:158-161); ws != NULL: a second
                                  (N,1,H,W) output = exp(out), the depth map of depth_model.py:425-433 */
     IDH_OP_COPY = 9,        /* channel-strided NHWC -> NHWC slice copy */
@@ -187,6 +189,20 @@ int idh_run_ops(const idh_op *ops_host, int n, void *stream);
 /* Number of kernel launches idh_run_ops() would issue for these ops (same validation and grouping decisions, nothing
  * is launched; usable without a GPU), or a negative IDH_E* code. */
 int idh_count_launches(const idh_op *ops_host, int n);
+
+/* Host-only query (ABI >= 108): the kernel variant idh_run_ops() would launch for ONE IDH_OP_CONV descriptor run alone - the same validation and
+ * dispatch decision (nothing is launched, no device access; usable without a GPU).  Returns what idh_run_ops would return for the op
+ * (IDH_EINVAL also for a NULL argument or another kind); on IDH_OK fills
+ *   out = { lds_rows, nj, tm, tn, S, up, norm, s2 }
+ *   lds_rows  8 / 4: LDS-staged 3x3 kernel with 8- / 4-row tiles; 0: direct kernel; 16: split-precision; 32 / 36: Winograd F(2x2) / F(4x4)
+ *   nj        LDS kernel: 16-channel output sub-tiles per workgroup (4, 2, 1); 0 otherwise
+ *   tm, tn    direct kernel: wave tile in 16-wide sub-tiles; split-precision / Winograd: the tile code and its tile rows; 0 on the LDS kernel
+ *   S         split count after clamping to the step / chunk count (1 = the kernel writes final values, ws unused)
+ *   up, norm  0 / 1: a source has fused x2-upsampled segments / source 0 is normalised on load
+ *   s2        0 / 1: the LDS kernel's stride-2 loader runs (a 3x3 stride-2 second source, or a lone one behind an empty first source)
+ * A request the LDS kernel does not cover (tile_m = 8 / 9 with Wo < 16, a Cout its channel tile does not divide, ...) is not an error: it
+ * runs on the direct kernel, and only this query tells. */
+int idh_conv_variant(const idh_op *op, int32_t out[8]);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
