@@ -516,6 +516,7 @@ extern "C" int idh_binary_mlp_f16x3_fwd(const float *feat_nhwc, int feat_cs, int
     if (B < 0 || P < 0 || HW <= 0 || Cf <= 0 || (Cf & 3) || (feat_cs & 3) || feat_cs < Cf) return IDH_EINVAL;
     if (B == 0 || P == 0) return IDH_OK;
     if (!feat_nhwc || !depth_bphw || !w1f_packed || !w2_f16 || !vecs6x128 || !out_bphw) return IDH_EINVAL;
+    if (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) return IDH_EINVAL;  // dwordx4 row loads (ABI 109)
     const long long M = (long long)B * HW;
     if (M >= (1ll << 31)) return IDH_EUNSUPPORTED;
     BinArgs a{feat_nhwc, depth_bphw, prior_bphw, w1f_packed, static_cast<const float *>(w2_f16), vecs6x128, out_bphw,
@@ -537,6 +538,7 @@ extern "C" int idh_binary_mlp_search_fwd(const float *feat_nhwc, int feat_cs, in
         return IDH_EINVAL;
     if (B == 0) return IDH_OK;
     if (!feat_nhwc || !w1f_packed || !w2_packed || !vecs6x128 || !search_depths_b1hw || !last_logits_b1hw) return IDH_EINVAL;
+    if (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) return IDH_EINVAL;  // dwordx4 row loads (ABI 109)
     const long long M = (long long)B * HW;
     if (M >= (1ll << 31)) return IDH_EUNSUPPORTED;
     BinArgs a{feat_nhwc, nullptr, prior_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits_b1hw,
@@ -558,6 +560,7 @@ extern "C" int idh_binary_mlp_search_thr_fwd(const float *feat_nhwc, int feat_cs
     if (B == 0) return IDH_OK;
     if (!feat_nhwc || !w1f_packed || !w2_packed || !vecs6x128 || !search_depths_b1hw || !last_logits_b1hw || !bins || !thr_logits)
         return IDH_EINVAL;
+    if (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) return IDH_EINVAL;  // dwordx4 row loads (ABI 109)
     const long long M = (long long)B * HW;
     if (M >= (1ll << 31)) return IDH_EUNSUPPORTED;
     BinArgs a{feat_nhwc, nullptr, prior_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits_b1hw,
@@ -579,6 +582,7 @@ extern "C" int idh_binary_mlp_search_f16x3_fwd(const float *feat_nhwc, int feat_
     if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
     if (B == 0) return IDH_OK;
     if (!feat_nhwc || !w1f_packed || !w2_f16 || !vecs6x128 || !search_depths_b1hw || !last_logits_b1hw) return IDH_EINVAL;
+    if (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) return IDH_EINVAL;  // dwordx4 row loads (ABI 109)
     const long long M = (long long)B * HW;
     if (M >= (1ll << 31)) return IDH_EUNSUPPORTED;
     BinArgs a{feat_nhwc, nullptr, prior_b1hw, w1f_packed, static_cast<const float *>(w2_f16), vecs6x128, last_logits_b1hw,

@@ -214,6 +214,12 @@ int idh_feature_volume_f16x3_fwd(const float *cur_nhwc, const float *src_nhwc, c
  *              (rows that are not 16-byte aligned - the reference's 65- / 66-float [depth | feat | prior] rows - are read with dword loads)
  *   depth_bphw (B,P,HW); prior_bphw (B,P,HW) or NULL (then prior_const is used when has_prior)
  *   out_bphw   (B,P,HW) logits
+ * Feature alignment per entry point (enforced: IDH_EINVAL otherwise; ABI 109):
+ *   idh_binary_mlp_fwd                    any feat_cs >= Cf, base 4-byte aligned
+ *   idh_binary_mlp_strided_fwd            base 4-byte aligned, pixel and channel stride > 0, batch stride >= 0
+ *   idh_binary_mlp_f16x3_fwd and the three idh_binary_mlp_search_*_fwd
+ *                                         feat_cs % 4 == 0 and base 16-byte aligned (rows are read with dwordx4 loads only)
+ * Cf % 4 == 0 everywhere; B * HW < 2^31 (IDH_EUNSUPPORTED beyond).  B == 0 (and P == 0 for the logit entry points) is IDH_OK and launches nothing.
  */
 size_t idh_packed_mlp_weight_floats(int n_in);
 int idh_pack_mlp_weight(const float *w_row_major, float *dst, int ld, int col0, int n_in, void *stream);
@@ -231,7 +237,7 @@ int idh_binary_mlp_strided_fwd(const float *feat, long long feat_batch_stride, i
                                float *out_bphw, void *stream);
 /* Same, with the per-plane 128x128 layer in "f16x3" split precision (w2_f16 from
  * idh_pack_mlp_weight_f16, csrc/split_f16.h) and ELU's exp on v_exp_f32: fp32-equivalent results
- * (tests/test_mlp_split_gpu.py) at a fraction of the fp32-MFMA cost. */
+ * (tests/test_mlp_split_gpu.py) at a fraction of the fp32-MFMA cost.  feat_cs % 4 == 0, feat_nhwc 16-byte aligned. */
 int idh_binary_mlp_f16x3_fwd(const float *feat_nhwc, int feat_cs, int Cf, const float *depth_bphw,
                              const float *prior_bphw, int has_prior, float prior_const,
                              const float *w1f_packed, const void *w2_f16, const float *vecs6x128, int B,
@@ -241,7 +247,9 @@ int idh_binary_mlp_f16x3_fwd(const float *feat_nhwc, int feat_cs, int Cf, const 
  * dependent evaluations of the same MLP at each pixel's current query depth, bounds [lo,hi], first
  * query (hi-lo)/2, a pixel is "visible" when sigmoid(logit) < threshold.  Outputs the final query
  * depths and the logits of the last evaluation (the reference's outputs["search_depths"] / ["pred_0"]).
- * Constant threshold; idh_binary_mlp_search_thr_fwd takes the per-depth Thresholder. */
+ * Constant threshold; idh_binary_mlp_search_thr_fwd takes the per-depth Thresholder.
+ * All three search entry points: feat_cs % 4 == 0 and feat_nhwc 16-byte aligned (IDH_EINVAL otherwise, ABI 109); iters > 0, hi > lo,
+ * threshold in (0, 1); prior_b1hw is (B,1,HW) or NULL (prior_const). */
 int idh_binary_mlp_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, const float *prior_b1hw,
                               int has_prior, float prior_const, const float *w1f_packed,
                               const float *w2_packed, const float *vecs6x128, int B, int HW, int iters,
