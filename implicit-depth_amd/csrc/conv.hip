@@ -1438,6 +1438,10 @@ int prep_conv(const idh_op &op, PreparedConv &pc) {
         // split-precision kernel (conv_split.hip): src[0].w holds idh_pack_conv_weight_split output
         if (!lds_ok || a.s[0].pad_mode != IDH_PAD_ZEROS || (op.Cout % 64) || a.S != 1 || op.Wo < kSplitTile || op.Ho < 1 || (op.tile_n != 0 && op.tile_n != 8 && op.tile_n != 16))
             return IDH_EUNSUPPORTED;
+        // second source: the kernel walks src[1] with source 0's H / W and reads ONE tap of weights per 16-channel chunk from the 1x1 panels of the
+        // blob - a 1x1 stride-1 projection of an output-sized plain tensor and nothing else (lds_ok also admits the LDS kernel's 3x3 stride-2 projection)
+        if (a.s[1].in && (a.s[1].ks != 1 || a.s[1].stride != 1 || a.s[1].H != op.Ho || a.s[1].W != op.Wo || a.s[1].up_in[0] || a.s[1].norm))
+            return IDH_EUNSUPPORTED;
         a.NT = op.Cout / 64;
         pc.lds_rows = 16;
         pc.tm = op.tile_m;

@@ -110,9 +110,10 @@ typedef struct idh_op {
                                3x3 stride-2 second source], or a LONE 3x3 stride-2 zero-padded source with Cout % 32 == 0 and
                                Wo >= 16 - conv1 of a stride-2 BasicBlock - which runs on the kernel's stride-2 loader);
                                tile_m = IDH_SPLIT_F16X3 selects the split-precision
-                               kernel (3x3 stride 1, one source, Cout % 64 == 0; src[0].w =
-                               idh_pack_conv_weight_split output of the same mode); there tile_n = 8
-                               selects 8-row instead of 16-row tiles */
+                               kernel (3x3 stride 1, zero padding, Cout % 64 == 0, Wo >= 16, split_k == 1; src[0].w =
+                               idh_pack_conv_weight_split output of the same mode; src[1], if any: a 1x1
+                               stride-1 projection of an output-sized tensor, no up / norm); there tile_n = 8
+                               selects 8-row instead of 16-row tiles (0 / 16: 16 rows; other values: IDH_EUNSUPPORTED) */
     int32_t group;        /* != 0: consecutive CONV / UPSAMPLE2 ops with the same id are mutually independent (one
                                dependency level of the plan, see Plan.schedule in nhwc.py) and may be launched as
                                ONE grid: runs of 4-row LDS convs with equal channel tiles always are; a mixed run
@@ -136,7 +137,9 @@ int idh_pack_conv_weight(const float *w_oihw, float *dst, int Cout, int Cin, int
  * (IDH_EUNSUPPORTED otherwise).
  * A fused 1x1 second source (src[1]: BasicBlock's downsample(x)) is packed into the same blob
  * (w_1x1 = (Cout, Cin_1x1) row-major or NULL / 0): [3x3 panels][1x1 panels: Cin_1x1_pad/16 x Cout/64 x
- * piece x half x 64 x 8][scales]; src[1].w is then ignored by the kernel. */
+ * piece x half x 64 x 8][scales]; src[1].w is then ignored by the kernel (but must be non-NULL).  src[1] must be exactly that: ks = 1,
+ * stride = 1, H x W = Ho x Wo, no up_in, no norm.  Any other second source - the 3x3 stride-2 projection the LDS-staged kernel takes
+ * included - is refused with IDH_EUNSUPPORTED (until ABI 109 that one was accepted and computed as if it were 1x1). */
 #define IDH_SPLIT_F16X3 11
 size_t idh_packed_split_weight_bytes(int Cout, int Cin, int Cin_1x1, int mode);
 int idh_pack_conv_weight_split(const float *w_oihw, const float *w_1x1, void *dst, int Cout, int Cin, int Cin_1x1, int mode,

@@ -26,11 +26,11 @@ def _check(case):
     spec = case.spec
     got, clean = R.read_output(case)
     ref, pre, B = R.reference(spec, case.t)
-    tol = R.tolerance(spec, ref, B)
+    tol = R.tolerance(spec, ref, B, case.t)
     err = (got.double() - ref).abs()
     ok = err <= tol  # (a NaN - an element never written - compares false)
     worst = (err / tol).nan_to_num(nan=float("inf")).max().item()
-    print(f"{spec.name}: max err {err.nan_to_num(nan=float('inf')).max().item():.3e}, max err / bound {worst:.3f}")
+    print(f"{spec.name} [{getattr(spec, 'family', 'up')}]: max err {err.nan_to_num(nan=float('inf')).max().item():.3e}, max err / bound {worst:.3f}")
     assert ok.all(), f"{spec.name}: {int((~ok).sum())} of {ok.numel()} elements exceed the bound, worst err / bound {worst:.3g}, first at {tuple((~ok).nonzero()[0].tolist())}"
     assert clean, f"{spec.name}: a store landed outside channels [{R.OUT_C0}, {R.OUT_C0 + case.cout}) of the output buffer"
     return got
