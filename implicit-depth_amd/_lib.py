@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IDH_LIB") or os.path.join(_HERE, "lib", "libidh.so")
 
 _lib = None
-MIN_ABI_VERSION = 108
+MIN_ABI_VERSION = 111
 
 f32p = C.c_void_p  # device pointers travel as integers
 
@@ -105,6 +105,33 @@ RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
 
+class ConvDescSrc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "cs", "Cin", "ks", "stride", "is_cat", "_r")]
+
+
+class ConvDesc(C.Structure):
+    """ctypes mirror of ``idh_conv_desc`` (include/idh_ops.h, kernel selection of one conv)."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("N", "Ho", "Wo", "Cout", "pad_mode", "act")] + [("slope", C.c_float)] +
+                [(n, C.c_int32) for n in ("out_cs", "res_cs", "has_res", "has_norm", "any_size", "math", "n_src")] + [("src", ConvDescSrc * 2)])
+
+
+class ConvTuning(C.Structure):
+    """ctypes mirror of ``idh_conv_tuning``: the field names are the lower-case names of nhwc.py's module globals."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("winograd", "winograd4", "winograd4_proj", "s2_first", "wino_min_tiles", "wino4_min_tiles", "split_min_blocks",
+                                          "narrow_tile_below", "narrowest_tile_below", "split_min_chunks", "split_max", "s2_first_min_blocks",
+                                          "fused_up_rows", "target_waves", "min_waves", "_r")] +
+                [(n, C.c_double) for n in ("wino_min_fill", "wino4_min_fill", "proj_chunk_weight")])
+
+
+class ConvChoice(C.Structure):
+    """ctypes mirror of ``idh_conv_choice``."""
+
+    _fields_ = [(n, C.c_int32) for n in ("tile_m", "tile_n", "split_k", "w_layout", "families", "lds_tile_m", "lds_split_k", "lds_subtiles", "split_rows",
+                                         "direct_tile_m", "direct_tile_n", "direct_split_k")]
+
+
 _SIGS = {
     "idh_version": (C.c_int, []),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
@@ -127,6 +154,10 @@ _SIGS = {
     "idh_run_ops": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "idh_count_launches": (C.c_int, [C.c_void_p, C.c_int]),
     "idh_conv_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "idh_conv_tuning_defaults": (None, [C.POINTER(ConvTuning)]),
+    "idh_conv_select": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvTuning), C.POINTER(ConvChoice)]),
+    "idh_sizeof_conv_select": (None, [C.POINTER(C.c_size_t)]),
+    "idh_schedule_ops": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "idh_packed_mlp_weight_floats": (C.c_size_t, [C.c_int]),
     "idh_pack_mlp_weight": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "idh_binary_mlp_fwd": (C.c_int, [f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_float, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
@@ -226,6 +257,10 @@ def lib():
                                   ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
+        sizes = (C.c_size_t * 3)()
+        h.idh_sizeof_conv_select(sizes)
+        if list(sizes) != [C.sizeof(ConvDesc), C.sizeof(ConvTuning), C.sizeof(ConvChoice)]:
+            raise IdhError(f"{LIB_PATH}: sizeof(idh_conv_desc / _tuning / _choice) = {list(sizes)} in the library, another in this binding")
         if h.idh_sizeof_volume_opts() != C.sizeof(VolumeOpts):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_volume_opts) = {h.idh_sizeof_volume_opts()} in the library, {C.sizeof(VolumeOpts)} in this binding")
         _lib = h

@@ -1,6 +1,6 @@
 #include "idh_common.h"
 
-extern "C" int idh_version(void) { return 110; }  // 101: idh_volume_opts.scratch / scratch_floats / struct_size; 102: Winograd F(4x4) conv (IDH_TILE_WINO4);
+extern "C" int idh_version(void) { return 111; }  // 101: idh_volume_opts.scratch / scratch_floats / struct_size; 102: Winograd F(4x4) conv (IDH_TILE_WINO4);
                                                    // 103: struct_size accepted when >= the fields it guards, hidden visibility (the C ABI is the only export);
                                                    // 104: IDH_OP_POINTWISE_UP, tile_m 8 / 9 for a lone 3x3 stride-2 source, split-K boundaries of the LDS conv in cost units
                                                    // 105: idh_binary_mlp_fwd takes any feature row stride / 4-byte-aligned base; network-level entry points idh_basic_block_fwd,
@@ -10,6 +10,7 @@ extern "C" int idh_version(void) { return 110; }  // 101: idh_volume_opts.scratc
                                                    // 108: idh_conv_variant (host-only query of the kernel an IDH_OP_CONV descriptor runs on); IDH_OP_SPLITK_REDUCE documented as reserved
                                                    // 109: idh_binary_mlp_f16x3_fwd and the three search entry points refuse a feature base that is not 16-byte aligned (they read rows with dwordx4 loads)
                                                    // 110: tile_m = IDH_SPLIT_F16X3 refuses a second source that is not a plain 1x1 stride-1 projection (a 3x3 stride-2 one was accepted and computed wrongly)
+                                                   // 111: idh_conv_select / idh_conv_tuning_defaults / idh_schedule_ops (csrc/plan_select.hip): the one kernel-selection rule and level scheduler of both plan builders
 extern "C" size_t idh_sizeof_volume_opts(void) { return sizeof(idh_volume_opts); }
 
 extern "C" const char *idh_error_string(int code) {

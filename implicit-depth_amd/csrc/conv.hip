@@ -323,7 +323,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const LdsConvArgs &la, unsigned
     const int nc0 = a.s[0].cblocks;
     const int nc1 = a.s[1].in ? a.s[1].cblocks : 0;
     // split boundaries in COST units, not chunks: a 3x3 chunk is 9 taps of MFMAs + one staging round, a 1x1 chunk one tap and (batched,
-    // lds_g1) a fraction of a round - about a ninth (measured flat between 4 and 9, tools/r05/job_c3.sh).  With equal weights the first split of a
+    // lds_g1) a fraction of a round - about a ninth (measured flat between 4 and 9).  With equal weights the first split of a
     // BasicBlock's conv2 + projection got all 3x3 chunks and the last ones only 1x1 chunks: the launch took as long as the unsplit 3x3 part.
     constexpr int kW3 = 9;
     const int w1 = S2 ? kW3 : 1;
@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_lds_up_k(const LdsConvArgs la)
 }
 
 // Grouped launch: up to kMaxGroup INDEPENDENT convolutions (same dependency level of a plan, see
-// implicit-depth_amd/nhwc.py:Plan.schedule) share one grid, so the small low-resolution layers of
+// idh_schedule_ops, csrc/plan_select.hip) share one grid, so the small low-resolution layers of
 // the UNet++ — each of which fills a fraction of the 256 CUs — run side by side.  Descriptors
 // travel by value in the kernel arguments (no device-side table to upload).
 constexpr int kMaxGroup = 12;

@@ -2,13 +2,13 @@
 // idh_run_ops.  Replaces BasicBlock.forward (reference modules/layers.py:78-95), CVEncoder.forward (modules/networks.py:186-215) and
 // BDDecoderPP / DepthDecoderPP.forward (modules/networks.py:64-84, 163-183) for hosts that are not Python.
 //
-// This file contains NO kernels of its own except a bias adder: it is the C++ twin of implicit-depth_amd/nhwc.py's Plan (fp32 arithmetic, default
-// thresholds) — buffers carved out of the caller's workspace, packed weights out of the caller's blob, the same tile selection per conv, the same
-// concat elimination (producers write channel slices), the same dependency-level schedule and launch groups, the same liveness reuse of the big
-// activation temporaries — so a pass is the same op list the Python drop-ins replay and the results are bit-identical to theirs
-// (tests/test_net_abi_gpu.py compares the two, and both with the reference's goldens).
+// This file contains NO kernels of its own except a bias adder: it is the plan builder of implicit-depth_amd/nhwc.py's Plan for hosts without Python (fp32
+// arithmetic, default tuning) - buffers carved out of the caller's workspace, packed weights out of the caller's blob, the same concat elimination
+// (producers write channel slices), the same liveness reuse of the big activation temporaries.  Kernel, tile and split-K of every conv come from
+// idh_conv_select and the dependency-level schedule with its launch groups from idh_schedule_ops (csrc/plan_select.hip), the functions nhwc.py calls
+// too - so a pass is the same op list the Python drop-ins replay and the results are bit-identical to theirs (tests/test_net_abi_gpu.py compares
+// the two, and both with the reference's goldens).
 #include <algorithm>
-#include <array>
 #include <cstring>
 #include <map>
 #include <tuple>
@@ -21,18 +21,8 @@
 
 namespace {
 
-// ---- the constants of nhwc.py this builder mirrors (the defaults; the Python side can be re-tuned at run time, this side is the shipped setting)
-constexpr int kWinoMinTiles = 128;        // WINO_MIN_TILES
-constexpr double kWinoMinFill = 0.74;     // WINO_MIN_FILL
-constexpr int kWino4MinTiles = 768;       // WINO4_MIN_TILES
-constexpr double kWino4MinFill = 0.85;    // WINO4_MIN_FILL
+// ---- the switches of nhwc.py this builder mirrors (the defaults; the Python side can be re-tuned at run time, this side is the shipped setting)
 constexpr long long kReuseMinBytes = 64ll << 20;  // REUSE_MIN_BYTES
-constexpr int kNarrowTileBelow = 400;     // NARROW_TILE_BELOW
-constexpr int kSplitMinChunks = 6, kSplitMax = 16;  // SPLIT_MIN_CHUNKS, SPLIT_MAX
-constexpr double kProjChunkWeight = 0.5;  // PROJ_CHUNK_WEIGHT
-constexpr int kS2FirstMinBlocks = 512;    // S2_FIRST_MIN_BLOCKS
-constexpr int kTargetWaves = 2048, kMinWaves = 1024;
-constexpr int kTileWino = IDH_TILE_WINO, kTileWino4 = IDH_TILE_WINO4;
 constexpr bool kFuseHeadNorm = true;      // FUSE_HEAD_NORM (matching-encoder head: InstanceNorm + LeakyReLU applied by the 3x3 conv on load)
 constexpr bool kFuseHeadImport = true;    // FUSE_HEAD_IMPORT (... and its 1x1 conv reading the backbone's NCHW map in place)
 
@@ -60,7 +50,7 @@ struct View {
 };
 
 struct Region {
-    int buf, c0, c1;
+    uint64_t buf, c0, c1;  // (idh_schedule_ops' triple)
 };
 
 struct Meta {
@@ -158,98 +148,34 @@ class Plan {
         pool.push_back(v.buf);
     }
 
-    static Region region(const View &v, bool pad16 = false) { return Region{v.buf, v.c0, v.c0 + (pad16 ? ceil16(v.C) : v.C)}; }
+    static Region region(const View &v, bool pad16 = false) { return Region{(uint64_t)v.buf, (uint64_t)v.c0, (uint64_t)(v.c0 + (pad16 ? ceil16(v.C) : v.C))}; }
 
-    // ---- kernel-family predicates (nhwc.py: wino_eligible, wino4_eligible, lds_eligible, s2_first_eligible) --------------------------------
-    bool wino_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int pad_mode = IDH_PAD_ZEROS) const {
-        const idh_conv_params &c0 = *srcs[0].cv;
-        if (c0.ks != 3 || c0.stride != 1 || pad_mode != IDH_PAD_ZEROS || cout % 32) return false;
-        if (srcs.size() > 1 && (srcs[1].cv->ks != 1 || srcs[1].cv->stride != 1)) return false;
-        const int ty = cdiv(Ho, 8), tx = cdiv(Wo, 32);
-        if ((double)Ho * Wo < kWinoMinFill * (ty * 8) * (tx * 32)) return false;
-        return (long long)n * ty * tx * (cout / 32) >= kWinoMinTiles;
-    }
-    bool wino4_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int act, float slope, const View &out, const View *res,
-                        int pad_mode = IDH_PAD_ZEROS, bool any_size = false) const {
-        const idh_conv_params &c0 = *srcs[0].cv;
-        const View &v0 = srcs[0].v;
-        if (c0.ks != 3 || c0.stride != 1 || pad_mode != IDH_PAD_ZEROS || cout % 64) return false;
-        if (srcs.size() > 1 && (srcs.size() > 2 || srcs[1].cv->ks != 1 || srcs[1].cv->stride != 1)) return false;
-        if ((act != IDH_ACT_NONE && act != IDH_ACT_LRELU && act != IDH_ACT_ELU) || (act == IDH_ACT_LRELU && !(slope >= 0.f && slope <= 1.f)) || c0.cin <= 16) return false;
-        if ((long long)H(v0) * W(v0) * cs(v0) * 4 >= (1ll << 30)) return false;
-        if ((long long)Ho * Wo * cs(out) * 4 >= (1ll << 31)) return false;
-        if (res && (long long)Ho * Wo * cs(*res) * 4 >= (1ll << 31)) return false;
-        if (srcs.size() > 1) {
-            const View &v1 = srcs[1].v;
-            if ((long long)H(v1) * W(v1) * cs(v1) * 4 >= (1ll << 31) || (long long)((srcs[1].cv->cin + 15) / 16) * 4 * ceil16(cout) * 64 >= (1ll << 31)) return false;
+    // ---- kernel selection: idh_conv_select on the shapes of the views (nhwc.Plan.conv asks the same function) ----------------------------------
+    int select(const std::vector<Src> &srcs, const View &out, int act, float slope, const View *res, int pad_mode, bool norm, bool any_size,
+               idh_conv_choice *c) const {
+        idh_conv_desc d{};
+        d.N = N(out); d.Ho = H(out); d.Wo = W(out); d.Cout = srcs[0].cv->cout; d.pad_mode = pad_mode; d.act = act; d.slope = slope;
+        d.out_cs = cs(out); d.has_res = res != nullptr; d.res_cs = res ? cs(*res) : 0; d.has_norm = norm; d.any_size = any_size;
+        d.n_src = (int)srcs.size();
+        for (size_t i = 0; i < srcs.size(); ++i) {
+            const View &v = srcs[i].v;
+            d.src[i] = idh_conv_desc_src{H(v), W(v), cs(v), srcs[i].cv->cin, srcs[i].cv->ks, srcs[i].cv->stride, 0, 0};
         }
-        if ((long long)((c0.cin + 15) / 16) * 4 * ceil16(cout) * 36 * 16 * 4 >= (1ll << 31)) return false;
-        if (any_size) return true;  // (nhwc.wino4_eligible any_size: the stem's layer1, batch-size-independent rounding)
-        const int ty = cdiv(Ho, 8), tx = cdiv(Wo, 32);
-        if ((double)Ho * Wo < kWino4MinFill * (ty * 8) * (tx * 32)) return false;
-        return (long long)n * ty * tx * (cout / 64) >= kWino4MinTiles;
-    }
-    static bool lds_eligible(const std::vector<Src> &srcs, int cout, int Wo, int pad_mode = IDH_PAD_ZEROS) {
-        const idh_conv_params &c0 = *srcs[0].cv;
-        if (c0.ks != 3 || c0.stride != 1 || cout % 16 || Wo < 16) return false;
-        if (pad_mode != IDH_PAD_ZEROS && (pad_mode != IDH_PAD_REPLICATE || srcs.size() > 1)) return false;
-        if (srcs.size() > 1) {
-            const idh_conv_params &c1 = *srcs[1].cv;
-            const bool strided3 = c1.ks == 3 && c1.stride == 2 && pad_mode == IDH_PAD_ZEROS && cout % 32 == 0;
-            if (!strided3 && (c1.ks != 1 || c1.stride != 1)) return false;
-        }
-        return true;
-    }
-    static int lds_subtiles(int cout) { return cout % 64 == 0 ? 4 : (cout % 32 == 0 ? 2 : 1); }
-    static bool s2_first_eligible(const std::vector<Src> &srcs, int cout, int n, int Ho, int Wo, int pad_mode = IDH_PAD_ZEROS) {
-        if (srcs.size() != 1) return false;
-        const idh_conv_params &c0 = *srcs[0].cv;
-        if (c0.ks != 3 || c0.stride != 2 || pad_mode != IDH_PAD_ZEROS || cout % 32 || Wo < 16) return false;
-        return (long long)n * cdiv(Wo, 16) * cdiv(Ho, 4) * (cout / (16 * lds_subtiles(cout))) >= kS2FirstMinBlocks;
-    }
-    static void choose_lds_tile(int n, int Ho, int Wo, int cout, int chunks, int &code, int &split) {
-        const long long per_row = (long long)n * cdiv(Wo, 16) * (cout / (16 * lds_subtiles(cout)));
-        code = 8;
-        int rows = 8;
-        if (per_row * cdiv(Ho, 8) < 768) { code = 9; rows = 4; }
-        const long long blocks = per_row * cdiv(Ho, rows);
-        long long s = (768 + blocks - 1) / blocks;
-        s = std::min<long long>(s, chunks / kSplitMinChunks);
-        s = std::min<long long>(s, kSplitMax);
-        split = (int)std::max<long long>(1, s);
-    }
-    static void choose_tiles(long long M, int cout, int steps, int &tm, int &tn, int &split) {
-        const int nsub = ceil16(cout) / 16;
-        tn = nsub % 4 == 0 ? 4 : (nsub % 2 == 0 ? 2 : 1);
-        long long waves = 0;
-        tm = 1;
-        for (int cand : {4, 2, 1}) {
-            waves = ((M + 16 * cand - 1) / (16 * cand)) * (nsub / tn);
-            tm = cand;
-            if (waves >= kTargetWaves) break;
-        }
-        split = 1;
-        if (waves < kMinWaves) {
-            long long s = (kMinWaves + waves - 1) / waves;
-            s = std::min<long long>(s, steps / 4);
-            s = std::min<long long>(s, 32);
-            split = (int)std::max<long long>(1, s);
-        }
+        return idh_conv_select(&d, nullptr, c);
     }
 
     // ---- weights -----------------------------------------------------------------------------------------------------------------------
-    enum WLayout { W_DIRECT, W_WINO, W_WINO4 };
-    const float *packed(const idh_conv_params &cv, WLayout lay) {
+    const float *packed(const idh_conv_params &cv, int lay) {  // lay: IDH_W_DIRECT / _WINO / _WINO4
         size_t n = 0;
-        if (lay == W_WINO4) n = idh_packed_wino4_weight_floats(cv.cout, cv.cin);
-        else if (lay == W_WINO) n = idh_packed_wino_weight_floats(cv.cout, cv.cin);
+        if (lay == IDH_W_WINO4) n = idh_packed_wino4_weight_floats(cv.cout, cv.cin);
+        else if (lay == IDH_W_WINO) n = idh_packed_wino_weight_floats(cv.cout, cv.cin);
         else n = idh_packed_weight_floats(cv.cout, cv.cin, cv.ks);
         float *dst = blob_alloc(n);
         if (mode_ == MODE_PACK) {
             if (!cv.weight) { err = IDH_EINVAL; return dst; }
             int rc;
-            if (lay == W_WINO4) rc = idh_pack_conv_weight_wino4(cv.weight, dst, cv.cout, cv.cin, st_);
-            else if (lay == W_WINO) rc = idh_pack_conv_weight_wino(cv.weight, dst, cv.cout, cv.cin, st_);
+            if (lay == IDH_W_WINO4) rc = idh_pack_conv_weight_wino4(cv.weight, dst, cv.cout, cv.cin, st_);
+            else if (lay == IDH_W_WINO) rc = idh_pack_conv_weight_wino(cv.weight, dst, cv.cout, cv.cin, st_);
             else rc = idh_pack_conv_weight(cv.weight, dst, cv.cout, cv.cin, cv.ks, st_);
             if (rc != IDH_OK) err = rc;
         }
@@ -277,20 +203,16 @@ class Plan {
         if (x2) srcs.push_back({*x2, cv2});
         const int n = N(out), Ho = H(out), Wo = W(out), cout = cv.cout;
         if (out.C != cout) { err = IDH_EINVAL; return out; }
-        bool use_wino = !norm && wino_eligible(srcs, cout, n, Ho, Wo, pad_mode);
-        const bool use_wino4 = !norm && (!x2 || !res) && wino4_eligible(srcs, cout, n, Ho, Wo, act, slope, out, res, pad_mode, wino4_any_size);
-        if (use_wino4) use_wino = false;
-        int steps = 0;
+        idh_conv_choice ch;
+        if ((err = select(srcs, out, act, slope, res, pad_mode, norm != nullptr, wino4_any_size, &ch)) != IDH_OK) return out;
         for (size_t i = 0; i < srcs.size(); ++i) {
             const View &v = srcs[i].v;
             const idh_conv_params &c = *srcs[i].cv;
             if (v.C != c.cin || (c.ks != 1 && c.ks != 3) || c.cout != cout) { err = IDH_EINVAL; return out; }
             if (v.C % 16 && (v.c0 != 0 || cs(v) != ceil16(v.C))) { err = IDH_EINVAL; return out; }  // odd channel counts: whole zero-padded buffers only
-            const WLayout lay = (use_wino4 && i == 0) ? W_WINO4 : (use_wino && i == 0) ? W_WINO : W_DIRECT;
             idh_conv_src &s = op.src[i];
-            s.in = ptr(v); s.w = packed(c, lay); s.cs = cs(v); s.H = H(v); s.W = W(v); s.Cin = v.C;
+            s.in = ptr(v); s.w = packed(c, i == 0 ? ch.w_layout : IDH_W_DIRECT); s.cs = cs(v); s.H = H(v); s.W = W(v); s.Cin = v.C;
             s.ks = c.ks; s.stride = c.stride; s.pad_mode = pad_mode;
-            steps += c.ks * c.ks * (ceil16(v.C) / 16);
         }
         op.bias = bias_of(cv, cv2);  // (always present in the blob - BasicBlock's convs all have one, layers.py:52-55; a NULL bias packs as zeros)
         if (res) { op.res = ptr(*res); op.res_cs = cs(*res); }
@@ -298,26 +220,9 @@ class Plan {
         op.Ho = Ho; op.Wo = Wo; op.Cout = cout;
         op.act = act; op.slope = slope;
         const long long M = (long long)n * Ho * Wo;
-        int tm, tn, split;
-        if (use_wino4) { tm = kTileWino4; tn = 0; split = 1; n_wino4 += !dry_; }
-        else if (use_wino) { tm = kTileWino; tn = 0; split = 1; n_wino2 += !dry_; }
-        else if (lds_eligible(srcs, cout, Wo, pad_mode)) {
-            double ch = 0;
-            for (const Src &s : srcs) ch += (ceil16(s.v.C) / 16) * (s.cv->ks == 3 ? 1.0 : kProjChunkWeight);
-            choose_lds_tile(n, Ho, Wo, cout, (int)ch, tm, split);
-            tn = lds_subtiles(cout);
-            if (tn == 4 && tm == 9 && kNarrowTileBelow) {
-                const long long blocks64 = (long long)n * cdiv(Ho, 4) * cdiv(Wo, 16) * (cout / 64) * split;
-                if (blocks64 < kNarrowTileBelow) tn = 2;
-            }
-            tn = tn == 4 ? 0 : tn;
-        } else if (!norm && s2_first_eligible(srcs, cout, n, Ho, Wo, pad_mode)) {
-            choose_lds_tile(n, Ho, Wo, cout, ceil16(x.C) / 16, tm, split);
-            tn = lds_subtiles(cout);
-            tn = tn == 4 ? 0 : tn;
-        } else {
-            choose_tiles(M, cout, steps, tm, tn, split);
-        }
+        const int tm = ch.tile_m, tn = ch.tile_n, split = ch.split_k;
+        n_wino4 += tm == IDH_TILE_WINO4 && !dry_;
+        n_wino2 += tm == IDH_TILE_WINO && !dry_;
         op.tile_m = tm; op.tile_n = tn; op.split_k = split;
         if (norm) {  // (Plan.conv: the LDS-staged kernel with 16-channel tiles and one source only)
             if ((tm != 8 && tm != 9) || tn != 1 || x2) { err = IDH_EINVAL; return out; }
@@ -328,7 +233,7 @@ class Plan {
         ops.push_back(op);
         Meta m;
         if (res) m.reads.push_back(region(*res));
-        if (norm) m.reads.push_back(Region{norm->buf, 0, 1});
+        if (norm) m.reads.push_back(Region{(uint64_t)norm->buf, 0, 1});
         for (const Src &s : srcs) m.reads.push_back(region(s.v, true));
         m.writes.push_back(region(out));
         meta.push_back(m);
@@ -413,7 +318,7 @@ class Plan {
             b.base = w + (size_t)N(x) * nchunks * 2 * x.C; b.N = N(x); b.H = 1; b.W = 1; b.cs = 1; b.internal = false;
             bufs.push_back(b);
             nm.stats = b.base; nm.buf = (int)bufs.size() - 1;
-            m.writes.push_back(Region{nm.buf, 0, 1});
+            m.writes.push_back(Region{(uint64_t)nm.buf, 0, 1});
         }
         meta.push_back(m);
         return nm;
@@ -428,7 +333,7 @@ class Plan {
         op.kind = IDH_OP_POINTWISE_NCHW; op.N = n;
         idh_conv_src &s = op.src[0];
         s.in = mode_ == MODE_RUN ? src : reinterpret_cast<const float *>(uintptr_t(6) << 32);
-        s.w = packed(cv, W_DIRECT); s.H = H_; s.W = W_; s.Cin = C; s.ks = 1; s.stride = 1;
+        s.w = packed(cv, IDH_W_DIRECT); s.H = H_; s.W = W_; s.Cin = C; s.ks = 1; s.stride = 1;
         op.bias = bias_of(cv, nullptr);
         op.out = ptr(out); op.out_cs = cs(out); op.Ho = H_; op.Wo = W_; op.Cout = cv.cout;
         ops.push_back(op);
@@ -485,46 +390,22 @@ class Plan {
         dry_ = false;
     }
 
-    // ---- Plan.schedule: dependency levels, launch order inside a level, group ids ----------------------------------------------------------
-    static bool overlap(const std::vector<Region> &a, const std::vector<Region> &b) {
-        for (const Region &x : a)
-            for (const Region &y : b)
-                if (x.buf == y.buf && x.c0 < y.c1 && y.c0 < x.c1) return true;
-        return false;
-    }
-    static void launch_rank(const idh_op &op, long long r[3]) {
-        r[0] = 3; r[1] = 0; r[2] = 0;
-        if (op.kind == IDH_OP_CONV && op.tile_m == kTileWino) { r[0] = -1; r[1] = op.src[1].in ? 1 : 0; r[2] = -(long long)op.N * op.Ho * op.Wo * op.Cout; }
-        else if (op.kind == IDH_OP_CONV && op.tile_m == 9) { r[0] = 0; r[1] = op.tile_n; }
-        else if (op.kind == IDH_OP_CONV && op.tile_m == 1 && op.tile_n == 4) { r[0] = 1; }
-        else if (op.kind == IDH_OP_UPSAMPLE2) { r[0] = 2; }
-        else if (op.kind == IDH_OP_NCHW_TO_NHWC) { r[0] = 2; r[1] = 1; }
-    }
-    // (Plan.schedule_segments: ops [0, n_first) and the rest are levelled and ordered each on their own - the volume kernel runs between them)
-    void schedule(int n_first = 0) {
-        const int n = (int)ops.size();
-        std::vector<int> level(n, 0), order(n);
-        for (int j = 0; j < n; ++j)
-            for (int i = j < n_first ? 0 : n_first; i < j; ++i)
-                if (overlap(meta[i].writes, meta[j].reads) || overlap(meta[i].writes, meta[j].writes) || overlap(meta[i].reads, meta[j].writes))
-                    level[j] = std::max(level[j], level[i] + 1);
-        std::vector<std::array<long long, 6>> key(n);
-        for (int k = 0; k < n; ++k) {
-            long long r[3];
-            launch_rank(ops[k], r);
-            key[k] = {k < n_first ? 0 : 1, level[k], r[0], r[1], r[2], k};
-            ops[k].group = r[0] < 3 ? level[k] + 1 : 0;
-            order[k] = k;
-        }
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-        std::vector<idh_op> o2(n);
-        for (int k = 0; k < n; ++k) o2[k] = ops[order[k]];
-        ops.swap(o2);
+    // ---- Plan.schedule_segments: idh_schedule_ops over the regions recorded per op (ops [0, n_first) and the rest are levelled and ordered each
+    // on their own - the volume kernel runs between them)
+    int schedule(int n_first = 0) {
+        std::vector<Region> flat;
+        std::vector<int32_t> offs{0};
+        for (const Meta &m : meta)
+            for (const std::vector<Region> *rs : {&m.reads, &m.writes}) {
+                flat.insert(flat.end(), rs->begin(), rs->end());
+                offs.push_back((int32_t)flat.size());
+            }
+        flat.push_back(Region{});  // (a non-NULL array for a plan whose ops touch nothing)
+        return idh_schedule_ops(ops.data(), (int)ops.size(), n_first, &flat[0].buf, offs.data(), IDH_SCHED_MERGE_LEVELS | IDH_SCHED_WINO_GROUP, nullptr, nullptr);
     }
 
     int finish(idh_net_sizes *sizes, int n_first = 0) {
-        if (err) return err;
-        schedule(n_first);
+        if (err || (err = schedule(n_first)) != IDH_OK) return err;
         if (sizes) {
             sizes->workspace_floats = ws_off;
             sizes->weight_floats = blob_off;
@@ -824,8 +705,9 @@ int idh_internal::conv_stage(int mode, ConvStage *s, float *ws, size_t ws_cap, f
             p.conv(x, c1, h, IDH_ACT_NONE, 0.2f, nullptr, nullptr, nullptr);
         }
         const View y = p.buffer(M, H, W, c2.cout);
-        const std::vector<Src> s2{{h, &c2}};
-        if (kFuseHeadNorm && h.C % 16 == 0 && Plan::lds_subtiles(c2.cout) == 1 && Plan::lds_eligible(s2, c2.cout, W, IDH_PAD_REPLICATE)) {
+        idh_conv_choice hc;  // (nhwc.norm_on_load_eligible: the LDS-staged 3x3 kernel with 16-channel tiles, whole 16-channel input blocks)
+        if (p.select({{h, &c2}}, y, IDH_ACT_NONE, 0.2f, nullptr, IDH_PAD_REPLICATE, false, false, &hc) != IDH_OK) return IDH_EINVAL;
+        if (kFuseHeadNorm && h.C % 16 == 0 && hc.lds_subtiles == 1 && (hc.families & IDH_FAMILY_LDS)) {
             const Norm nm = p.instance_norm(h, nullptr, IDH_ACT_NONE, 0.2f);
             Norm on = nm;
             on.act = IDH_ACT_LRELU; on.slope = 0.2f;

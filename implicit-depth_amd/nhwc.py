@@ -120,14 +120,6 @@ def _region(v: "View", pad16: bool = False):
     return (v.buf.data_ptr(), v.c0, v.c0 + (ceil16(v.C) if pad16 else v.C))
 
 
-def _overlap(ra, rb) -> bool:
-    for (ba, a0, a1) in ra:
-        for (bb, b0, b1) in rb:
-            if ba == bb and a0 < b1 and b0 < a1:
-                return True
-    return False
-
-
 def packed_weight(conv: nn.Conv2d) -> torch.Tensor:
     """[tap][ci/4][co][ci%4] copy of a Conv2d weight, cached on the module and refreshed when
     the parameter is modified in place or moved."""
@@ -204,17 +196,7 @@ WINO_GROUP = True
 
 
 def wino_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int) -> bool:
-    (v0, c0) = srcs[0]
-    if c0.kernel_size[0] != 3 or c0.stride[0] != 1 or pad_mode != PAD_ZEROS or cout % 32 or isinstance(v0, CatView):
-        return False
-    if len(srcs) > 1:  # fused second source: BasicBlock's 1x1 stride-1 projection (accumulated in the output domain)
-        (v1, c1) = srcs[1]
-        if c1.kernel_size[0] != 1 or c1.stride[0] != 1 or isinstance(v1, CatView):
-            return False
-    ty, tx = -(-Ho // 8), -(-Wo // 32)
-    if Ho * Wo < WINO_MIN_FILL * (ty * 8) * (tx * 32):
-        return False
-    return N * ty * tx * (cout // 32) >= WINO_MIN_TILES
+    return bool(select(srcs, cout, N, Ho, Wo, pad_mode).families & FAMILY_WINO)
 
 
 # Winograd F(4x4,3x3) (csrc/conv_wino4.hip, conv3x3_wino4_k) for the plain 3x3 layers: 1.78x fewer MFMAs than F(2x2); 32 x 8 pixel x 64
@@ -235,35 +217,9 @@ WINO4_MIN_FILL = 0.85
 
 
 def wino4_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int, act: int, out=None, res=None, slope: float = 0.2, any_size: bool = False) -> bool:
-    """Mirror of ``idh_conv::wino4_supported`` (csrc/conv_wino4.hip) plus the fill / tile-count rules.  ``out`` / ``res``: the views the op
-    writes / adds - their per-image byte sizes (with the channel stride of a wider concat buffer) are 32-bit buffer ranges in the kernel, so a
-    layer that exceeds them is planned onto F(2x2) / the direct kernels here instead of failing at run time with IDH_EUNSUPPORTED."""
-    (v0, c0) = srcs[0]
-    if c0.kernel_size[0] != 3 or c0.stride[0] != 1 or pad_mode != PAD_ZEROS or cout % 64 or isinstance(v0, CatView):
-        return False
-    if len(srcs) > 1:  # fused second source: BasicBlock's 1x1 stride-1 projection (accumulated in the pixel domain after the output transform)
-        (v1, c1) = srcs[1]
-        if not WINOGRAD4_PROJ or len(srcs) > 2 or c1.kernel_size[0] != 1 or c1.stride[0] != 1 or isinstance(v1, CatView):
-            return False
-    if act not in (ACT_NONE, ACT_LRELU, ACT_ELU) or (act == ACT_LRELU and not 0.0 <= slope <= 1.0) or c0.in_channels <= 16:  # (<= 16: the copy pipeline runs a pair of 8-channel stages ahead)
-        return False
-    if getattr(v0, "H", 0) * getattr(v0, "W", 0) * getattr(v0, "cs", 0) * 4 >= 1 << 30:  # (csrc: the halo's 32-bit offsets run a few rows past an image)
-        return False
-    for v in (out, res):  # output / residual image: 32-bit byte offsets
-        if v is not None and Ho * Wo * getattr(v, "cs", 0) * 4 >= 1 << 31:
-            return False
-    if len(srcs) > 1:
-        (v1, c1) = srcs[1]
-        if getattr(v1, "H", 0) * getattr(v1, "W", 0) * getattr(v1, "cs", 0) * 4 >= 1 << 31 or ((c1.in_channels + 15) // 16) * 4 * (((cout + 15) // 16) * 16) * 64 >= 1 << 31:
-            return False
-    if ((c0.in_channels + 15) // 16) * 4 * (((cout + 15) // 16) * 16) * 36 * 16 * 4 >= 1 << 31:  # packed weights
-        return False
-    if any_size:  # (the shape family alone: a caller that needs the same kernel - the same rounding - at every batch size)
-        return True
-    ty, tx = -(-Ho // 8), -(-Wo // 32)
-    if Ho * Wo < WINO4_MIN_FILL * (ty * 8) * (tx * 32):
-        return False
-    return N * ty * tx * (cout // 64) >= WINO4_MIN_TILES
+    """``idh_conv::wino4_supported`` (csrc/conv_wino4.hip) plus the fill / tile-count rules.  ``out`` / ``res``: the views the op writes / adds -
+    their per-image byte sizes are 32-bit buffer ranges in the kernel, so a layer that exceeds them is planned onto F(2x2) / the direct kernels."""
+    return bool(select(srcs, cout, N, Ho, Wo, pad_mode, act, slope, out, res, any_size=any_size).families & FAMILY_WINO4)
 
 
 SPLIT_CODE = {"f16x3": 11}  # IDH_SPLIT_F16X3 of include/idh_ops.h == the op's tile_m
@@ -311,24 +267,13 @@ SPLIT_MIN_BLOCKS = 256  # fewer 8x16x64 tiles than CUs: the fp32 kernels' finer 
 
 
 def split_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int) -> bool:
-    (v0, c0) = srcs[0]
-    if c0.kernel_size[0] != 3 or c0.stride[0] != 1 or pad_mode != PAD_ZEROS or cout % 64:
-        return False
-    if len(srcs) > 1 and (srcs[1][1].kernel_size[0] != 1 or srcs[1][1].stride[0] != 1):
-        return False  # the fused second source is a 1x1 projection (BasicBlock downsample at stride 1)
-    if Wo < 16 or Ho < 8:
-        return False
-    return N * (-(-Ho // 8)) * (-(-Wo // 16)) * (cout // 64) >= SPLIT_MIN_BLOCKS
+    return bool(select(srcs, cout, N, Ho, Wo, pad_mode).families & FAMILY_SPLIT)
 
 
 def choose_split_rows(N: int, Ho: int, Wo: int, cout: int) -> int:
     """16-row tiles (best weight-panel amortisation) when they fill 256 CUs x 3 resident workgroups
     without wasting rows, else 8-row tiles (twice the workgroups, no waste on 24-row maps)."""
-    def eff(rows, bonus):
-        ty = -(-Ho // rows)
-        blocks = N * ty * (-(-Wo // 16)) * (cout // 64)
-        return bonus * (Ho / (ty * rows)) * min(1.0, blocks / 768.0)
-    return 16 if Ho >= 16 and eff(16, 1.0) >= eff(8, 0.93) else 8
+    return select([(None, _conv_shape(16, 3))], cout, N, Ho, Wo).split_rows
 
 
 # Decoder concats: optionally fold the x2 upsampling (and the concat itself) into the consumer conv's halo loader
@@ -357,17 +302,7 @@ MIN_WAVES = 1024
 
 def lds_eligible(srcs, cout: int, Wo: int, pad_mode: int) -> bool:
     """Shape family of the LDS-staged kernel (csrc/conv.hip conv3x3_lds_k)."""
-    (v0, c0) = srcs[0]
-    if c0.kernel_size[0] != 3 or c0.stride[0] != 1 or cout % 16 or Wo < 16:
-        return False
-    if pad_mode != PAD_ZEROS and (pad_mode != PAD_REPLICATE or len(srcs) > 1):
-        return False
-    if len(srcs) > 1:
-        (v1, c1) = srcs[1]
-        strided3 = c1.kernel_size[0] == 3 and c1.stride[0] == 2 and pad_mode == PAD_ZEROS and cout % 32 == 0 and not isinstance(v1, CatView)
-        if not strided3 and (c1.kernel_size[0] != 1 or c1.stride[0] != 1):  # BasicBlock's downsample(x): 1x1, or 3x3 stride 2
-            return False
-    return True
+    return bool(select(srcs, cout, 1, 1, Wo, pad_mode).families & FAMILY_LDS)
 
 
 # A lone 3x3 stride-2 conv (conv1 of a stride-2 BasicBlock, layers.py:62-66) on the LDS-staged kernel's stride-2 loader (the one the strided
@@ -379,18 +314,13 @@ S2_FIRST_MIN_BLOCKS = 512
 
 
 def s2_first_eligible(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int) -> bool:
-    if not S2_FIRST or len(srcs) != 1:
-        return False
-    (v0, c0) = srcs[0]
-    if c0.kernel_size[0] != 3 or c0.stride[0] != 2 or pad_mode != PAD_ZEROS or cout % 32 or Wo < 16 or isinstance(v0, CatView):
-        return False
-    return N * (-(-Wo // 16)) * (-(-Ho // 4)) * (cout // (16 * lds_subtiles(cout))) >= S2_FIRST_MIN_BLOCKS
+    return bool(select(srcs, cout, N, Ho, Wo, pad_mode).families & FAMILY_S2_FIRST)
 
 
 def lds_subtiles(cout: int) -> int:
     """16-channel output sub-tiles per workgroup of the LDS-staged kernel (the op's tile_n): 64 channels when the
     layer has them, else 32 / 16 (the matching encoder's 128 -> 16 conv)."""
-    return 4 if cout % 64 == 0 else (2 if cout % 32 == 0 else 1)
+    return select([(None, _conv_shape(16, 3))], cout, 1, 1, 1).lds_subtiles
 
 
 # Small grids (one frame, low-resolution levels): halve the workgroup's channel tile (64 -> 32) when even 4-row tiles
@@ -417,27 +347,47 @@ def choose_lds_tile(N: int, Ho: int, Wo: int, cout: int, chunks: int):
     256 CUs x 3 resident workgroups, else 4-row tiles (code 9); split K only when the grid still
     cannot fill the chip AND every split keeps >= 6 chunks of 16 channels (measured on MI355X,
     tools/perf_conv_layers.py)."""
-    per_row_tiles = N * (-(-Wo // 16)) * (cout // (16 * lds_subtiles(cout)))
-    code, rows = 8, 8
-    if per_row_tiles * (-(-Ho // 8)) < 768:
-        code, rows = 9, 4
-    blocks = per_row_tiles * (-(-Ho // rows))
-    return code, max(1, min(-(-768 // blocks), chunks // SPLIT_MIN_CHUNKS, SPLIT_MAX))
+    ch = select([(None, _conv_shape(16 * chunks, 3))], cout, N, Ho, Wo)
+    return ch.lds_tile_m, ch.lds_split_k
 
 
 def choose_tiles(M: int, cout: int, steps: int):
-    nsub = ceil16(cout) // 16
-    tn = 4 if nsub % 4 == 0 else (2 if nsub % 2 == 0 else 1)
-    tm, waves = 1, 0
-    for cand in (4, 2, 1):
-        waves = -(-M // (16 * cand)) * (nsub // tn)
-        tm = cand
-        if waves >= TARGET_WAVES:
-            break
-    split = 1
-    if waves < MIN_WAVES:
-        split = max(1, min(-(-MIN_WAVES // waves), steps // 4, 32))
-    return tm, tn, split
+    ch = select([(None, _conv_shape(16 * steps, 1))], cout, 1, 1, M)
+    return ch.direct_tile_m, ch.direct_tile_n, ch.direct_split_k
+
+
+# --- the one kernel-selection rule: idh_conv_select (csrc/plan_select.hip), which the C++ plan builder calls too --------------------
+W_DIRECT, W_WINO, W_WINO4, W_SPLIT = 0, 1, 2, 3  # IDH_W_* of include/idh_ops.h
+FAMILY_WINO, FAMILY_WINO4, FAMILY_SPLIT, FAMILY_LDS, FAMILY_S2_FIRST = 1, 2, 4, 8, 16  # IDH_FAMILY_*
+SCHED_MERGE_LEVELS, SCHED_WINO_GROUP = 1, 2  # IDH_SCHED_*
+
+
+def _conv_shape(cin: int, ks: int, stride: int = 1):
+    """What ``select`` reads of an nn.Conv2d, for the choosers that are asked about a bare shape."""
+    import types
+
+    return types.SimpleNamespace(in_channels=cin, kernel_size=(ks, ks), stride=(stride, stride))
+
+
+def conv_tuning() -> "_lib.ConvTuning":
+    """``idh_conv_tuning`` from the module globals as they are NOW (tests and tools assign them and expect the next plan to see them)."""
+    return _lib.ConvTuning(WINOGRAD, WINOGRAD4, WINOGRAD4_PROJ, S2_FIRST, WINO_MIN_TILES, WINO4_MIN_TILES, SPLIT_MIN_BLOCKS, NARROW_TILE_BELOW,
+                           NARROWEST_TILE_BELOW, SPLIT_MIN_CHUNKS, SPLIT_MAX, S2_FIRST_MIN_BLOCKS, FUSED_UP_ROWS, TARGET_WAVES, MIN_WAVES, 0,
+                           WINO_MIN_FILL, WINO4_MIN_FILL, PROJ_CHUNK_WEIGHT)
+
+
+def select(srcs, cout: int, N: int, Ho: int, Wo: int, pad_mode: int = PAD_ZEROS, act: int = ACT_NONE, slope: float = 0.2, out=None, res=None,
+           norm: bool = False, any_size: bool = False, math: str = "fp32") -> "_lib.ConvChoice":
+    """``idh_conv_select`` for a conv of ``srcs`` = [(view, nn.Conv2d), ...] under the current tuning.  Of a view only H, W, cs are read and of a
+    conv only in_channels, kernel_size, stride - 0 where a shape-only stand-in has none."""
+    d = _lib.ConvDesc(N, Ho, Wo, cout, pad_mode, act, slope, getattr(out, "cs", 0), getattr(res, "cs", 0), res is not None, norm, any_size,
+                      SPLIT_CODE.get(math, 0), len(srcs))
+    for s, (v, cv) in zip(d.src, srcs):
+        s.H, s.W, s.cs, s.is_cat = getattr(v, "H", 0), getattr(v, "W", 0), getattr(v, "cs", 0), isinstance(v, CatView)
+        s.Cin, s.ks, s.stride = getattr(cv, "in_channels", 0), cv.kernel_size[0], cv.stride[0]
+    ch = _lib.ConvChoice()
+    _lib.check(_bind().idh_conv_select(C.byref(d), C.byref(conv_tuning()), C.byref(ch)), "idh_conv_select")
+    return ch
 
 
 class Plan:
@@ -497,35 +447,26 @@ class Plan:
         op.kind = OP_CONV
         op.N = x.N
         srcs = [(x, conv)] + ([(x2, conv2)] if x2 is not None else [])
-        steps = 0
-        use_split = self.math != "fp32" and split_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode)
-        use_wino = (WINOGRAD and self.math == "fp32" and norm is None and
-                    wino_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode))
-        use_wino4 = (WINOGRAD4 and self.math == "fp32" and norm is None and (x2 is None or res is None) and
-                     wino4_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode, act, out, res, slope, wino4_any_size))
-        if use_wino4:
-            use_wino = False
-        for i, (v, cv) in enumerate(srcs):
-            ks, st = cv.kernel_size[0], cv.stride[0]
+        for v, cv in srcs:
             if v.C != cv.in_channels:
                 raise _lib.IdhError(f"conv expects {cv.in_channels} input channels, view has {v.C}")
+        ch = select(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode, act, slope, out, res, norm is not None, wino4_any_size, self.math)
+        pack = (packed_weight, packed_wino_weight, packed_wino4_weight)
+        for i, (v, cv) in enumerate(srcs):
+            ks, st = cv.kernel_size[0], cv.stride[0]
             cat = v if isinstance(v, CatView) else None
             if cat is not None:
-                if use_split or not lds_eligible(srcs, conv.out_channels, out.W, pad_mode) or st != 1:
+                if ch.w_layout == W_SPLIT or not ch.families & FAMILY_LDS or st != 1:
                     raise _lib.IdhError("a fused-upsample concat can only feed the LDS-staged fp32 conv kernel")
                 if cat.direct.C % 16 or any(u.C != cat.ups[0].C or u.C % 16 or (2 * u.H, 2 * u.W) != (cat.H, cat.W) for u in cat.ups) or not 1 <= len(cat.ups) <= 2:
                     raise _lib.IdhError("fused-upsample concat: channel counts must be multiples of 16 and the maps exactly half size")
                 v = cat.direct
             elif v.C % 16 and (v.c0 != 0 or v.cs != ceil16(v.C)):
                 raise _lib.IdhError("a conv input whose channel count is not a multiple of 16 must be a whole zero-padded buffer")
-            if use_split:  # one blob: [3x3 panels][1x1 panels of the second source][scales]
+            if ch.w_layout == W_SPLIT:  # one blob: [3x3 panels][1x1 panels of the second source][scales]
                 w = split_packed_weight(conv, self.math, conv2)
-            elif use_wino4 and i == 0:
-                w = packed_wino4_weight(cv)
-            elif use_wino and i == 0:
-                w = packed_wino_weight(cv)
             else:
-                w = packed_weight(cv)
+                w = pack[ch.w_layout if i == 0 else W_DIRECT](cv)
             self.keep.append(w)
             s = op.src[i]
             cin = cat.C if cat is not None else v.C
@@ -535,7 +476,6 @@ class Plan:
                 s.up_c0, s.up_C = cat.direct.C, cat.ups[0].C
                 for ui, u in enumerate(cat.ups):
                     s.up_in[ui], s.up_cs[ui] = u.ptr, u.cs
-            steps += ks * ks * (ceil16(cin) // 16)
             self.flops += 2 * out.N * out.H * out.W * cv.out_channels * cv.in_channels * ks * ks
         bias = conv.bias
         if conv2 is not None and conv2.bias is not None:
@@ -550,31 +490,7 @@ class Plan:
         op.Ho, op.Wo, op.Cout = out.H, out.W, conv.out_channels
         op.act, op.slope = act, slope
         M = out.N * out.H * out.W
-        if use_split:
-            tm, tn, split = SPLIT_CODE[self.math], choose_split_rows(out.N, out.H, out.W, conv.out_channels), 1
-        elif use_wino4:
-            tm, tn, split = TILE_WINO4, 0, 1
-        elif use_wino:
-            tm, tn, split = TILE_WINO, 0, 1
-        elif lds_eligible(srcs, conv.out_channels, out.W, pad_mode):
-            # split-K factor from the chunk count in units of a 3x3 chunk: a 1x1 (projection) chunk is PROJ_CHUNK_WEIGHT of one
-            chunks = int(sum((ceil16(v.C) // 16) * (1.0 if cv.kernel_size[0] == 3 else PROJ_CHUNK_WEIGHT) for v, cv in srcs))
-            tm, split = choose_lds_tile(out.N, out.H, out.W, conv.out_channels, chunks)
-            if tm == 8 and FUSED_UP_ROWS == 4 and any(isinstance(v, CatView) for v, _ in srcs):
-                tm = 9
-            tn = lds_subtiles(conv.out_channels)
-            if tn == 4 and tm == 9 and NARROW_TILE_BELOW and not any(isinstance(v, CatView) for v, _ in srcs):
-                blocks64 = out.N * (-(-out.H // 4)) * (-(-out.W // 16)) * (conv.out_channels // 64) * split
-                if blocks64 < NARROW_TILE_BELOW:
-                    tn = 1 if blocks64 < NARROWEST_TILE_BELOW else 2
-            tn = 0 if tn == 4 else tn
-        elif self.math == "fp32" and norm is None and s2_first_eligible(srcs, conv.out_channels, out.N, out.H, out.W, pad_mode):
-            tm, split = choose_lds_tile(out.N, out.H, out.W, conv.out_channels, ceil16(x.C) // 16)
-            tn = lds_subtiles(conv.out_channels)
-            tn = 0 if tn == 4 else tn
-        else:
-            tm, tn, split = choose_tiles(M, conv.out_channels, steps)
-        op.tile_m, op.tile_n, op.split_k = tm, tn, split
+        op.tile_m, op.tile_n, op.split_k = tm, tn, split = ch.tile_m, ch.tile_n, ch.split_k
         if norm is not None:
             stats, n_act, n_slope = norm
             if tm not in (8, 9) or tn != 1 or x2 is not None or isinstance(x, CatView) or tuple(stats.shape) != (x.N, 2, x.C):
@@ -845,47 +761,25 @@ class Plan:
         — the reference executes them strictly one after another."""
         self.schedule_segments(0)
 
-    @staticmethod
-    def _launch_rank(op) -> tuple:
-        """Order of the ops of one dependency level, and which of them carry the level's group id (rank < 3):
-        4-row LDS convs first, by channel tile (one ``conv3x3_lds_group_k`` grid per run of equal tiles); then, with
-        ``MERGE_LEVELS``, the other members a mixed ``level_k`` launch can host (csrc/conv.hip: the stride-2 /
-        1x1 direct conv with 16x64 wave tiles, bilinear x2 upsampling); everything else runs on its own."""
-        if WINO_GROUP and op.kind == OP_CONV and op.tile_m == TILE_WINO:
-            # Winograd convs of a level share one persistent grid (conv3x3_wino_group_k): plain ones, then those with a fused
-            # 1x1 source; the largest first so that the small ones fill its tail
-            return (-1, 1 if op.src[1].in_ else 0, -op.N * op.Ho * op.Wo * op.Cout)
-        if op.kind == OP_CONV and op.tile_m == 9:
-            return (0, op.tile_n)
-        if MERGE_LEVELS and op.kind == OP_CONV and op.tile_m == 1 and op.tile_n == 4:
-            return (1, 0)
-        if MERGE_LEVELS and op.kind == OP_UPSAMPLE2:
-            return (2, 0)
-        if MERGE_LEVELS and op.kind == OP_IMPORT:
-            return (2, 1)  # the layout imports of a level: adjacent and under the level's group id -> one import_nchw_group_k grid when they are small
-        return (3, 0)
-
     def schedule_segments(self, n_first: int) -> int:
         """``schedule()`` for a plan that is replayed in two pieces — ops [0, n_first) then the rest — because a
         kernel outside the plan (the fused cost volume) consumes the first piece's output and produces the second
         piece's input.  Each piece is levelled on its own; returns the length of the first piece."""
         n = len(self.ops)
         n_first = max(0, min(int(n_first), n))
-        order: List[int] = []
-        level = [0] * n
-        for lo, hi in ((0, n_first), (n_first, n)):
-            for j in range(lo, hi):
-                mj = self.meta[j]
-                for i in range(lo, j):
-                    mi = self.meta[i]
-                    if _overlap(mi["writes"], mj["reads"]) or _overlap(mi["writes"], mj["writes"]) or _overlap(mi["reads"], mj["writes"]):
-                        level[j] = max(level[j], level[i] + 1)
-            order += sorted(range(lo, hi), key=lambda k: (level[k],) + self._launch_rank(self.ops[k]) + (k,))
-        for k in range(n):
-            self.ops[k].group = level[k] + 1 if self._launch_rank(self.ops[k])[0] < 3 else 0
-        self.ops = [self.ops[k] for k in order]
+        arr = (Op * n)(*self.ops)
+        regions, offs = [], [0]  # idh_schedule_ops: flat (buffer id, c0, c1) triples; op k reads [offs[2k], offs[2k+1]) and writes [offs[2k+1], offs[2k+2])
+        for m in self.meta:
+            for rs in (m["reads"], m["writes"]):
+                regions += [x for r in rs for x in r]
+                offs.append(len(regions) // 3)
+        order, levels = (C.c_int32 * n)(), (C.c_int32 * n)()
+        flags = (SCHED_MERGE_LEVELS if MERGE_LEVELS else 0) | (SCHED_WINO_GROUP if WINO_GROUP else 0)
+        _lib.check(_bind().idh_schedule_ops(arr, n, n_first, (C.c_uint64 * (len(regions) + 1))(*regions), (C.c_int32 * len(offs))(*offs), flags, order, levels),
+                   "idh_schedule_ops")
+        self.ops = list(arr)
         self.meta = [self.meta[k] for k in order]
-        self.levels = [level[k] for k in order]
+        self.levels = list(levels)
         pos = [0] * n
         for new, old in enumerate(order):
             pos[old] = new

@@ -8,9 +8,10 @@
  *   idh_cvencoder_fwd     replaces CVEncoder.forward             modules/networks.py:186-215
  *   idh_unetpp_fwd        replaces BDDecoderPP / DepthDecoderPP  modules/networks.py:20-84, 118-183 (+ upsample, utils/generic_utils.py:94-103)
  *
- * Each is a thin host-side builder (csrc/networks.hip) over idh_run_ops: it lays the network out as idh_op descriptors — the same kernel
- * selection (Winograd F(4x4) / F(2x2) / LDS-staged / direct by tile counts), concat elimination, split-K, level scheduling and activation-buffer
- * reuse as nhwc.py's Plan with its default thresholds, so results are bit-identical to the Python drop-ins — and submits them on the caller's
+ * Each is a thin host-side builder (csrc/networks.hip) over idh_run_ops: it lays the network out as idh_op descriptors — kernel selection
+ * (Winograd F(4x4) / F(2x2) / LDS-staged / direct by tile counts), split-K and level scheduling by idh_conv_select / idh_schedule_ops
+ * (idh_ops.h) with the default tuning, the functions nhwc.py's Plan calls too, and the same concat elimination and activation-buffer
+ * reuse, so results are bit-identical to the Python drop-ins — and submits them on the caller's
  * stream.  No device allocation, no synchronisation: the caller passes
  *   - a WEIGHT BLOB filled once per (parameters, shape) by the matching *_pack call (packed weights in the layout each layer's kernel reads +
  *     summed biases; the layouts depend on the kernel selection, hence on N / H / W), and

@@ -13,6 +13,7 @@
 #ifndef IDH_OPS_H_
 #define IDH_OPS_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -115,7 +116,7 @@ typedef struct idh_op {
                                stride-1 projection of an output-sized tensor, no up / norm); there tile_n = 8
                                selects 8-row instead of 16-row tiles (0 / 16: 16 rows; other values: IDH_EUNSUPPORTED) */
     int32_t group;        /* != 0: consecutive CONV / UPSAMPLE2 ops with the same id are mutually independent (one
-                               dependency level of the plan, see Plan.schedule in nhwc.py) and may be launched as
+                               dependency level of the plan, see idh_schedule_ops below) and may be launched as
                                ONE grid: runs of 4-row LDS convs with equal channel tiles always are; a mixed run
                                (4-row LDS convs with 64- / 32-channel tiles, the 16x64-tile direct conv, bilinear
                                upsampling) is when each member has <= 512 workgroups, i.e. at small batch */
@@ -206,6 +207,68 @@ int idh_count_launches(const idh_op *ops_host, int n);
  * A request the LDS kernel does not cover (tile_m = 8 / 9 with Wo < 16, a Cout its channel tile does not divide, ...) is not an error: it
  * runs on the direct kernel, and only this query tells. */
 int idh_conv_variant(const idh_op *op, int32_t out[8]);
+
+/* Kernel selection of one IDH_OP_CONV (ABI >= 111; csrc/plan_select.hip: host only, no device access, usable without a GPU).  THE rule
+ * of the library: nhwc.Plan.conv and the C++ plan builder behind include/idh_net.h / idh_model.h both fill a descriptor and take the
+ * answer, so the two produce the same op for the same layer by construction. */
+typedef struct idh_conv_desc_src {
+    int32_t H, W, cs;        /* the source view; 0 where unknown (a size that is 0 passes the 32-bit range checks) */
+    int32_t Cin, ks, stride; /* ks 1 / 3; Cin 0: unknown (then never F(4x4)) */
+    int32_t is_cat, _r;      /* a fused-upsample concat source (idh_conv_src.up_in) */
+} idh_conv_desc_src;
+
+typedef struct idh_conv_desc {
+    int32_t N, Ho, Wo, Cout, pad_mode, act;
+    float slope;
+    int32_t out_cs, res_cs, has_res; /* channel strides of the output / residual tensors (0: unknown) */
+    int32_t has_norm;                /* source 0 is normalised on load (idh_conv_src.norm) */
+    int32_t any_size;                /* F(4x4) for its whole shape family, whatever the tile count (batch-size-independent rounding) */
+    int32_t math;                    /* 0 = fp32, IDH_SPLIT_F16X3 */
+    int32_t n_src;                   /* 1 / 2 */
+    idh_conv_desc_src src[2];
+} idh_conv_desc;
+
+/* Every knob that shapes the choice; the shipped values and their measurements are the module globals of nhwc.py of the same names. */
+typedef struct idh_conv_tuning {
+    int32_t winograd, winograd4, winograd4_proj, s2_first; /* switches */
+    int32_t wino_min_tiles, wino4_min_tiles, split_min_blocks, narrow_tile_below, narrowest_tile_below, split_min_chunks, split_max,
+        s2_first_min_blocks, fused_up_rows, target_waves, min_waves, _r;
+    double wino_min_fill, wino4_min_fill, proj_chunk_weight;
+} idh_conv_tuning;
+void idh_conv_tuning_defaults(idh_conv_tuning *t);
+
+#define IDH_W_DIRECT 0 /* idh_pack_conv_weight */
+#define IDH_W_WINO 1   /* idh_pack_conv_weight_wino */
+#define IDH_W_WINO4 2  /* idh_pack_conv_weight_wino4 */
+#define IDH_W_SPLIT 3  /* idh_pack_conv_weight_split (one blob for both sources) */
+#define IDH_FAMILY_WINO 1 /* shape families the layer belongs to, whichever of them the cascade picks */
+#define IDH_FAMILY_WINO4 2
+#define IDH_FAMILY_SPLIT 4
+#define IDH_FAMILY_LDS 8
+#define IDH_FAMILY_S2_FIRST 16
+
+typedef struct idh_conv_choice {
+    int32_t tile_m, tile_n, split_k; /* what the idh_op carries */
+    int32_t w_layout;                /* IDH_W_*: packed layout of src[0].w (the other source: IDH_W_DIRECT, or the same blob for IDH_W_SPLIT) */
+    int32_t families;                /* IDH_FAMILY_* bits */
+    /* the choosers on their own, whatever family wins: LDS-staged kernel (0 unless Cout % 16 == 0), split-precision tile rows, direct kernel */
+    int32_t lds_tile_m, lds_split_k, lds_subtiles, split_rows, direct_tile_m, direct_tile_n, direct_split_k;
+} idh_conv_choice;
+
+/* IDH_EINVAL: NULL desc / out, n_src not 1 / 2, ks not 1 / 3, non-positive N / Ho / Wo / Cout, a negative size of a source, an unknown math, tuning->split_min_chunks < 1.  tuning == NULL: the defaults. */
+int idh_conv_select(const idh_conv_desc *desc, const idh_conv_tuning *tuning, idh_conv_choice *out);
+/* sizeof of the three structs as compiled into the library: out = { desc, tuning, choice } */
+void idh_sizeof_conv_select(size_t out[3]);
+
+/* The level scheduler of a plan (ABI >= 111; host only): ops [0, n_first) and [n_first, n) are two segments, each levelled on its own (a kernel
+ * outside the plan may run between them).  An op's level = 1 + the highest level of an earlier op of its segment it depends on (read after write,
+ * write after write, write after read of overlapping regions); each segment is sorted IN PLACE by (level, launch rank, build index), and `group`
+ * is set to level + 1 for the ops a grouped launch can host (idh_op.group) and to 0 for the others.  Regions are (buffer id, first channel,
+ * one-past-last channel) triples in `regions`; op k reads regions [offsets[2k], offsets[2k+1]) and writes [offsets[2k+1], offsets[2k+2]).
+ * order[i] (optional) = the build index of the op now at position i, levels[i] (optional) = its level. */
+#define IDH_SCHED_MERGE_LEVELS 1 /* the direct 16x64-tile conv, bilinear upsampling and layout imports of a level join its group (level_k) */
+#define IDH_SCHED_WINO_GROUP 2   /* the F(2x2) convs of a level lead it, under its group id (conv3x3_wino_group_k) */
+int idh_schedule_ops(idh_op *ops, int n, int n_first, const uint64_t *regions, const int32_t *offsets, int flags, int32_t *order, int32_t *levels);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -233,23 +233,21 @@ def test_network_entry_point_size_queries_run_without_a_gpu():
 
 
 def test_cpp_plan_builder_mirrors_the_python_thresholds():
-    """csrc/networks.hip (the C++ twin of nhwc.Plan behind idh_basic_block_fwd / idh_cvencoder_fwd / idh_unetpp_fwd) carries the kernel-selection
-    thresholds as constants: they must equal nhwc.py's defaults, or the two builders stop producing the same op lists."""
-    from implicit_depth_amd import nhwc
+    """Both plan builders take kernel, tile and split-K from idh_conv_select; csrc/networks.hip (behind idh_basic_block_fwd / idh_cvencoder_fwd /
+    idh_unetpp_fwd / idh_model_fwd) asks with the library's default tuning, nhwc.Plan with its module globals: every field of
+    idh_conv_tuning_defaults() must equal nhwc.py's default of the same name, or the two stop producing the same op lists."""
+    from implicit_depth_amd import _lib, nhwc
 
+    t = _lib.ConvTuning()
+    _lib.lib().idh_conv_tuning_defaults(ctypes.byref(t))
+    names = [n for n, _ in _lib.ConvTuning._fields_ if n != "_r"]
+    assert len(names) == 18
+    for n in names:
+        assert getattr(t, n) == getattr(nhwc, n.upper()), n
+        assert getattr(nhwc.conv_tuning(), n) == getattr(t, n), n
     src = open(os.path.join(ROOT, "implicit-depth_amd", "csrc", "networks.hip")).read()
-
-    def const(name):
-        m = re.search(rf"\b{name}\s*=\s*([0-9.]+(?:ll)?(?:\s*<<\s*[0-9]+)?)", src)
-        assert m, name
-        return eval(m.group(1).replace("ll", ""))
-
-    assert const("kWinoMinTiles") == nhwc.WINO_MIN_TILES and const("kWinoMinFill") == nhwc.WINO_MIN_FILL
-    assert const("kWino4MinTiles") == nhwc.WINO4_MIN_TILES and const("kWino4MinFill") == nhwc.WINO4_MIN_FILL
-    assert const("kReuseMinBytes") == nhwc.REUSE_MIN_BYTES and const("kNarrowTileBelow") == nhwc.NARROW_TILE_BELOW
-    assert const("kSplitMinChunks") == nhwc.SPLIT_MIN_CHUNKS and const("kSplitMax") == nhwc.SPLIT_MAX
-    assert const("kProjChunkWeight") == nhwc.PROJ_CHUNK_WEIGHT and const("kS2FirstMinBlocks") == nhwc.S2_FIRST_MIN_BLOCKS
-    assert const("kTargetWaves") == nhwc.TARGET_WAVES and const("kMinWaves") == nhwc.MIN_WAVES
+    m = re.search(r"\bkReuseMinBytes\s*=\s*([0-9]+)ll\s*<<\s*([0-9]+)", src)
+    assert m and int(m.group(1)) << int(m.group(2)) == nhwc.REUSE_MIN_BYTES
     # switches the C++ builder assumes at their defaults
     assert (nhwc.WINOGRAD, nhwc.WINOGRAD4, nhwc.WINOGRAD4_PROJ, nhwc.BUFFER_REUSE, nhwc.S2_FIRST, nhwc.MERGE_LEVELS, nhwc.WINO_GROUP) == (True,) * 7
     assert (nhwc.FUSE_UPSAMPLE, nhwc.PROJ_LOWRES, nhwc.NARROWEST_TILE_BELOW, nhwc.DEFAULT_MATH) == (False, False, 0, "fp32")

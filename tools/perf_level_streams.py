@@ -20,7 +20,7 @@ torch.cuda.synchronize()
 ent = next(iter(wl.model._plans.values()))
 p, n_head = ent["plan"], ent["n_head_ops"]
 n = len(p.ops)
-# launch classes inside a level, in the scheduler's order (Plan._launch_rank): F(2x2) group | 4-row LDS group (+ level_k members) | the rest one by one
+# launch classes inside a level, in the scheduler's order (idh_schedule_ops): F(2x2) group | 4-row LDS group (+ level_k members) | the rest one by one
 levels = []
 i = n_head
 while i < n:
@@ -28,8 +28,8 @@ while i < n:
     while j < n and p.levels[j] == p.levels[i]: j += 1
     cls, k = [], i
     def key(q):
-        r = nhwc.Plan._launch_rank(p.ops[q])[0]
-        return "w" if r == -1 else "g" if r < 3 else f"s{q}"
+        op = p.ops[q]  # (group != 0: a member of its level's grouped launches; the F(2x2) convs lead the level)
+        return "w" if op.group and op.kind == nhwc.OP_CONV and op.tile_m == nhwc.TILE_WINO else "g" if op.group else f"s{q}"
     while k < j:
         m = k + 1
         while m < j and key(m) == key(k): m += 1
