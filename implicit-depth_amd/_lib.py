@@ -101,6 +101,19 @@ class IngestDepthArgs(C.Structure):
         self.struct_size = C.sizeof(IngestDepthArgs)
 
 
+class Bank(C.Structure):
+    """ctypes mirror of ``idh_bank`` (include/idh_bank.h, keyframe feature bank)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("feats", C.c_void_p), ("mats", C.c_void_p), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("C", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(Bank)
+
+
+BANK_MAX_SLOTS, BANK_MAX_VIEWS = 64, 1024  # IDH_BANK_MAX_*
+
 RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
@@ -212,6 +225,9 @@ _SIGS = {
     "idh_sizeof_ingest_depth_args": (C.c_size_t, []),
     "idh_ingest_color_fwd": (C.c_int, [C.POINTER(IngestColorArgs), C.c_void_p]),
     "idh_ingest_depth_fwd": (C.c_int, [C.POINTER(IngestDepthArgs), C.c_void_p]),
+    "idh_sizeof_bank": (C.c_size_t, []),
+    "idh_bank_commit_fwd": (C.c_int, [C.POINTER(Bank), C.c_int, f32p, f32p, f32p, f32p, C.c_void_p]),
+    "idh_bank_gather_fwd": (C.c_int, [C.POINTER(Bank), C.POINTER(C.c_int32), f32p, f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -254,7 +270,8 @@ def lib():
         if h.idh_sizeof_composite_args() != C.sizeof(CompositeArgs):
             raise IdhError(f"{LIB_PATH}: sizeof(idh_composite_args) = {h.idh_sizeof_composite_args()} in the library, {C.sizeof(CompositeArgs)} in this binding")
         for what, got, mirror in (("idh_ingest_color_args", h.idh_sizeof_ingest_color_args(), IngestColorArgs),
-                                  ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs)):
+                                  ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs),
+                                  ("idh_bank", h.idh_sizeof_bank(), Bank)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

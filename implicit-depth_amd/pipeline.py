@@ -134,7 +134,8 @@ class HotPath(nn.Module):
                 return_mask: bool = False, return_features: bool = False,
                 prior_inputs: Optional[Dict[str, torch.Tensor]] = None, infer_depth: bool = False,
                 matching_layer1: Optional[torch.Tensor] = None, return_matching_feats: bool = False,
-                frame_chain: Optional[Dict[str, torch.Tensor]] = None, matching_images: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                frame_chain: Optional[Dict[str, torch.Tensor]] = None, matching_images: Optional[torch.Tensor] = None,
+                matching_nhwc: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """``matching_layer1`` (B, K+1, 64, H, W): output of the matching backbone (conv1..layer1 of the ResNet18,
         third-party, run by the caller) for frame b's current image followed by its K source images — the order
         reference bd_model.py:149-160 builds; contiguous or channels-last per image
@@ -154,8 +155,18 @@ class HotPath(nn.Module):
         sigmoid and pose are the next call's chain start).
         ``matching_images`` (B, K+1, 3, h, w): instead of ``matching_layer1``, the raw images in the same order; the matching encoder's
         ResNet18 stem (conv1 .. layer1, backbone.py) then runs natively inside this call as well, the whole encoder in the same plan.
-        Needs a ``matching_model`` whose ``net[:5]`` passes ``backbone.stem_is_native_eligible`` (eval mode)."""
+        Needs a ``matching_model`` whose ``net[:5]`` passes ``backbone.stem_is_native_eligible`` (eval mode).
+        ``matching_nhwc`` = (cur (B,H,W,C), src (B,K,H,W,C)): FINISHED matching features that are already channels-last and contiguous
+        (``FeatureBank.gather``'s output, ``ResnetMatchingEncoder(..., channels_last=True)``); the volume kernel reads them in place, with no
+        layout import.  Excludes the four other forms."""
         _lib.require_cuda_f32(matching_cur_feats, matching_src_feats, matching_layer1, matching_images, src_cam_T_cur_cam, src_K, cur_invK, rendered_depth, prior, *cur_feats)
+        if matching_nhwc is not None:
+            if matching_cur_feats is not None or matching_src_feats is not None or matching_layer1 is not None or matching_images is not None:
+                raise _lib.IdhError("pass one of finished matching features (NCHW or matching_nhwc), matching_layer1 or matching_images")
+            cur_n, src_n = matching_nhwc
+            _lib.require_cuda_f32(cur_n, src_n)
+            if src_n.dim() != 5 or tuple(cur_n.shape) != (src_n.shape[0], *src_n.shape[2:]) or not (cur_n.is_contiguous() and src_n.is_contiguous()):
+                raise _lib.IdhError(f"matching_nhwc must be contiguous (B,H,W,C) and (B,K,H,W,C), got {tuple(cur_n.shape)} and {tuple(src_n.shape)}")
         head = None
         head_ch = 0
         images = None
@@ -188,6 +199,8 @@ class HotPath(nn.Module):
                 head = "nhwc"
             else:
                 l1, head = l1.contiguous(), "nchw"
+        elif matching_nhwc is not None:
+            B, K, H, W, C = src_n.shape
         else:
             B, K, C, H, W = matching_src_feats.shape
         dev = src_K.device
@@ -204,12 +217,15 @@ class HotPath(nn.Module):
         if head is not None:
             p.set_in(ent["i_l1"], l1)
             p.run(0, ent["n_head_ops"])
+        elif matching_nhwc is not None:
+            pass  # read in place below
         elif not zero_volume:
             mc = matching_cur_feats if matching_cur_feats.is_contiguous() else matching_cur_feats.contiguous()
             ms = matching_src_feats if matching_src_feats.is_contiguous() else matching_src_feats.contiguous()
             _lib.check(L.idh_nchw_to_nhwc_f32(mc.data_ptr(), st["cur_n"].data_ptr(), B, C, H * W, sp), "idh_nchw_to_nhwc_f32")
             _lib.check(L.idh_nchw_to_nhwc_f32(ms.data_ptr(), st["src_n"].data_ptr(), B * K, C, H * W, sp), "idh_nchw_to_nhwc_f32")
-        cur_ptr, src_ptr, dims, cbs, sbs = ent["feats"]
+        feats = ent["feats"] if matching_nhwc is None else (cur_n.data_ptr(), src_n.data_ptr(), (B, K, C, H, W), 0, 0)
+        cur_ptr, src_ptr, dims, cbs, sbs = feats
 
         # 1. cost volume, written NHWC straight into the CVEncoder's input buffer
         lowest = torch.empty(B, H, W, device=dev)
@@ -226,7 +242,7 @@ class HotPath(nn.Module):
                                                     self.min_depth, self.max_depth, B, K, C, H, W, D, ent["cv_in"].ptr, ent["cv_in"].cs,
                                                     lowest.data_ptr(), st["planes"].data_ptr(), opts, sp), "idh_cost_volume_dot_ex_fwd")
         else:
-            lowest, mask = self.cost_volume.fused_into(ent["cv_in"], st, ent["feats"], src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK,
+            lowest, mask = self.cost_volume.fused_into(ent["cv_in"], st, feats, src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK,
                                                        self.min_depth, self.max_depth, return_mask)
 
         # 2. CVEncoder + UNet++ decoder: one idh_run_ops call

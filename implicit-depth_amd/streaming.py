@@ -1,0 +1,145 @@
+"""A live sequence: ``StreamingSession`` joins frame ingest, the keyframe buffer, the feature bank and the fused forward.
+
+The reference builds its test tuples off line (data_scripts/generate_test_tuples.py:161-212: ``KeyframeBuffer`` over a scan's poses) and
+its forward runs the matching encoder on the current image AND the K source images of every tuple (bd_model.py:149-160).  In a stream
+the K source views are keyframes whose features were computed when they were the current frame.  Per frame the session
+
+1. asks ``keyframes.KeyframeBuffer`` (the host pose decides: return codes 0-5); a frame the buffer does not store costs nothing more;
+2. runs the matching encoder (native stem, layer1 and head) on the ONE current image, channels-last;
+3. commits its features, poses and ``K_s1`` to the ``FeatureBank`` slot the buffer handed out;
+4. on a new keyframe selects K measurement slots - the reference's choice in the reference's order - and gathers them in one launch;
+5. runs ``HotPath`` from the finished channels-last features (``matching_nhwc``): volume, CVEncoder, decoder, occlusion MLP / depth heads.
+
+With ``use_prior`` the previous prediction's ``sigmoid(pred_0)`` and ``cam_T_world`` are carried to the next prediction
+(inference/inference.py:139-157).  The image encoder stays the model's own torch module, as in ``dropin.fused_forward``.
+
+Mode ``"keyframe"`` predicts on return code 1 only, as the DVMVS buffer intends (``default_dvmvs_tuples``).  The reference's dense rule
+(``dense_dvmvs_tuples``, generate_test_tuples.py:264-336) is NOT provided: for every frame it walks back over ALL earlier frames with a
+fresh ``OfflineKeyframeBuffer`` until 30 of them are accepted, so any earlier frame - keyframe or not, arbitrarily far back when the camera
+moves slowly - can be a source view; a ring that keeps the features of the last N keyframes cannot serve that choice."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, keyframes
+from .feature_bank import FeatureBank
+from .pipeline import HotPath
+
+MODES = ("keyframe",)
+
+
+class StreamingSession:
+    """``model``: a reference ``BDModel`` / ``DepthModel`` (converted in place by ``dropin.hot_path_of``; its ``encoder`` is the image
+    encoder) or a ``HotPath`` with a ``matching_model`` (then pass ``image_encoder``).  The matching encoder's stem must be eligible for
+    the native kernels (``backbone.stem_is_native_eligible``).  ``num_source_views``: K; read off an MLP feature volume, required for the
+    dot-product volume.  ``buffer_size``: keyframes kept (the ring's slots, at most 64 and more than K); ``config``: the DVMVS thresholds."""
+
+    def __init__(self, model: nn.Module, num_source_views: Optional[int] = None, buffer_size: Optional[int] = None, mode: str = "keyframe",
+                 config=keyframes.DVMVS_Config, image_encoder: Optional[nn.Module] = None, math: Optional[str] = None):
+        if mode not in MODES:
+            raise _lib.IdhError(f"mode must be one of {MODES}, got {mode!r} (the reference's dense tuples cannot be served from a keyframe "
+                                "ring: see the module docstring)")
+        self._model = None
+        if isinstance(model, HotPath):
+            self.hot, self.image_encoder = model, image_encoder
+            use_prior = bool(getattr(model.binary_mlp, "use_prior", False))
+        else:
+            from .dropin import hot_path_of
+
+            if getattr(getattr(model, "run_opts", None), "matching_scale", 1) != 1:
+                raise _lib.IdhError("the streaming session covers matching_scale = 1, as dropin.fused_forward")
+            self._model = model
+            self.hot = hot_path_of(model, math=math, native_matching_stem=True)
+            self.image_encoder = image_encoder if image_encoder is not None else model.encoder
+            use_prior = bool(getattr(getattr(model, "run_opts", None), "use_prior", False)) and self.hot.binary_mlp is not None
+        if self.image_encoder is None:
+            raise _lib.IdhError("StreamingSession(HotPath) needs image_encoder=...")
+        if self.hot.matching_model is None:
+            raise _lib.IdhError("StreamingSession needs a ResnetMatchingEncoder (HotPath(matching_model=...))")
+        from .nhwc import require_native_stem
+
+        require_native_stem(self.hot.matching_model)
+        self.use_prior = use_prior
+        K = getattr(self.hot.cost_volume, "num_source_views", None) or num_source_views
+        if K is None:
+            raise _lib.IdhError("num_source_views is required for a dot-product cost volume")
+        if num_source_views is not None and int(num_source_views) != int(K):
+            raise _lib.IdhError(f"the feature volume was built for {K} source views, got num_source_views={num_source_views}")
+        self.K = int(K)
+        size = config.test_keyframe_buffer_size if buffer_size is None else int(buffer_size)
+        if not self.K < size <= _lib.BANK_MAX_SLOTS:
+            raise _lib.IdhError(f"buffer_size must be in ({self.K}, {_lib.BANK_MAX_SLOTS}]: K source views plus the current keyframe, got {size}")
+        self.mode = mode
+        self.buffer = keyframes.KeyframeBuffer.from_config(config, buffer_size=size)
+        self.bank: Optional[FeatureBank] = None
+        self.frame_index = 0
+        self.last_code: Optional[int] = None
+        self.last_slots: Optional[Tuple[int, ...]] = None    # ring slots of the last prediction's source views, in order
+        self.last_indices: Optional[Tuple[int, ...]] = None  # their frame numbers
+        self.last_matching: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # (cur (1,H,W,C), src (1,K,H,W,C)) of the last prediction
+        self._prior: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+
+    def reset(self) -> None:
+        """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
+        self.buffer = keyframes.KeyframeBuffer(self.buffer.buffer_size, self.buffer.keyframe_pose_distance, self.buffer.optimal_t_score,
+                                               self.buffer.optimal_R_score)
+        self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
+
+    def step(self, cur_data: Dict[str, torch.Tensor], world_T_cam=None, dist_to_last_valid=None, return_mask: bool = False,
+             infer_depth: bool = False) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
+        """``cur_data``: what ``FrameIngest`` returns for ONE frame (``image_b3hw``, ``world_T_cam_b44``, ``cam_T_world_b44``, ``K_s0/s1_b44``,
+        ``invK_s0/s1_b44``; for a BDModel also ``rendered_depth``).  ``world_T_cam``: the same pose as a (4,4) host array, in the dtype the
+        selection is to be computed in - the keyframe decision is taken on the host; without it the pose is read back from the device, which synchronises.
+        Returns ``(outputs, code)``: the output dictionary of ``fused_forward`` when a prediction is due, else None - first frame, not enough
+        motion, no pose, tracking lost, or fewer than K keyframes stored so far; ``code`` is the buffer's return code either way."""
+        image = cur_data["image_b3hw"]
+        if image.dim() != 4 or image.shape[0] != 1:
+            raise _lib.IdhError(f"step() takes one frame: image_b3hw must be (1,3,h,w), got {tuple(image.shape)}")
+        if world_T_cam is None:
+            world_T_cam = cur_data["world_T_cam_b44"][0].detach().cpu().numpy()
+        pose = np.asarray(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else world_T_cam)  # dtype kept: the reference's arithmetic is its caller's
+        if pose.shape != (4, 4):
+            raise _lib.IdhError(f"world_T_cam {pose.shape} must be (4,4)")
+        index = self.frame_index
+        self.frame_index += 1
+        code = self.last_code = self.buffer.try_new_keyframe(pose, dist_to_last_valid, index=index)
+        if code == keyframes.CODE_TRACKING_LOST:
+            self._prior = None  # the previous prediction belongs to a track that ended
+        slot = self.buffer.stored_slot
+        if slot is None:
+            return None, code
+        from .nhwc import matching_encoder_forward
+
+        with torch.inference_mode():
+            cur_n = matching_encoder_forward(self.hot.matching_model, image, channels_last=True)  # (1,H,W,C)
+            _, H, W, C = cur_n.shape
+            if self.bank is None or (self.bank.H, self.bank.W, self.bank.C) != (H, W, C) or self.bank.device != cur_n.device:
+                self.bank = FeatureBank(self.buffer.buffer_size, H, W, C, device=cur_n.device)
+            self.bank.commit(slot, cur_n, cur_data["world_T_cam_b44"], cur_data["cam_T_world_b44"], cur_data["K_s1_b44"])
+            if code != keyframes.CODE_KEYFRAME or len(self.buffer) - 1 < self.K:
+                return None, code
+            frames = self.buffer.get_best_measurement_frames(self.K)
+            self.last_slots, self.last_indices = tuple(s for _, s, _ in frames), tuple(i for _, _, i in frames)
+            g = self.bank.gather([self.last_slots], cur_data["world_T_cam_b44"], cur_data["cam_T_world_b44"])
+            self.last_matching = (cur_n, g["src_nhwc"])
+            kw = {}
+            if self.hot.binary_mlp is not None:
+                kw["rendered_depth"], kw["infer_depth"] = cur_data["rendered_depth"], infer_depth
+                if self.use_prior and self._prior is not None:
+                    kw["prior_inputs"] = {"prior_prediction": self._prior[0], "prior_cam_T_world": self._prior[1],
+                                          "world_T_cam_b44": cur_data["world_T_cam_b44"], "K_s0_b44": cur_data["K_s0_b44"],
+                                          "invK_s0_b44": cur_data["invK_s0_b44"]}
+            if self._model is not None:
+                self.hot.thresholder = getattr(self._model, "thresholder", None)
+            cur_feats = list(self.image_encoder(image))
+            out = self.hot(None, None, cur_feats, g["src_E"], g["src_poses"], g["src_K"], cur_data["invK_s1_b44"], return_mask=return_mask,
+                           matching_nhwc=self.last_matching, **kw)
+            if self.use_prior and "pred_0" in out:
+                self._prior = (torch.sigmoid(out["pred_0"]), cur_data["cam_T_world_b44"])  # sigmoid_custom(x, 1.0), inference.py:154
+        if "prior_mask" in out:
+            cur_data["prior_mask"] = out.pop("prior_mask")  # as fused_forward: run_mlp_val stores it on the inputs (bd_model.py:431)
+        return out, code

@@ -450,3 +450,40 @@ def static_vertex_scene(height: int, width: int, step: int = 4):
     verts = torch.tensor(corners + pts, dtype=torch.float64).float()
     faces = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int64)
     return verts, faces, torch.eye(4)[None], Km.float()[None]
+
+
+KEYFRAME_TRAJECTORIES = ("orbit", "nan_gap", "jump", "stream12")
+
+
+def keyframe_trajectory(kind: str, seed: int = 0):
+    """A camera track for the keyframe buffer (keyframes.py): ``world_T_cam`` (T,4,4) float64 and the per-frame ``dist_to_last_valid``
+    list ``try_new_keyframe`` takes (None entries: not given).  The camera orbits a point 1.5 m in front of it, with a seeded jitter of a
+    few millimetres.  ``orbit``: 120 poses, 0.02 rad a frame (a keyframe about every third frame); ``nan_gap``: the same with poses
+    50..89 NaN, ten more than the tracking-lost threshold; ``jump``: ``dist_to_last_valid`` is 1 except 45 at frame 60, where the camera
+    also moves 3 m; ``stream12``: 12 poses at 0.08 rad a frame (every frame a keyframe) except frame 6, which repeats frame 5 within a
+    millimetre, and frame 9, whose pose is NaN."""
+    if kind not in KEYFRAME_TRAJECTORIES:
+        raise ValueError(f"kind must be one of {KEYFRAME_TRAJECTORIES}, got {kind!r}")
+    T, step = (12, 0.08) if kind == "stream12" else (120, 0.02)
+    jitter = _rng(seed, "keyframe_" + kind).standard_normal(size=(T, 3)) * 0.004
+    poses = np.empty((T, 4, 4), dtype=np.float64)
+    back = np.eye(4)
+    back[2, 3] = -1.5
+    for t in range(T):
+        if kind == "stream12" and t == 6:
+            w = poses[5].copy()
+            w[:3, 3] += jitter[t] * 0.25
+        else:
+            w = _rot_y(step * t).numpy() @ back
+            w[:3, 3] += jitter[t]
+        if kind == "jump" and t >= 60:
+            w[0, 3] += 3.0
+        poses[t] = w
+    dists = [None] * T
+    if kind == "nan_gap":
+        poses[50:90] = np.nan
+    elif kind == "jump":
+        dists = [45 if t == 60 else 1 for t in range(T)]
+    elif kind == "stream12":
+        poses[9] = np.nan
+    return poses, dists
