@@ -229,6 +229,9 @@ _SIGS = {
     "idh_bank_commit_fwd": (C.c_int, [C.POINTER(Bank), C.c_int, f32p, f32p, f32p, f32p, C.c_void_p]),
     "idh_bank_gather_fwd": (C.c_int, [C.POINTER(Bank), C.POINTER(C.c_int32), f32p, f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_void_p]),
     "idh_sample_prior_fwd": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
+    "idh_binary_mlp_rays_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_float, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_void_p]),
+    "idh_project_points_fwd": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
         [f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_float] + [C.c_int] * 6 + [f32p, C.c_int, f32p, f32p, C.c_void_p],
@@ -257,7 +260,10 @@ def lib():
             )
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in _all_sigs().items():
-            fn = getattr(h, name)
+            try:
+                fn = getattr(h, name)
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd) are found missing here
+                raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
         # the ABI this mirror was written against (include/idh.h): struct layouts, tile codes and packed-weight layouts changed at these versions

@@ -11,6 +11,8 @@ extern "C" int idh_version(void) { return 111; }  // 101: idh_volume_opts.scratc
                                                    // 109: idh_binary_mlp_f16x3_fwd and the three search entry points refuse a feature base that is not 16-byte aligned (they read rows with dwordx4 loads)
                                                    // 110: tile_m = IDH_SPLIT_F16X3 refuses a second source that is not a plain 1x1 stride-1 projection (a 3x3 stride-2 one was accepted and computed wrongly)
                                                    // 111: idh_conv_select / idh_conv_tuning_defaults / idh_schedule_ops (csrc/plan_select.hip): the one kernel-selection rule and level scheduler of both plan builders
+                                                   // (still 111) idh_binary_mlp_rays_fwd / idh_project_points_fwd (csrc/mlp_rays.hip) are additive: no struct, code or packed layout changed, so the
+                                                   //      version stays; a binding that needs them finds them missing by name when it loads an older library
 extern "C" size_t idh_sizeof_volume_opts(void) { return sizeof(idh_volume_opts); }
 
 extern "C" const char *idh_error_string(int code) {

@@ -1,0 +1,283 @@
+// Occlusion MLP at sparse rays, and the projection of world points to such rays (gfx950, fp32 MFMA).
+//
+// Fused form of the reference's ray path  BDModel.run_mlp_train (experiment_modules/bd_model.py:313-393):
+//     sampled_rays (B,N,2) in pixel-centre units of the supervision grid -> (x / grid_w - 0.5) * 2            (:325-326)
+//     for each scale s: rays[:, ::(s+1)], depths[:, ::(s+1)]                                                   (:352-353)
+//         F.grid_sample(feature_s, rays, bilinear, zeros, align_corners=False) -> expand over the S samples    (:357-364)
+//         cat([depth | feature | (prior)]) -> permute -> BinaryMLPNetwork                                      (:367-384)
+// i.e. a (B, N, S, 1 + Cf) tensor per scale.  Here the feature row of a ray is blended from its four corner rows of the NHWC map
+// straight into the MFMA B-operand registers, pre1 = W1f . feat + b1 is formed once per ray, and the S depth samples run through
+// the same register-resident loop as the planes of binary_mlp_k (csrc/mlp.hip): one ray per column instead of one pixel.
+//
+// The exact fp32 expression of the gather is stated in include/idh.h (tests/ray_query_ref.py derives its bound from it).
+#include <type_traits>
+
+#include "idh_common.h"
+#include "mlp_common.h"
+
+namespace {
+
+using namespace idh_mlp;
+
+struct RayArgs {
+    const float *feat;   // NHWC rows, B*H*W x cs
+    const float *rays;   // B,N,2
+    const float *depth;  // B,N,S
+    const float *prior;  // B,N,S or null
+    const float *w1f, *w2, *vecs;  // as BinArgs of csrc/mlp.hip
+    float *out;          // B,Nq,S
+    int M, Nq, N, S, ray_step;  // M = B * Nq rays of this launch
+    int H, W, cs, Cf;
+    float grid_w, grid_h;
+    int has_prior;
+    float prior_const;
+    int feat_unaligned;  // 1: rows are not 16-byte aligned, dword loads
+    int nchunk, s_chunk;  // the S samples of a ray tile are cut into nchunk runs of s_chunk: one work item (= one wave pass) each
+};
+
+constexpr int kRayMaxThreads = 768;  // 12 waves, as binary_mlp_k; small launches use 4 (ray_mlp_launch)
+constexpr int kW1LdsMaxBlocks = 4;   // Cf <= 64 -> W1f in LDS, as binary_mlp_k
+
+__global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int nthreads = blockDim.x, nwaves = nthreads >> 6;
+    f32x4 *sW2 = reinterpret_cast<f32x4 *>(smem_raw);
+    const int cblocks = (a.Cf + 15) >> 4;
+    const bool w1_lds = cblocks <= kW1LdsMaxBlocks;
+    f32x4 *sW1 = sW2 + kNS * kNS * 64;
+    float *s_vec = reinterpret_cast<float *>(sW1 + (w1_lds ? cblocks * kNS * 64 : 0));
+    {
+        const f32x4 *g2 = reinterpret_cast<const f32x4 *>(a.w2), *g1 = reinterpret_cast<const f32x4 *>(a.w1f);
+        for (int i = threadIdx.x; i < kNS * kNS * 64; i += nthreads) sW2[i] = g2[i];
+        if (w1_lds)
+            for (int i = threadIdx.x; i < cblocks * kNS * 64; i += nthreads) sW1[i] = g1[i];
+        for (int i = threadIdx.x; i < 6 * kHidden; i += nthreads) s_vec[i] = a.vecs[i];
+    }
+    __syncthreads();
+    const float *s_b1 = s_vec, *s_wd = s_vec + kHidden, *s_wp = s_vec + 2 * kHidden, *s_b2 = s_vec + 3 * kHidden,
+                *s_w3 = s_vec + 4 * kHidden;
+    const float b3 = s_vec[5 * kHidden];
+
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ln = lane & 15, q = lane >> 4;
+    const int tiles = (a.M + 15) >> 4;
+    const int items = tiles * a.nchunk;
+    const float Wf = (float)a.W, Hf = (float)a.H;
+
+    for (int item = blockIdx.x * nwaves + wave; item < items; item += gridDim.x * nwaves) {
+        const int tile = item / a.nchunk, ch = item - tile * a.nchunk;
+        const int r = tile * 16 + ln;
+        const bool rok = r < a.M;
+        const int rr = rok ? r : a.M - 1;
+        const int b = rr / a.Nq, j = rr - b * a.Nq;
+        const size_t src = (size_t)b * a.N + (size_t)j * a.ray_step;  // ray j of the launch is rays[b, j * ray_step]
+        // ---- gather: the expression of include/idh.h, one rounding per operation (-ffp-contract=off) ----
+        const float x = a.rays[2 * src], y = a.rays[2 * src + 1];
+        const float gx = (x / a.grid_w - 0.5f) * 2.f, gy = (y / a.grid_h - 0.5f) * 2.f;              // bd_model.py:325-326
+        const float ix = ((gx + 1.f) * Wf - 1.f) * 0.5f, iy = ((gy + 1.f) * Hf - 1.f) * 0.5f;        // grid_sample, align_corners=False
+        const float x0 = floorf(ix), y0 = floorf(iy);
+        const float wx0 = (x0 + 1.f) - ix, wx1 = ix - x0, wy0 = (y0 + 1.f) - iy, wy1 = iy - y0;
+        const float wgt[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};  // nw, ne, sw, se
+        // validity in float first: a far or non-finite coordinate never reaches the integer conversion (NaN fails every comparison)
+        const bool vx0 = x0 >= 0.f && x0 <= Wf - 1.f, vx1 = x0 >= -1.f && x0 <= Wf - 2.f;
+        const bool vy0 = y0 >= 0.f && y0 <= Hf - 1.f, vy1 = y0 >= -1.f && y0 <= Hf - 2.f;
+        const int xi = (vx0 || vx1) ? (int)x0 : 0, yi = (vy0 || vy1) ? (int)y0 : 0;
+        const bool cv[4] = {vx0 && vy0, vx1 && vy0, vx0 && vy1, vx1 && vy1};
+        const int base = b * a.H * a.W;
+        const int crow[4] = {base + yi * a.W + xi, base + yi * a.W + xi + 1, base + (yi + 1) * a.W + xi, base + (yi + 1) * a.W + xi + 1};
+
+        // ---- layer 1, sample-independent part: pre1^T = W1f . feat^T + b1 ----
+        f32x4 pre1[kNS][1];
+#pragma unroll
+        for (int i = 0; i < kNS; ++i) pre1[i][0] = *reinterpret_cast<const f32x4 *>(s_b1 + 16 * i + 4 * q);
+#pragma unroll 1
+        for (int c = 0; c < cblocks; ++c) {
+            f32x4 Bf = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if ((16 * c + 4 * q) < a.Cf) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (cv[k]) {  // a corner outside the map is not read
+                        const float *fp = a.feat + (size_t)crow[k] * a.cs + 16 * c + 4 * q;
+                        f32x4 v;
+                        if (a.feat_unaligned) v = (f32x4){fp[0], fp[1], fp[2], fp[3]};
+                        else v = *reinterpret_cast<const f32x4 *>(fp);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) Bf[e] = Bf[e] + v[e] * wgt[k];
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < kNS; ++i) {
+                const f32x4 A = w1_lds ? sW1[(c * kNS + i) * 64 + lane]
+                                       : *reinterpret_cast<const f32x4 *>(a.w1f + ((size_t)(c * kNS + i) * 64 + lane) * 4);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) pre1[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], Bf[kk], pre1[i][0], 0, 0, 0);
+            }
+        }
+        // ---- per depth sample: exactly the plane loop of binary_mlp_k ----
+        const size_t doff = src * a.S, ooff = (size_t)rr * a.S;
+        const int s_begin = ch * a.s_chunk, s_end = min(a.S, s_begin + a.s_chunk);
+#pragma unroll 1
+        for (int s = s_begin; s < s_end; ++s) {
+            const float dv = a.depth[doff + s];
+            const float pv = a.has_prior ? (a.prior ? a.prior[doff + s] : a.prior_const) : 0.f;
+            f32x4 h1[kNS][1], acc[kNS][1];
+            auto layer1 = [&](auto with_prior) {
+#pragma unroll
+                for (int i = 0; i < kNS; ++i) {
+                    const f32x4 wd = *reinterpret_cast<const f32x4 *>(s_wd + 16 * i + 4 * q);
+                    f32x4 wp = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (decltype(with_prior)::value) wp = *reinterpret_cast<const f32x4 *>(s_wp + 16 * i + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float v = fmaf(wd[e], dv, pre1[i][0][e]);
+                        if (decltype(with_prior)::value) v = fmaf(wp[e], pv, v);
+                        h1[i][0][e] = elu1(v);
+                    }
+                    acc[i][0] = *reinterpret_cast<const f32x4 *>(s_b2 + 16 * i + 4 * q);
+                }
+            };
+            if (a.has_prior) layer1(std::true_type{});
+            else layer1(std::false_type{});
+            __builtin_amdgcn_s_setprio(0);
+            dense128<1>(h1, sW2, lane, acc);
+            __builtin_amdgcn_s_setprio(2);
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < kNS; ++i) {
+                const f32x4 w3 = *reinterpret_cast<const f32x4 *>(s_w3 + 16 * i + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t = fmaf(w3[e], elu1(acc[i][0][e]), t);
+            }
+            t += __shfl_xor(t, 16, 64);
+            t += __shfl_xor(t, 32, 64);
+            if (q == 0 && rok) a.out[ooff + s] = t + b3;
+        }
+    }
+}
+
+// ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
+// Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
+// With a prior: the point goes through the prior camera's P' the same way and BDModel.sample_prior's nearest sample
+// (bd_model.py:405-409) is taken at (u', v'), with sample_prior_k's rounding; -1 where the prior camera's z <= 0 or the texel is outside.
+__global__ __launch_bounds__(256) void project_points_k(const float *__restrict__ pts, const float *__restrict__ cam_T_world,
+                                                        const float *__restrict__ Kmat, int N, int H, int W, float *__restrict__ rays,
+                                                        float *__restrict__ depth, unsigned char *__restrict__ valid,
+                                                        const float *__restrict__ prior_pred, const float *__restrict__ prior_cam_T_world,
+                                                        const float *__restrict__ prior_K, float *__restrict__ prior_out) {
+    __shared__ float sP[2][12];
+    const int b = blockIdx.y;
+    if (threadIdx.x < 2 && (threadIdx.x == 0 || prior_pred)) {
+        const float *Kb = (threadIdx.x ? prior_K : Kmat) + (size_t)b * 16, *T = (threadIdx.x ? prior_cam_T_world : cam_T_world) + (size_t)b * 16;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 4; ++j) {
+                float s = 0.f;
+                for (int m = 0; m < 4; ++m) s = fmaf(Kb[i * 4 + m], T[m * 4 + j], s);
+                sP[threadIdx.x][i * 4 + j] = s;
+            }
+    }
+    __syncthreads();
+    const float Wf = (float)W, Hf = (float)H;
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
+        const size_t o = (size_t)b * N + n;
+        const float X0 = pts[3 * o], X1 = pts[3 * o + 1], X2 = pts[3 * o + 2];
+        const float *P = sP[0];
+        const float cx = fmaf(P[0], X0, fmaf(P[1], X1, fmaf(P[2], X2, P[3])));
+        const float cy = fmaf(P[4], X0, fmaf(P[5], X1, fmaf(P[6], X2, P[7])));
+        const float cz = fmaf(P[8], X0, fmaf(P[9], X1, fmaf(P[10], X2, P[11])));
+        const float z = fmaxf(cz, 1e-5f);
+        const float u = cx / z, v = cy / z;
+        rays[2 * o] = u;
+        rays[2 * o + 1] = v;
+        depth[o] = z;
+        valid[o] = (cz > 0.f && u >= 0.f && u < Wf && v >= 0.f && v < Hf) ? 1 : 0;
+        if (prior_pred) {
+            const float *Q = sP[1];
+            const float px = fmaf(Q[0], X0, fmaf(Q[1], X1, fmaf(Q[2], X2, Q[3])));
+            const float py = fmaf(Q[4], X0, fmaf(Q[5], X1, fmaf(Q[6], X2, Q[7])));
+            const float pz = fmaf(Q[8], X0, fmaf(Q[9], X1, fmaf(Q[10], X2, Q[11])));
+            const float zz = fmaxf(pz, 1e-5f);
+            const float pu = px / zz, pw = py / zz;
+            const float gx = (pu / Wf - 0.5f) * 2.f, gy = (pw / Hf - 0.5f) * 2.f;
+            const float sx = ((gx + 1.f) * Wf - 1.f) * 0.5f, sy = ((gy + 1.f) * Hf - 1.f) * 0.5f;
+            const float xr = rintf(sx), yr = rintf(sy);  // round-half-even, as sample_prior_k
+            float val = -1.f;
+            if (pz > 0.f && xr >= 0.f && xr <= Wf - 1.f && yr >= 0.f && yr <= Hf - 1.f)
+                val = prior_pred[(size_t)b * H * W + (size_t)((int)yr * W + (int)xr)];
+            prior_out[o] = val;
+        }
+    }
+}
+
+}  // namespace
+
+// Work partition of one launch (host side, also what tests/ray_query_ref.py restates for its persistent-loop case):
+// an item is 16 rays x one run of samples.  While the ray tiles alone do not give every SIMD of the device (256 CUs x 4) a wave, the S
+// samples of a tile are cut into runs of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256
+// per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.
+static int ray_mlp_launch(RayArgs a, void *stream) {
+    constexpr int kSimds = 256 * 4, kMinChunk = 8;
+    const long long tiles = ((long long)a.M + 15) / 16;
+    int nchunk = 1;
+    if (tiles < kSimds) {
+        nchunk = (int)((kSimds + tiles - 1) / tiles);
+        const int most = (a.S + kMinChunk - 1) / kMinChunk;
+        if (nchunk > most) nchunk = most;
+    }
+    a.s_chunk = (a.S + nchunk - 1) / nchunk;
+    a.nchunk = (a.S + a.s_chunk - 1) / a.s_chunk;
+    const long long items = tiles * a.nchunk;
+    // 4-wave workgroups, as many as there are items, while that leaves at most one workgroup per CU; beyond that the persistent 12-wave
+    // form of binary_mlp_k (3 waves per SIMD share one copy of the weights)
+    const int waves = items <= 256 * 4 ? 4 : kRayMaxThreads / 64;
+    long long grid = (items + waves - 1) / waves;
+    if (grid > 256) grid = 256;
+    const int cblocks = (a.Cf + 15) >> 4;
+    const size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
+                       6 * kHidden * sizeof(float);
+    static IdhDeviceOnce attr_set;
+    if (attr_set.first()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ray_mlp_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return IDH_ELAUNCH;
+        attr_set.mark();
+    }
+    hipLaunchKernelGGL(ray_mlp_k, dim3((unsigned)grid), dim3(waves * 64), lds, idh_stream(stream), a);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" int idh_binary_mlp_rays_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rays_bn2,
+                                       const float *depth_bns, const float *prior_bns, int has_prior, float prior_const, int N, int S,
+                                       int ray_step, int grid_w, int grid_h, const float *w1f_packed, const float *w2_packed,
+                                       const float *vecs6x128, float *out_bqs, void *stream) {
+    if (B < 0 || N < 0 || S <= 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || ray_step < 1 || grid_w <= 0 || grid_h <= 0)
+        return IDH_EINVAL;
+    if (B == 0 || N == 0) return IDH_OK;
+    if (!feat_nhwc || !rays_bn2 || !depth_bns || !w1f_packed || !w2_packed || !vecs6x128 || !out_bqs) return IDH_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(feat_nhwc) & 3) || (reinterpret_cast<uintptr_t>(rays_bn2) & 3) || (reinterpret_cast<uintptr_t>(depth_bns) & 3) ||
+        (reinterpret_cast<uintptr_t>(prior_bns) & 3) || (reinterpret_cast<uintptr_t>(out_bqs) & 3))
+        return IDH_EINVAL;
+    const int Nq = (int)(((long long)N + ray_step - 1) / ray_step);
+    const long long M = (long long)B * Nq;
+    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31) || (M + 15) / 16 * ((S + 7) / 8) >= (1ll << 30)) return IDH_EUNSUPPORTED;
+    RayArgs a{feat_nhwc, rays_bn2, depth_bns, prior_bns, w1f_packed, w2_packed, vecs6x128, out_bqs, (int)M, Nq, N, S, ray_step, H, W, feat_cs, Cf,
+              (float)grid_w, (float)grid_h, has_prior, prior_const, 0, 1, S};
+    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
+    return ray_mlp_launch(a, stream);
+}
+
+extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,
+                                      float *rays_bn2, float *depth_bn, unsigned char *valid_bn, const float *prior_pred_b1hw,
+                                      const float *prior_cam_T_world_44, const float *prior_K_44, float *prior_bn, void *stream) {
+    if (B < 0 || N < 0 || H <= 0 || W <= 0 || B > 65535) return IDH_EINVAL;
+    if (B == 0 || N == 0) return IDH_OK;
+    if (!points_bn3 || !cam_T_world_44 || !K_44 || !rays_bn2 || !depth_bn || !valid_bn) return IDH_EINVAL;
+    if (prior_pred_b1hw && (!prior_cam_T_world_44 || !prior_K_44 || !prior_bn)) return IDH_EINVAL;
+    if ((long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    int gx = idh_cdiv(N, 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(project_points_k, dim3(gx, B), dim3(256), 0, idh_stream(stream), points_bn3, cam_T_world_44, K_44, N, H, W, rays_bn2, depth_bn,
+                       valid_bn, prior_pred_b1hw, prior_cam_T_world_44, prior_K_44, prior_bn);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}

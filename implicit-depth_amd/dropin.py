@@ -151,6 +151,8 @@ def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool
     model's own torch modules - unless ``native_matching_stem`` is set: the stem (conv1 .. layer1, which must pass
     ``backbone.stem_is_native_eligible``; ``IdhError`` otherwise) then runs on the gfx950 kernels inside the same pass, from the raw images.  ``model.forward = fused_forward(model)`` installs it; the model's config / checkpoint
     surface is untouched (the hot-path modules are converted in place and share their parameters with the pipeline).
+    If ``cur_data`` carries ``sampled_rays`` (B,N,2) and ``sampled_depths`` (B,N,S), the outputs gain ``ray_pred_0..3``: the occlusion
+    logits of ``BDModel.run_mlp_train`` (bd_model.py:313-387) at those rays (``HotPath.query_rays``); ``phase == "train"`` keeps raising.
     Side effects on the input dicts are the reference's: ``cur_data["prior_mask"]`` and, with ``bd_edge_regularision``,
     ``cur_data["edge_mask"]`` (computed by the reference's own ``get_edge_mask``, which must then be importable)."""
     from . import _lib
@@ -193,8 +195,16 @@ def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool
             else:
                 mc, msrc = model.compute_matching_feats(cur_image, src_image, unbatched_matching_encoder_forward)
             if is_bd:
-                kw["rendered_depth"] = cur_data["rendered_depth"]
+                sparse = cur_data.get("sampled_rays") is not None and cur_data.get("sampled_depths") is not None
+                kw["rendered_depth"] = cur_data.get("rendered_depth") if sparse else cur_data["rendered_depth"]
                 kw["infer_depth"] = infer_depth
+                if sparse:
+                    # the ray path of run_mlp_train (bd_model.py:313-387) at inference: ray_pred_0..3 at the reference's shapes, the rays in
+                    # pixel-centre units of the supervision map (:314-318, :325-326), the prior the constant -1 (run_mlp_val :433-434).
+                    # cur_data["sampled_rays"] is left as it is (the reference normalises it in place, :320-326)
+                    g = cur_data.get("full_res_depth_b1hw") if getattr(opts, "full_depth_supervision", False) else cur_data.get("depth_b1hw")
+                    kw.update(query_rays=cur_data["sampled_rays"], query_depths=cur_data["sampled_depths"], query_scales=(0, 1, 2, 3),
+                              query_grid=None if g is None else tuple(g.shape[-2:]))
                 if getattr(opts, "use_prior", False) and cur_data.get("prior_prediction", None) is not None:
                     kw["prior_inputs"] = {k: cur_data[k] for k in ("prior_prediction", "world_T_cam_b44", "prior_cam_T_world", "K_s0_b44", "invK_s0_b44")}
             out = hot(mc, msrc, cur_feats, src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK, return_mask=return_mask, **kw)

@@ -156,6 +156,75 @@ def sample_prior(rendered_depth: torch.Tensor, prior_prediction: torch.Tensor, c
     return out
 
 
+def ray_logits(net, feat_view, rays: torch.Tensor, depths: torch.Tensor, prior=None, scale: int = 0, grid=None, ray_step: int = 1) -> torch.Tensor:
+    """The occlusion MLP of ``scale`` at sparse rays: the fused form of one scale of ``BDModel.run_mlp_train`` (reference
+    bd_model.py:348-387) on ``idh_binary_mlp_rays_fwd``.  ``feat_view``: an ``nhwc.View`` of that scale's decoder output (B,H,W,Cf slice);
+    ``rays`` (B,N,2): (x, y) in pixel-centre units of ``grid`` = (grid_h, grid_w) - the shape of the reference's ``depth_b1hw`` /
+    ``full_res_depth_b1hw``; None = the feature map's own (H, W); ``depths`` (B,N,S); ``prior``: None (a prior-enabled network then sees
+    the constant -1, bd_model.py:433-434), a float constant or a (B,N,S) tensor; ``ray_step``: every ray_step-th ray and its depths (the
+    reference's ``[:, ::(scale + 1)]``).  Returns logits (B,1,Nq,S), Nq = ceil(N / ray_step): the reference's output layout (:387).
+    ``rays`` is never written: the reference normalises ``inputs["sampled_rays"]`` IN PLACE through its ``unsqueeze(2)`` view
+    (:320-326), so a caller that passes the same dictionary twice there samples different rays the second time."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_rays_fwd; set mlp_math = 'fp32'")
+    prior_t = prior if isinstance(prior, torch.Tensor) else None
+    _lib.require_cuda_f32(feat_view.buf, rays, depths, prior_t)
+    B, H, W = feat_view.N, feat_view.H, feat_view.W
+    if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+        raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+    N = rays.shape[1]
+    if depths.dim() != 3 or tuple(depths.shape[:2]) != (B, N):
+        raise _lib.IdhError(f"depths must be ({B}, {N}, S), got {tuple(depths.shape)}")
+    S = depths.shape[2]
+    if ray_step < 1:
+        raise _lib.IdhError(f"ray_step must be >= 1, got {ray_step}")
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    gh, gw = (H, W) if grid is None else (int(grid[0]), int(grid[1]))
+    w1p, w2p, vecs = _prepared(net.mlps[f"s{scale}"], feat_view.C, net.use_prior, "fp32")
+    r, d = rays.contiguous(), depths.contiguous()  # alive until enqueued
+    pt = prior_t.expand(B, N, S).contiguous() if prior_t is not None else None
+    Nq = (N + ray_step - 1) // ray_step
+    out = torch.empty(B, 1, Nq, S, device=rays.device, dtype=torch.float32)
+    _lib.check(
+        _lib.lib().idh_binary_mlp_rays_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, r.data_ptr(), d.data_ptr(), _lib.ptr(pt),
+                                           int(net.use_prior), -1.0 if prior is None or prior_t is not None else float(prior), N, S, ray_step,
+                                           gw, gh, w1p.data_ptr(), w2p.data_ptr(), vecs.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
+        "idh_binary_mlp_rays_fwd")
+    return out
+
+
+def project_points(points_bn3: torch.Tensor, cam_T_world: torch.Tensor, K: torch.Tensor, H: int, W: int, prior_pred: Optional[torch.Tensor] = None,
+                   prior_cam_T_world: Optional[torch.Tensor] = None, prior_K: Optional[torch.Tensor] = None):
+    """World points (B,N,3) -> (rays (B,N,2), depth (B,N), valid (B,N) bool, prior (B,N) | None) in the H x W view of ``K`` /
+    ``cam_T_world`` (B,4,4), as ``Project3D`` (reference geometry_utils.py:77-89); with ``prior_pred`` (B,1,H,W) also its nearest sample
+    in the prior camera (``BDModel.sample_prior``, bd_model.py:395-410; -1 behind that camera or outside).  ``idh_project_points_fwd``."""
+    _lib.require_cuda_f32(points_bn3, cam_T_world, K, prior_pred, prior_cam_T_world, prior_K)
+    if points_bn3.dim() != 3 or points_bn3.shape[2] != 3:
+        raise _lib.IdhError(f"points must be (B, N, 3), got {tuple(points_bn3.shape)}")
+    B, N, _ = points_bn3.shape
+    mats = [cam_T_world, K] + ([prior_cam_T_world, prior_K] if prior_pred is not None else [])
+    for m in mats:
+        if m is None or tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"cam_T_world / K (and the prior's) must be ({B}, 4, 4)")
+    if prior_pred is not None and tuple(prior_pred.shape) != (B, 1, H, W):
+        raise _lib.IdhError(f"prior prediction {tuple(prior_pred.shape)} must be ({B}, 1, {H}, {W})")
+    dev = points_bn3.device
+    pts, keep = points_bn3.contiguous(), [m.contiguous() for m in mats]
+    pp = prior_pred.contiguous() if prior_pred is not None else None
+    # one allocation for the float outputs (a query of a few hundred points is bound by host work, not by the kernel)
+    buf = torch.empty((4 if pp is not None else 3) * B * N, device=dev)
+    rays, depth = buf[: 2 * B * N].view(B, N, 2), buf[2 * B * N: 3 * B * N].view(B, N)
+    prior = buf[3 * B * N:].view(B, N) if pp is not None else None
+    valid = torch.empty(B, N, device=dev, dtype=torch.uint8)
+    _lib.check(
+        _lib.lib().idh_project_points_fwd(pts.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr(), B, N, H, W, rays.data_ptr(), depth.data_ptr(),
+                                          valid.data_ptr(), _lib.ptr(pp), keep[2].data_ptr() if pp is not None else None,
+                                          keep[3].data_ptr() if pp is not None else None, _lib.ptr(prior), _lib.stream_ptr()),
+        "idh_project_points_fwd")
+    return rays, depth, valid.view(torch.bool), prior  # the kernel writes 0 / 1: reinterpreted, no conversion pass
+
+
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:
     """``BinaryMLPNetwork.forward(list of (..., Cin) tensors, max_scale_only)`` (reference networks.py:106-115); row = [depth | features |
     (prior)].  fp32: the rows are read IN PLACE through ``idh_binary_mlp_strided_fwd`` whatever their strides - in particular the

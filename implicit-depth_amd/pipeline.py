@@ -47,16 +47,60 @@ class HotPath(nn.Module):
         self.min_depth, self.max_depth = float(min_depth), float(max_depth)
         self.thresholder = None  # like BDModel.thresholder (bd_model.py:141): per-depth thresholds of the infer_depth search
         self._plans = nhwc.PlanCache()  # LRU: a ragged last batch / alternating shapes replay instead of rebuilding
+        self._last = None  # decoder output of the last forward (plan-owned final[i] views): what query_rays / query_points read
         _lib.watch_state_dict_loads(self)
 
     # ------------------------------------------------------------------------------------
-    def _scales(self, return_features: bool) -> int:
+    def _scales(self, return_features: bool, query_scales: Sequence[int] = ()) -> int:
         """The decoder scales a call reads (nhwc.build_decoder): the occlusion MLP takes scale 0 only, so a BDDecoderPP behind it builds
-        output_1..3 just for the callers that ask for the feature maps; depth / regression heads are outputs at every scale."""
+        output_1..3 just for the callers that ask for the feature maps or for ray queries at those scales; depth / regression heads are
+        outputs at every scale."""
         dec = self.depth_decoder
-        if return_features or self.binary_mlp is None or getattr(dec, "depth_head", False) or hasattr(dec, "out1"):
+        if return_features or any(s != 0 for s in query_scales) or self.binary_mlp is None or getattr(dec, "depth_head", False) or hasattr(dec, "out1"):
             return nhwc.ALL_SCALES
         return 0b0001
+
+    @staticmethod
+    def _check_query_scales(scales) -> tuple:
+        scales = tuple(int(s) for s in scales)
+        if not scales or any(s not in (0, 1, 2, 3) for s in scales):
+            raise _lib.IdhError(f"query_scales must be a non-empty subset of (0, 1, 2, 3), got {scales}")
+        return scales
+
+    def query_rays(self, rays: torch.Tensor, depths: torch.Tensor, prior=None, grid: Optional[Sequence[int]] = None,
+                   scales: Sequence[int] = (0,)) -> Dict[str, torch.Tensor]:
+        """Occlusion logits at sparse rays against the decoder output of the LAST ``forward`` on this HotPath (the plan-owned buffers stay
+        valid until that plan is replayed): no conv runs, one ``mlp.ray_logits`` launch per scale.  ``rays`` (B,N,2) in pixel-centre units
+        of ``grid`` = (h, w) (None: the scale-0 map's own shape), ``depths`` (B,N,S), ``prior`` None | float | (B,N,S).  Scale s takes every
+        (s+1)-th ray, as the reference's run_mlp_train (bd_model.py:352-353).  Returns {"ray_pred_{s}": (B,1,ceil(N/(s+1)),S)}.
+        ``IdhError`` when no forward has run, when B differs, or when that forward did not build a requested scale."""
+        from .mlp import ray_logits
+
+        scales = self._check_query_scales(scales)
+        final = _last_final(self, rays.shape[0], scales)
+        _lib.require_cuda_f32(rays, depths, prior if isinstance(prior, torch.Tensor) else None)
+        if grid is None:
+            grid = (final[0].H, final[0].W)
+        return {f"ray_pred_{s}": ray_logits(self.binary_mlp, final[s], rays, depths, prior, scale=s, grid=grid, ray_step=s + 1) for s in scales}
+
+    def query_points(self, points_bn3: torch.Tensor, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor,
+                     prior_inputs: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Occlusion of world points (B,N,3) against the LAST forward: each point is projected into the scale-0 map with ``K_s0_b44`` /
+        ``cam_T_world_b44`` (``mlp.project_points``) and asked at its own depth along its ray.  ``prior_inputs``: {"prior_prediction"
+        (B,1,H/2,W/2), "prior_cam_T_world" (B,4,4)} (and optionally the prior view's own "K_s0_b44") - the point is projected into that
+        camera and the prediction sampled there (nearest, -1 outside), as BDModel.sample_prior does per pixel.  Returns {"point_pred"
+        (B,1,N,1) logits, "point_valid" (B,N) bool: in front of the camera and inside the image, "point_depth" (B,N), "point_rays" (B,N,2)}."""
+        from .mlp import project_points, ray_logits
+
+        final = _last_final(self, points_bn3.shape[0], (0,))
+        _lib.require_cuda_f32(points_bn3, cam_T_world_b44, K_s0_b44)
+        f0 = final[0]
+        pp = pc = pk = None
+        if prior_inputs is not None and prior_inputs.get("prior_prediction") is not None:
+            pp, pc, pk = prior_inputs["prior_prediction"], prior_inputs["prior_cam_T_world"], prior_inputs.get("K_s0_b44", K_s0_b44)
+        rays, depth, valid, prior = project_points(points_bn3, cam_T_world_b44, K_s0_b44, f0.H, f0.W, pp, pc, pk)
+        pred = ray_logits(self.binary_mlp, f0, rays, depth.unsqueeze(-1), None if prior is None else prior.unsqueeze(-1), scale=0)
+        return {"point_pred": pred, "point_valid": valid, "point_depth": depth, "point_rays": rays}
 
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
               images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):
@@ -135,7 +179,9 @@ class HotPath(nn.Module):
                 prior_inputs: Optional[Dict[str, torch.Tensor]] = None, infer_depth: bool = False,
                 matching_layer1: Optional[torch.Tensor] = None, return_matching_feats: bool = False,
                 frame_chain: Optional[Dict[str, torch.Tensor]] = None, matching_images: Optional[torch.Tensor] = None,
-                matching_nhwc: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                matching_nhwc: Optional[Sequence[torch.Tensor]] = None, query_rays: Optional[torch.Tensor] = None,
+                query_depths: Optional[torch.Tensor] = None, query_prior=None, query_grid: Optional[Sequence[int]] = None,
+                query_scales: Sequence[int] = (0,)) -> Dict[str, torch.Tensor]:
         """``matching_layer1`` (B, K+1, 64, H, W): output of the matching backbone (conv1..layer1 of the ResNet18,
         third-party, run by the caller) for frame b's current image followed by its K source images — the order
         reference bd_model.py:149-160 builds; contiguous or channels-last per image
@@ -158,8 +204,14 @@ class HotPath(nn.Module):
         Needs a ``matching_model`` whose ``net[:5]`` passes ``backbone.stem_is_native_eligible`` (eval mode).
         ``matching_nhwc`` = (cur (B,H,W,C), src (B,K,H,W,C)): FINISHED matching features that are already channels-last and contiguous
         (``FeatureBank.gather``'s output, ``ResnetMatchingEncoder(..., channels_last=True)``); the volume kernel reads them in place, with no
-        layout import.  Excludes the four other forms."""
+        layout import.  Excludes the four other forms.
+        ``query_rays`` (B,N,2) + ``query_depths`` (B,N,S): sparse occlusion queries against this forward's decoder output, with or without
+        ``rendered_depth`` - see ``query_rays()``; adds ``out["ray_pred_{s}"]`` (B,1,ceil(N/(s+1)),S) for s in ``query_scales``.  Scales 1-3
+        need the full decoder plan (the plan key's ``scales``)."""
         _lib.require_cuda_f32(matching_cur_feats, matching_src_feats, matching_layer1, matching_images, src_cam_T_cur_cam, src_K, cur_invK, rendered_depth, prior, *cur_feats)
+        if (query_rays is None) != (query_depths is None):
+            raise _lib.IdhError("query_rays and query_depths come together")
+        query_scales = self._check_query_scales(query_scales) if query_rays is not None else ()
         if matching_nhwc is not None:
             if matching_cur_feats is not None or matching_src_feats is not None or matching_layer1 is not None or matching_images is not None:
                 raise _lib.IdhError("pass one of finished matching features (NCHW or matching_nhwc), matching_layer1 or matching_images")
@@ -205,7 +257,7 @@ class HotPath(nn.Module):
             B, K, C, H, W = matching_src_feats.shape
         dev = src_K.device
         cur_feats = [f if f.is_contiguous() else f.contiguous() for f in cur_feats]
-        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch, images, self._scales(return_features))
+        ent = self._plan(B, K, C, H, W, [f.shape for f in cur_feats], dev, head, head_ch, images, self._scales(return_features, query_scales))
         p, st = ent["plan"], ent["state"]
         L = _lib.lib()
         sp = _lib.stream_ptr()
@@ -258,6 +310,7 @@ class HotPath(nn.Module):
                 out[f"log_depth_pred_s{i}_b1hw"] = t
                 out[f"depth_pred_s{i}_b1hw"] = e
         p.run(ent["n_head_ops"])
+        self._last = {"ent": ent, "final": final, "B": B}  # (the entry keeps its buffers alive if the cache drops it)
 
         # 3. occlusion MLP over every query plane (BDModel only)
         if self.binary_mlp is not None and rendered_depth is not None and frame_chain is not None:
@@ -303,6 +356,8 @@ class HotPath(nn.Module):
                                                               thresholder=self.thresholder)
             else:
                 out["pred_0"] = occlusion_logits(self.binary_mlp, f0.buf, f0.c0, f0.C, rendered_depth, prior)
+        if query_rays is not None:
+            out.update(self.query_rays(query_rays, query_depths, query_prior, query_grid, query_scales))
         if return_features:
             for i, v in final.items():
                 out[f"feature_s{i}_b1hw"] = _export(v)
@@ -313,6 +368,20 @@ class HotPath(nn.Module):
         out["lowest_cost_bhw"] = lowest
         out["overall_mask_bhw"] = mask
         return out
+
+
+def _last_final(hot: HotPath, B: int, scales: Sequence[int]):
+    if hot.binary_mlp is None:
+        raise _lib.IdhError("occlusion queries need a HotPath with a binary_mlp")
+    last = hot._last
+    if last is None:
+        raise _lib.IdhError("no forward has run on this HotPath yet: queries read the decoder output of the last forward")
+    if last["B"] != B:
+        raise _lib.IdhError(f"the last forward had batch size {last['B']}, the query has {B}")
+    missing = [s for s in scales if s not in last["final"]]
+    if missing:
+        raise _lib.IdhError(f"the last forward built no decoder output at scales {missing}: pass query_scales (or return_features=True) to that forward")
+    return last["final"]
 
 
 def _export(v: nhwc.View) -> torch.Tensor:

@@ -82,20 +82,24 @@ class StreamingSession:
         self.last_indices: Optional[Tuple[int, ...]] = None  # their frame numbers
         self.last_matching: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # (cur (1,H,W,C), src (1,K,H,W,C)) of the last prediction
         self._prior: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's pose and intrinsics: what query_points projects with
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
         self.buffer = keyframes.KeyframeBuffer(self.buffer.buffer_size, self.buffer.keyframe_pose_distance, self.buffer.optimal_t_score,
                                                self.buffer.optimal_R_score)
         self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
+        self._key = None
 
     def step(self, cur_data: Dict[str, torch.Tensor], world_T_cam=None, dist_to_last_valid=None, return_mask: bool = False,
-             infer_depth: bool = False) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
+             infer_depth: bool = False, query_points: Optional[torch.Tensor] = None) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
         """``cur_data``: what ``FrameIngest`` returns for ONE frame (``image_b3hw``, ``world_T_cam_b44``, ``cam_T_world_b44``, ``K_s0/s1_b44``,
         ``invK_s0/s1_b44``; for a BDModel also ``rendered_depth``).  ``world_T_cam``: the same pose as a (4,4) host array, in the dtype the
         selection is to be computed in - the keyframe decision is taken on the host; without it the pose is read back from the device, which synchronises.
         Returns ``(outputs, code)``: the output dictionary of ``fused_forward`` when a prediction is due, else None - first frame, not enough
-        motion, no pose, tracking lost, or fewer than K keyframes stored so far; ``code`` is the buffer's return code either way."""
+        motion, no pose, tracking lost, or fewer than K keyframes stored so far; ``code`` is the buffer's return code either way.
+        ``query_points`` (1,N,3) world points: when a prediction is due, its outputs gain ``point_pred`` / ``point_valid`` / ``point_depth`` /
+        ``point_rays`` (``HotPath.query_points`` against this prediction); on the other frames ask ``session.query_points``."""
         image = cur_data["image_b3hw"]
         if image.dim() != 4 or image.shape[0] != 1:
             raise _lib.IdhError(f"step() takes one frame: image_b3hw must be (1,3,h,w), got {tuple(image.shape)}")
@@ -140,6 +144,32 @@ class StreamingSession:
                            matching_nhwc=self.last_matching, **kw)
             if self.use_prior and "pred_0" in out:
                 self._prior = (torch.sigmoid(out["pred_0"]), cur_data["cam_T_world_b44"])  # sigmoid_custom(x, 1.0), inference.py:154
+            if self.hot.binary_mlp is not None:
+                self._key = {"cam_T_world_b44": cur_data["cam_T_world_b44"], "K_s0_b44": cur_data["K_s0_b44"]}
+                if query_points is not None:
+                    out.update(self.query_points(query_points))
         if "prior_mask" in out:
             cur_data["prior_mask"] = out.pop("prior_mask")  # as fused_forward: run_mlp_val stores it on the inputs (bd_model.py:431)
         return out, code
+
+    def query_points(self, points_bn3: torch.Tensor, world_T_cam=None) -> Dict[str, torch.Tensor]:
+        """Occlusion of points (1,N,3) against the LAST prediction's decoder features and pose - also on the frames where ``step`` returned
+        None: no network runs, the features and the camera are the keyframe's.  The points are world points, or - with ``world_T_cam``, a
+        (4,4) array or tensor - points in that (live) camera's frame, taken to the world first.  With ``use_prior`` the carried prior - the
+        sigmoid of that prediction's ``pred_0``, which the next prediction will see - is sampled at the points' projections into the
+        keyframe's camera.  Returns ``HotPath.query_points``' dictionary."""
+        if self._key is None:
+            raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
+        _lib.require_cuda_f32(points_bn3)
+        k = self._key
+        if world_T_cam is not None:
+            T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
+            T = T.to(device=points_bn3.device, dtype=torch.float32)
+            if tuple(T.shape) != (4, 4):
+                raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
+            points_bn3 = points_bn3 @ T[:3, :3].t() + T[:3, 3]
+        pi = None
+        if self.use_prior and self._prior is not None:
+            pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
+        with torch.inference_mode():
+            return self.hot.query_points(points_bn3, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi)

@@ -283,6 +283,43 @@ int idh_sample_prior_fwd(const float *rendered_depth_bphw, const float *prior_pr
                          const float *K_44, const float *invK_44, int B, int P, int H, int W,
                          float *out_bphw, void *stream);
 
+/* ---- occlusion queries at sparse rays and 3D points (additive: idh_version() stays 111; csrc/mlp_rays.hip) -------- */
+/* Fused form of BDModel.run_mlp_train's ray path (reference experiment_modules/bd_model.py:313-393): per ray, the feature row is
+ * sampled bilinearly from an NHWC map (F.grid_sample, align_corners=False, zero padding, :357-362) and the S depth samples of the ray go
+ * through the MLP of idh_binary_mlp_fwd on that one row:
+ *   out[b, j, s] = MLP([depth[b, j*ray_step, s] | feat(rays[b, j*ray_step]) | (prior[b, j*ray_step, s])]),  j < Nq = ceil(N / ray_step)
+ * (ray_step = scale + 1 is the reference's rays[:, ::(scale + 1)], :352-353).
+ *   feat_nhwc   B*H*W rows of Cf floats, feat_cs floats apart: any feat_cs >= Cf, base 4-byte aligned (a channel slice of a wider buffer);
+ *               dwordx4 loads when the base is 16-byte aligned and feat_cs % 4 == 0, dword loads otherwise.  Cf % 4 == 0.
+ *   rays_bn2    (x, y) in pixel-centre units of a grid_w x grid_h grid: pixel (i, j) of that grid is (i + 0.5, j + 0.5) (:325-326)
+ *   depth_bns   (B,N,S); prior_bns (B,N,S) or NULL (then prior_const when has_prior); out_bqs (B,Nq,S) dense
+ *   w1f_packed / w2_packed / vecs6x128: as idh_binary_mlp_fwd.  fp32 only (there is no f16x3 form of this entry point).
+ * The gather, in fp32 with one rounding per operation (no contraction), per ray and for y alike:
+ *   g  = (x / (float)grid_w - 0.5f) * 2.f                  ix = ((g + 1.f) * (float)W - 1.f) * 0.5f
+ *   x0 = floorf(ix)        wx0 = (x0 + 1.f) - ix           wx1 = ix - x0
+ *   w_nw = wx0 * wy0   w_ne = wx1 * wy0   w_sw = wx0 * wy1   w_se = wx1 * wy1         (torch's (x0+1-ix)(y0+1-iy) ...)
+ *   f[c] = (((0 + F[y0][x0][c] * w_nw) + F[y0][x0+1][c] * w_ne) + F[y0+1][x0][c] * w_sw) + F[y0+1][x0+1][c] * w_se
+ * where a corner outside [0,W-1] x [0,H-1] contributes nothing and is not read (a non-finite ray has no corner: f = 0).
+ * IDH_EINVAL: a NULL pointer (prior_bns may be NULL), negative B or N, S, H, W, Cf <= 0, Cf % 4, feat_cs < Cf, ray_step < 1, grid_w or
+ * grid_h <= 0, a pointer that is not 4-byte aligned.  B == 0 or N == 0: IDH_OK, no launch.  IDH_EUNSUPPORTED: B * Nq or B * H * W >= 2^31.
+ * Everything is checked on the host before the device is touched. */
+int idh_binary_mlp_rays_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rays_bn2,
+                            const float *depth_bns, const float *prior_bns, int has_prior, float prior_const, int N, int S,
+                            int ray_step, int grid_w, int grid_h, const float *w1f_packed, const float *w2_packed,
+                            const float *vecs6x128, float *out_bqs, void *stream);
+/* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
+ * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
+ *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
+ *   rays_bn2 (B,N,2) = (u, v); depth_bn (B,N); valid_bn (B,N) uint8 = c_z > 0 && 0 <= u < W && 0 <= v < H
+ * Optional prior_pred_b1hw (B,1,H,W) with prior_cam_T_world_44 and prior_K_44 (B,4,4): prior_bn (B,N) is the nearest sample of
+ * BDModel.sample_prior (bd_model.py:395-410) with the point projected directly into the prior camera - the same normalise /
+ * un-normalise / rintf chain as idh_sample_prior_fwd - and -1 where that camera's z <= 0 or the texel lies outside.
+ * IDH_EINVAL: a NULL required pointer, a prior without its matrices or output, negative B or N, H or W <= 0, B > 65535.
+ * B == 0 or N == 0: IDH_OK, no launch. */
+int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,
+                           float *rays_bn2, float *depth_bn, unsigned char *valid_bn, const float *prior_pred_b1hw,
+                           const float *prior_cam_T_world_44, const float *prior_K_44, float *prior_bn, void *stream);
+
 /* ---- evaluation metrics (the step right after the path; rows of the metrics all-gather) ---- */
 /* Plane IoU — PlaneEvaluator.compute_batch_scores / compute_batch_scores_test (reference
  * utils/binary_metrics_utils.py:59-192): out[b,d,t,{iou, iou_pos, iou_neg}] over pixels with gt > 0 and
