@@ -10,6 +10,10 @@
 // the same register-resident loop as the planes of binary_mlp_k (csrc/mlp.hip): one ray per column instead of one pixel.
 //
 // The exact fp32 expression of the gather is stated in include/idh.h (tests/ray_query_ref.py derives its bound from it).
+//
+// ray_search_k is the same text with the sample loop replaced by the binary depth search of binary_mlp_k (BDModel.forward(infer_depth=True),
+// bd_model.py:273-292): lo / hi / query / flags of a ray live in the registers of its four quarter-lanes, which see the same reduced logit
+// and so stay in step; the final query is back-projected to a camera- or world-space hit point (BackprojectDepth, geometry_utils.py:39,60-61).
 #include <type_traits>
 
 #include "idh_common.h"
@@ -33,12 +37,23 @@ struct RayArgs {
     float prior_const;
     int feat_unaligned;  // 1: rows are not 16-byte aligned, dword loads
     int nchunk, s_chunk;  // the S samples of a ray tile are cut into nchunk runs of s_chunk: one work item (= one wave pass) each
+    // ray_search_k only (S = 1, ray_step = 1, nchunk = 1; `prior` is (B,N), `out` the logits of the last evaluation):
+    int iters;
+    float lo, hi, thr_logit;
+    const float *bins, *thr_logits;  // per-depth Thresholder: n_bins sorted edges, logit(threshold) per bin; n_bins = 0: thr_logit
+    int n_bins;
+    float *sdepth;         // B,N final queries
+    unsigned char *flags;  // B,N or null: bit 0 = hi moved, bit 1 = lo moved
+    float *points;         // B,N,3 or null
+    const float *invK, *wTc;  // B,4,4; wTc may be null (camera-space points)
 };
 
 constexpr int kRayMaxThreads = 768;  // 12 waves, as binary_mlp_k; small launches use 4 (ray_mlp_launch)
 constexpr int kW1LdsMaxBlocks = 4;   // Cf <= 64 -> W1f in LDS, as binary_mlp_k
 
-__global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) {
+// kSearch = false: the S depth samples of `depth`; true: `iters` dependent evaluations at the ray's current search depth
+template <bool kSearch>
+__device__ __forceinline__ void ray_body(const RayArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int nthreads = blockDim.x, nwaves = nthreads >> 6;
     f32x4 *sW2 = reinterpret_cast<f32x4 *>(smem_raw);
@@ -114,13 +129,8 @@ __global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) {
                 for (int kk = 0; kk < 4; ++kk) pre1[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], Bf[kk], pre1[i][0], 0, 0, 0);
             }
         }
-        // ---- per depth sample: exactly the plane loop of binary_mlp_k ----
-        const size_t doff = src * a.S, ooff = (size_t)rr * a.S;
-        const int s_begin = ch * a.s_chunk, s_end = min(a.S, s_begin + a.s_chunk);
-#pragma unroll 1
-        for (int s = s_begin; s < s_end; ++s) {
-            const float dv = a.depth[doff + s];
-            const float pv = a.has_prior ? (a.prior ? a.prior[doff + s] : a.prior_const) : 0.f;
+        // ---- one evaluation at depth dv, prior pv: exactly the plane body of binary_mlp_k; every lane of a ray returns the same logit ----
+        auto eval = [&](const float dv, const float pv) -> float {
             f32x4 h1[kNS][1], acc[kNS][1];
             auto layer1 = [&](auto with_prior) {
 #pragma unroll
@@ -151,10 +161,62 @@ __global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) {
             }
             t += __shfl_xor(t, 16, 64);
             t += __shfl_xor(t, 32, 64);
-            if (q == 0 && rok) a.out[ooff + s] = t + b3;
+            return t + b3;
+        };
+        if constexpr (!kSearch) {
+            const size_t doff = src * a.S, ooff = (size_t)rr * a.S;
+            const int s_begin = ch * a.s_chunk, s_end = min(a.S, s_begin + a.s_chunk);
+#pragma unroll 1
+            for (int s = s_begin; s < s_end; ++s) {
+                const float dv = a.depth[doff + s];
+                const float pv = a.has_prior ? (a.prior ? a.prior[doff + s] : a.prior_const) : 0.f;
+                const float logit = eval(dv, pv);
+                if (q == 0 && rok) a.out[ooff + s] = logit;
+            }
+        } else {
+            // ---- the search rule of binary_mlp_k: first query (hi - lo) / 2 (the reference's, not the midpoint), "visible" = logit < thr moves hi ----
+            const float pv = a.has_prior ? (a.prior ? a.prior[src] : a.prior_const) : 0.f;  // one value per ray, as plane 0 of the dense search's prior
+            float lo = a.lo, hi = a.hi, sd = (a.hi - a.lo) * 0.5f, logit = 0.f;
+            unsigned moved = 0;
+#pragma unroll 1
+            for (int p = 0; p < a.iters; ++p) {
+                logit = eval(sd, pv);
+                float thr = a.thr_logit;
+                if (a.n_bins > 0) {  // torch.bucketize(depth, bins): number of edges strictly below the query depth
+                    int idx = 0;
+                    for (int e = 0; e < a.n_bins; ++e) idx += a.bins[e] < sd ? 1 : 0;
+                    thr = a.thr_logits[idx < a.n_bins ? idx : a.n_bins - 1];
+                }
+                if (logit < thr) { hi = sd; moved |= 1u; }
+                else { lo = sd; moved |= 2u; }
+                sd = (hi + lo) * 0.5f;
+            }
+            if (q == 0 && rok) {  // ray rr = (b, j) with ray_step = 1: src == rr
+                a.sdepth[src] = sd;
+                a.out[src] = logit;
+                if (a.flags) a.flags[src] = (unsigned char)moved;
+                if (a.points) {  // the expression of include/idh.h: BackprojectDepth on the ray's own (x, y), then world_T_cam
+                    const float *iK = a.invK + (size_t)b * 16;
+                    float X[3];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) X[i] = sd * fmaf(iK[4 * i], x, fmaf(iK[4 * i + 1], y, iK[4 * i + 2]));
+                    if (a.wTc) {
+                        const float *T = a.wTc + (size_t)b * 16;
+#pragma unroll
+                        for (int i = 0; i < 3; ++i)
+                            a.points[3 * src + i] = fmaf(T[4 * i], X[0], fmaf(T[4 * i + 1], X[1], fmaf(T[4 * i + 2], X[2], T[4 * i + 3])));
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) a.points[3 * src + i] = X[i];
+                    }
+                }
+            }
         }
     }
 }
+
+__global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) { ray_body<false>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void ray_search_k(const RayArgs a) { ray_body<true>(a); }
 
 // ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
 // Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
@@ -214,8 +276,9 @@ __global__ __launch_bounds__(256) void project_points_k(const float *__restrict_
 // Work partition of one launch (host side, also what tests/ray_query_ref.py restates for its persistent-loop case):
 // an item is 16 rays x one run of samples.  While the ray tiles alone do not give every SIMD of the device (256 CUs x 4) a wave, the S
 // samples of a tile are cut into runs of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256
-// per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.
-static int ray_mlp_launch(RayArgs a, void *stream) {
+// per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.  The search (S = 1) has one item per tile: its iterations are
+// dependent, so there is nothing to split.
+static int ray_mlp_launch(RayArgs a, void *stream, bool search = false) {
     constexpr int kSimds = 256 * 4, kMinChunk = 8;
     const long long tiles = ((long long)a.M + 15) / 16;
     int nchunk = 1;
@@ -235,13 +298,14 @@ static int ray_mlp_launch(RayArgs a, void *stream) {
     const int cblocks = (a.Cf + 15) >> 4;
     const size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
                        6 * kHidden * sizeof(float);
-    static IdhDeviceOnce attr_set;
-    if (attr_set.first()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ray_mlp_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    static IdhDeviceOnce attr_set[2];
+    const auto kernel = search ? ray_search_k : ray_mlp_k;
+    if (attr_set[search].first()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return IDH_ELAUNCH;
-        attr_set.mark();
+        attr_set[search].mark();
     }
-    hipLaunchKernelGGL(ray_mlp_k, dim3((unsigned)grid), dim3(waves * 64), lds, idh_stream(stream), a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(waves * 64), lds, idh_stream(stream), a);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }
@@ -264,6 +328,34 @@ extern "C" int idh_binary_mlp_rays_fwd(const float *feat_nhwc, int feat_cs, int 
               (float)grid_w, (float)grid_h, has_prior, prior_const, 0, 1, S};
     a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
     return ray_mlp_launch(a, stream);
+}
+
+// Depth and hit point per ray by binary search (reference BDModel.forward(infer_depth=True), bd_model.py:273-292, at the rays of
+// run_mlp_train): the gather of idh_binary_mlp_rays_fwd once, then `iters` dependent evaluations in one launch.  include/idh.h states the rule.
+extern "C" int idh_binary_mlp_rays_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rays_bn2,
+                                              const float *prior_bn, int has_prior, float prior_const, int N, int grid_w, int grid_h,
+                                              const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi,
+                                              float threshold, const float *bins, const float *thr_logits, int n_bins, const float *invK_44,
+                                              const float *world_T_cam_44, float *depth_bn, float *last_logits_bn, unsigned char *flags_bn,
+                                              float *points_bn3, void *stream) {
+    if (B < 0 || N < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || grid_w <= 0 || grid_h <= 0 || iters <= 0 || !(hi > lo) || n_bins < 0)
+        return IDH_EINVAL;
+    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
+    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
+    if (points_bn3 && !invK_44) return IDH_EINVAL;
+    if (B == 0 || N == 0) return IDH_OK;
+    if (!feat_nhwc || !rays_bn2 || !w1f_packed || !w2_packed || !vecs6x128 || !depth_bn || !last_logits_bn) return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)prior_bn, (const void *)bins, (const void *)thr_logits,
+                          (const void *)invK_44, (const void *)world_T_cam_44, (const void *)depth_bn, (const void *)last_logits_bn, (const void *)points_bn3})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    const long long M = (long long)B * N;
+    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    RayArgs a{feat_nhwc, rays_bn2, nullptr, prior_bn, w1f_packed, w2_packed, vecs6x128, last_logits_bn, (int)M, N, N, 1, 1, H, W, feat_cs, Cf,
+              (float)grid_w, (float)grid_h, has_prior, prior_const, 0, 1, 1,
+              iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth_bn, flags_bn, points_bn3, invK_44,
+              world_T_cam_44};
+    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
+    return ray_mlp_launch(a, stream, true);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

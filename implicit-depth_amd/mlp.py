@@ -92,6 +92,17 @@ def occlusion_logits(net, feat_nhwc: torch.Tensor, feat_c0: int, n_feat: int, de
     return out
 
 
+def _thresholder_tables(thresholder, dev):
+    """(bins, logit(thresholds)) fp32 on ``dev`` for the search kernels, (None, None) without a thresholder."""
+    if thresholder is None:
+        return None, None
+    bins = thresholder.bins.to(device=dev, dtype=torch.float32).contiguous()
+    thr = thresholder.thresholds.to(device=dev, dtype=torch.float32)
+    if bins.dim() != 1 or thr.shape != bins.shape or not bool(((thr > 0) & (thr < 1)).all()):
+        raise _lib.IdhError("thresholder needs 1-D bins / thresholds of equal length with thresholds in (0, 1)")
+    return bins, torch.log(thr / (1 - thr)).contiguous()
+
+
 def infer_depth(net, feat_nhwc: torch.Tensor, feat_c0: int, n_feat: int, prior_b1hw: Optional[torch.Tensor] = None,
                 iters: int = 12, lo: float = 0.5, hi: float = 8.0, threshold: float = 0.5, thresholder=None):
     """Fused form of the reference's ``infer_depth`` loop (bd_model.py:273-292): returns
@@ -105,14 +116,7 @@ def infer_depth(net, feat_nhwc: torch.Tensor, feat_c0: int, n_feat: int, prior_b
     prior = prior_b1hw.contiguous() if prior_b1hw is not None else None
     sd = torch.empty(B, 1, H, W, device=feat_nhwc.device)
     logits = torch.empty(B, 1, H, W, device=feat_nhwc.device)
-    bins = thr_logits = None
-    if thresholder is not None:
-        dev = feat_nhwc.device
-        bins = thresholder.bins.to(device=dev, dtype=torch.float32).contiguous()
-        thr = thresholder.thresholds.to(device=dev, dtype=torch.float32)
-        if bins.dim() != 1 or thr.shape != bins.shape or not bool(((thr > 0) & (thr < 1)).all()):
-            raise _lib.IdhError("thresholder needs 1-D bins / thresholds of equal length with thresholds in (0, 1)")
-        thr_logits = torch.log(thr / (1 - thr)).contiguous()
+    bins, thr_logits = _thresholder_tables(thresholder, feat_nhwc.device)
     if math == "f16x3":
         _lib.check(
             _lib.lib().idh_binary_mlp_search_f16x3_fwd(feat_nhwc.data_ptr() + 4 * feat_c0, CS, n_feat, _lib.ptr(prior), int(net.use_prior), -1.0,
@@ -192,6 +196,53 @@ def ray_logits(net, feat_view, rays: torch.Tensor, depths: torch.Tensor, prior=N
                                            gw, gh, w1p.data_ptr(), w2p.data_ptr(), vecs.data_ptr(), out.data_ptr(), _lib.stream_ptr()),
         "idh_binary_mlp_rays_fwd")
     return out
+
+
+def ray_depths(net, feat_view, rays: torch.Tensor, prior=None, grid=None, iters: int = 12, lo: float = 0.5, hi: float = 8.0, threshold: float = 0.5,
+               thresholder=None, invK: Optional[torch.Tensor] = None, world_T_cam: Optional[torch.Tensor] = None):
+    """Where each ray hits the scene: the ``infer_depth`` search (bd_model.py:273-292) at sparse rays, on ``idh_binary_mlp_rays_search_fwd`` -
+    one launch gathers each ray's feature row once and runs the ``iters`` dependent evaluations in registers.  ``feat_view`` / ``rays`` /
+    ``grid`` as ``ray_logits`` (scale 0); ``prior``: None (a prior-enabled network sees the constant -1, bd_model.py:433-434), a float
+    or a (B,N) tensor; ``thresholder`` as ``infer_depth``.  ``invK`` (B,4,4) at the resolution of ``grid``: also return the hit points
+    ``d * invK (x, y, 1)`` (BackprojectDepth, geometry_utils.py:39,60-61), taken to the world by ``world_T_cam`` (B,4,4) when given.
+    Returns (depth (B,N), logits of the last evaluation (B,N), hit (B,N) uint8, points (B,N,3) | None); hit: bit 0 = the far bound moved,
+    bit 1 = the near bound moved - 3: the surface lies inside [lo, hi]; 1 / 2: the search ran into ``lo`` / ``hi``, no hit in range."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_rays_search_fwd; set mlp_math = 'fp32'")
+    prior_t = prior if isinstance(prior, torch.Tensor) else None
+    _lib.require_cuda_f32(feat_view.buf, rays, prior_t, invK, world_T_cam)
+    B, H, W = feat_view.N, feat_view.H, feat_view.W
+    if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+        raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+    N = rays.shape[1]
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if prior_t is not None and tuple(prior_t.shape) != (B, N):
+        raise _lib.IdhError(f"prior must be ({B}, {N}), got {tuple(prior_t.shape)}")
+    if world_T_cam is not None and invK is None:
+        raise _lib.IdhError("world_T_cam without invK: the hit points need the intrinsics of the rays' grid")
+    for m in (invK, world_T_cam):
+        if m is not None and tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"invK / world_T_cam must be ({B}, 4, 4), got {tuple(m.shape)}")
+    gh, gw = (H, W) if grid is None else (int(grid[0]), int(grid[1]))
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
+    bins, thr_logits = _thresholder_tables(thresholder, rays.device)
+    r = rays.contiguous()  # alive until enqueued
+    pt = prior_t.contiguous() if prior_t is not None else None
+    iK = invK.contiguous() if invK is not None else None
+    wT = world_T_cam.contiguous() if world_T_cam is not None else None
+    buf = torch.empty((5 if iK is not None else 2) * B * N, device=rays.device)  # one allocation for the float outputs, as project_points
+    depth, logits = buf[: B * N].view(B, N), buf[B * N: 2 * B * N].view(B, N)
+    points = buf[2 * B * N:].view(B, N, 3) if iK is not None else None
+    hit = torch.empty(B, N, device=rays.device, dtype=torch.uint8)
+    _lib.check(
+        _lib.lib().idh_binary_mlp_rays_search_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, r.data_ptr(), _lib.ptr(pt), int(net.use_prior),
+                                                  -1.0 if prior is None or prior_t is not None else float(prior), N, gw, gh, w1p.data_ptr(),
+                                                  w2p.data_ptr(), vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
+                                                  0 if bins is None else bins.numel(), _lib.ptr(iK), _lib.ptr(wT), depth.data_ptr(),
+                                                  logits.data_ptr(), hit.data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
+        "idh_binary_mlp_rays_search_fwd")
+    return depth, logits, hit, points
 
 
 def project_points(points_bn3: torch.Tensor, cam_T_world: torch.Tensor, K: torch.Tensor, H: int, W: int, prior_pred: Optional[torch.Tensor] = None,

@@ -83,6 +83,23 @@ class HotPath(nn.Module):
             grid = (final[0].H, final[0].W)
         return {f"ray_pred_{s}": ray_logits(self.binary_mlp, final[s], rays, depths, prior, scale=s, grid=grid, ray_step=s + 1) for s in scales}
 
+    def query_ray_depths(self, rays: torch.Tensor, prior=None, grid: Optional[Sequence[int]] = None, thresholder=None,
+                         invK_s0_b44: Optional[torch.Tensor] = None, world_T_cam_b44: Optional[torch.Tensor] = None, iters: int = 12,
+                         lo: float = 0.5, hi: float = 8.0, threshold: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Where sparse rays hit the scene, against the scale-0 decoder output of the LAST ``forward`` (valid as for ``query_rays``): the
+        ``infer_depth`` search (bd_model.py:273-292) per ray in one ``mlp.ray_depths`` launch, no conv runs.  ``rays`` (B,N,2) in
+        pixel-centre units of ``grid`` = (h, w) (None: the scale-0 map's own shape); ``prior`` None | float | (B,N); ``thresholder``: None =
+        this HotPath's ``thresholder`` (None there: the constant ``threshold``).  ``invK_s0_b44`` (B,4,4), the inverse intrinsics at the
+        resolution of ``grid``, adds the hit points; ``world_T_cam_b44`` takes them to the world.  Returns {"ray_depth" (B,N), "ray_pred"
+        (B,N) logits of the last evaluation, "ray_hit" (B,N) uint8 (3 = bracketed inside [lo, hi]; 1 / 2 = ran into lo / hi), "ray_points"
+        (B,N,3) | None}."""
+        from .mlp import ray_depths
+
+        final = _last_final(self, rays.shape[0], (0,))
+        depth, pred, hit, points = ray_depths(self.binary_mlp, final[0], rays, prior, grid, iters, lo, hi, threshold,
+                                              self.thresholder if thresholder is None else thresholder, invK_s0_b44, world_T_cam_b44)
+        return {"ray_depth": depth, "ray_pred": pred, "ray_hit": hit, "ray_points": points}
+
     def query_points(self, points_bn3: torch.Tensor, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor,
                      prior_inputs: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """Occlusion of world points (B,N,3) against the LAST forward: each point is projected into the scale-0 map with ``K_s0_b44`` /

@@ -82,7 +82,7 @@ class StreamingSession:
         self.last_indices: Optional[Tuple[int, ...]] = None  # their frame numbers
         self.last_matching: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # (cur (1,H,W,C), src (1,K,H,W,C)) of the last prediction
         self._prior: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-        self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's pose and intrinsics: what query_points projects with
+        self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's poses and intrinsics: what query_points / raycast use
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -145,7 +145,8 @@ class StreamingSession:
             if self.use_prior and "pred_0" in out:
                 self._prior = (torch.sigmoid(out["pred_0"]), cur_data["cam_T_world_b44"])  # sigmoid_custom(x, 1.0), inference.py:154
             if self.hot.binary_mlp is not None:
-                self._key = {"cam_T_world_b44": cur_data["cam_T_world_b44"], "K_s0_b44": cur_data["K_s0_b44"]}
+                self._key = {"cam_T_world_b44": cur_data["cam_T_world_b44"], "K_s0_b44": cur_data["K_s0_b44"],
+                             "world_T_cam_b44": cur_data["world_T_cam_b44"], "invK_s0_b44": cur_data["invK_s0_b44"]}
                 if query_points is not None:
                     out.update(self.query_points(query_points))
         if "prior_mask" in out:
@@ -173,3 +174,17 @@ class StreamingSession:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
         with torch.inference_mode():
             return self.hot.query_points(points_bn3, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi)
+
+    def raycast(self, rays: torch.Tensor, thresholder=None) -> Dict[str, torch.Tensor]:
+        """The hit test: where rays (1,N,2) - (x, y) in pixel-centre units of the keyframe's scale-0 map - meet the scene, against the LAST
+        prediction's decoder features, also on the frames where ``step`` returned None.  ``HotPath.query_ray_depths`` with the keyframe's
+        ``invK_s0`` and ``world_T_cam``: "ray_points" are WORLD points, "ray_hit" == 3 marks the rays whose surface lies inside the search
+        range.  ``thresholder``: None = the model's.  With ``use_prior`` the network sees the constant -1 in its prior channel, as the
+        reference does where no prior prediction exists (bd_model.py:433-434): the carried prior is a dense map of the PREVIOUS
+        prediction in the keyframe's view, not a per-ray value."""
+        if self._key is None:
+            raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
+        _lib.require_cuda_f32(rays)
+        k = self._key
+        with torch.inference_mode():
+            return self.hot.query_ray_depths(rays, thresholder=thresholder, invK_s0_b44=k["invK_s0_b44"], world_T_cam_b44=k["world_T_cam_b44"])

@@ -307,6 +307,30 @@ int idh_binary_mlp_rays_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, 
                             const float *depth_bns, const float *prior_bns, int has_prior, float prior_const, int N, int S,
                             int ray_step, int grid_w, int grid_h, const float *w1f_packed, const float *w2_packed,
                             const float *vecs6x128, float *out_bqs, void *stream);
+/* Depth and hit point per ray: the binary search of idh_binary_mlp_search_*_fwd (reference BDModel.forward(infer_depth=True),
+ * bd_model.py:273-292) at the sparse rays of idh_binary_mlp_rays_fwd, in one launch.  Per ray, once: exactly the gather above (a corner
+ * outside the map is not read; a non-finite ray has no corner, f = 0) and pre1 = W1f . f + b1.  Then `iters` dependent evaluations:
+ *   q_0 = (hi - lo) * 0.5f   (the reference's first query, not the midpoint)
+ *   visible = logit(q_n) < thr(q_n):  visible -> hi = q_n, otherwise lo = q_n;   q_{n+1} = (hi + lo) * 0.5f
+ *   thr = logf(threshold / (1 - threshold)) when n_bins == 0, else thr_logits[min(#{bins[e] < q_n}, n_bins - 1)]   (bd_model.py:282-283)
+ *   prior_bn (B,N): one value per ray, or NULL (then prior_const when has_prior) - as plane 0 of the dense search's prior
+ * Outputs (B,N): depth_bn = q_iters, the final query; last_logits_bn = logit(q_{iters-1}); optional flags_bn (uint8): bit 0 = hi moved at
+ * some step, bit 1 = lo moved: 3 = the surface was bracketed inside [lo, hi], 1 or 2 = the search ran into a bound (no hit in range).
+ * Optional points_bn3 (B,N,3), needs invK_44 (B,4,4) at the resolution of the rays' grid: with d = depth_bn and (x, y) the ray - whose
+ * pixel-centre units already carry BackprojectDepth's + 0.5 (reference utils/geometry_utils.py:39,60-61) - and iK = invK_44[b], T =
+ * world_T_cam_44[b], in fp32 with one rounding per operation / fma:
+ *   c_i = fmaf(iK[4i], x, fmaf(iK[4i+1], y, iK[4i+2]))     X_i = d * c_i                                                  i = 0..2
+ *   p_i = fmaf(T[4i], X_0, fmaf(T[4i+1], X_1, fmaf(T[4i+2], X_2, T[4i+3])))      (world_T_cam_44 == NULL: p_i = X_i, camera space)
+ * fp32 only.  IDH_EINVAL: the conditions of idh_binary_mlp_rays_fwd that apply (NULL feat / rays / weights, negative B or N, H, W, Cf <= 0,
+ * Cf % 4, feat_cs < Cf, grid_w or grid_h <= 0), iters <= 0, !(hi > lo), n_bins < 0, n_bins == 0 with threshold outside (0, 1), n_bins > 0
+ * with a NULL table, points_bn3 without invK_44, a NULL depth_bn or last_logits_bn, a pointer that is not 4-byte aligned (flags_bn: any).
+ * B == 0 or N == 0: IDH_OK, no launch.  IDH_EUNSUPPORTED: B * N or B * H * W >= 2^31.  Everything is checked on the host first. */
+int idh_binary_mlp_rays_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rays_bn2,
+                                   const float *prior_bn, int has_prior, float prior_const, int N, int grid_w, int grid_h,
+                                   const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi,
+                                   float threshold, const float *bins, const float *thr_logits, int n_bins, const float *invK_44,
+                                   const float *world_T_cam_44, float *depth_bn, float *last_logits_bn, unsigned char *flags_bn,
+                                   float *points_bn3, void *stream);
 /* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
  * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
  *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
