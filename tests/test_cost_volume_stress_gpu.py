@@ -3,39 +3,17 @@ order): random rotations up to ~1 rad about random axes, translations up to 2 m 
 behind and inside the swept volume), random focal lengths / principal points, depth ranges and map sizes.  Guards the
 window kernel's table logic — run skipping, window placement, per-lane global fall-back — where a wrong decision
 would silently drop or corrupt samples."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
+import volume_geometry as vg
+
 pytestmark = pytest.mark.gpu
 
 
-def _rot(axis, ang):
-    axis = axis / np.linalg.norm(axis)
-    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + math.sin(ang) * K + (1 - math.cos(ang)) * (K @ K)
-
-
 def _case(rng, B, K, H, W):
-    f = rng.uniform(0.6, 2.0) * W
-    Kmat = np.eye(4)
-    Kmat[0, 0] = f
-    Kmat[1, 1] = f * rng.uniform(0.9, 1.1)
-    Kmat[0, 2] = W * rng.uniform(0.4, 0.6)
-    Kmat[1, 2] = H * rng.uniform(0.4, 0.6)
-    poses = np.tile(np.eye(4), (B, K, 1, 1))
-    for b in range(B):
-        for k in range(K):
-            mode = rng.integers(0, 4)
-            ang = rng.uniform(0, 0.15) if mode == 0 else rng.uniform(0, 1.0)
-            poses[b, k, :3, :3] = _rot(rng.standard_normal(3), ang)
-            scale = (0.2, 0.8, 2.0, 0.05)[mode]
-            poses[b, k, :3, 3] = rng.standard_normal(3) * scale
-    E = np.linalg.inv(poses)
-    t = lambda a: torch.tensor(a, dtype=torch.float32).cuda().contiguous()
-    return {"src_extrinsics": t(E), "src_poses": t(poses), "src_Ks": t(np.tile(Kmat, (B, K, 1, 1))), "cur_invK": t(np.tile(np.linalg.inv(Kmat), (B, 1, 1)))}
+    return {k: v.cuda() for k, v in vg.random_geometry(rng, B, K, H, W).items()}
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -130,21 +108,31 @@ def test_source_camera_plane_cuts_through_tiles(seed):
     inp = _case(rng, B, K, H, W)
     lo = float(rng.uniform(0.2, 1.0))
     hi = lo * float(rng.uniform(3.0, 20.0))
-    E = inp["src_extrinsics"].cpu().double().numpy()
-    invK = inp["cur_invK"].cpu().double().numpy()
-    for b in range(B):
-        for k in range(0, K, 2):  # every other view is a crossing view, the rest stay random
-            axis = np.array([0.0, 1.0, 0.0]) if rng.integers(0, 2) else np.array([1.0, 0.0, 0.0])
-            R = _rot(axis + 0.05 * rng.standard_normal(3), rng.uniform(1.22, 1.92) * (1 if rng.integers(0, 2) else -1))
-            px = np.array([W * rng.uniform(0.3, 0.7), H * rng.uniform(0.3, 0.7), 1.0])
-            X = math.sqrt(lo * hi) * (invK[b, :3, :3] @ px)
-            t = -R @ X  # the point lands on the source camera's centre: z (and x, y) change sign around it
-            t[:2] += rng.standard_normal(2) * 0.3
-            E[b, k, :3, :3], E[b, k, :3, 3] = R, t
+    inp = {k: v.cuda() for k, v in vg.cross_source_plane(rng, {k: v.cpu() for k, v in inp.items()}, H, W, lo, hi).items()}
     g = torch.Generator().manual_seed(seed)
-    inp["src_extrinsics"] = torch.tensor(E, dtype=torch.float32).cuda().contiguous()
-    inp["src_poses"] = torch.tensor(np.linalg.inv(E), dtype=torch.float32).cuda().contiguous()
     inp["cur_feats"] = torch.randn(B, 16, H, W, generator=g).cuda()
     inp["src_feats"] = torch.randn(B, K, 16, H, W, generator=g).cuda()
     inp["min_depth"], inp["max_depth"] = lo, hi
     _check_all_kernels_vs_fp64(inp, H, W, D, ("z-cross", seed, B, K, H, W, D))
+
+
+# (B, K, H, W, D) of the four seeds below: maps of at least 48 x 12 (the window kernel's smallest), odd sizes, one and several tiles per row
+GEOMETRY_SHAPES = [(2, 3, 14, 50, 9), (3, 8, 20, 67, 21), (2, 5, 14, 50, 9), (3, 7, 20, 67, 21)]
+GEOMETRY_FAMILIES = ("intrinsics", "roll_pitch")
+
+
+def geometry_case(family, seed):
+    """CPU inputs of one case of the test below (tests/test_volume_geometry_cpu.py checks the same cases against the mutations)"""
+    B, K, H, W, D = GEOMETRY_SHAPES[seed]
+    return vg.build_case(family, 100 + seed, B, K, 16, H, W)
+
+
+@pytest.mark.parametrize("family", GEOMETRY_FAMILIES)
+@pytest.mark.parametrize("seed", range(4))
+def test_every_kernel_vs_fp64_oracle_per_view_intrinsics_and_roll_pitch(seed, family):
+    """``intrinsics``: another K for every (b, k) and another current-frame K for every b - the cases above repeat one matrix, so that the
+    indexing src_K + (b * K + k) * 16 / cur_invK + b * 16 of the four build_homography call sites never mattered; ``roll_pitch``: rolls of 30
+    and 90 degrees and pitches of 20 degrees, a large column 1 of every homography.  Lane, quad and window kernel, the bars of the cases above.  (The eight cases: 1.0 s on the MI355X host.)"""
+    B, K, H, W, D = GEOMETRY_SHAPES[seed]
+    inp = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in geometry_case(family, seed).items()}
+    _check_all_kernels_vs_fp64(inp, H, W, D, (family, seed, B, K, H, W, D))

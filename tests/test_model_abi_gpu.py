@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import implicit_depth_amd.synthetic as syn
+import volume_geometry as vg
 from hot_helpers import holder, rel_poses, to_cuda
 
 pytestmark = pytest.mark.gpu
@@ -125,6 +126,31 @@ def test_bit_identical_to_hotpath(case):
     _same(got2, ref, keys)
     if "pred_0" in keys:
         assert bool(torch.isfinite(got["pred_0"]).all())
+
+
+@pytest.mark.parametrize("volume,K", [("mlp", 7), ("dot", 8)])
+def test_per_view_intrinsics_bit_identical_to_hotpath(volume, K):
+    """idh_model_fwd with another src_K for every (b, k), another cur_invK for every b and general rotations (tests/volume_geometry.py): the
+    cases above repeat one K and rotate about y alone.  A second call on the same plan with other matrices must follow them."""
+    B, img_h, img_w = 3, 64, 128
+    H, W = img_h // 4, img_w // 4
+    hp, ent, cur, args = _setup(K, volume, "bd", False, B, img_h, img_w)
+    rd = cur["rendered_depth"].contiguous()
+    keys = ["lowest_cost_bhw", "pred_0"] + (["overall_mask_bhw"] if volume == "mlp" else [])
+    with torch.inference_mode():
+        plan = ent.prepare(B, K, 16, H, W, rd.shape[1], return_mask=volume == "mlp", ws_fill=float("nan"))
+        lows = []
+        for seed in (300, 301):
+            c = to_cuda(vg.build_case("intrinsics", seed, B, K, 16, H, W))
+            a = dict(args, matching_cur_feats=c["cur_feats"], matching_src_feats=c["src_feats"], src_cam_T_cur_cam=c["src_extrinsics"],
+                     cur_cam_T_src_cam=c["src_poses"], src_K=c["src_Ks"], cur_invK=c["cur_invK"])
+            ref = hp(**a, rendered_depth=rd, return_mask=volume == "mlp")
+            got = ent(**a, rendered_depth=rd, return_mask=volume == "mlp", plan=plan)
+            torch.cuda.synchronize()
+            _same(got, ref, keys)
+            assert bool(torch.isfinite(got["pred_0"]).all())
+            lows.append(got["lowest_cost_bhw"].clone())
+    assert not torch.equal(lows[0], lows[1])
 
 
 def test_frame_chain_matches_hotpath():

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 import implicit_depth_amd.synthetic as syn
+import volume_geometry as vg
 from conftest import TOL, rel_err
 from oracle import cost_volume as ocv
 from oracle import networks as onet
@@ -66,6 +67,45 @@ def test_bd_hot_path_matches_oracle(cfg):
     enc = model.cost_volume_net(cvol, [t.cuda() for t in pyr[1:]])
     feats = model.depth_decoder([pyr[0].cuda()] + enc)
     assert rel_err(out2["feature_s0_b1hw"], feats["feature_s0_b1hw"]) < 1e-6
+
+
+def test_feature_volume_hot_path_follows_per_view_intrinsics():
+    """HotPath == module-by-module (the bar of test_feature_volume_gpu.py::test_pipeline_with_feature_volume) on cameras with general rotations,
+    another K for every (b, k) and another current-frame K for every b; then the same shapes again - a plan-cache hit - with every intrinsic
+    matrix redrawn: the second call must follow the new values."""
+    import numpy as np
+
+    from implicit_depth_amd import networks as net
+    from implicit_depth_amd.cost_volume import FeatureVolumeManager
+    from implicit_depth_amd.pipeline import HotPath
+
+    B, K, H, W, D, P = 2, 7, 16, 24, 16, 2
+    cv = FeatureVolumeManager(H, W, D, num_source_views=K)
+    syn.fill_state_dict(cv.mlp, seed=5, gain=1.4)
+    cve = net.CVEncoder(D, [48, 64, 160, 256], [64, 128, 256, 384])
+    dec = net.BDDecoderPP([24, 64, 128, 256, 384])
+    mlp = net.BinaryMLPNetwork(dec.num_ch_dec)
+    for i, mm in enumerate((cve, dec, mlp)):
+        syn.fill_state_dict(mm, seed=60 + i)
+    model = HotPath(cv, cve, dec, mlp).cuda()
+    pyr = [t.cuda() for t in syn.encoder_pyramid(B, H * 4, W * 4, seed=2)]
+    rd = syn.rendered_depth_planes(B, H * 2, W * 2, P).cuda()
+    first = vg.build_case("intrinsics", 200, B, K, 16, H, W)
+    second = vg.per_view_intrinsics(np.random.default_rng(201), {k: (v.clone() if torch.is_tensor(v) else v) for k, v in first.items()}, H, W)
+    assert not torch.equal(first["src_Ks"], second["src_Ks"]) and not torch.equal(first["cur_invK"], second["cur_invK"])
+    outs = []
+    for n, case in enumerate((first, second)):
+        inp = {k: v.cuda() for k, v in case.items() if torch.is_tensor(v)}
+        out = model(inp["cur_feats"], inp["src_feats"], pyr, inp["src_extrinsics"], inp["src_poses"], inp["src_Ks"], inp["cur_invK"],
+                    rendered_depth=rd, return_mask=True, return_features=True)
+        assert len(model._plans.d) == 1  # the second call replays the first one's plan
+        vol, low, _, mask = cv(**dict(inp, min_depth=0.25, max_depth=5.0), return_mask=True)
+        enc = cve(vol, pyr[1:])
+        feats = dec([pyr[0]] + enc)
+        assert rel_err(out["feature_s0_b1hw"], feats["feature_s0_b1hw"]) < 1e-6, n
+        assert torch.equal(out["overall_mask_bhw"], mask) and torch.equal(out["lowest_cost_bhw"], low), n
+        outs.append({k: out[k].clone() for k in ("feature_s0_b1hw", "lowest_cost_bhw")})
+    assert not torch.equal(outs[0]["lowest_cost_bhw"], outs[1]["lowest_cost_bhw"])
 
 
 def test_depth_model_hot_path_matches_oracle():

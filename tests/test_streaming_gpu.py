@@ -41,10 +41,16 @@ def _model(volume, K, use_prior=False):
     return m.cuda().eval()
 
 
-def _frame(t, poses, P=3):
-    """``FrameIngest``'s dictionary for frame t of the track, built by hand (float32, on the GPU)."""
+def _frame(t, poses, P=3, own_K=False):
+    """``FrameIngest``'s dictionary for frame t of the track, built by hand (float32, on the GPU).  ``own_K``: the frame's matching-scale
+    intrinsics are its own (focal lengths 0.8 .. 1.25 of the shared ones, principal point up to 10 % of the map size away)."""
     Hm, Wm = IMG_H // 4, IMG_W // 4
     K1, K0 = syn.intrinsics(Wm, Hm).float(), syn.intrinsics(IMG_W // 2, IMG_H // 2).float()
+    if own_K:
+        K1[0, 0] *= 0.8 + 0.45 * ((5 * t + 2) % 12) / 11
+        K1[1, 1] *= 0.8 + 0.45 * ((7 * t + 5) % 12) / 11
+        K1[0, 2] += 0.1 * Wm * (((5 * t + 3) % 12) / 5.5 - 1)
+        K1[1, 2] += 0.1 * Hm * (((7 * t + 1) % 12) / 5.5 - 1)
     w = poses[t].astype(np.float32)
     c = np.linalg.inv(w) if np.isfinite(w).all() else np.full((4, 4), np.nan, np.float32)
     return to_cuda({
@@ -117,6 +123,39 @@ def test_session_equals_fused_forward_on_recomputed_keyframes(volume, K):
     expected = [t for t in range(T) if codes[t] == 1 and sel[t, -1] >= 0]
     assert predicted == expected and len(predicted) >= 6
     print(f"{volume}: predicted on frames {predicted}; cached == recomputed bits on {sum(same_bits)} of {len(same_bits)}")
+
+
+@pytest.mark.parametrize("volume,K", [("mlp", 3), ("dot", 2)])
+def test_session_follows_per_frame_intrinsics(volume, K):
+    """Every frame of the track has its own K_s1_b44 / invK_s1_b44 (a stream that mixes cameras, or a zoom): the keyframe bank must hand each
+    stored view its own K and the current frame its own inverse.  The first seven frames of the track, compared as above with the forward fed
+    the selected keyframes by hand; the same keyframes with frame 0's K for every view must give another volume."""
+    from implicit_depth_amd.dropin import fused_forward
+    from implicit_depth_amd.streaming import StreamingSession
+
+    poses, dists = syn.keyframe_trajectory("stream12", seed=0)
+    m = _model(volume, K)
+    session = StreamingSession(m, num_source_views=K, buffer_size=BUFFER)
+    reference = fused_forward(m, native_matching_stem=True)
+    frames = [_frame(t, poses, own_K=True) for t in range(7)]
+    every = [tuple(f[k].flatten().tolist()) for f in frames for k in ("K_s1_b44", "invK_s1_b44")]
+    assert len(set(every)) == len(every)
+    n = 0
+    for t in range(7):
+        out, code = session.step(frames[t], world_T_cam=poses[t], dist_to_last_valid=dists[t], return_mask=True)
+        if out is None:
+            continue
+        src = _src_of(frames, session.last_indices)
+        ref = reference("test", dict(frames[t]), src, return_mask=True)
+        torch.cuda.synchronize()
+        _compare(out, ref, f"{volume} own K, frame {t}")
+        shared = dict(src, K_s1_b44=frames[0]["K_s1_b44"][None].expand_as(src["K_s1_b44"]).contiguous())
+        blind = reference("test", dict(frames[t]), shared, return_mask=True)
+        moved = rel_err(blind["pred_0"].cpu(), ref["pred_0"].cpu())
+        print(f"{volume} own K, frame {t}: one K for every view moves pred_0 by {moved:.2e} of its scale")
+        assert moved > 100 * TOL, (t, moved)
+        n += 1
+    assert n >= 2, n
 
 
 def test_prior_is_handed_over_between_predictions():
