@@ -14,6 +14,11 @@
 // ray_search_k is the same text with the sample loop replaced by the binary depth search of binary_mlp_k (BDModel.forward(infer_depth=True),
 // bd_model.py:273-292): lo / hi / query / flags of a ray live in the registers of its four quarter-lanes, which see the same reduced logit
 // and so stay in step; the final query is back-projected to a camera- or world-space hit point (BackprojectDepth, geometry_utils.py:39,60-61).
+//
+// view_mlp_k is the same text again with the rays drawn from a depth map in another camera: a ray is one pixel (b, p, row, col) of
+// rendered (B,P,h,w); it is back-projected with that view's invK / world_T_cam (BackprojectDepth, geometry_utils.py:55-63), projected into
+// the keyframe's scale-0 map with the expression of project_points_k below (Project3D, :77-89) and asked at its keyframe z, S = 1, with the
+// nearest sample of a prior prediction (bd_model.py:405-409) when there is one.  Rays, depth, valid and prior never reach HBM.
 #include <type_traits>
 
 #include "idh_common.h"
@@ -46,13 +51,24 @@ struct RayArgs {
     unsigned char *flags;  // B,N or null: bit 0 = hi moved, bit 1 = lo moved
     float *points;         // B,N,3 or null
     const float *invK, *wTc;  // B,4,4; wTc may be null (camera-space points)
+    // view_mlp_k only (S = 1, ray_step = 1, nchunk = 1, Nq = N = vP * vh * vw, grid = (H, W)): `depth` is rendered (B,vP,vh,vw), invK / wTc
+    // the VIEW's (both required), `prior` a (B,1,H,W) map or null, `flags` valid or null, `sdepth` the keyframe z or null, `points` or null
+    const float *key_cTw, *key_K;      // B,4,4: the keyframe's cam_T_world and K at H x W
+    const float *prior_cTw, *prior_K;  // B,4,4, with a prior map
+    int nb, vP, vh, vw;                // nb = B
+    float fill;
 };
+
+enum { kSamples = 0, kSearch = 1, kView = 2 };
+constexpr int kViewMaxBatch = 128;  // 24 KiB of cameras next to at most 96 KiB of weights
+constexpr int kCamFloats = 48;  // per batch in LDS: P = K cam_T_world (12), the prior camera's (12), rows 0-2 of the view's invK (12) and world_T_cam (12)
 
 constexpr int kRayMaxThreads = 768;  // 12 waves, as binary_mlp_k; small launches use 4 (ray_mlp_launch)
 constexpr int kW1LdsMaxBlocks = 4;   // Cf <= 64 -> W1f in LDS, as binary_mlp_k
 
-// kSearch = false: the S depth samples of `depth`; true: `iters` dependent evaluations at the ray's current search depth
-template <bool kSearch>
+// kSamples: the S depth samples of `depth`; kSearch: `iters` dependent evaluations at the ray's current search depth; kView: one evaluation
+// per pixel of a depth map seen from another camera
+template <int kMode>
 __device__ __forceinline__ void ray_body(const RayArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int nthreads = blockDim.x, nwaves = nthreads >> 6;
@@ -67,6 +83,25 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         if (w1_lds)
             for (int i = threadIdx.x; i < cblocks * kNS * 64; i += nthreads) sW1[i] = g1[i];
         for (int i = threadIdx.x; i < 6 * kHidden; i += nthreads) s_vec[i] = a.vecs[i];
+    }
+    float *s_cam = s_vec + 6 * kHidden;
+    if constexpr (kMode == kView) {
+        // P = K cam_T_world of the keyframe (and of the prior camera), once per workgroup and batch: the fma loop of project_points_k
+        for (int t = threadIdx.x; t < 2 * a.nb; t += nthreads) {
+            const int b = t >> 1, pc = t & 1;
+            if (pc && !a.prior) continue;
+            const float *Kb = (pc ? a.prior_K : a.key_K) + (size_t)b * 16, *T = (pc ? a.prior_cTw : a.key_cTw) + (size_t)b * 16;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    float s = 0.f;
+                    for (int m = 0; m < 4; ++m) s = fmaf(Kb[i * 4 + m], T[m * 4 + j], s);
+                    s_cam[b * kCamFloats + 12 * pc + i * 4 + j] = s;
+                }
+        }
+        for (int t = threadIdx.x; t < 24 * a.nb; t += nthreads) {  // rows 0-2 of the view's invK and world_T_cam, as they are
+            const int b = t / 24, e = t - b * 24;
+            s_cam[b * kCamFloats + 24 + e] = (e < 12 ? a.invK : a.wTc)[(size_t)b * 16 + (e < 12 ? e : e - 12)];
+        }
     }
     __syncthreads();
     const float *s_b1 = s_vec, *s_wd = s_vec + kHidden, *s_wp = s_vec + 2 * kHidden, *s_b2 = s_vec + 3 * kHidden,
@@ -86,8 +121,67 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         const int rr = rok ? r : a.M - 1;
         const int b = rr / a.Nq, j = rr - b * a.Nq;
         const size_t src = (size_t)b * a.N + (size_t)j * a.ray_step;  // ray j of the launch is rays[b, j * ray_step]
+        float x, y;
+        // view: the pixel's world point, its keyframe z, prior sample and validity
+        float vX[3] = {0.f, 0.f, 0.f}, vz = 0.f, vprior = 0.f;
+        bool vdok = false, vvalid = false;
+        if constexpr (kMode != kView) {
+            x = a.rays[2 * src];
+            y = a.rays[2 * src + 1];
+        } else {
+            // ---- the pixel's ray: the expressions of include/idh.h; every quarter-lane of a ray computes the same values ----
+            const int pix = j % (a.vh * a.vw), row = pix / a.vw, col = pix - row * a.vw;
+            const float dr = a.depth[src];
+            vdok = dr > 0.f && dr <= 3.4028234663852886e38f;  // finite and positive (NaN fails both); anything else is asked as d = 0 and stores `fill`
+            const float d = vdok ? dr : 0.f;
+            const float px = (float)col + 0.5f, py = (float)row + 0.5f;  // BackprojectDepth's pixel centres (geometry_utils.py:39)
+            const float *cam = s_cam + b * kCamFloats;
+            const float *iK = cam + 24, *T = cam + 36;
+            float Xc[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Xc[i] = d * fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
+#pragma unroll
+            for (int i = 0; i < 3; ++i) vX[i] = fmaf(T[4 * i], Xc[0], fmaf(T[4 * i + 1], Xc[1], fmaf(T[4 * i + 2], Xc[2], T[4 * i + 3])));
+            const float X0 = vX[0], X1 = vX[1], X2 = vX[2];
+            const float *P = cam;  // project_points_k, verbatim
+            const float cx = fmaf(P[0], X0, fmaf(P[1], X1, fmaf(P[2], X2, P[3])));
+            const float cy = fmaf(P[4], X0, fmaf(P[5], X1, fmaf(P[6], X2, P[7])));
+            const float cz = fmaf(P[8], X0, fmaf(P[9], X1, fmaf(P[10], X2, P[11])));
+            const float z = fmaxf(cz, 1e-5f);
+            const float u = cx / z, v = cy / z;
+            vvalid = vdok && cz > 0.f && u >= 0.f && u < Wf && v >= 0.f && v < Hf;
+            vz = z;
+            vprior = a.prior_const;
+            if (a.prior) {
+                const float *Q = cam + 12;
+                const float qx = fmaf(Q[0], X0, fmaf(Q[1], X1, fmaf(Q[2], X2, Q[3])));
+                const float qy = fmaf(Q[4], X0, fmaf(Q[5], X1, fmaf(Q[6], X2, Q[7])));
+                const float pz = fmaf(Q[8], X0, fmaf(Q[9], X1, fmaf(Q[10], X2, Q[11])));
+                const float zz = fmaxf(pz, 1e-5f);
+                const float pu = qx / zz, pw = qy / zz;
+                const float gx = (pu / Wf - 0.5f) * 2.f, gy = (pw / Hf - 0.5f) * 2.f;
+                const float sx = ((gx + 1.f) * Wf - 1.f) * 0.5f, sy = ((gy + 1.f) * Hf - 1.f) * 0.5f;
+                const float xr = rintf(sx), yr = rintf(sy);  // round-half-even, as sample_prior_k
+                const bool in = vvalid && pz > 0.f && xr >= 0.f && xr <= Wf - 1.f && yr >= 0.f && yr <= Hf - 1.f;  // an invalid pixel reads no texel
+                const float texel = a.prior[(size_t)b * a.H * a.W + (size_t)(in ? (int)yr * a.W + (int)xr : 0)];  // texel 0 exists: no branch
+                vprior = in ? texel : -1.f;
+            }
+            x = u;
+            y = v;
+            if (!__any(vvalid)) {  // no valid ray in the tile (wave-uniform): no gather, no MLP
+                if (q == 0 && rok) {
+                    a.out[src] = a.fill;
+                    if (a.flags) a.flags[src] = 0;
+                    if (a.sdepth) a.sdepth[src] = vdok ? vz : 0.f;
+                    if (a.points) {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) a.points[3 * src + i] = vdok ? vX[i] : 0.f;
+                    }
+                }
+                continue;
+            }
+        }
         // ---- gather: the expression of include/idh.h, one rounding per operation (-ffp-contract=off) ----
-        const float x = a.rays[2 * src], y = a.rays[2 * src + 1];
         const float gx = (x / a.grid_w - 0.5f) * 2.f, gy = (y / a.grid_h - 0.5f) * 2.f;              // bd_model.py:325-326
         const float ix = ((gx + 1.f) * Wf - 1.f) * 0.5f, iy = ((gy + 1.f) * Hf - 1.f) * 0.5f;        // grid_sample, align_corners=False
         const float x0 = floorf(ix), y0 = floorf(iy);
@@ -97,7 +191,8 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         const bool vx0 = x0 >= 0.f && x0 <= Wf - 1.f, vx1 = x0 >= -1.f && x0 <= Wf - 2.f;
         const bool vy0 = y0 >= 0.f && y0 <= Hf - 1.f, vy1 = y0 >= -1.f && y0 <= Hf - 2.f;
         const int xi = (vx0 || vx1) ? (int)x0 : 0, yi = (vy0 || vy1) ? (int)y0 : 0;
-        const bool cv[4] = {vx0 && vy0, vx1 && vy0, vx0 && vy1, vx1 && vy1};
+        const bool live = kMode != kView || vvalid;  // an invalid pixel of a view reads no corner
+        const bool cv[4] = {live && vx0 && vy0, live && vx1 && vy0, live && vx0 && vy1, live && vx1 && vy1};
         const int base = b * a.H * a.W;
         const int crow[4] = {base + yi * a.W + xi, base + yi * a.W + xi + 1, base + (yi + 1) * a.W + xi, base + (yi + 1) * a.W + xi + 1};
 
@@ -163,7 +258,18 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             t += __shfl_xor(t, 32, 64);
             return t + b3;
         };
-        if constexpr (!kSearch) {
+        if constexpr (kMode == kView) {
+            const float logit = eval(vz, vprior);
+            if (q == 0 && rok) {
+                a.out[src] = vvalid ? logit : a.fill;
+                if (a.flags) a.flags[src] = vvalid ? 1 : 0;
+                if (a.sdepth) a.sdepth[src] = vdok ? vz : 0.f;
+                if (a.points) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) a.points[3 * src + i] = vdok ? vX[i] : 0.f;
+                }
+            }
+        } else if constexpr (kMode == kSamples) {
             const size_t doff = src * a.S, ooff = (size_t)rr * a.S;
             const int s_begin = ch * a.s_chunk, s_end = min(a.S, s_begin + a.s_chunk);
 #pragma unroll 1
@@ -215,8 +321,9 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
     }
 }
 
-__global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) { ray_body<false>(a); }
-__global__ __launch_bounds__(kRayMaxThreads) void ray_search_k(const RayArgs a) { ray_body<true>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) { ray_body<kSamples>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void ray_search_k(const RayArgs a) { ray_body<kSearch>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_mlp_k(const RayArgs a) { ray_body<kView>(a); }
 
 // ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
 // Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
@@ -278,7 +385,7 @@ __global__ __launch_bounds__(256) void project_points_k(const float *__restrict_
 // samples of a tile are cut into runs of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256
 // per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.  The search (S = 1) has one item per tile: its iterations are
 // dependent, so there is nothing to split.
-static int ray_mlp_launch(RayArgs a, void *stream, bool search = false) {
+static int ray_mlp_launch(RayArgs a, void *stream, int mode = kSamples) {
     constexpr int kSimds = 256 * 4, kMinChunk = 8;
     const long long tiles = ((long long)a.M + 15) / 16;
     int nchunk = 1;
@@ -297,13 +404,13 @@ static int ray_mlp_launch(RayArgs a, void *stream, bool search = false) {
     if (grid > 256) grid = 256;
     const int cblocks = (a.Cf + 15) >> 4;
     const size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
-                       6 * kHidden * sizeof(float);
-    static IdhDeviceOnce attr_set[2];
-    const auto kernel = search ? ray_search_k : ray_mlp_k;
-    if (attr_set[search].first()) {
+                       6 * kHidden * sizeof(float) + (mode == kView ? (size_t)a.nb * kCamFloats * sizeof(float) : 0);
+    static IdhDeviceOnce attr_set[3];
+    const auto kernel = mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
+    if (attr_set[mode].first()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return IDH_ELAUNCH;
-        attr_set[search].mark();
+        attr_set[mode].mark();
     }
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(waves * 64), lds, idh_stream(stream), a);
     IDH_CHECK_LAUNCH();
@@ -355,7 +462,37 @@ extern "C" int idh_binary_mlp_rays_search_fwd(const float *feat_nhwc, int feat_c
               iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth_bn, flags_bn, points_bn3, invK_44,
               world_T_cam_44};
     a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    return ray_mlp_launch(a, stream, true);
+    return ray_mlp_launch(a, stream, kSearch);
+}
+
+// Dense occlusion in another camera: every pixel of rendered (B,P,h,w) is back-projected in its own view, projected into the keyframe's
+// scale-0 map and asked there, in one launch (view_mlp_k).  include/idh.h states the expression and the validity rule.
+extern "C" int idh_binary_mlp_view_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rendered_bphw, int P, int h,
+                                       int w, const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44,
+                                       const float *key_K_44, const float *prior_pred_b1hw, const float *prior_cam_T_world_44,
+                                       const float *prior_K_44, int has_prior, float prior_const, const float *w1f_packed, const float *w2_packed,
+                                       const float *vecs6x128, float fill, float *logits_bphw, unsigned char *valid_bphw, float *view_depth_bphw,
+                                       float *view_points_bphw3, void *stream) {
+    if (B < 0 || P < 0 || h < 0 || w < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf) return IDH_EINVAL;
+    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
+    if (B == 0 || P == 0 || h == 0 || w == 0) return IDH_OK;
+    if (!feat_nhwc || !rendered_bphw || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 ||
+        !logits_bphw)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_nhwc, (const void *)rendered_bphw, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
+                          (const void *)prior_K_44, (const void *)logits_bphw, (const void *)view_depth_bphw, (const void *)view_points_bphw3})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    if ((long long)P * h >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (the product below stays inside 64 bits)
+    const long long Nq = (long long)P * h * w, M = (long long)B * Nq;
+    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
+    RayArgs a{feat_nhwc, nullptr, rendered_bphw, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, logits_bphw, (int)M, (int)Nq, (int)Nq, 1, 1, H, W,
+              feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
+              0, 0.f, 0.f, 0.f, nullptr, nullptr, 0, view_depth_bphw, valid_bphw, view_points_bphw3, invK_44, world_T_cam_44,
+              key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, P, h, w, fill};
+    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
+    return ray_mlp_launch(a, stream, kView);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

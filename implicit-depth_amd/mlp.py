@@ -276,6 +276,53 @@ def project_points(points_bn3: torch.Tensor, cam_T_world: torch.Tensor, K: torch
     return rays, depth, valid.view(torch.bool), prior  # the kernel writes 0 / 1: reinterpreted, no conversion pass
 
 
+def view_logits(net, feat_view, rendered_bphw: torch.Tensor, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, key_cam_T_world_b44: torch.Tensor,
+                key_K_s0_b44: torch.Tensor, prior=None, fill: float = 0.0, return_points: bool = False):
+    """Dense occlusion in another camera on ``idh_binary_mlp_view_fwd``: every pixel of ``rendered_bphw`` (B,P,h,w) - an asset's depth in
+    the view of ``invK_b44`` (at h x w) / ``world_T_cam_b44`` - is back-projected (``BackprojectDepth``, reference geometry_utils.py:55-63),
+    projected into the keyframe's scale-0 map ``feat_view`` with ``key_K_s0_b44 @ key_cam_T_world_b44`` (``Project3D``, :77-89), and the
+    scale-0 MLP is asked there at the point's keyframe depth: one launch, no rays, depths or validity in memory.  ``prior``: None (a
+    prior-enabled network sees the constant -1, bd_model.py:433-434), a float, or (prior_pred (B,1,H,W), prior_cam_T_world (B,4,4),
+    prior_K (B,4,4)) - sampled nearest at the point's projection into that camera, -1 outside (``BDModel.sample_prior``, :405-409).
+    A pixel is valid when its depth is finite and positive and the point lies in front of the keyframe camera and inside its image;
+    the others hold ``fill``.  Returns (logits (B,P,h,w), valid (B,P,h,w) bool, view_depth (B,P,h,w): the keyframe z, points (B,P,h,w,3)
+    world points | None)."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_fwd; set mlp_math = 'fp32'")
+    pmap = prior if isinstance(prior, (tuple, list)) else None
+    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
+    _lib.require_cuda_f32(feat_view.buf, rendered_bphw, *mats, pmap[0] if pmap is not None else None)
+    B, H, W = feat_view.N, feat_view.H, feat_view.W
+    if rendered_bphw.dim() != 4 or rendered_bphw.shape[0] != B:
+        raise _lib.IdhError(f"rendered depth must be ({B}, P, h, w), got {tuple(rendered_bphw.shape)}")
+    _, P, h, w = rendered_bphw.shape
+    for m in mats:
+        if m is None or tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
+        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
+    dev = rendered_bphw.device
+    rd, keep = rendered_bphw.contiguous(), [m.contiguous() for m in mats]  # alive until enqueued
+    pp = pmap[0].contiguous() if pmap is not None else None
+    n = B * P * h * w
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    logits, depth = buf[:n].view(B, P, h, w), buf[n: 2 * n].view(B, P, h, w)
+    points = buf[2 * n:].view(B, P, h, w, 3) if return_points else None
+    valid = torch.empty(B, P, h, w, device=dev, dtype=torch.uint8)
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, rd.data_ptr(), P, h, w, keep[0].data_ptr(),
+                                           keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
+                                           keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
+                                           int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
+                                           w2p.data_ptr(), vecs.data_ptr(), float(fill), logits.data_ptr(), valid.data_ptr(), depth.data_ptr(),
+                                           _lib.ptr(points), _lib.stream_ptr()),
+        "idh_binary_mlp_view_fwd")
+    return logits, valid.view(torch.bool), depth, points  # the kernel writes 0 / 1: reinterpreted, no conversion pass
+
+
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:
     """``BinaryMLPNetwork.forward(list of (..., Cin) tensors, max_scale_only)`` (reference networks.py:106-115); row = [depth | features |
     (prior)].  fp32: the rows are read IN PLACE through ``idh_binary_mlp_strided_fwd`` whatever their strides - in particular the

@@ -47,7 +47,7 @@ class HotPath(nn.Module):
         self.min_depth, self.max_depth = float(min_depth), float(max_depth)
         self.thresholder = None  # like BDModel.thresholder (bd_model.py:141): per-depth thresholds of the infer_depth search
         self._plans = nhwc.PlanCache()  # LRU: a ragged last batch / alternating shapes replay instead of rebuilding
-        self._last = None  # decoder output of the last forward (plan-owned final[i] views): what query_rays / query_points read
+        self._last = None  # decoder output of the last forward (plan-owned final[i] views): what query_rays / query_points / query_view read
         _lib.watch_state_dict_loads(self)
 
     # ------------------------------------------------------------------------------------
@@ -118,6 +118,27 @@ class HotPath(nn.Module):
         rays, depth, valid, prior = project_points(points_bn3, cam_T_world_b44, K_s0_b44, f0.H, f0.W, pp, pc, pk)
         pred = ray_logits(self.binary_mlp, f0, rays, depth.unsqueeze(-1), None if prior is None else prior.unsqueeze(-1), scale=0)
         return {"point_pred": pred, "point_valid": valid, "point_depth": depth, "point_rays": rays}
+
+    def query_view(self, rendered_depth: torch.Tensor, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, cam_T_world_b44: torch.Tensor,
+                   K_s0_b44: torch.Tensor, prior_inputs: Optional[Dict[str, torch.Tensor]] = None, fill: float = 0.0,
+                   return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """Dense occlusion of an asset seen from ANOTHER camera against the LAST forward (valid as for ``query_rays``): ``rendered_depth``
+        (B,P,h,w) is the asset's depth in the view of ``invK_b44`` (at h x w) / ``world_T_cam_b44``; every pixel is back-projected, projected
+        into the scale-0 map with ``K_s0_b44`` / ``cam_T_world_b44`` - the camera of that forward - and asked at its own depth there, in
+        one ``mlp.view_logits`` launch.  The same answers as ``query_points`` on the back-projected pixels, bit for bit.  ``prior_inputs`` as
+        ``query_points``.  Returns {"view_pred" (B,P,h,w) logits, ``fill`` where "view_valid" (B,P,h,w) bool is False (no finite positive
+        depth, behind the camera or outside its image), "view_depth" (B,P,h,w): depth in the forward's camera, "view_points" (B,P,h,w,3)
+        world points with ``return_points``, else None}."""
+        from .mlp import view_logits
+
+        final = _last_final(self, rendered_depth.shape[0], (0,))
+        _lib.require_cuda_f32(rendered_depth, invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44)
+        prior = None
+        if prior_inputs is not None and prior_inputs.get("prior_prediction") is not None:
+            prior = (prior_inputs["prior_prediction"], prior_inputs["prior_cam_T_world"], prior_inputs.get("K_s0_b44", K_s0_b44))
+        pred, valid, depth, points = view_logits(self.binary_mlp, final[0], rendered_depth, invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44,
+                                                 prior, fill, return_points)
+        return {"view_pred": pred, "view_valid": valid, "view_depth": depth, "view_points": points}
 
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
               images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):

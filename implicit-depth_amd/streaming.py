@@ -82,7 +82,7 @@ class StreamingSession:
         self.last_indices: Optional[Tuple[int, ...]] = None  # their frame numbers
         self.last_matching: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # (cur (1,H,W,C), src (1,K,H,W,C)) of the last prediction
         self._prior: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-        self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's poses and intrinsics: what query_points / raycast use
+        self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's poses and intrinsics: what query_points / raycast / occlusion_for_view use
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -174,6 +174,29 @@ class StreamingSession:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
         with torch.inference_mode():
             return self.hot.query_points(points_bn3, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi)
+
+    def occlusion_for_view(self, rendered_depth: torch.Tensor, world_T_cam, invK: torch.Tensor, fill: float = 0.0) -> Dict[str, Optional[torch.Tensor]]:
+        """Occlusion logits of an asset in the LIVE camera, also on the frames where ``step`` returned None: ``rendered_depth`` (1,P,h,w) is
+        the asset's depth rendered in the camera at ``world_T_cam`` - a (4,4) array or tensor - with inverse intrinsics ``invK`` ((4,4) or
+        (1,4,4), at h x w; any resolution).  Every pixel is asked against the LAST prediction's decoder features through the keyframe's
+        ``cam_T_world`` and ``K_s0`` (``HotPath.query_view``, one launch); with ``use_prior`` the carried prior is sampled as in
+        ``query_points``.  Returns ``HotPath.query_view``'s dictionary: "view_pred" (1,P,h,w) is in the live view, ``fill`` where
+        "view_valid" is False, and feeds ``compositing.composite_mask(image_u8, view_pred)`` as a prediction's ``pred_0`` does."""
+        if self._key is None:
+            raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
+        _lib.require_cuda_f32(rendered_depth, invK)
+        k = self._key
+        T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
+        if tuple(T.shape) != (4, 4):
+            raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
+        T = T.to(device=rendered_depth.device, dtype=torch.float32)[None]
+        if invK.dim() == 2:
+            invK = invK[None]
+        pi = None
+        if self.use_prior and self._prior is not None:
+            pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
+        with torch.inference_mode():
+            return self.hot.query_view(rendered_depth, invK, T, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi, fill=fill)
 
     def raycast(self, rays: torch.Tensor, thresholder=None) -> Dict[str, torch.Tensor]:
         """The hit test: where rays (1,N,2) - (x, y) in pixel-centre units of the keyframe's scale-0 map - meet the scene, against the LAST

@@ -331,6 +331,33 @@ int idh_binary_mlp_rays_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, 
                                    float threshold, const float *bins, const float *thr_logits, int n_bins, const float *invK_44,
                                    const float *world_T_cam_44, float *depth_bn, float *last_logits_bn, unsigned char *flags_bn,
                                    float *points_bn3, void *stream);
+/* Dense occlusion in a moving camera: every pixel of a depth map rendered in ANY camera is asked against the keyframe's scale-0 features, in one
+ * launch, with nothing intermediate in memory (view_mlp_k).  Per pixel (b, p, row, col) of rendered_bphw (B,P,h,w), in fp32 with one rounding per
+ * operation / fma (no contraction), with d = rendered[b,p,row,col], iK = invK_44[b], T = world_T_cam_44[b] of the VIEW:
+ *   BackprojectDepth (reference utils/geometry_utils.py:55-63, pixel centres :39), as idh_binary_mlp_rays_search_fwd's points:
+ *     x = (float)col + 0.5f   y = (float)row + 0.5f
+ *     c_i = fmaf(iK[4i], x, fmaf(iK[4i+1], y, iK[4i+2]))     X_i = d * c_i                                                i = 0..2
+ *     p_i = fmaf(T[4i], X_0, fmaf(T[4i+1], X_1, fmaf(T[4i+2], X_2, T[4i+3])))                                             the world point
+ *   Project3D (:77-89) into the keyframe, exactly idh_project_points_fwd on p with key_cam_T_world_44 / key_K_44 (K at H x W; the product of
+ *   BDModel.sample_prior, experiment_modules/bd_model.py:400-403): P = K cam_T_world, c = P[:3] (p, 1), z = fmaxf(c_z, 1e-5f), (u, v) = c_xy / z
+ *   prior (has_prior): with prior_pred_b1hw (B,1,H,W), prior_cam_T_world_44 and prior_K_44 the nearest sample of idh_project_points_fwd
+ *     (bd_model.py:405-409; -1 behind that camera or outside the map); without a map the constant prior_const
+ *   logit = MLP([z | feat(u, v) | (prior)]): the gather of idh_binary_mlp_rays_fwd with grid = (H, W) on F.grid_sample(bilinear, zeros,
+ *     align_corners=False) of feature_s0, then BinaryMLPNetwork - the depth is the point's z in the KEYFRAME camera
+ * A pixel is valid when d is finite and d > 0, c_z > 0, 0 <= u < W and 0 <= v < H (decided on floats before any integer conversion).  An
+ * invalid pixel stores `fill` in logits_bphw and reads no feature corner and no prior texel; a 16-pixel tile without a valid pixel skips the MLP.
+ * Outputs: logits_bphw (B,P,h,w); optional (NULL: not written) valid_bphw uint8 0 / 1, view_depth_bphw = z, view_points_bphw3 (B,P,h,w,3) = p;
+ * where d is not finite and positive, view_depth and view_points are 0.  For every other pixel logits / view_depth / valid carry the bits
+ * of idh_project_points_fwd + idh_binary_mlp_rays_fwd (S = 1) on view_points.
+ * fp32 only.  IDH_EINVAL: a NULL required pointer (feat, rendered, the four matrices, weights, logits), a prior map without has_prior or without
+ * its two matrices, negative B, P, h or w, H, W, Cf <= 0, Cf % 4, feat_cs < Cf, a float pointer that is not 4-byte aligned.  B == 0 or an empty map
+ * (P, h or w == 0): IDH_OK, no launch.  IDH_EUNSUPPORTED: B * P * h * w or B * H * W >= 2^31, B > 128 (the cameras of a launch sit in LDS).
+ * Everything is checked on the host before the device is touched. */
+int idh_binary_mlp_view_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rendered_bphw, int P, int h, int w,
+                            const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44, const float *key_K_44,
+                            const float *prior_pred_b1hw, const float *prior_cam_T_world_44, const float *prior_K_44, int has_prior,
+                            float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, float fill,
+                            float *logits_bphw, unsigned char *valid_bphw, float *view_depth_bphw, float *view_points_bphw3, void *stream);
 /* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
  * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
  *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
