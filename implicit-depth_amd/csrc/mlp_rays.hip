@@ -19,6 +19,10 @@
 // rendered (B,P,h,w); it is back-projected with that view's invK / world_T_cam (BackprojectDepth, geometry_utils.py:55-63), projected into
 // the keyframe's scale-0 map with the expression of project_points_k below (Project3D, :77-89) and asked at its keyframe z, S = 1, with the
 // nearest sample of a prior prediction (bd_model.py:405-409) when there is one.  Rays, depth, valid and prior never reach HBM.
+//
+// view_search_k is the search of ray_search_k along the rays of another camera: the query is the z-depth in THAT camera, so the sample point
+// moves across the keyframe's image from step to step and every step is one whole view_mlp_k pixel (back-projection, projection, validity,
+// prior texel, gather, W1f . f, MLP) at rendered = q_n; an invalid probe's logit is `fill`.  The threshold is keyed by the probe's keyframe z.
 #include <type_traits>
 
 #include "idh_common.h"
@@ -57,17 +61,24 @@ struct RayArgs {
     const float *prior_cTw, *prior_K;  // B,4,4, with a prior map
     int nb, vP, vh, vw;                // nb = B
     float fill;
+    // view_search_k: view_mlp_k's cameras, prior and fill with ray_search_k's iters / lo / hi / thresholds and outputs; there is no `depth`;
+    // `rays` (B,N,2) in pixel-centre units of the VIEW, or null: the vh x vw grid of its pixel centres (vP = 1, Nq = N = vh * vw);
+    // `points` are world points; flags gain bit 2 = some probe was invalid
 };
 
-enum { kSamples = 0, kSearch = 1, kView = 2 };
+enum { kSamples = 0, kSearch = 1, kView = 2, kViewSearch = 3 };
 constexpr int kViewMaxBatch = 128;  // 24 KiB of cameras next to at most 96 KiB of weights
 constexpr int kCamFloats = 48;  // per batch in LDS: P = K cam_T_world (12), the prior camera's (12), rows 0-2 of the view's invK (12) and world_T_cam (12)
 
 constexpr int kRayMaxThreads = 768;  // 12 waves, as binary_mlp_k; small launches use 4 (ray_mlp_launch)
 constexpr int kW1LdsMaxBlocks = 4;   // Cf <= 64 -> W1f in LDS, as binary_mlp_k
+#ifndef IDH_VIEW_SEARCH_SKIP
+#define IDH_VIEW_SEARCH_SKIP 1
+#endif
+constexpr bool kViewSearchSkip = IDH_VIEW_SEARCH_SKIP;  // view_search_k: skip gather and MLP of a step at which no ray of the tile has a valid probe
 
 // kSamples: the S depth samples of `depth`; kSearch: `iters` dependent evaluations at the ray's current search depth; kView: one evaluation
-// per pixel of a depth map seen from another camera
+// per pixel of a depth map seen from another camera; kViewSearch: `iters` dependent kView evaluations along a ray of that other camera
 template <int kMode>
 __device__ __forceinline__ void ray_body(const RayArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -85,7 +96,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         for (int i = threadIdx.x; i < 6 * kHidden; i += nthreads) s_vec[i] = a.vecs[i];
     }
     float *s_cam = s_vec + 6 * kHidden;
-    if constexpr (kMode == kView) {
+    if constexpr (kMode == kView || kMode == kViewSearch) {
         // P = K cam_T_world of the keyframe (and of the prior camera), once per workgroup and batch: the fma loop of project_points_k
         for (int t = threadIdx.x; t < 2 * a.nb; t += nthreads) {
             const int b = t >> 1, pc = t & 1;
@@ -125,31 +136,21 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         // view: the pixel's world point, its keyframe z, prior sample and validity
         float vX[3] = {0.f, 0.f, 0.f}, vz = 0.f, vprior = 0.f;
         bool vdok = false, vvalid = false;
-        if constexpr (kMode != kView) {
-            x = a.rays[2 * src];
-            y = a.rays[2 * src + 1];
-        } else {
-            // ---- the pixel's ray: the expressions of include/idh.h; every quarter-lane of a ray computes the same values ----
-            const int pix = j % (a.vh * a.vw), row = pix / a.vw, col = pix - row * a.vw;
-            const float dr = a.depth[src];
-            vdok = dr > 0.f && dr <= 3.4028234663852886e38f;  // finite and positive (NaN fails both); anything else is asked as d = 0 and stores `fill`
-            const float d = vdok ? dr : 0.f;
-            const float px = (float)col + 0.5f, py = (float)row + 0.5f;  // BackprojectDepth's pixel centres (geometry_utils.py:39)
-            const float *cam = s_cam + b * kCamFloats;
-            const float *iK = cam + 24, *T = cam + 36;
-            float Xc[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) Xc[i] = d * fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
+        const float *cam = s_cam + b * kCamFloats;  // (kView / kViewSearch)
+        // ---- one point Xc of the view camera's frame: world point, Project3D into the keyframe (project_points_k, verbatim), validity, nearest
+        // prior sample; the expressions of include/idh.h.  Every quarter-lane of a ray computes the same values ----
+        auto probe = [&](const float (&Xc)[3], const bool dok) {
+            const float *T = cam + 36;
 #pragma unroll
             for (int i = 0; i < 3; ++i) vX[i] = fmaf(T[4 * i], Xc[0], fmaf(T[4 * i + 1], Xc[1], fmaf(T[4 * i + 2], Xc[2], T[4 * i + 3])));
             const float X0 = vX[0], X1 = vX[1], X2 = vX[2];
-            const float *P = cam;  // project_points_k, verbatim
+            const float *P = cam;
             const float cx = fmaf(P[0], X0, fmaf(P[1], X1, fmaf(P[2], X2, P[3])));
             const float cy = fmaf(P[4], X0, fmaf(P[5], X1, fmaf(P[6], X2, P[7])));
             const float cz = fmaf(P[8], X0, fmaf(P[9], X1, fmaf(P[10], X2, P[11])));
             const float z = fmaxf(cz, 1e-5f);
             const float u = cx / z, v = cy / z;
-            vvalid = vdok && cz > 0.f && u >= 0.f && u < Wf && v >= 0.f && v < Hf;
+            vvalid = dok && cz > 0.f && u >= 0.f && u < Wf && v >= 0.f && v < Hf;
             vz = z;
             vprior = a.prior_const;
             if (a.prior) {
@@ -168,6 +169,22 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             }
             x = u;
             y = v;
+        };
+        float vc[3] = {0.f, 0.f, 0.f};  // kViewSearch: the ray's direction invK (x, y, 1), once
+        if constexpr (kMode == kSamples || kMode == kSearch) {
+            x = a.rays[2 * src];
+            y = a.rays[2 * src + 1];
+        } else if constexpr (kMode == kView) {
+            const int pix = j % (a.vh * a.vw), row = pix / a.vw, col = pix - row * a.vw;
+            const float dr = a.depth[src];
+            vdok = dr > 0.f && dr <= 3.4028234663852886e38f;  // finite and positive (NaN fails both); anything else is asked as d = 0 and stores `fill`
+            const float d = vdok ? dr : 0.f;
+            const float px = (float)col + 0.5f, py = (float)row + 0.5f;  // BackprojectDepth's pixel centres (geometry_utils.py:39)
+            const float *iK = cam + 24;
+            float Xc[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Xc[i] = d * fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
+            probe(Xc, vdok);
             if (!__any(vvalid)) {  // no valid ray in the tile (wave-uniform): no gather, no MLP
                 if (q == 0 && rok) {
                     a.out[src] = a.fill;
@@ -180,50 +197,65 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
                 }
                 continue;
             }
+        } else {
+            float px, py;
+            if (a.rays) {
+                px = a.rays[2 * src];
+                py = a.rays[2 * src + 1];
+            } else {
+                const int row = j / a.vw, col = j - row * a.vw;
+                px = (float)col + 0.5f;
+                py = (float)row + 0.5f;
+            }
+            const float *iK = cam + 24;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) vc[i] = fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
         }
-        // ---- gather: the expression of include/idh.h, one rounding per operation (-ffp-contract=off) ----
-        const float gx = (x / a.grid_w - 0.5f) * 2.f, gy = (y / a.grid_h - 0.5f) * 2.f;              // bd_model.py:325-326
-        const float ix = ((gx + 1.f) * Wf - 1.f) * 0.5f, iy = ((gy + 1.f) * Hf - 1.f) * 0.5f;        // grid_sample, align_corners=False
-        const float x0 = floorf(ix), y0 = floorf(iy);
-        const float wx0 = (x0 + 1.f) - ix, wx1 = ix - x0, wy0 = (y0 + 1.f) - iy, wy1 = iy - y0;
-        const float wgt[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};  // nw, ne, sw, se
-        // validity in float first: a far or non-finite coordinate never reaches the integer conversion (NaN fails every comparison)
-        const bool vx0 = x0 >= 0.f && x0 <= Wf - 1.f, vx1 = x0 >= -1.f && x0 <= Wf - 2.f;
-        const bool vy0 = y0 >= 0.f && y0 <= Hf - 1.f, vy1 = y0 >= -1.f && y0 <= Hf - 2.f;
-        const int xi = (vx0 || vx1) ? (int)x0 : 0, yi = (vy0 || vy1) ? (int)y0 : 0;
-        const bool live = kMode != kView || vvalid;  // an invalid pixel of a view reads no corner
-        const bool cv[4] = {live && vx0 && vy0, live && vx1 && vy0, live && vx0 && vy1, live && vx1 && vy1};
-        const int base = b * a.H * a.W;
-        const int crow[4] = {base + yi * a.W + xi, base + yi * a.W + xi + 1, base + (yi + 1) * a.W + xi, base + (yi + 1) * a.W + xi + 1};
-
-        // ---- layer 1, sample-independent part: pre1^T = W1f . feat^T + b1 ----
         f32x4 pre1[kNS][1];
+        // gather + layer 1 of the row sampled at (x, y); `live` false: no corner is read (an invalid pixel of a view), f = 0
+        auto gather = [&](const bool live) {
+            // ---- gather: the expression of include/idh.h, one rounding per operation (-ffp-contract=off) ----
+            const float gx = (x / a.grid_w - 0.5f) * 2.f, gy = (y / a.grid_h - 0.5f) * 2.f;              // bd_model.py:325-326
+            const float ix = ((gx + 1.f) * Wf - 1.f) * 0.5f, iy = ((gy + 1.f) * Hf - 1.f) * 0.5f;        // grid_sample, align_corners=False
+            const float x0 = floorf(ix), y0 = floorf(iy);
+            const float wx0 = (x0 + 1.f) - ix, wx1 = ix - x0, wy0 = (y0 + 1.f) - iy, wy1 = iy - y0;
+            const float wgt[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};  // nw, ne, sw, se
+            // validity in float first: a far or non-finite coordinate never reaches the integer conversion (NaN fails every comparison)
+            const bool vx0 = x0 >= 0.f && x0 <= Wf - 1.f, vx1 = x0 >= -1.f && x0 <= Wf - 2.f;
+            const bool vy0 = y0 >= 0.f && y0 <= Hf - 1.f, vy1 = y0 >= -1.f && y0 <= Hf - 2.f;
+            const int xi = (vx0 || vx1) ? (int)x0 : 0, yi = (vy0 || vy1) ? (int)y0 : 0;
+            const bool cv[4] = {live && vx0 && vy0, live && vx1 && vy0, live && vx0 && vy1, live && vx1 && vy1};
+            const int base = b * a.H * a.W;
+            const int crow[4] = {base + yi * a.W + xi, base + yi * a.W + xi + 1, base + (yi + 1) * a.W + xi, base + (yi + 1) * a.W + xi + 1};
+
+            // ---- layer 1, sample-independent part: pre1^T = W1f . feat^T + b1 ----
 #pragma unroll
-        for (int i = 0; i < kNS; ++i) pre1[i][0] = *reinterpret_cast<const f32x4 *>(s_b1 + 16 * i + 4 * q);
+            for (int i = 0; i < kNS; ++i) pre1[i][0] = *reinterpret_cast<const f32x4 *>(s_b1 + 16 * i + 4 * q);
 #pragma unroll 1
-        for (int c = 0; c < cblocks; ++c) {
-            f32x4 Bf = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if ((16 * c + 4 * q) < a.Cf) {
+            for (int c = 0; c < cblocks; ++c) {
+                f32x4 Bf = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if ((16 * c + 4 * q) < a.Cf) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (cv[k]) {  // a corner outside the map is not read
-                        const float *fp = a.feat + (size_t)crow[k] * a.cs + 16 * c + 4 * q;
-                        f32x4 v;
-                        if (a.feat_unaligned) v = (f32x4){fp[0], fp[1], fp[2], fp[3]};
-                        else v = *reinterpret_cast<const f32x4 *>(fp);
+                    for (int k = 0; k < 4; ++k) {
+                        if (cv[k]) {  // a corner outside the map is not read
+                            const float *fp = a.feat + (size_t)crow[k] * a.cs + 16 * c + 4 * q;
+                            f32x4 v;
+                            if (a.feat_unaligned) v = (f32x4){fp[0], fp[1], fp[2], fp[3]};
+                            else v = *reinterpret_cast<const f32x4 *>(fp);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) Bf[e] = Bf[e] + v[e] * wgt[k];
+                            for (int e = 0; e < 4; ++e) Bf[e] = Bf[e] + v[e] * wgt[k];
+                        }
                     }
                 }
-            }
 #pragma unroll
-            for (int i = 0; i < kNS; ++i) {
-                const f32x4 A = w1_lds ? sW1[(c * kNS + i) * 64 + lane]
-                                       : *reinterpret_cast<const f32x4 *>(a.w1f + ((size_t)(c * kNS + i) * 64 + lane) * 4);
+                for (int i = 0; i < kNS; ++i) {
+                    const f32x4 A = w1_lds ? sW1[(c * kNS + i) * 64 + lane]
+                                           : *reinterpret_cast<const f32x4 *>(a.w1f + ((size_t)(c * kNS + i) * 64 + lane) * 4);
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) pre1[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], Bf[kk], pre1[i][0], 0, 0, 0);
+                    for (int kk = 0; kk < 4; ++kk) pre1[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], Bf[kk], pre1[i][0], 0, 0, 0);
+                }
             }
-        }
+        };
         // ---- one evaluation at depth dv, prior pv: exactly the plane body of binary_mlp_k; every lane of a ray returns the same logit ----
         auto eval = [&](const float dv, const float pv) -> float {
             f32x4 h1[kNS][1], acc[kNS][1];
@@ -258,6 +290,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             t += __shfl_xor(t, 32, 64);
             return t + b3;
         };
+        if constexpr (kMode != kViewSearch) gather(kMode != kView || vvalid);  // an invalid pixel of a view reads no corner
         if constexpr (kMode == kView) {
             const float logit = eval(vz, vprior);
             if (q == 0 && rok) {
@@ -279,7 +312,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
                 const float logit = eval(dv, pv);
                 if (q == 0 && rok) a.out[ooff + s] = logit;
             }
-        } else {
+        } else if constexpr (kMode == kSearch) {
             // ---- the search rule of binary_mlp_k: first query (hi - lo) / 2 (the reference's, not the midpoint), "visible" = logit < thr moves hi ----
             const float pv = a.has_prior ? (a.prior ? a.prior[src] : a.prior_const) : 0.f;  // one value per ray, as plane 0 of the dense search's prior
             float lo = a.lo, hi = a.hi, sd = (a.hi - a.lo) * 0.5f, logit = 0.f;
@@ -317,6 +350,46 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
                     }
                 }
             }
+        } else {
+            // ---- the same rule along a ray of the view: every step is a view_mlp_k pixel at rendered = sd; thr is keyed by the probe's keyframe z ----
+            float lo = a.lo, hi = a.hi, sd = (a.hi - a.lo) * 0.5f, logit = 0.f;
+            unsigned moved = 0;
+            float Xc[3];
+#pragma unroll 1
+            for (int p = 0; p < a.iters; ++p) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) Xc[i] = sd * vc[i];
+                probe(Xc, true);
+                logit = a.fill;
+                if (kViewSearchSkip ? __any(vvalid) : true) {  // a tile without a valid probe at this step: no gather, no MLP (wave-uniform); `fill` either way
+                    gather(vvalid);
+                    const float l = eval(vz, vprior);
+                    logit = vvalid ? l : a.fill;
+                }
+                float thr = a.thr_logit;
+                if (a.n_bins > 0) {
+                    int idx = 0;
+                    for (int e = 0; e < a.n_bins; ++e) idx += a.bins[e] < vz ? 1 : 0;
+                    thr = a.thr_logits[idx < a.n_bins ? idx : a.n_bins - 1];
+                }
+                if (logit < thr) { hi = sd; moved |= 1u; }
+                else { lo = sd; moved |= 2u; }
+                if (!vvalid) moved |= 4u;
+                sd = (hi + lo) * 0.5f;
+            }
+            if (q == 0 && rok) {
+                a.sdepth[src] = sd;
+                a.out[src] = logit;
+                if (a.flags) a.flags[src] = (unsigned char)moved;
+                if (a.points) {  // the world point of the final query, by the expressions of the probes
+                    const float *T = cam + 36;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) Xc[i] = sd * vc[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        a.points[3 * src + i] = fmaf(T[4 * i], Xc[0], fmaf(T[4 * i + 1], Xc[1], fmaf(T[4 * i + 2], Xc[2], T[4 * i + 3])));
+                }
+            }
         }
     }
 }
@@ -324,6 +397,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
 __global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) { ray_body<kSamples>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void ray_search_k(const RayArgs a) { ray_body<kSearch>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void view_mlp_k(const RayArgs a) { ray_body<kView>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_search_k(const RayArgs a) { ray_body<kViewSearch>(a); }
 
 // ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
 // Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
@@ -404,9 +478,9 @@ static int ray_mlp_launch(RayArgs a, void *stream, int mode = kSamples) {
     if (grid > 256) grid = 256;
     const int cblocks = (a.Cf + 15) >> 4;
     const size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
-                       6 * kHidden * sizeof(float) + (mode == kView ? (size_t)a.nb * kCamFloats * sizeof(float) : 0);
-    static IdhDeviceOnce attr_set[3];
-    const auto kernel = mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
+                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0);
+    static IdhDeviceOnce attr_set[4];
+    const auto kernel = mode == kViewSearch ? view_search_k : mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
     if (attr_set[mode].first()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return IDH_ELAUNCH;
@@ -493,6 +567,41 @@ extern "C" int idh_binary_mlp_view_fwd(const float *feat_nhwc, int feat_cs, int 
               key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, P, h, w, fill};
     a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
     return ray_mlp_launch(a, stream, kView);
+}
+
+// Depth along the rays of another camera: the search of idh_binary_mlp_rays_search_fwd with every step one pixel of idh_binary_mlp_view_fwd at
+// rendered = q_n, in one launch (view_search_k).  include/idh.h states the expressions and the invalid-probe rule.
+extern "C" int idh_binary_mlp_view_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, int h, int w, const float *rays_bn2,
+                                              int N, const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44,
+                                              const float *key_K_44, const float *prior_pred_b1hw, const float *prior_cam_T_world_44,
+                                              const float *prior_K_44, int has_prior, float prior_const, const float *w1f_packed,
+                                              const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi, float threshold,
+                                              const float *bins, const float *thr_logits, int n_bins, float fill, float *depth, float *last_logits,
+                                              unsigned char *flags, float *points, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || iters <= 0 || n_bins < 0) return IDH_EINVAL;
+    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    const float fmax = 3.4028234663852886e38f;
+    if (!(lo > 0.f) || !(hi > lo) || !(lo <= fmax) || !(hi <= fmax)) return IDH_EINVAL;  // (NaN fails every comparison)
+    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
+    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
+    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
+    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
+    if (!feat_nhwc || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth || !last_logits)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
+                          (const void *)prior_K_44, (const void *)bins, (const void *)thr_logits, (const void *)depth, (const void *)last_logits,
+                          (const void *)points})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, M = (long long)B * Nq;
+    if (Nq >= (1ll << 31) || M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
+    RayArgs a{feat_nhwc, rays_bn2, nullptr, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)M, (int)Nq, (int)Nq, 1, 1, H, W,
+              feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
+              iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags, points, invK_44,
+              world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, 1, rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
+    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
+    return ray_mlp_launch(a, stream, kViewSearch);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

@@ -323,6 +323,66 @@ def view_logits(net, feat_view, rendered_bphw: torch.Tensor, invK_b44: torch.Ten
     return logits, valid.view(torch.bool), depth, points  # the kernel writes 0 / 1: reinterpreted, no conversion pass
 
 
+def view_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, key_cam_T_world_b44: torch.Tensor, key_K_s0_b44: torch.Tensor,
+                size=None, rays: Optional[torch.Tensor] = None, prior=None, iters: int = 12, lo: float = 0.5, hi: float = 8.0,
+                threshold: float = 0.5, thresholder=None, fill: float = 0.0, return_points: bool = False):
+    """Depth along the rays of another camera on ``idh_binary_mlp_view_search_fwd``: the ``infer_depth`` search (bd_model.py:273-292) with
+    the query the z-depth in the view of ``invK_b44`` / ``world_T_cam_b44``; every step is one ``view_logits`` pixel at that depth (its
+    projection into the keyframe's scale-0 map ``feat_view``, validity, prior sample, gather and MLP), all ``iters`` steps in one launch.
+    Exactly one of ``size`` = (h, w) - every pixel centre of the view at that resolution - and ``rays`` (B,N,2) - (x, y) in pixel-centre
+    units of the view, a tap at pixel (i, j) is (j + 0.5, i + 0.5); rays outside the view's image are legal.  ``prior`` as ``view_logits``
+    (a map is sampled per probe).  A probe outside the keyframe's view has the logit ``fill``: -inf counts it as visible (the search
+    retreats towards ``lo``), +inf as hidden (towards ``hi``).  The threshold of a step is looked up at the probe's KEYFRAME depth.
+    Returns (depth (B,1,h,w) | (B,N), logits of the last step, flags uint8: bit 0 = ``hi`` moved, bit 1 = ``lo`` moved, bit 2 = some probe
+    was invalid, world points (...,3) | None).  The MLP answers occlusion as seen from the keyframe: the depth is where the view's ray
+    crosses into the region hidden from the keyframe - the surface as far as both cameras see the same side of it."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_search_fwd; set mlp_math = 'fp32'")
+    if (size is None) == (rays is None):
+        raise _lib.IdhError("view_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
+    pmap = prior if isinstance(prior, (tuple, list)) else None
+    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
+    _lib.require_cuda_f32(feat_view.buf, rays, *mats, pmap[0] if pmap is not None else None)
+    B, H, W = feat_view.N, feat_view.H, feat_view.W
+    for m in mats:
+        if m is None or tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
+    if rays is not None:
+        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
+    else:
+        h, w = int(size[0]), int(size[1])
+        if h < 0 or w < 0:
+            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
+        N, shape = h * w, (B, 1, h, w)
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
+        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
+    dev = feat_view.buf.device
+    bins, thr_logits = _thresholder_tables(thresholder, dev)
+    keep = [m.contiguous() for m in mats]  # alive until enqueued
+    r = rays.contiguous() if rays is not None else None
+    pp = pmap[0].contiguous() if pmap is not None else None
+    n = B * N
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
+    points = buf[2 * n:].view(*shape, 3) if return_points else None
+    flags = torch.empty(shape, device=dev, dtype=torch.uint8)
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_search_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, h, w, _lib.ptr(r), N if r is not None else 0,
+                                                  keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
+                                                  keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
+                                                  int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
+                                                  w2p.data_ptr(), vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
+                                                  0 if bins is None else bins.numel(), float(fill), depth.data_ptr(), logits.data_ptr(),
+                                                  flags.data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
+        "idh_binary_mlp_view_search_fwd")
+    return depth, logits, flags, points
+
+
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:
     """``BinaryMLPNetwork.forward(list of (..., Cin) tensors, max_scale_only)`` (reference networks.py:106-115); row = [depth | features |
     (prior)].  fp32: the rows are read IN PLACE through ``idh_binary_mlp_strided_fwd`` whatever their strides - in particular the

@@ -140,6 +140,35 @@ class HotPath(nn.Module):
                                                  prior, fill, return_points)
         return {"view_pred": pred, "view_valid": valid, "view_depth": depth, "view_points": points}
 
+    def query_view_depths(self, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor,
+                          size: Optional[Sequence[int]] = None, rays: Optional[torch.Tensor] = None,
+                          prior_inputs: Optional[Dict[str, torch.Tensor]] = None, thresholder=None, iters: int = 12, lo: float = 0.5,
+                          hi: float = 8.0, threshold: float = 0.5, fill: float = 0.0, return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """Depth seen from ANOTHER camera against the LAST forward (valid as for ``query_rays``): the ``infer_depth`` search (bd_model.py:273-292)
+        along the rays of the view of ``invK_b44`` / ``world_T_cam_b44`` - every pixel centre of ``size`` = (h, w), or ``rays`` (B,N,2) in
+        pixel-centre units of that view (exactly one of the two) - with every probe projected into the scale-0 map through ``K_s0_b44`` /
+        ``cam_T_world_b44``, the camera of that forward, as ``query_view`` does, in one ``mlp.view_depths`` launch.  The query is the
+        z-depth in the VIEW; the threshold of a step is looked up at the probe's depth in the forward's camera.  ``prior_inputs`` as
+        ``query_points`` (the map is sampled per probe); ``thresholder``: None = this HotPath's ``thresholder`` (None there: the constant
+        ``threshold``).  A probe outside the forward's image or behind its camera has the logit ``fill``.  Returns {"view_search_depths"
+        (B,1,h,w) | (B,N), "view_search_logits": logits of the last step, "view_search_flags" uint8 (bit 0 / 1: the far / near bound
+        moved, 3 = bracketed inside [lo, hi]; bit 2: some probe was invalid), "view_search_points" (...,3) world points with
+        ``return_points``, else None}.  The occlusion is the one seen from the forward's camera: the depth is where the view's ray
+        enters the region hidden from THAT camera."""
+        from .mlp import view_depths
+
+        if (size is None) == (rays is None):
+            raise _lib.IdhError("query_view_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
+        final = _last_final(self, invK_b44.shape[0], (0,))
+        _lib.require_cuda_f32(invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44, rays)
+        prior = None
+        if prior_inputs is not None and prior_inputs.get("prior_prediction") is not None:
+            prior = (prior_inputs["prior_prediction"], prior_inputs["prior_cam_T_world"], prior_inputs.get("K_s0_b44", K_s0_b44))
+        depth, pred, flags, points = view_depths(self.binary_mlp, final[0], invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44, size, rays, prior,
+                                                 iters, lo, hi, threshold, self.thresholder if thresholder is None else thresholder, fill,
+                                                 return_points)
+        return {"view_search_depths": depth, "view_search_logits": pred, "view_search_flags": flags, "view_search_points": points}
+
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
               images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):
         """``scales``: bit i = the plan builds the decoder's output_i result (part of the plan key: the full plan is built on first demand).

@@ -19,7 +19,7 @@ fresh ``OfflineKeyframeBuffer`` until 30 of them are accepted, so any earlier fr
 moves slowly - can be a source view; a ring that keeps the features of the last N keyframes cannot serve that choice."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -197,6 +197,42 @@ class StreamingSession:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
         with torch.inference_mode():
             return self.hot.query_view(rendered_depth, invK, T, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi, fill=fill)
+
+    def _view_search(self, world_T_cam, invK: torch.Tensor, size, rays, thresholder, fill: float):
+        if self._key is None:
+            raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
+        _lib.require_cuda_f32(invK, rays)
+        k = self._key
+        T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
+        if tuple(T.shape) != (4, 4):
+            raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
+        T = T.to(device=invK.device, dtype=torch.float32)[None]
+        if invK.dim() == 2:
+            invK = invK[None]
+        pi = None
+        if self.use_prior and self._prior is not None:
+            pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
+        with torch.inference_mode():
+            return self.hot.query_view_depths(invK, T, k["cam_T_world_b44"], k["K_s0_b44"], size=size, rays=rays, prior_inputs=pi,
+                                              thresholder=thresholder, fill=fill, return_points=True)
+
+    def depth_for_view(self, world_T_cam, invK: torch.Tensor, size: Sequence[int], thresholder=None, fill: float = 0.0) -> Dict[str, Optional[torch.Tensor]]:
+        """A dense depth map of the LIVE camera, also on the frames where ``step`` returned None: for every pixel centre of the ``size`` =
+        (h, w) image of the camera at ``world_T_cam`` - a (4,4) array or tensor - with inverse intrinsics ``invK`` ((4,4) or (1,4,4), at
+        h x w; any resolution), the depth search along that pixel's ray against the LAST prediction's decoder features
+        (``HotPath.query_view_depths``, one launch).  With ``use_prior`` the carried prior is sampled at every probe, as in
+        ``occlusion_for_view``.  ``thresholder``: None = the model's.  Returns ``HotPath.query_view_depths``' dictionary with
+        "view_search_points" (1,1,h,w,3) WORLD points; "view_search_flags" == 3 marks the pixels whose crossing lies inside the search
+        range and whose probes all fell inside the keyframe's view.  The depth is where the live ray enters the region hidden from the
+        KEYFRAME camera: the surface as far as both cameras see the same side of it."""
+        return self._view_search(world_T_cam, invK, tuple(size), None, thresholder, fill)
+
+    def raycast_view(self, rays: torch.Tensor, world_T_cam, invK: torch.Tensor, thresholder=None, fill: float = 0.0) -> Dict[str, Optional[torch.Tensor]]:
+        """The hit test from the LIVE screen, also on the frames where ``step`` returned None: ``rays`` (1,N,2) are (x, y) in pixel-centre
+        units of the camera at ``world_T_cam`` / ``invK`` (a tap at pixel (i, j) is (j + 0.5, i + 0.5)).  ``depth_for_view`` at those rays:
+        "view_search_depths" (1,N) is the z-depth in the live camera, "view_search_points" (1,N,3) the WORLD hit points.  Unlike
+        ``raycast``, the carried prior (``use_prior``) is sampled per probe: the probes move across the keyframe's image."""
+        return self._view_search(world_T_cam, invK, None, rays, thresholder, fill)
 
     def raycast(self, rays: torch.Tensor, thresholder=None) -> Dict[str, torch.Tensor]:
         """The hit test: where rays (1,N,2) - (x, y) in pixel-centre units of the keyframe's scale-0 map - meet the scene, against the LAST

@@ -358,6 +358,42 @@ int idh_binary_mlp_view_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, 
                             const float *prior_pred_b1hw, const float *prior_cam_T_world_44, const float *prior_K_44, int has_prior,
                             float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, float fill,
                             float *logits_bphw, unsigned char *valid_bphw, float *view_depth_bphw, float *view_points_bphw3, void *stream);
+/* Depth in a moving camera: the binary search of idh_binary_mlp_rays_search_fwd (reference BDModel.forward(infer_depth=True),
+ * experiment_modules/bd_model.py:273-292) along the rays of ANY camera, against the keyframe's scale-0 features, in one launch (view_search_k).
+ * A ray is one pixel (b, row, col) of an h x w grid of the view - x = (float)col + 0.5f, y = (float)row + 0.5f - or, with rays_bn2 != NULL, one
+ * entry (x, y) of a (B,N,2) list in pixel-centre units of that camera (h and w are then ignored; the view has no bounds, any finite ray is
+ * legal; a non-finite ray has no valid probe).  In fp32 with one rounding per operation / fma (no contraction), iK = invK_44[b], T =
+ * world_T_cam_44[b] of the VIEW.  Per ray, once:
+ *     c_i = fmaf(iK[4i], x, fmaf(iK[4i+1], y, iK[4i+2]))                                                                  i = 0..2
+ * then `iters` dependent steps at the query q_n - the z-depth in the VIEW camera, the d of BackprojectDepth (utils/geometry_utils.py:55-63):
+ *   1. X_i = q_n * c_i,  p_i = fmaf(T[4i], X_0, fmaf(T[4i+1], X_1, fmaf(T[4i+2], X_2, T[4i+3]))),  Project3D (:77-89) into the keyframe:
+ *      P = K cam_T_world, c = P[:3] (p, 1), z = fmaxf(c_z, 1e-5f), (u, v) = c_xy / z, and the nearest prior sample (bd_model.py:405-409) -
+ *      idh_binary_mlp_view_fwd's expressions, verbatim
+ *   2. the probe is valid when c_z > 0, 0 <= u < W and 0 <= v < H (on floats, before any integer conversion).  A valid probe's
+ *      logit = MLP([z | feat(u, v) | (prior)]); an invalid probe reads no feature corner and no prior texel and its logit IS `fill`.
+ *      One step is, by definition, idh_binary_mlp_view_fwd on the map rendered = q_n.
+ *   3. thr = logf(threshold / (1 - threshold)) when n_bins == 0, else thr_logits[min(#{bins[e] < z}, n_bins - 1)]: keyed by the probe's
+ *      KEYFRAME z, the depth the MLP sees and Thresholder.get_thresholds is calibrated on (bd_model.py:282-283); an invalid probe uses its z too
+ *   4. q_0 = (hi - lo) * 0.5f;  logit < thr -> hi = q_n (flag bit 0), otherwise lo = q_n (flag bit 1);  q_{n+1} = (hi + lo) * 0.5f
+ *      (bd_model.py:286-290).  Flag bit 2: some probe of the ray was invalid.  A NaN or infinite `fill` simply goes through `<`:
+ *      fill = -inf (or any value below every threshold) makes "outside the keyframe's view" count as visible, so the search retreats
+ *      towards lo; fill = +inf or NaN makes it count as hidden, so the search advances towards hi.
+ * Outputs, (B,h,w) or (B,N): depth = q_iters; last_logits = the logit of step iters - 1 (`fill` when that probe was invalid); optional flags
+ * (uint8, any alignment); optional points (...,3) = the world point p of q_iters by the expressions of step 1.
+ * The MLP answers occlusion AS SEEN FROM THE KEYFRAME: along a ray of the view the search finds the crossing into the region hidden from the
+ * keyframe - the surface only to the extent that both cameras see the same side of it - and assumes one crossing inside [lo, hi], as the
+ * reference's search does along its own rays.
+ * fp32 only.  IDH_EINVAL: the conditions of both parents that apply (a NULL feat / matrix / weights / depth / last_logits, a prior map
+ * without has_prior or without its two matrices, negative B, h, w (grid form) or N (list form), H, W, Cf <= 0, Cf % 4, feat_cs < Cf,
+ * iters <= 0, n_bins < 0, n_bins == 0 with threshold outside (0, 1), n_bins > 0 with a NULL table, a float pointer that is not 4-byte
+ * aligned), !(lo > 0), !(hi > lo), a non-finite lo or hi.  B == 0 or an empty grid / list: IDH_OK, no launch.  IDH_EUNSUPPORTED: B * rays or
+ * B * H * W >= 2^31, B > 128 (the cameras of a launch sit in LDS).  Everything is checked on the host before the device is touched. */
+int idh_binary_mlp_view_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, int h, int w, const float *rays_bn2, int N,
+                                   const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44, const float *key_K_44,
+                                   const float *prior_pred_b1hw, const float *prior_cam_T_world_44, const float *prior_K_44, int has_prior,
+                                   float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters, float lo,
+                                   float hi, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
+                                   float *last_logits, unsigned char *flags, float *points, void *stream);
 /* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
  * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
  *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
