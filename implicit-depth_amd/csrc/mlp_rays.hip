@@ -23,6 +23,10 @@
 // view_search_k is the search of ray_search_k along the rays of another camera: the query is the z-depth in THAT camera, so the sample point
 // moves across the keyframe's image from step to step and every step is one whole view_mlp_k pixel (back-projection, projection, validity,
 // prior texel, gather, W1f . f, MLP) at rendered = q_n; an invalid probe's logit is `fill`.  The threshold is keyed by the probe's keyframe z.
+//
+// view_keys_k / view_keys_search_k are those two with the projection looped over M remembered keyframes (a ring of feature maps, cameras and
+// priors, indexed by slot): the world point is projected into key_slots[0..M-1] in turn, the first key in which it is valid is selected, and
+// the prior texel, the four corners and the MLP are those of the selected key alone - one MLP pass per pixel whatever M is.
 #include <type_traits>
 
 #include "idh_common.h"
@@ -66,7 +70,19 @@ struct RayArgs {
     // `points` are world points; flags gain bit 2 = some probe was invalid
 };
 
-enum { kSamples = 0, kSearch = 1, kView = 2, kViewSearch = 3 };
+// view_keys_k / view_keys_search_k: `feat`, `key_cTw`, `key_K`, `prior`, `prior_cTw`, `prior_K` are rings indexed by slot - the features of
+// slot s start at feat + s * key_stride, the matrices are (n_slots,B,4,4), the prior maps (n_slots,B,1,H,W).  A separate struct: the four
+// single-key kernels keep their argument block as it is.
+constexpr int kMaxKeys = 16;
+struct KeysArgs : RayArgs {
+    long long key_stride;     // floats between the feature blocks of two slots
+    int nkeys;                // M <= kMaxKeys keys, asked in this order
+    int key_slots[kMaxKeys];  // their slots
+    unsigned char *keyout;    // view_keys_search_k: the key of the last step (position in key_slots, 255 = none) or null; view_keys_k writes it to `flags`
+};
+
+enum { kSamples = 0, kSearch = 1, kView = 2, kViewSearch = 3, kViewKeys = 4, kViewKeysSearch = 5 };
+constexpr int kKeyCamFloats = 24;  // per (key, batch) in LDS: P = K cam_T_world (12), the prior camera's (12); then per batch rows 0-2 of the view's invK (12) and world_T_cam (12)
 constexpr int kViewMaxBatch = 128;  // 24 KiB of cameras next to at most 96 KiB of weights
 constexpr int kCamFloats = 48;  // per batch in LDS: P = K cam_T_world (12), the prior camera's (12), rows 0-2 of the view's invK (12) and world_T_cam (12)
 
@@ -79,8 +95,10 @@ constexpr bool kViewSearchSkip = IDH_VIEW_SEARCH_SKIP;  // view_search_k: skip g
 
 // kSamples: the S depth samples of `depth`; kSearch: `iters` dependent evaluations at the ray's current search depth; kView: one evaluation
 // per pixel of a depth map seen from another camera; kViewSearch: `iters` dependent kView evaluations along a ray of that other camera
-template <int kMode>
-__device__ __forceinline__ void ray_body(const RayArgs &a) {
+template <int kMode, class Args = RayArgs>
+__device__ __forceinline__ void ray_body(const Args &a) {
+    constexpr bool kKeys = kMode == kViewKeys || kMode == kViewKeysSearch;
+    constexpr bool kDense = kMode == kView || kMode == kViewKeys;  // one evaluation per pixel of a depth map
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int nthreads = blockDim.x, nwaves = nthreads >> 6;
     f32x4 *sW2 = reinterpret_cast<f32x4 *>(smem_raw);
@@ -96,7 +114,27 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         for (int i = threadIdx.x; i < 6 * kHidden; i += nthreads) s_vec[i] = a.vecs[i];
     }
     float *s_cam = s_vec + 6 * kHidden;
-    if constexpr (kMode == kView || kMode == kViewSearch) {
+    if constexpr (kKeys) {
+        // P = K cam_T_world of every key (and of its prior camera), once per workgroup, key and batch: the fma loop of project_points_k
+        for (int t = threadIdx.x; t < 2 * a.nkeys * a.nb; t += nthreads) {
+            const int mb = t >> 1, pc = t & 1;
+            if (pc && !a.prior) continue;
+            const int m = mb / a.nb, b = mb - m * a.nb;
+            const size_t cam_i = ((size_t)a.key_slots[m] * a.nb + b) * 16;
+            const float *Kb = (pc ? a.prior_K : a.key_K) + cam_i, *T = (pc ? a.prior_cTw : a.key_cTw) + cam_i;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    float s = 0.f;
+                    for (int k = 0; k < 4; ++k) s = fmaf(Kb[i * 4 + k], T[k * 4 + j], s);
+                    s_cam[mb * kKeyCamFloats + 12 * pc + i * 4 + j] = s;
+                }
+        }
+        float *s_view = s_cam + a.nkeys * a.nb * kKeyCamFloats;
+        for (int t = threadIdx.x; t < 24 * a.nb; t += nthreads) {  // rows 0-2 of the view's invK and world_T_cam, as they are
+            const int b = t / 24, e = t - b * 24;
+            s_view[t] = (e < 12 ? a.invK : a.wTc)[(size_t)b * 16 + (e < 12 ? e : e - 12)];
+        }
+    } else if constexpr (kMode == kView || kMode == kViewSearch) {
         // P = K cam_T_world of the keyframe (and of the prior camera), once per workgroup and batch: the fma loop of project_points_k
         for (int t = threadIdx.x; t < 2 * a.nb; t += nthreads) {
             const int b = t >> 1, pc = t & 1;
@@ -137,13 +175,65 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         float vX[3] = {0.f, 0.f, 0.f}, vz = 0.f, vprior = 0.f;
         bool vdok = false, vvalid = false;
         const float *cam = s_cam + b * kCamFloats;  // (kView / kViewSearch)
+        // the view's invK rows (12) and world_T_cam rows (12) of batch b
+        const float *vcam = cam + 24;
+        int vkey = 255, vslot = 0;  // (keys) the selected key - its position in key_slots - and its slot
+        if constexpr (kKeys) vcam = s_cam + (a.nkeys * a.nb + b) * kKeyCamFloats;
         // ---- one point Xc of the view camera's frame: world point, Project3D into the keyframe (project_points_k, verbatim), validity, nearest
         // prior sample; the expressions of include/idh.h.  Every quarter-lane of a ray computes the same values ----
         auto probe = [&](const float (&Xc)[3], const bool dok) {
-            const float *T = cam + 36;
+            const float *T = vcam + 12;
 #pragma unroll
             for (int i = 0; i < 3; ++i) vX[i] = fmaf(T[4 * i], Xc[0], fmaf(T[4 * i + 1], Xc[1], fmaf(T[4 * i + 2], Xc[2], T[4 * i + 3])));
             const float X0 = vX[0], X1 = vX[1], X2 = vX[2];
+            if constexpr (kKeys) {
+                // the projection and the validity rule below, once per key; the first valid key is kept in scalars (u, v, z, key, slot), key 0's z
+                // stands in where none is valid.  The prior texel is the selected key's alone
+                float bu = 0.f, bv = 0.f, bz = 0.f, z0 = 0.f;
+                bool found = false;
+                vkey = 255;
+                vslot = 0;
+#pragma unroll 1
+                for (int m = 0; m < a.nkeys; ++m) {
+                    const float *P = s_cam + (m * a.nb + b) * kKeyCamFloats;
+                    const float cx = fmaf(P[0], X0, fmaf(P[1], X1, fmaf(P[2], X2, P[3])));
+                    const float cy = fmaf(P[4], X0, fmaf(P[5], X1, fmaf(P[6], X2, P[7])));
+                    const float cz = fmaf(P[8], X0, fmaf(P[9], X1, fmaf(P[10], X2, P[11])));
+                    const float z = fmaxf(cz, 1e-5f);
+                    const float u = cx / z, v = cy / z;
+                    const bool ok = dok && cz > 0.f && u >= 0.f && u < Wf && v >= 0.f && v < Hf;
+                    const bool take = ok && !found;
+                    const int slot = a.key_slots[m];  // (m is wave-uniform)
+                    if (m == 0) z0 = z;
+                    bu = take ? u : bu;
+                    bv = take ? v : bv;
+                    bz = take ? z : bz;
+                    vkey = take ? m : vkey;
+                    vslot = take ? slot : vslot;
+                    found = found || ok;
+                }
+                vvalid = found;
+                vz = found ? bz : z0;
+                vprior = a.prior_const;
+                if (a.prior) {
+                    const float *Q = s_cam + ((found ? vkey : 0) * a.nb + b) * kKeyCamFloats + 12;
+                    const float qx = fmaf(Q[0], X0, fmaf(Q[1], X1, fmaf(Q[2], X2, Q[3])));
+                    const float qy = fmaf(Q[4], X0, fmaf(Q[5], X1, fmaf(Q[6], X2, Q[7])));
+                    const float pz = fmaf(Q[8], X0, fmaf(Q[9], X1, fmaf(Q[10], X2, Q[11])));
+                    const float zz = fmaxf(pz, 1e-5f);
+                    const float pu = qx / zz, pw = qy / zz;
+                    const float gx = (pu / Wf - 0.5f) * 2.f, gy = (pw / Hf - 0.5f) * 2.f;
+                    const float sx = ((gx + 1.f) * Wf - 1.f) * 0.5f, sy = ((gy + 1.f) * Hf - 1.f) * 0.5f;
+                    const float xr = rintf(sx), yr = rintf(sy);  // round-half-even, as sample_prior_k
+                    const bool in = vvalid && pz > 0.f && xr >= 0.f && xr <= Wf - 1.f && yr >= 0.f && yr <= Hf - 1.f;  // no valid key: no texel is read
+                    // (texel 0 of the selected key's map - of the first key's where none is valid - exists: no branch)
+                    const float texel = a.prior[((size_t)(found ? vslot : a.key_slots[0]) * a.nb + b) * a.H * a.W + (size_t)(in ? (int)yr * a.W + (int)xr : 0)];
+                    vprior = in ? texel : -1.f;
+                }
+                x = bu;
+                y = bv;
+                return;
+            }
             const float *P = cam;
             const float cx = fmaf(P[0], X0, fmaf(P[1], X1, fmaf(P[2], X2, P[3])));
             const float cy = fmaf(P[4], X0, fmaf(P[5], X1, fmaf(P[6], X2, P[7])));
@@ -174,13 +264,13 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
         if constexpr (kMode == kSamples || kMode == kSearch) {
             x = a.rays[2 * src];
             y = a.rays[2 * src + 1];
-        } else if constexpr (kMode == kView) {
+        } else if constexpr (kDense) {
             const int pix = j % (a.vh * a.vw), row = pix / a.vw, col = pix - row * a.vw;
             const float dr = a.depth[src];
             vdok = dr > 0.f && dr <= 3.4028234663852886e38f;  // finite and positive (NaN fails both); anything else is asked as d = 0 and stores `fill`
             const float d = vdok ? dr : 0.f;
             const float px = (float)col + 0.5f, py = (float)row + 0.5f;  // BackprojectDepth's pixel centres (geometry_utils.py:39)
-            const float *iK = cam + 24;
+            const float *iK = vcam;
             float Xc[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) Xc[i] = d * fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
@@ -188,7 +278,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             if (!__any(vvalid)) {  // no valid ray in the tile (wave-uniform): no gather, no MLP
                 if (q == 0 && rok) {
                     a.out[src] = a.fill;
-                    if (a.flags) a.flags[src] = 0;
+                    if (a.flags) a.flags[src] = kKeys ? 255 : 0;
                     if (a.sdepth) a.sdepth[src] = vdok ? vz : 0.f;
                     if (a.points) {
 #pragma unroll
@@ -207,7 +297,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
                 px = (float)col + 0.5f;
                 py = (float)row + 0.5f;
             }
-            const float *iK = cam + 24;
+            const float *iK = vcam;
 #pragma unroll
             for (int i = 0; i < 3; ++i) vc[i] = fmaf(iK[4 * i], px, fmaf(iK[4 * i + 1], py, iK[4 * i + 2]));
         }
@@ -226,6 +316,8 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             const int xi = (vx0 || vx1) ? (int)x0 : 0, yi = (vy0 || vy1) ? (int)y0 : 0;
             const bool cv[4] = {live && vx0 && vy0, live && vx1 && vy0, live && vx0 && vy1, live && vx1 && vy1};
             const int base = b * a.H * a.W;
+            const float *feat = a.feat;
+            if constexpr (kKeys) feat += (size_t)vslot * a.key_stride;  // the selected key's block; no key selected: nothing is read
             const int crow[4] = {base + yi * a.W + xi, base + yi * a.W + xi + 1, base + (yi + 1) * a.W + xi, base + (yi + 1) * a.W + xi + 1};
 
             // ---- layer 1, sample-independent part: pre1^T = W1f . feat^T + b1 ----
@@ -238,7 +330,7 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         if (cv[k]) {  // a corner outside the map is not read
-                            const float *fp = a.feat + (size_t)crow[k] * a.cs + 16 * c + 4 * q;
+                            const float *fp = feat + (size_t)crow[k] * a.cs + 16 * c + 4 * q;
                             f32x4 v;
                             if (a.feat_unaligned) v = (f32x4){fp[0], fp[1], fp[2], fp[3]};
                             else v = *reinterpret_cast<const f32x4 *>(fp);
@@ -290,12 +382,12 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
             t += __shfl_xor(t, 32, 64);
             return t + b3;
         };
-        if constexpr (kMode != kViewSearch) gather(kMode != kView || vvalid);  // an invalid pixel of a view reads no corner
-        if constexpr (kMode == kView) {
+        if constexpr (kMode != kViewSearch && kMode != kViewKeysSearch) gather(!kDense || vvalid);  // an invalid pixel of a view reads no corner
+        if constexpr (kDense) {
             const float logit = eval(vz, vprior);
             if (q == 0 && rok) {
                 a.out[src] = vvalid ? logit : a.fill;
-                if (a.flags) a.flags[src] = vvalid ? 1 : 0;
+                if (a.flags) a.flags[src] = kKeys ? (unsigned char)vkey : (vvalid ? 1 : 0);
                 if (a.sdepth) a.sdepth[src] = vdok ? vz : 0.f;
                 if (a.points) {
 #pragma unroll
@@ -381,8 +473,11 @@ __device__ __forceinline__ void ray_body(const RayArgs &a) {
                 a.sdepth[src] = sd;
                 a.out[src] = logit;
                 if (a.flags) a.flags[src] = (unsigned char)moved;
+                if constexpr (kKeys) {
+                    if (a.keyout) a.keyout[src] = (unsigned char)vkey;  // of the last step
+                }
                 if (a.points) {  // the world point of the final query, by the expressions of the probes
-                    const float *T = cam + 36;
+                    const float *T = vcam + 12;
 #pragma unroll
                     for (int i = 0; i < 3; ++i) Xc[i] = sd * vc[i];
 #pragma unroll
@@ -398,6 +493,8 @@ __global__ __launch_bounds__(kRayMaxThreads) void ray_mlp_k(const RayArgs a) { r
 __global__ __launch_bounds__(kRayMaxThreads) void ray_search_k(const RayArgs a) { ray_body<kSearch>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void view_mlp_k(const RayArgs a) { ray_body<kView>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void view_search_k(const RayArgs a) { ray_body<kViewSearch>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_keys_k(const KeysArgs a) { ray_body<kViewKeys>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_keys_search_k(const KeysArgs a) { ray_body<kViewKeysSearch>(a); }
 
 // ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
 // Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
@@ -459,7 +556,10 @@ __global__ __launch_bounds__(256) void project_points_k(const float *__restrict_
 // samples of a tile are cut into runs of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256
 // per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.  The search (S = 1) has one item per tile: its iterations are
 // dependent, so there is nothing to split.
-static int ray_mlp_launch(RayArgs a, void *stream, int mode = kSamples) {
+// view_keys_k / view_keys_search_k (KeysArgs): the same tile partition, one item per tile, M (B + 1) x 24 floats of cameras in LDS.
+template <class Args>
+static int ray_mlp_launch(Args a, void *stream, int mode = kSamples) {
+    constexpr bool keys = std::is_same<Args, KeysArgs>::value;
     constexpr int kSimds = 256 * 4, kMinChunk = 8;
     const long long tiles = ((long long)a.M + 15) / 16;
     int nchunk = 1;
@@ -477,10 +577,17 @@ static int ray_mlp_launch(RayArgs a, void *stream, int mode = kSamples) {
     long long grid = (items + waves - 1) / waves;
     if (grid > 256) grid = 256;
     const int cblocks = (a.Cf + 15) >> 4;
-    const size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
-                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0);
-    static IdhDeviceOnce attr_set[4];
-    const auto kernel = mode == kViewSearch ? view_search_k : mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
+    size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
+                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0) +
+                       (keys ? (size_t)a.nb * kKeyCamFloats * sizeof(float) : 0);
+    static IdhDeviceOnce attr_set[6];
+    void (*kernel)(const Args);
+    if constexpr (keys) {
+        lds += (size_t)a.nkeys * a.nb * kKeyCamFloats * sizeof(float);
+        kernel = mode == kViewKeysSearch ? view_keys_search_k : view_keys_k;
+    } else {
+        kernel = mode == kViewSearch ? view_search_k : mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
+    }
     if (attr_set[mode].first()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return IDH_ELAUNCH;
@@ -602,6 +709,101 @@ extern "C" int idh_binary_mlp_view_search_fwd(const float *feat_nhwc, int feat_c
               world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, 1, rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
     a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
     return ray_mlp_launch(a, stream, kViewSearch);
+}
+
+// The checks the two multi-key entry points add to their parents': the order of the keys and the ring's geometry.  IDH_OK: k is filled in.
+static int keys_args(KeysArgs &k, long long key_stride, int n_slots, const int *key_slots, int M, int B, int H, int W, int feat_cs,
+                     const float *feat) {
+    if (!key_slots || M <= 0 || n_slots <= 0 || key_stride < 0) return IDH_EINVAL;
+    if (M > kMaxKeys) return IDH_EUNSUPPORTED;
+    for (int m = 0; m < M; ++m) {
+        if (key_slots[m] < 0 || key_slots[m] >= n_slots) return IDH_EINVAL;
+        for (int o = 0; o < m; ++o)
+            if (key_slots[o] == key_slots[m]) return IDH_EINVAL;
+    }
+    if (n_slots > 1 && key_stride < (long long)B * H * W * feat_cs) return IDH_EINVAL;
+    if ((long long)M * B > kViewMaxBatch || (long long)n_slots * B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    k.key_stride = key_stride;
+    k.nkeys = M;
+    for (int m = 0; m < kMaxKeys; ++m) k.key_slots[m] = m < M ? key_slots[m] : 0;
+    k.keyout = nullptr;
+    k.feat_unaligned = ((feat_cs & 3) || (key_stride & 3) || (reinterpret_cast<uintptr_t>(feat) & 15)) ? 1 : 0;
+    return IDH_OK;
+}
+
+// Dense occlusion in another camera against M remembered keyframes: idh_binary_mlp_view_fwd with the projection looped over the keys and the
+// first valid key selected per pixel, in one launch (view_keys_k).  include/idh.h states the expression.
+extern "C" int idh_binary_mlp_view_keys_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride, int n_slots,
+                                            const int *key_slots, int M, const float *rendered_bphw, int P, int h, int w, const float *invK_44,
+                                            const float *world_T_cam_44, const float *key_cam_T_world_s44, const float *key_K_s44,
+                                            const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44, const float *prior_K_s44,
+                                            int has_prior, float prior_const, const float *w1f_packed, const float *w2_packed,
+                                            const float *vecs6x128, float fill, float *logits_bphw, unsigned char *key_bphw,
+                                            float *view_depth_bphw, float *view_points_bphw3, void *stream) {
+    if (B < 0 || P < 0 || h < 0 || w < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf) return IDH_EINVAL;
+    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
+    if (B == 0 || P == 0 || h == 0 || w == 0) return IDH_OK;
+    if (!feat_ring || !rendered_bphw || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed ||
+        !vecs6x128 || !logits_bphw)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_ring, (const void *)rendered_bphw, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
+                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)logits_bphw, (const void *)view_depth_bphw,
+                          (const void *)view_points_bphw3})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    KeysArgs k{};
+    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
+    if ((long long)P * h >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (the product below stays inside 64 bits)
+    const long long Nq = (long long)P * h * w, Mr = (long long)B * Nq;
+    if (Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
+    const int unaligned = k.feat_unaligned;
+    static_cast<RayArgs &>(k) = RayArgs{feat_ring, nullptr, rendered_bphw, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, logits_bphw, (int)Mr,
+                                        (int)Nq, (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
+                                        0, 0.f, 0.f, 0.f, nullptr, nullptr, 0, view_depth_bphw, key_bphw, view_points_bphw3, invK_44, world_T_cam_44,
+                                        key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, P, h, w, fill};
+    return ray_mlp_launch(k, stream, kViewKeys);
+}
+
+// Depth along the rays of another camera against M remembered keyframes: idh_binary_mlp_view_search_fwd with every step one pixel of
+// idh_binary_mlp_view_keys_fwd at rendered = q_n - every step selects its own key - in one launch (view_keys_search_k).
+extern "C" int idh_binary_mlp_view_keys_search_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride,
+                                                   int n_slots, const int *key_slots, int M, int h, int w, const float *rays_bn2, int N,
+                                                   const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_s44,
+                                                   const float *key_K_s44, const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44,
+                                                   const float *prior_K_s44, int has_prior, float prior_const, const float *w1f_packed,
+                                                   const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi, float threshold,
+                                                   const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
+                                                   float *last_logits, unsigned char *flags, float *points, unsigned char *key, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || iters <= 0 || n_bins < 0) return IDH_EINVAL;
+    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    const float fmax = 3.4028234663852886e38f;
+    if (!(lo > 0.f) || !(hi > lo) || !(lo <= fmax) || !(hi <= fmax)) return IDH_EINVAL;  // (NaN fails every comparison)
+    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
+    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
+    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
+    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
+    if (!feat_ring || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth ||
+        !last_logits)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_ring, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
+                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)bins, (const void *)thr_logits,
+                          (const void *)depth, (const void *)last_logits, (const void *)points})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    KeysArgs k{};
+    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
+    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, Mr = (long long)B * Nq;
+    if (Nq >= (1ll << 31) || Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
+    const int unaligned = k.feat_unaligned;
+    static_cast<RayArgs &>(k) = RayArgs{feat_ring, rays_bn2, nullptr, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)Mr, (int)Nq,
+                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
+                                        iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
+                                        points, invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, 1,
+                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
+    k.keyout = key;
+    return ray_mlp_launch(k, stream, kViewKeysSearch);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

@@ -383,6 +383,127 @@ def view_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: torch.T
     return depth, logits, flags, points
 
 
+MAX_VIEW_KEYS, MAX_VIEW_KEY_CAMERAS = 16, 128  # idh_binary_mlp_view_keys_fwd: M <= 16, M * B <= 128
+
+
+def _view_keys_common(net, what, feat_ring, feat_c0, n_feat, key_slots, invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior):
+    """The checks and arguments the two multi-key wrappers share: (B, H, W, n_slots, slots array, M, matrices kept alive, prior map | None)."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError(f"ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of {what}; set mlp_math = 'fp32'")
+    pmap = prior if isinstance(prior, (tuple, list)) else None
+    _lib.require_cuda_f32(feat_ring, invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, *(pmap if pmap is not None else ()))
+    if feat_ring.dim() != 5 or not feat_ring.is_contiguous():
+        raise _lib.IdhError(f"the feature ring must be a dense (n_slots, B, H, W, C) tensor, got {tuple(feat_ring.shape)}")
+    n_slots, B, H, W, cs = feat_ring.shape
+    if feat_c0 < 0 or n_feat <= 0 or feat_c0 + n_feat > cs:
+        raise _lib.IdhError(f"channels [{feat_c0}, {feat_c0 + n_feat}) are not inside the ring's {cs}")
+    for m in (invK_b44, world_T_cam_b44):
+        if tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"invK / world_T_cam must be ({B}, 4, 4), got {tuple(m.shape)}")
+    rings = [key_cam_T_world_sb44, key_K_s0_sb44] + ([pmap[1], pmap[2]] if pmap is not None else [])
+    for m in rings:
+        if tuple(m.shape) != (n_slots, B, 4, 4):
+            raise _lib.IdhError(f"the camera rings must be ({n_slots}, {B}, 4, 4), got {tuple(m.shape)}")
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if pmap is not None and tuple(pmap[0].shape) != (n_slots, B, 1, H, W):
+        raise _lib.IdhError(f"prior ring {tuple(pmap[0].shape)} must be ({n_slots}, {B}, 1, {H}, {W})")
+    slots = [int(k) for k in key_slots]
+    if not slots or len(set(slots)) != len(slots) or any(k < 0 or k >= n_slots for k in slots):
+        raise _lib.IdhError(f"key_slots must be a non-empty list of distinct slots in [0, {n_slots}), got {slots}")
+    if len(slots) > MAX_VIEW_KEYS or len(slots) * B > MAX_VIEW_KEY_CAMERAS:
+        raise _lib.IdhError(f"{what} takes at most {MAX_VIEW_KEYS} keys and {MAX_VIEW_KEY_CAMERAS} key cameras (keys x batch), got {len(slots)} x {B} (IDH_EUNSUPPORTED)")
+    import ctypes as C
+
+    keep = [m.contiguous() for m in [invK_b44, world_T_cam_b44] + rings]  # alive until enqueued
+    pp = pmap[0].contiguous() if pmap is not None else None
+    return B, H, W, n_slots, (C.c_int * len(slots))(*slots), len(slots), keep, pp
+
+
+def view_keys_logits(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, rendered_bphw: torch.Tensor, invK_b44: torch.Tensor,
+                     world_T_cam_b44: torch.Tensor, key_cam_T_world_sb44: torch.Tensor, key_K_s0_sb44: torch.Tensor, prior=None, fill: float = 0.0,
+                     return_points: bool = False):
+    """``view_logits`` against several remembered keyframes on ``idh_binary_mlp_view_keys_fwd``: every pixel of ``rendered_bphw`` (B,P,h,w)
+    is projected into the keys ``key_slots`` - slots of the dense ring ``feat_ring`` (n_slots,B,H,W,CS), channels [feat_c0, feat_c0 + n_feat),
+    with cameras ``key_cam_T_world_sb44`` / ``key_K_s0_sb44`` (n_slots,B,4,4) - in that order, and asked in the first key in which it is
+    valid: one launch and one MLP pass per pixel.  ``prior``: None, a float, or rings (prior_pred (n_slots,B,1,H,W), prior_cam_T_world,
+    prior_K (n_slots,B,4,4)) - the selected key's own prior is sampled.  Returns (logits (B,P,h,w), ``fill`` where no key is valid, key
+    (B,P,h,w) uint8: the position in ``key_slots`` of the selected key, 255 = none, view_depth (B,P,h,w): z in the selected key (in the
+    first key where none is valid), points (B,P,h,w,3) | None)."""
+    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_fwd", feat_ring, feat_c0, n_feat, key_slots, invK_b44,
+                                                              world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
+    _lib.require_cuda_f32(rendered_bphw)
+    if rendered_bphw.dim() != 4 or rendered_bphw.shape[0] != B:
+        raise _lib.IdhError(f"rendered depth must be ({B}, P, h, w), got {tuple(rendered_bphw.shape)}")
+    _, P, h, w = rendered_bphw.shape
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
+    dev = rendered_bphw.device
+    rd = rendered_bphw.contiguous()
+    n = B * P * h * w
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    logits, depth = buf[:n].view(B, P, h, w), buf[n: 2 * n].view(B, P, h, w)
+    points = buf[2 * n:].view(B, P, h, w, 3) if return_points else None
+    key = torch.empty(B, P, h, w, device=dev, dtype=torch.uint8)
+    cs = feat_ring.shape[-1]
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_keys_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
+                                                rd.data_ptr(), P, h, w, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(),
+                                                keep[3].data_ptr(), _lib.ptr(pp), keep[4].data_ptr() if pp is not None else None,
+                                                keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
+                                                -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
+                                                vecs.data_ptr(), float(fill), logits.data_ptr(), key.data_ptr(), depth.data_ptr(),
+                                                _lib.ptr(points), _lib.stream_ptr()),
+        "idh_binary_mlp_view_keys_fwd")
+    return logits, key, depth, points
+
+
+def view_keys_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor,
+                     key_cam_T_world_sb44: torch.Tensor, key_K_s0_sb44: torch.Tensor, size=None, rays: Optional[torch.Tensor] = None, prior=None,
+                     iters: int = 12, lo: float = 0.5, hi: float = 8.0, threshold: float = 0.5, thresholder=None, fill: float = 0.0,
+                     return_points: bool = False):
+    """``view_depths`` against several remembered keyframes on ``idh_binary_mlp_view_keys_search_fwd``: the same search, every step one
+    ``view_keys_logits`` pixel that selects its own key (the first of ``key_slots`` in which the probe is valid); the threshold of a step
+    is looked up at the probe's depth in the selected key (in the first key where none is valid).  Ring arguments as ``view_keys_logits``,
+    the others as ``view_depths``.  Returns (depth, logits of the last step, flags uint8 - bit 2: no key was valid at some probe -, world
+    points | None, key uint8: the position in ``key_slots`` of the key the LAST step selected, 255 = none)."""
+    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_search_fwd", feat_ring, feat_c0, n_feat, key_slots,
+                                                              invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
+    if (size is None) == (rays is None):
+        raise _lib.IdhError("view_keys_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
+    _lib.require_cuda_f32(rays)
+    if rays is not None:
+        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
+    else:
+        h, w = int(size[0]), int(size[1])
+        if h < 0 or w < 0:
+            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
+        N, shape = h * w, (B, 1, h, w)
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
+    dev = feat_ring.device
+    bins, thr_logits = _thresholder_tables(thresholder, dev)
+    r = rays.contiguous() if rays is not None else None
+    n = B * N
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
+    points = buf[2 * n:].view(*shape, 3) if return_points else None
+    flags = torch.empty((2,) + tuple(shape), device=dev, dtype=torch.uint8)
+    cs = feat_ring.shape[-1]
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_keys_search_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
+                                                       h, w, _lib.ptr(r), N if r is not None else 0, keep[0].data_ptr(), keep[1].data_ptr(),
+                                                       keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
+                                                       keep[4].data_ptr() if pp is not None else None,
+                                                       keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
+                                                       -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
+                                                       vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
+                                                       0 if bins is None else bins.numel(), float(fill), depth.data_ptr(), logits.data_ptr(),
+                                                       flags[0].data_ptr(), _lib.ptr(points), flags[1].data_ptr(), _lib.stream_ptr()),
+        "idh_binary_mlp_view_keys_search_fwd")
+    return depth, logits, flags[0], points, flags[1]
+
+
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:
     """``BinaryMLPNetwork.forward(list of (..., Cin) tensors, max_scale_only)`` (reference networks.py:106-115); row = [depth | features |
     (prior)].  fp32: the rows are read IN PLACE through ``idh_binary_mlp_strided_fwd`` whatever their strides - in particular the

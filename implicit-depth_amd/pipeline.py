@@ -29,6 +29,80 @@ from .cost_volume import CostVolumeManager, ZeroCostVolumeManager, volume_opts
 from .mlp import occlusion_logits
 
 
+MAX_RING_CAPACITY = 16  # idh_binary_mlp_view_keys_fwd asks at most 16 keys
+
+
+class PredictionRing:
+    """The last ``capacity`` predictions a caller chose to remember, for the multi-key queries (``mlp.view_keys_logits`` /
+    ``view_keys_depths``): a dense (capacity,B,H,W,Cf) ring of scale-0 decoder features, their cameras (capacity,B,4,4) and - once a
+    prediction is pushed with one - a prior ring (capacity,B,1,H,W) with its cameras.  Storage is allocated on the first ``push``.  A
+    prediction pushed without a prior into a ring that has one holds the constant -1 there, which is what a prior-enabled network
+    sees where no prior prediction exists (reference bd_model.py:433-434)."""
+
+    def __init__(self, capacity: int = 4):
+        capacity = int(capacity)
+        if not 1 <= capacity <= MAX_RING_CAPACITY:
+            raise _lib.IdhError(f"ring capacity must be in [1, {MAX_RING_CAPACITY}], got {capacity}")
+        self.capacity = capacity
+        self.feat = self.cam_T_world = self.K = self.prior = self.prior_cam_T_world = self.prior_K = None
+        self._next, self._count = 0, 0
+
+    def __len__(self) -> int:
+        return self._count
+
+    @property
+    def B(self) -> Optional[int]:
+        return None if self.feat is None else self.feat.shape[1]
+
+    def clear(self) -> None:
+        """Forget every prediction; the storage is kept."""
+        self._next, self._count = 0, 0
+
+    def push(self, final0_view: nhwc.View, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor, prior=None) -> int:
+        """Copy the scale-0 ``View`` of a forward - one strided device copy on the current stream, so it is ordered before any later
+        replay of the plan that owns the view - and its camera into the next slot (the oldest once the ring is full); ``prior``: None or
+        (prior_pred (B,1,H,W), prior_cam_T_world (B,4,4), prior_K (B,4,4)).  Returns the slot."""
+        v = final0_view
+        B, H, W, C = v.N, v.H, v.W, v.C
+        _lib.require_cuda_f32(v.buf, cam_T_world_b44, K_s0_b44, *(prior if prior is not None else ()))
+        for m in (cam_T_world_b44, K_s0_b44) + (tuple(prior[1:]) if prior is not None else ()):
+            if tuple(m.shape) != (B, 4, 4):
+                raise _lib.IdhError(f"cam_T_world / K_s0 (and the prior's) must be ({B}, 4, 4), got {tuple(m.shape)}")
+        if prior is not None and tuple(prior[0].shape) != (B, 1, H, W):
+            raise _lib.IdhError(f"prior prediction {tuple(prior[0].shape)} must be ({B}, 1, {H}, {W})")
+        dev = v.buf.device
+        if self.feat is None or tuple(self.feat.shape[1:]) != (B, H, W, C) or self.feat.device != dev:
+            self.feat = torch.empty(self.capacity, B, H, W, C, device=dev)
+            self.cam_T_world, self.K = torch.empty(self.capacity, B, 4, 4, device=dev), torch.empty(self.capacity, B, 4, 4, device=dev)
+            self.prior = self.prior_cam_T_world = self.prior_K = None
+            self.clear()
+        if prior is not None and self.prior is None:
+            self.prior = torch.full((self.capacity, B, 1, H, W), -1.0, device=dev)
+            self.prior_cam_T_world, self.prior_K = self.cam_T_world.clone(), self.K.clone()
+        slot = self._next
+        self.feat[slot].copy_(v.dense())
+        self.cam_T_world[slot].copy_(cam_T_world_b44)
+        self.K[slot].copy_(K_s0_b44)
+        if self.prior is not None:
+            if prior is not None:
+                self.prior[slot].copy_(prior[0])
+                self.prior_cam_T_world[slot].copy_(prior[1])
+                self.prior_K[slot].copy_(prior[2])
+            else:
+                self.prior[slot].fill_(-1.0)
+                self.prior_cam_T_world[slot].copy_(cam_T_world_b44)
+                self.prior_K[slot].copy_(K_s0_b44)
+        self._next = (slot + 1) % self.capacity
+        self._count = min(self._count + 1, self.capacity)
+        return slot
+
+    def slots_newest_first(self) -> List[int]:
+        return [(self._next - 1 - i) % self.capacity for i in range(self._count)]
+
+    def prior_rings(self):
+        return None if self.prior is None else (self.prior, self.prior_cam_T_world, self.prior_K)
+
+
 class HotPath(nn.Module):
     """Owns (or shares) the hot-path modules of a BDModel / DepthModel: the cost volume, the CVEncoder, the
     depth decoder, the occlusion MLP and — optionally — the matching encoder, whose head then runs inside the
@@ -48,6 +122,7 @@ class HotPath(nn.Module):
         self.thresholder = None  # like BDModel.thresholder (bd_model.py:141): per-depth thresholds of the infer_depth search
         self._plans = nhwc.PlanCache()  # LRU: a ragged last batch / alternating shapes replay instead of rebuilding
         self._last = None  # decoder output of the last forward (plan-owned final[i] views): what query_rays / query_points / query_view read
+        self._ring: Optional[PredictionRing] = None  # predictions kept by remember(): what query_view_keys / query_view_depths_keys read
         _lib.watch_state_dict_loads(self)
 
     # ------------------------------------------------------------------------------------
@@ -168,6 +243,74 @@ class HotPath(nn.Module):
                                                  iters, lo, hi, threshold, self.thresholder if thresholder is None else thresholder, fill,
                                                  return_points)
         return {"view_search_depths": depth, "view_search_logits": pred, "view_search_flags": flags, "view_search_points": points}
+
+    def remember(self, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor, prior_inputs: Optional[Dict[str, torch.Tensor]] = None,
+                 capacity: int = 4) -> int:
+        """Keep the LAST forward for the multi-key queries: its scale-0 decoder features are copied - on the current stream, before the
+        plan can be replayed - into a ``PredictionRing`` of ``capacity`` (<= 16) predictions together with the camera of that forward
+        (``cam_T_world_b44``, ``K_s0_b44``) and, with ``prior_inputs`` as ``query_points``, the prior that belongs to it.  The oldest
+        prediction leaves once the ring is full; another ``capacity`` or batch size starts a new ring.  Returns the slot."""
+        final = _last_final(self, cam_T_world_b44.shape[0], (0,))
+        if self._ring is None or self._ring.capacity != int(capacity):
+            self._ring = PredictionRing(capacity)
+        prior = None
+        if prior_inputs is not None and prior_inputs.get("prior_prediction") is not None:
+            prior = (prior_inputs["prior_prediction"], prior_inputs["prior_cam_T_world"], prior_inputs.get("K_s0_b44", K_s0_b44))
+        return self._ring.push(final[0], cam_T_world_b44, K_s0_b44, prior)
+
+    def forget(self) -> None:
+        """Empty the ring of remembered predictions (its storage is kept)."""
+        if self._ring is not None:
+            self._ring.clear()
+
+    def _remembered(self, B: int, order):
+        if self.binary_mlp is None:
+            raise _lib.IdhError("occlusion queries need a HotPath with a binary_mlp")
+        ring = self._ring
+        if ring is None or len(ring) == 0:
+            raise _lib.IdhError("nothing is remembered on this HotPath yet: call remember() after a forward")
+        if ring.B != B:
+            raise _lib.IdhError(f"the remembered predictions have batch size {ring.B}, the query has {B}")
+        live = ring.slots_newest_first()
+        slots = live if order is None else [int(s) for s in order]
+        if any(s not in live for s in slots):
+            raise _lib.IdhError(f"order {slots} names a slot that holds no prediction (remembered: {live})")
+        prior = ring.prior_rings() if getattr(self.binary_mlp, "use_prior", False) else None
+        return ring, slots, prior
+
+    def query_view_keys(self, rendered_depth: torch.Tensor, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor,
+                        order: Optional[Sequence[int]] = None, fill: float = 0.0, return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """``query_view`` against the predictions kept by ``remember``: every pixel is asked in the first remembered prediction - in
+        ``order``, a list of ring slots; None = newest first - whose camera sees it, in one ``mlp.view_keys_logits`` launch with one MLP
+        pass per pixel.  The answers are those of ``query_view`` on that prediction, bit for bit; the prior is the one remembered with it.
+        Returns ``query_view``'s dictionary - "view_depth" is the depth in the selected prediction's camera - plus "view_key" (B,P,h,w)
+        uint8: the position in the order of the prediction that answered, 255 where none did ("view_valid" False, "view_pred" ``fill``).
+        ``IdhError`` when nothing is remembered or when B differs."""
+        from .mlp import view_keys_logits
+
+        ring, slots, prior = self._remembered(rendered_depth.shape[0], order)
+        pred, key, depth, points = view_keys_logits(self.binary_mlp, ring.feat, 0, ring.feat.shape[-1], slots, rendered_depth, invK_b44,
+                                                    world_T_cam_b44, ring.cam_T_world, ring.K, prior, fill, return_points)
+        return {"view_pred": pred, "view_valid": key != 255, "view_depth": depth, "view_points": points, "view_key": key}
+
+    def query_view_depths_keys(self, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, size: Optional[Sequence[int]] = None,
+                               rays: Optional[torch.Tensor] = None, order: Optional[Sequence[int]] = None, thresholder=None, iters: int = 12,
+                               lo: float = 0.5, hi: float = 8.0, threshold: float = 0.5, fill: float = 0.0,
+                               return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """``query_view_depths`` against the predictions kept by ``remember``: the same search, every probe asked in the first remembered
+        prediction (``order`` as ``query_view_keys``) whose camera sees it, in one ``mlp.view_keys_depths`` launch.  Returns
+        ``query_view_depths``' dictionary - flag bit 2: no prediction saw some probe - plus "view_search_key": the position in the order
+        of the prediction the LAST step asked, 255 = none.  ``IdhError`` when nothing is remembered or when B differs."""
+        from .mlp import view_keys_depths
+
+        if (size is None) == (rays is None):
+            raise _lib.IdhError("query_view_depths_keys takes exactly one of size=(h, w) and rays=(B,N,2)")
+        ring, slots, prior = self._remembered(invK_b44.shape[0], order)
+        depth, pred, flags, points, key = view_keys_depths(self.binary_mlp, ring.feat, 0, ring.feat.shape[-1], slots, invK_b44, world_T_cam_b44,
+                                                           ring.cam_T_world, ring.K, size, rays, prior, iters, lo, hi, threshold,
+                                                           self.thresholder if thresholder is None else thresholder, fill, return_points)
+        return {"view_search_depths": depth, "view_search_logits": pred, "view_search_flags": flags, "view_search_points": points,
+                "view_search_key": key}
 
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
               images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):

@@ -27,19 +27,35 @@ from torch import nn
 
 from . import _lib, keyframes
 from .feature_bank import FeatureBank
-from .pipeline import HotPath
+from .pipeline import MAX_RING_CAPACITY, HotPath
 
 MODES = ("keyframe",)
+
+
+def nearest_keys_first(live_world_T_cam, key_poses_newest_first) -> list:
+    """The order in which a live view asks the remembered keyframes: indices into ``key_poses_newest_first`` - (4,4) camera-to-world host
+    arrays, newest first - sorted by ``keyframes.pose_distance`` from the live pose, nearest first; equal distances go to the newer key."""
+    live = np.asarray(live_world_T_cam, dtype=np.float64)
+    dist = [float(keyframes.pose_distance(live, np.asarray(p, dtype=np.float64))[0]) for p in key_poses_newest_first]
+    return sorted(range(len(dist)), key=lambda i: (dist[i], i))
 
 
 class StreamingSession:
     """``model``: a reference ``BDModel`` / ``DepthModel`` (converted in place by ``dropin.hot_path_of``; its ``encoder`` is the image
     encoder) or a ``HotPath`` with a ``matching_model`` (then pass ``image_encoder``).  The matching encoder's stem must be eligible for
     the native kernels (``backbone.stem_is_native_eligible``).  ``num_source_views``: K; read off an MLP feature volume, required for the
-    dot-product volume.  ``buffer_size``: keyframes kept (the ring's slots, at most 64 and more than K); ``config``: the DVMVS thresholds."""
+    dot-product volume.  ``buffer_size``: keyframes kept (the ring's slots, at most 64 and more than K); ``config``: the DVMVS thresholds.
+    ``query_keyframes``: how many predictions ``occlusion_for_view`` / ``depth_for_view`` / ``raycast_view`` ask.  1 (the default): the
+    last one, as ever.  N in [2, 16]: every prediction is remembered (``HotPath.remember``, with its own ``sigmoid(pred_0[:, :1])`` and
+    camera as its prior under ``use_prior``) and a live pixel is asked in the first of the last N whose camera sees it, nearest pose
+    first (``nearest_keys_first``); the dictionaries gain "view_key" / "view_search_key".  ``reset()`` empties that ring; like the last
+    prediction it survives a tracking-lost code."""
 
     def __init__(self, model: nn.Module, num_source_views: Optional[int] = None, buffer_size: Optional[int] = None, mode: str = "keyframe",
-                 config=keyframes.DVMVS_Config, image_encoder: Optional[nn.Module] = None, math: Optional[str] = None):
+                 config=keyframes.DVMVS_Config, image_encoder: Optional[nn.Module] = None, math: Optional[str] = None,
+                 query_keyframes: int = 1):
+        if not 1 <= int(query_keyframes) <= MAX_RING_CAPACITY:
+            raise _lib.IdhError(f"query_keyframes must be in [1, {MAX_RING_CAPACITY}], got {query_keyframes}")
         if mode not in MODES:
             raise _lib.IdhError(f"mode must be one of {MODES}, got {mode!r} (the reference's dense tuples cannot be served from a keyframe "
                                 "ring: see the module docstring)")
@@ -83,6 +99,11 @@ class StreamingSession:
         self.last_matching: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # (cur (1,H,W,C), src (1,K,H,W,C)) of the last prediction
         self._prior: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._key: Optional[Dict[str, torch.Tensor]] = None  # the last prediction's poses and intrinsics: what query_points / raycast / occlusion_for_view use
+        # query_keyframes = N > 1: every prediction is remembered on the HotPath's ring (HotPath.remember) and occlusion_for_view /
+        # depth_for_view / raycast_view ask the last N of them, nearest pose first.  Like _key the ring survives a tracking-lost code -
+        # and so do the priors remembered with its predictions, while the single-key queries drop theirs there; reset() empties it.
+        self.query_keyframes = int(query_keyframes)
+        self._ring_poses: Dict[int, np.ndarray] = {}  # ring slot -> that prediction's world_T_cam on the host
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -90,6 +111,9 @@ class StreamingSession:
                                                self.buffer.optimal_R_score)
         self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
         self._key = None
+        if self.query_keyframes > 1:
+            self.hot.forget()
+            self._ring_poses = {}
 
     def step(self, cur_data: Dict[str, torch.Tensor], world_T_cam=None, dist_to_last_valid=None, return_mask: bool = False,
              infer_depth: bool = False, query_points: Optional[torch.Tensor] = None) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
@@ -147,6 +171,12 @@ class StreamingSession:
             if self.hot.binary_mlp is not None:
                 self._key = {"cam_T_world_b44": cur_data["cam_T_world_b44"], "K_s0_b44": cur_data["K_s0_b44"],
                              "world_T_cam_b44": cur_data["world_T_cam_b44"], "invK_s0_b44": cur_data["invK_s0_b44"]}
+                if self.query_keyframes > 1:
+                    pi = None
+                    if self.use_prior and "pred_0" in out:
+                        pi = {"prior_prediction": torch.sigmoid(out["pred_0"][:, :1]), "prior_cam_T_world": cur_data["cam_T_world_b44"]}
+                    slot = self.hot.remember(cur_data["cam_T_world_b44"], cur_data["K_s0_b44"], prior_inputs=pi, capacity=self.query_keyframes)
+                    self._ring_poses[slot] = np.array(pose, dtype=np.float64)
                 if query_points is not None:
                     out.update(self.query_points(query_points))
         if "prior_mask" in out:
@@ -189,14 +219,24 @@ class StreamingSession:
         T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
         if tuple(T.shape) != (4, 4):
             raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
+        T_host = T
         T = T.to(device=rendered_depth.device, dtype=torch.float32)[None]
         if invK.dim() == 2:
             invK = invK[None]
+        if self.query_keyframes > 1:
+            with torch.inference_mode():
+                return self.hot.query_view_keys(rendered_depth, invK, T, order=self._key_order(T_host), fill=fill)
         pi = None
         if self.use_prior and self._prior is not None:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
         with torch.inference_mode():
             return self.hot.query_view(rendered_depth, invK, T, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi, fill=fill)
+
+    def _key_order(self, T_host: torch.Tensor) -> list:
+        """Ring slots of the remembered predictions, nearest pose to the live camera first (``nearest_keys_first``; host arithmetic)."""
+        slots = self.hot._ring.slots_newest_first()
+        order = nearest_keys_first(T_host.double().numpy(), [self._ring_poses[s] for s in slots])
+        return [slots[i] for i in order]
 
     def _view_search(self, world_T_cam, invK: torch.Tensor, size, rays, thresholder, fill: float):
         if self._key is None:
@@ -206,9 +246,14 @@ class StreamingSession:
         T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
         if tuple(T.shape) != (4, 4):
             raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
+        T_host = T
         T = T.to(device=invK.device, dtype=torch.float32)[None]
         if invK.dim() == 2:
             invK = invK[None]
+        if self.query_keyframes > 1:
+            with torch.inference_mode():
+                return self.hot.query_view_depths_keys(invK, T, size=size, rays=rays, order=self._key_order(T_host), thresholder=thresholder, fill=fill,
+                                                       return_points=True)
         pi = None
         if self.use_prior and self._prior is not None:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}

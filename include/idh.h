@@ -394,6 +394,50 @@ int idh_binary_mlp_view_search_fwd(const float *feat_nhwc, int feat_cs, int Cf, 
                                    float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters, float lo,
                                    float hi, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
                                    float *last_logits, unsigned char *flags, float *points, void *stream);
+/* Dense occlusion in a moving camera against SEVERAL remembered keyframes, in one launch (view_keys_k): idh_binary_mlp_view_fwd with the
+ * projection looped over M keys and ONE MLP pass per pixel.  The keys live in rings indexed by slot s in [0, n_slots):
+ *   feat_ring: the (B,H,W,feat_cs) NHWC block of slot s starts at feat_ring + s * key_stride (key_stride in floats)
+ *   key_cam_T_world_s44, key_K_s44: (n_slots,B,4,4);  optional prior ring: prior_pred_sb1hw (n_slots,B,1,H,W) with prior_cam_T_world_s44 and
+ *   prior_K_s44 (n_slots,B,4,4) - the prior of slot s belongs to the key of slot s
+ *   key_slots: HOST array of M distinct slots in priority order (copied into the kernel arguments; it may be freed on return)
+ * Per pixel (b, p, row, col), in fp32 with one rounding per operation / fma (no contraction):
+ *   the world point p: idh_binary_mlp_view_fwd's BackprojectDepth expressions, verbatim, once
+ *   for m = 0 .. M-1: Project3D of p into key key_slots[m] - P_m = K cam_T_world, c = P_m[:3] (p, 1), z_m = fmaxf(c_z, 1e-5f),
+ *     (u_m, v_m) = c_xy / z_m, idh_project_points_fwd's expressions - and idh_binary_mlp_view_fwd's validity rule: d finite and > 0,
+ *     c_z > 0, 0 <= u_m < W, 0 <= v_m < H
+ *   sel = the first m that is valid.  logit = MLP([z_sel | feat_sel(u_sel, v_sel) | prior_sel]): the gather, the nearest prior sample (in
+ *     the prior camera of slot key_slots[sel]; without a prior ring the constant prior_const) and the network of idh_binary_mlp_view_fwd on
+ *     the selected key alone - no feature corner and no prior texel of another key is read
+ *   no valid m: the logit IS `fill`, nothing is gathered; a 16-pixel tile without a pixel that has a valid key skips the MLP
+ * Outputs: logits_bphw (B,P,h,w); optional (NULL: not written) key_bphw uint8 = sel (the position in key_slots, NOT the slot), 255 = none;
+ * view_depth_bphw = z_sel, z_0 where no key is valid, 0 where d is not finite and positive; view_points_bphw3 (B,P,h,w,3) = p (0 where d
+ * is not finite and positive).  By construction the outputs carry the bits of M launches of idh_binary_mlp_view_fwd, one per key in
+ * key_slots order, followed by a per-pixel select of the first launch whose valid byte is 1; with M = 1 they are that launch's.
+ * fp32 only.  IDH_EINVAL: every condition of idh_binary_mlp_view_fwd that applies, and - with a non-empty map - M <= 0, n_slots <= 0, a NULL
+ * key_slots, a slot outside [0, n_slots), a duplicate slot, key_stride < 0, key_stride < B * H * W * feat_cs when n_slots > 1.  IDH_EUNSUPPORTED:
+ * M > 16, M * B > 128 (the cameras of a launch sit in LDS: 24 floats per key and batch element, 24 per batch element for the view),
+ * n_slots * B * H * W >= 2^31, and the parent's size limits.  The 16-byte loads need feat_ring, feat_cs and key_stride all 16-byte compatible;
+ * anything else takes the dword path.  B == 0 or an empty map: IDH_OK, no launch.  Everything is checked on the host before the device is touched. */
+int idh_binary_mlp_view_keys_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride, int n_slots,
+                                 const int *key_slots, int M, const float *rendered_bphw, int P, int h, int w, const float *invK_44,
+                                 const float *world_T_cam_44, const float *key_cam_T_world_s44, const float *key_K_s44,
+                                 const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44, const float *prior_K_s44, int has_prior,
+                                 float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, float fill,
+                                 float *logits_bphw, unsigned char *key_bphw, float *view_depth_bphw, float *view_points_bphw3, void *stream);
+/* Depth in a moving camera against several remembered keyframes, in one launch (view_keys_search_k): idh_binary_mlp_view_search_fwd's rule,
+ * step by step, with every step one pixel of idh_binary_mlp_view_keys_fwd on the map rendered = q_n - every step selects its own key.
+ * The rings, key_slots and their limits are idh_binary_mlp_view_keys_fwd's; rays, h, w, N, iters, lo, hi, the thresholds and `fill` are
+ * idh_binary_mlp_view_search_fwd's.  Per step: thr is keyed by z_sel, by z_0 (key key_slots[0]) when no key is valid; flag bit 2: no key
+ * was valid at some probe.  Outputs as the parent's - depth, last_logits, optional flags, optional world points - plus optional key
+ * (uint8, any alignment): the sel of step iters - 1, 255 = none.
+ * IDH_EINVAL / IDH_EUNSUPPORTED: the conditions of both parents.  B == 0 or an empty grid / list: IDH_OK, no launch. */
+int idh_binary_mlp_view_keys_search_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride, int n_slots,
+                                        const int *key_slots, int M, int h, int w, const float *rays_bn2, int N, const float *invK_44,
+                                        const float *world_T_cam_44, const float *key_cam_T_world_s44, const float *key_K_s44,
+                                        const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44, const float *prior_K_s44, int has_prior,
+                                        float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters,
+                                        float lo, float hi, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill,
+                                        float *depth, float *last_logits, unsigned char *flags, float *points, unsigned char *key, void *stream);
 /* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
  * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
  *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
