@@ -246,6 +246,13 @@ _SIGS = {
                                                       C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int,
                                                       C.c_float, f32p, f32p, f32p, C.c_int, C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_int,
                                                       C.c_float, f32p, f32p, C.c_void_p, f32p, C.c_void_p, C.c_void_p]),
+    "idh_binary_mlp_view_march_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, f32p, f32p, f32p, f32p,
+                                                f32p, f32p, C.c_int, C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, f32p,
+                                                C.c_int, C.c_float, f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p]),
+    "idh_binary_mlp_view_keys_march_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_int),
+                                                     C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int,
+                                                     C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_int,
+                                                     C.c_float, f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, C.c_void_p]),
     "idh_project_points_fwd": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -277,7 +284,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args

@@ -27,6 +27,10 @@
 // view_keys_k / view_keys_search_k are those two with the projection looped over M remembered keyframes (a ring of feature maps, cameras and
 // priors, indexed by slot): the world point is projected into key_slots[0..M-1] in turn, the first key in which it is valid is selected, and
 // the prior texel, the four corners and the MLP are those of the selected key alone - one MLP pass per pixel whatever M is.
+//
+// view_march_k / view_keys_march_k are view_search_k / view_keys_search_k with the bracket found instead of assumed: every ray probes the
+// shared samples march_depths[0 .. n_march-1] in turn until the first probe that is behind the surface, then bisects `refine` steps inside
+// [previous sample, that sample].  Rays of a tile finish at different steps: a finished ray rides along as an invalid probe with its state frozen.
 #include <type_traits>
 
 #include "idh_common.h"
@@ -81,7 +85,18 @@ struct KeysArgs : RayArgs {
     unsigned char *keyout;    // view_keys_search_k: the key of the last step (position in key_slots, 255 = none) or null; view_keys_k writes it to `flags`
 };
 
-enum { kSamples = 0, kSearch = 1, kView = 2, kViewSearch = 3, kViewKeys = 4, kViewKeysSearch = 5 };
+// view_march_k / view_keys_march_k: view_search_k's / view_keys_search_k's arguments without iters / lo / hi, plus the march.  Derived structs:
+// the six kernels above keep their argument blocks as they are.
+template <class Base>
+struct MarchArgsT : Base {
+    const float *march_depths;  // n_march samples shared by all rays: finite, positive, strictly increasing (the caller's precondition)
+    int n_march, refine;        // 1 <= n_march <= 255, refine >= 0
+    unsigned char *hit_step;    // the first sample that is behind, 255 = none, or null
+};
+using MarchArgs = MarchArgsT<RayArgs>;
+using KeysMarchArgs = MarchArgsT<KeysArgs>;
+
+enum { kSamples = 0, kSearch = 1, kView = 2, kViewSearch = 3, kViewKeys = 4, kViewKeysSearch = 5, kViewMarch = 6, kViewKeysMarch = 7, kRayModes = 8 };
 constexpr int kKeyCamFloats = 24;  // per (key, batch) in LDS: P = K cam_T_world (12), the prior camera's (12); then per batch rows 0-2 of the view's invK (12) and world_T_cam (12)
 constexpr int kViewMaxBatch = 128;  // 24 KiB of cameras next to at most 96 KiB of weights
 constexpr int kCamFloats = 48;  // per batch in LDS: P = K cam_T_world (12), the prior camera's (12), rows 0-2 of the view's invK (12) and world_T_cam (12)
@@ -94,10 +109,12 @@ constexpr int kW1LdsMaxBlocks = 4;   // Cf <= 64 -> W1f in LDS, as binary_mlp_k
 constexpr bool kViewSearchSkip = IDH_VIEW_SEARCH_SKIP;  // view_search_k: skip gather and MLP of a step at which no ray of the tile has a valid probe
 
 // kSamples: the S depth samples of `depth`; kSearch: `iters` dependent evaluations at the ray's current search depth; kView: one evaluation
-// per pixel of a depth map seen from another camera; kViewSearch: `iters` dependent kView evaluations along a ray of that other camera
+// per pixel of a depth map seen from another camera; kViewSearch: `iters` dependent kView evaluations along a ray of that other camera;
+// kViewMarch: at most n_march + refine dependent kView evaluations along such a ray, first the shared samples, then the bisection of the bracket
 template <int kMode, class Args = RayArgs>
 __device__ __forceinline__ void ray_body(const Args &a) {
-    constexpr bool kKeys = kMode == kViewKeys || kMode == kViewKeysSearch;
+    constexpr bool kKeys = kMode == kViewKeys || kMode == kViewKeysSearch || kMode == kViewKeysMarch;
+    constexpr bool kMarch = kMode == kViewMarch || kMode == kViewKeysMarch;
     constexpr bool kDense = kMode == kView || kMode == kViewKeys;  // one evaluation per pixel of a depth map
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int nthreads = blockDim.x, nwaves = nthreads >> 6;
@@ -134,7 +151,7 @@ __device__ __forceinline__ void ray_body(const Args &a) {
             const int b = t / 24, e = t - b * 24;
             s_view[t] = (e < 12 ? a.invK : a.wTc)[(size_t)b * 16 + (e < 12 ? e : e - 12)];
         }
-    } else if constexpr (kMode == kView || kMode == kViewSearch) {
+    } else if constexpr (kMode == kView || kMode == kViewSearch || kMode == kViewMarch) {
         // P = K cam_T_world of the keyframe (and of the prior camera), once per workgroup and batch: the fma loop of project_points_k
         for (int t = threadIdx.x; t < 2 * a.nb; t += nthreads) {
             const int b = t >> 1, pc = t & 1;
@@ -260,7 +277,7 @@ __device__ __forceinline__ void ray_body(const Args &a) {
             x = u;
             y = v;
         };
-        float vc[3] = {0.f, 0.f, 0.f};  // kViewSearch: the ray's direction invK (x, y, 1), once
+        float vc[3] = {0.f, 0.f, 0.f};  // kViewSearch / kViewMarch: the ray's direction invK (x, y, 1), once
         if constexpr (kMode == kSamples || kMode == kSearch) {
             x = a.rays[2 * src];
             y = a.rays[2 * src + 1];
@@ -382,7 +399,7 @@ __device__ __forceinline__ void ray_body(const Args &a) {
             t += __shfl_xor(t, 32, 64);
             return t + b3;
         };
-        if constexpr (kMode != kViewSearch && kMode != kViewKeysSearch) gather(!kDense || vvalid);  // an invalid pixel of a view reads no corner
+        if constexpr (kMode != kViewSearch && kMode != kViewKeysSearch && !kMarch) gather(!kDense || vvalid);  // an invalid pixel of a view reads no corner
         if constexpr (kDense) {
             const float logit = eval(vz, vprior);
             if (q == 0 && rok) {
@@ -442,6 +459,72 @@ __device__ __forceinline__ void ray_body(const Args &a) {
                     }
                 }
             }
+        } else if constexpr (kMarch) {
+            // ---- first hit along a ray of the view (include/idh.h): the samples march_depths[s] in turn until the first probe that is behind
+            // (logit < thr), then `refine` steps of the rule below inside [previous sample, that sample].  st: -1 marching, n > 0 refining with n steps
+            // left, 0 done.  A marching ray's sample index is the loop counter, so the sample is one scalar load per step; while marching "in front
+            // moves lo, behind moves hi" leaves exactly the bracket the refinement starts from.  A ray that is done rides along as an invalid probe:
+            // it reads nothing and its state is frozen ----
+            float lo = 0.f, hi = 0.f, sd = 0.f, logit = 0.f;
+            unsigned moved = 0;
+            int st = -1, hit = 255, lkey = 255;
+            const int steps = a.n_march + a.refine;
+            float Xc[3];
+#pragma unroll 1
+            for (int it = 0; it < steps; ++it) {
+                const bool active = st != 0;
+                if (!__any(active)) break;  // every ray of the tile is done (wave-uniform)
+                const float qm = a.march_depths[it < a.n_march ? it : a.n_march - 1];  // (it is wave-uniform)
+                sd = st < 0 ? qm : sd;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) Xc[i] = sd * vc[i];
+                probe(Xc, active);
+                float l = a.fill;
+                if (kViewSearchSkip ? __any(vvalid) : true) {  // no active ray of the tile has a valid probe at this step: no gather, no MLP (wave-uniform)
+                    gather(vvalid);
+                    const float e = eval(vz, vprior);
+                    l = vvalid ? e : a.fill;
+                }
+                float thr = a.thr_logit;
+                if (a.n_bins > 0) {
+                    int idx = 0;
+                    for (int e = 0; e < a.n_bins; ++e) idx += a.bins[e] < vz ? 1 : 0;
+                    thr = a.thr_logits[idx < a.n_bins ? idx : a.n_bins - 1];
+                }
+                const bool behind = l < thr, marching = st < 0;
+                // the state after this step, formed for every lane and taken by the active ones
+                const float nhi = behind ? sd : hi, nlo = behind ? lo : sd;
+                const bool bracket = marching && behind && it > 0;  // s* > 0: refine inside [march_depths[s* - 1], march_depths[s*]]
+                const int nst = marching ? (behind ? (it > 0 ? a.refine : 0) : (it == a.n_march - 1 ? 0 : -1)) : st - 1;
+                const float nsd = (bracket || !marching) ? (nhi + nlo) * 0.5f : sd;  // s* = 0 and "none" keep the sample itself
+                if (active) {
+                    logit = l;
+                    moved |= (behind ? 1u : 2u) | (vvalid ? 0u : 4u);
+                    hit = (marching && behind) ? it : hit;
+                    hi = nhi;
+                    lo = nlo;
+                    sd = nsd;
+                    st = nst;
+                    if constexpr (kKeys) lkey = vkey;
+                }
+            }
+            if (q == 0 && rok) {
+                a.sdepth[src] = sd;
+                a.out[src] = logit;
+                if (a.flags) a.flags[src] = (unsigned char)moved;
+                if (a.hit_step) a.hit_step[src] = (unsigned char)hit;
+                if constexpr (kKeys) {
+                    if (a.keyout) a.keyout[src] = (unsigned char)lkey;  // of the last evaluated probe
+                }
+                if (a.points) {  // the world point of the final depth, by the expressions of the probes
+                    const float *T = vcam + 12;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) Xc[i] = sd * vc[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        a.points[3 * src + i] = fmaf(T[4 * i], Xc[0], fmaf(T[4 * i + 1], Xc[1], fmaf(T[4 * i + 2], Xc[2], T[4 * i + 3])));
+                }
+            }
         } else {
             // ---- the same rule along a ray of the view: every step is a view_mlp_k pixel at rendered = sd; thr is keyed by the probe's keyframe z ----
             float lo = a.lo, hi = a.hi, sd = (a.hi - a.lo) * 0.5f, logit = 0.f;
@@ -495,6 +578,8 @@ __global__ __launch_bounds__(kRayMaxThreads) void view_mlp_k(const RayArgs a) { 
 __global__ __launch_bounds__(kRayMaxThreads) void view_search_k(const RayArgs a) { ray_body<kViewSearch>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void view_keys_k(const KeysArgs a) { ray_body<kViewKeys>(a); }
 __global__ __launch_bounds__(kRayMaxThreads) void view_keys_search_k(const KeysArgs a) { ray_body<kViewKeysSearch>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_march_k(const MarchArgs a) { ray_body<kViewMarch>(a); }
+__global__ __launch_bounds__(kRayMaxThreads) void view_keys_march_k(const KeysMarchArgs a) { ray_body<kViewKeysMarch>(a); }
 
 // ---- world points -> rays of the current view (+ the nearest sample of a prior prediction) ----
 // Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world, c = P[:3] X, depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
@@ -557,9 +642,10 @@ __global__ __launch_bounds__(256) void project_points_k(const float *__restrict_
 // per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.  The search (S = 1) has one item per tile: its iterations are
 // dependent, so there is nothing to split.
 // view_keys_k / view_keys_search_k (KeysArgs): the same tile partition, one item per tile, M (B + 1) x 24 floats of cameras in LDS.
+// view_march_k / view_keys_march_k (MarchArgs / KeysMarchArgs): as their search parents, S = 1 and so one item per tile.
 template <class Args>
 static int ray_mlp_launch(Args a, void *stream, int mode = kSamples) {
-    constexpr bool keys = std::is_same<Args, KeysArgs>::value;
+    constexpr bool keys = std::is_base_of<KeysArgs, Args>::value;
     constexpr int kSimds = 256 * 4, kMinChunk = 8;
     const long long tiles = ((long long)a.M + 15) / 16;
     int nchunk = 1;
@@ -578,12 +664,16 @@ static int ray_mlp_launch(Args a, void *stream, int mode = kSamples) {
     if (grid > 256) grid = 256;
     const int cblocks = (a.Cf + 15) >> 4;
     size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
-                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0) +
+                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch || mode == kViewMarch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0) +
                        (keys ? (size_t)a.nb * kKeyCamFloats * sizeof(float) : 0);
-    static IdhDeviceOnce attr_set[6];
+    static IdhDeviceOnce attr_set[kRayModes];
     void (*kernel)(const Args);
-    if constexpr (keys) {
-        lds += (size_t)a.nkeys * a.nb * kKeyCamFloats * sizeof(float);
+    if constexpr (keys) lds += (size_t)a.nkeys * a.nb * kKeyCamFloats * sizeof(float);
+    if constexpr (std::is_same<Args, KeysMarchArgs>::value) {
+        kernel = view_keys_march_k;
+    } else if constexpr (std::is_same<Args, MarchArgs>::value) {
+        kernel = view_march_k;
+    } else if constexpr (keys) {
         kernel = mode == kViewKeysSearch ? view_keys_search_k : view_keys_k;
     } else {
         kernel = mode == kViewSearch ? view_search_k : mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
@@ -804,6 +894,97 @@ extern "C" int idh_binary_mlp_view_keys_search_fwd(const float *feat_ring, int f
                                         rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
     k.keyout = key;
     return ray_mlp_launch(k, stream, kViewKeysSearch);
+}
+
+// First-hit depth along the rays of another camera: the samples march_depths[0 .. n_march-1] in turn until the first probe that is behind, then
+// `refine` steps of idh_binary_mlp_view_search_fwd's rule inside the bracket, in one launch (view_march_k).  include/idh.h states the rule.
+// The checks the two march entry points add to their search parents' (those apply without iters / lo / hi).
+static int march_args_ok(const float *march_depths, int n_march, int refine) {
+    if (n_march <= 0 || n_march > 255 || refine < 0 || !march_depths || (reinterpret_cast<uintptr_t>(march_depths) & 3)) return IDH_EINVAL;
+    if (refine > (1 << 30)) return IDH_EUNSUPPORTED;  // (n_march + refine stays an int)
+    return IDH_OK;
+}
+
+extern "C" int idh_binary_mlp_view_march_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, int h, int w, const float *rays_bn2,
+                                             int N, const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44,
+                                             const float *key_K_44, const float *prior_pred_b1hw, const float *prior_cam_T_world_44,
+                                             const float *prior_K_44, int has_prior, float prior_const, const float *w1f_packed,
+                                             const float *w2_packed, const float *vecs6x128, const float *march_depths, int n_march, int refine,
+                                             float threshold, const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
+                                             float *last_logits, unsigned char *flags, unsigned char *hit_step, float *points, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || n_bins < 0) return IDH_EINVAL;
+    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    if (const int rc = march_args_ok(march_depths, n_march, refine)) return rc;
+    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
+    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
+    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
+    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
+    if (!feat_nhwc || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth || !last_logits)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
+                          (const void *)prior_K_44, (const void *)bins, (const void *)thr_logits, (const void *)depth, (const void *)last_logits,
+                          (const void *)points})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, M = (long long)B * Nq;
+    if (Nq >= (1ll << 31) || M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
+    MarchArgs a{};
+    static_cast<RayArgs &>(a) = RayArgs{feat_nhwc, rays_bn2, nullptr, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)M, (int)Nq,
+                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
+                                        0, 0.f, 0.f, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
+                                        points, invK_44, world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, 1,
+                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
+    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
+    a.march_depths = march_depths;
+    a.n_march = n_march;
+    a.refine = refine;
+    a.hit_step = hit_step;
+    return ray_mlp_launch(a, stream, kViewMarch);
+}
+
+// The same against M remembered keyframes: every probe selects its own key, as in idh_binary_mlp_view_keys_search_fwd (view_keys_march_k).
+extern "C" int idh_binary_mlp_view_keys_march_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride,
+                                                  int n_slots, const int *key_slots, int M, int h, int w, const float *rays_bn2, int N,
+                                                  const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_s44,
+                                                  const float *key_K_s44, const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44,
+                                                  const float *prior_K_s44, int has_prior, float prior_const, const float *w1f_packed,
+                                                  const float *w2_packed, const float *vecs6x128, const float *march_depths, int n_march,
+                                                  int refine, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill,
+                                                  float *depth, float *last_logits, unsigned char *flags, unsigned char *hit_step, float *points,
+                                                  unsigned char *key, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || n_bins < 0) return IDH_EINVAL;
+    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    if (const int rc = march_args_ok(march_depths, n_march, refine)) return rc;
+    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
+    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
+    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
+    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
+    if (!feat_ring || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth ||
+        !last_logits)
+        return IDH_EINVAL;
+    for (const void *p : {(const void *)feat_ring, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
+                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
+                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)bins, (const void *)thr_logits,
+                          (const void *)depth, (const void *)last_logits, (const void *)points})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
+    KeysMarchArgs k{};
+    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
+    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, Mr = (long long)B * Nq;
+    if (Nq >= (1ll << 31) || Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
+    const int unaligned = k.feat_unaligned;
+    static_cast<RayArgs &>(k) = RayArgs{feat_ring, rays_bn2, nullptr, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)Mr, (int)Nq,
+                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
+                                        0, 0.f, 0.f, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
+                                        points, invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, 1,
+                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
+    k.keyout = key;
+    k.march_depths = march_depths;
+    k.n_march = n_march;
+    k.refine = refine;
+    k.hit_step = hit_step;
+    return ray_mlp_launch(k, stream, kViewKeysMarch);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

@@ -504,6 +504,180 @@ def view_keys_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, ke
     return depth, logits, flags[0], points, flags[1]
 
 
+MAX_MARCH_SAMPLES = 255  # idh_binary_mlp_view_march_fwd: hit_step is a byte, 255 = none
+
+
+def march_samples(n: int, lo: float = 0.5, hi: float = 8.0, spacing: str = "linear") -> torch.Tensor:
+    """``n`` march depths from ``lo`` to ``hi`` as a host fp32 tensor, every operation rounded to fp32: t_i = i / (n - 1);
+    "linear": lo + (hi - lo) * t_i; "inverse" (uniform in 1 / depth): 1 / (1 / lo + (1 / hi - 1 / lo) * t_i); the first and last samples are
+    ``lo`` and ``hi`` themselves, n = 1 gives [lo]."""
+    n = int(n)
+    if n < 1 or n > MAX_MARCH_SAMPLES:
+        raise _lib.IdhError(f"the march takes 1 to {MAX_MARCH_SAMPLES} samples, got {n}")
+    if spacing not in ("linear", "inverse"):
+        raise _lib.IdhError(f"spacing must be 'linear' or 'inverse', got {spacing!r}")
+    lo_t, hi_t = torch.tensor(float(lo), dtype=torch.float32), torch.tensor(float(hi), dtype=torch.float32)
+    if not (torch.isfinite(lo_t) and torch.isfinite(hi_t) and lo_t > 0 and (hi_t > lo_t or n == 1)):
+        raise _lib.IdhError(f"the march needs finite 0 < lo < hi, got lo = {lo}, hi = {hi}")
+    if n == 1:
+        return lo_t.reshape(1)
+    t = torch.arange(n, dtype=torch.float32) / torch.tensor(float(n - 1), dtype=torch.float32)
+    if spacing == "linear":
+        out = lo_t + (hi_t - lo_t) * t
+    else:
+        one = torch.tensor(1.0, dtype=torch.float32)
+        out = one / (one / lo_t + (one / hi_t - one / lo_t) * t)
+    out[0], out[-1] = lo_t, hi_t
+    return _checked_samples(out)
+
+
+def _checked_samples(host: torch.Tensor) -> torch.Tensor:
+    """The precondition the C entry points cannot check (they never read device memory): finite, positive, strictly increasing."""
+    if host.dim() != 1 or host.numel() < 1 or host.numel() > MAX_MARCH_SAMPLES:
+        raise _lib.IdhError(f"march samples must be a vector of 1 to {MAX_MARCH_SAMPLES} depths, got shape {tuple(host.shape)}")
+    if not bool(torch.isfinite(host).all()) or not bool((host > 0).all()) or not bool((host[1:] > host[:-1]).all()):
+        raise _lib.IdhError("march samples must be finite, positive and strictly increasing")
+    return host
+
+
+_march_cache: Dict[tuple, torch.Tensor] = {}
+_MARCH_CACHE_MAX = 16  # settings kept on the device; a caller sweeping lo / hi starts over instead of growing the table
+
+
+def _march_depths(samples, lo, hi, spacing, dev) -> torch.Tensor:
+    """The device vector of march depths: a caller's float32 tensor - validated through one host copy, i.e. one synchronisation per call -
+    or ``samples`` = an integer n, built by ``march_samples`` and kept per (n, lo, hi, spacing, device), so a per-frame caller uploads
+    nothing and never synchronises."""
+    if isinstance(samples, torch.Tensor):
+        if samples.dtype != torch.float32:
+            raise _lib.IdhError(f"march samples must be float32, got {samples.dtype}")
+        _checked_samples(samples.detach().cpu())
+        return samples.detach().to(dev).contiguous()
+    if isinstance(samples, bool) or not isinstance(samples, int):
+        raise _lib.IdhError(f"march samples must be a float32 tensor or an integer count, got {type(samples).__name__}")
+    key = (samples, float(lo), float(hi), spacing, str(dev))
+    t = _march_cache.get(key)
+    if t is None:
+        if len(_march_cache) >= _MARCH_CACHE_MAX:
+            _march_cache.clear()
+        t = _march_cache[key] = march_samples(samples, lo, hi, spacing).to(dev)
+    return t
+
+
+def view_march_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, key_cam_T_world_b44: torch.Tensor,
+                      key_K_s0_b44: torch.Tensor, size=None, rays: Optional[torch.Tensor] = None, prior=None, samples=16, lo: float = 0.5,
+                      hi: float = 8.0, spacing: str = "linear", refine: int = 8, threshold: float = 0.5, thresholder=None, fill: float = 0.0,
+                      return_points: bool = False):
+    """First-hit depth along the rays of another camera on ``idh_binary_mlp_view_march_fwd``: every ray probes the shared depths ``samples``
+    - a float32 vector (finite, positive, strictly increasing, at most 255), or an integer n with ``lo`` / ``hi`` / ``spacing`` ("linear" |
+    "inverse", ``march_samples``) - in turn until the first probe that is behind the surface (logit < threshold), then bisects ``refine``
+    steps inside [previous sample, that sample]; all in one launch.  Where ``view_depths`` assumes one crossing inside [lo, hi], this returns
+    the first one at the resolution of the samples.  Every probe is one ``view_logits`` pixel; the other arguments as ``view_depths``.
+    A probe outside the keyframe's view has the logit ``fill``: a negative ``fill`` makes it a hit, a positive one marches on.
+    Returns (depth (B,1,h,w) | (B,N), logits of each ray's last probe, flags uint8: 3 = bracketed, 1 = behind at the first sample (depth is
+    that sample), 2 = no hit (depth is the last sample), bit 2 = some evaluated probe was invalid, hit_step uint8: the first sample that was
+    behind, 255 = none, world points (...,3) | None)."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_march_fwd; set mlp_math = 'fp32'")
+    if (size is None) == (rays is None):
+        raise _lib.IdhError("view_march_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
+    if int(refine) < 0:
+        raise _lib.IdhError(f"refine must be >= 0, got {refine}")
+    pmap = prior if isinstance(prior, (tuple, list)) else None
+    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
+    _lib.require_cuda_f32(feat_view.buf, rays, *mats, pmap[0] if pmap is not None else None)
+    B, H, W = feat_view.N, feat_view.H, feat_view.W
+    for m in mats:
+        if m is None or tuple(m.shape) != (B, 4, 4):
+            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
+    if rays is not None:
+        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
+    else:
+        h, w = int(size[0]), int(size[1])
+        if h < 0 or w < 0:
+            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
+        N, shape = h * w, (B, 1, h, w)
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
+        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
+    dev = feat_view.buf.device
+    md = _march_depths(samples, lo, hi, spacing, dev)
+    bins, thr_logits = _thresholder_tables(thresholder, dev)
+    keep = [m.contiguous() for m in mats]  # alive until enqueued
+    r = rays.contiguous() if rays is not None else None
+    pp = pmap[0].contiguous() if pmap is not None else None
+    n = B * N
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
+    points = buf[2 * n:].view(*shape, 3) if return_points else None
+    flags = torch.empty((2,) + tuple(shape), device=dev, dtype=torch.uint8)
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_march_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, h, w, _lib.ptr(r), N if r is not None else 0,
+                                                 keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
+                                                 keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
+                                                 int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
+                                                 w2p.data_ptr(), vecs.data_ptr(), md.data_ptr(), md.numel(), int(refine), threshold, _lib.ptr(bins),
+                                                 _lib.ptr(thr_logits), 0 if bins is None else bins.numel(), float(fill), depth.data_ptr(),
+                                                 logits.data_ptr(), flags[0].data_ptr(), flags[1].data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
+        "idh_binary_mlp_view_march_fwd")
+    return depth, logits, flags[0], flags[1], points
+
+
+def view_keys_march_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor,
+                           key_cam_T_world_sb44: torch.Tensor, key_K_s0_sb44: torch.Tensor, size=None, rays: Optional[torch.Tensor] = None,
+                           prior=None, samples=16, lo: float = 0.5, hi: float = 8.0, spacing: str = "linear", refine: int = 8,
+                           threshold: float = 0.5, thresholder=None, fill: float = 0.0, return_points: bool = False):
+    """``view_march_depths`` against several remembered keyframes on ``idh_binary_mlp_view_keys_march_fwd``: the same march and refinement,
+    every probe one ``view_keys_logits`` pixel that selects its own key (the first of ``key_slots`` in which it is valid); flag bit 2: no key
+    was valid at some evaluated probe.  Ring arguments as ``view_keys_logits``, the others as ``view_march_depths``.  Returns (depth, logits
+    of the last probe, flags, hit_step, world points | None, key uint8: the position in ``key_slots`` of the key the ray's LAST evaluated
+    probe selected, 255 = none)."""
+    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_march_fwd", feat_ring, feat_c0, n_feat, key_slots,
+                                                              invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
+    if (size is None) == (rays is None):
+        raise _lib.IdhError("view_keys_march_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
+    if int(refine) < 0:
+        raise _lib.IdhError(f"refine must be >= 0, got {refine}")
+    _lib.require_cuda_f32(rays)
+    if rays is not None:
+        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
+    else:
+        h, w = int(size[0]), int(size[1])
+        if h < 0 or w < 0:
+            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
+        N, shape = h * w, (B, 1, h, w)
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
+    dev = feat_ring.device
+    md = _march_depths(samples, lo, hi, spacing, dev)
+    bins, thr_logits = _thresholder_tables(thresholder, dev)
+    r = rays.contiguous() if rays is not None else None
+    n = B * N
+    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
+    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
+    points = buf[2 * n:].view(*shape, 3) if return_points else None
+    flags = torch.empty((3,) + tuple(shape), device=dev, dtype=torch.uint8)
+    cs = feat_ring.shape[-1]
+    _lib.check(
+        _lib.lib().idh_binary_mlp_view_keys_march_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
+                                                      h, w, _lib.ptr(r), N if r is not None else 0, keep[0].data_ptr(), keep[1].data_ptr(),
+                                                      keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
+                                                      keep[4].data_ptr() if pp is not None else None,
+                                                      keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
+                                                      -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
+                                                      vecs.data_ptr(), md.data_ptr(), md.numel(), int(refine), threshold, _lib.ptr(bins),
+                                                      _lib.ptr(thr_logits), 0 if bins is None else bins.numel(), float(fill), depth.data_ptr(),
+                                                      logits.data_ptr(), flags[0].data_ptr(), flags[1].data_ptr(), _lib.ptr(points),
+                                                      flags[2].data_ptr(), _lib.stream_ptr()),
+        "idh_binary_mlp_view_keys_march_fwd")
+    return depth, logits, flags[0], flags[1], points, flags[2]
+
+
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:
     """``BinaryMLPNetwork.forward(list of (..., Cin) tensors, max_scale_only)`` (reference networks.py:106-115); row = [depth | features |
     (prior)].  fp32: the rows are read IN PLACE through ``idh_binary_mlp_strided_fwd`` whatever their strides - in particular the

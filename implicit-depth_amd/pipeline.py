@@ -312,6 +312,54 @@ class HotPath(nn.Module):
         return {"view_search_depths": depth, "view_search_logits": pred, "view_search_flags": flags, "view_search_points": points,
                 "view_search_key": key}
 
+    def query_view_first_hit(self, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, cam_T_world_b44: torch.Tensor, K_s0_b44: torch.Tensor,
+                             size: Optional[Sequence[int]] = None, rays: Optional[torch.Tensor] = None,
+                             prior_inputs: Optional[Dict[str, torch.Tensor]] = None, thresholder=None, samples=16, lo: float = 0.5,
+                             hi: float = 8.0, spacing: str = "linear", refine: int = 8, threshold: float = 0.5, fill: float = 0.0,
+                             return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """FIRST depth along the rays of ANOTHER camera at which the probe is behind the surface, against the LAST forward (valid as for
+        ``query_rays``): where ``query_view_depths`` bisects [lo, hi] and so assumes one crossing, every ray here probes the shared depths
+        ``samples`` (a float32 vector, or n with ``lo`` / ``hi`` / ``spacing``; ``mlp.march_samples``) in turn until its first hit and then
+        bisects ``refine`` steps inside the bracket, in one ``mlp.view_march_depths`` launch.  The other arguments as ``query_view_depths``.
+        Returns {"view_march_depths" (B,1,h,w) | (B,N), "view_march_logits": logits of each ray's last probe, "view_march_flags" uint8
+        (3 = bracketed; 1 = behind at the first sample; 2 = no hit, the depth is the last sample; bit 2: some evaluated probe was invalid),
+        "view_march_hit_step" uint8: the first sample that was behind, 255 = none, "view_march_points" (...,3) world points with
+        ``return_points``, else None}."""
+        from .mlp import view_march_depths
+
+        if (size is None) == (rays is None):
+            raise _lib.IdhError("query_view_first_hit takes exactly one of size=(h, w) and rays=(B,N,2)")
+        final = _last_final(self, invK_b44.shape[0], (0,))
+        _lib.require_cuda_f32(invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44, rays)
+        prior = None
+        if prior_inputs is not None and prior_inputs.get("prior_prediction") is not None:
+            prior = (prior_inputs["prior_prediction"], prior_inputs["prior_cam_T_world"], prior_inputs.get("K_s0_b44", K_s0_b44))
+        depth, pred, flags, step, points = view_march_depths(self.binary_mlp, final[0], invK_b44, world_T_cam_b44, cam_T_world_b44, K_s0_b44, size,
+                                                             rays, prior, samples, lo, hi, spacing, refine, threshold,
+                                                             self.thresholder if thresholder is None else thresholder, fill, return_points)
+        return {"view_march_depths": depth, "view_march_logits": pred, "view_march_flags": flags, "view_march_hit_step": step,
+                "view_march_points": points}
+
+    def query_view_first_hit_keys(self, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, size: Optional[Sequence[int]] = None,
+                                  rays: Optional[torch.Tensor] = None, order: Optional[Sequence[int]] = None, thresholder=None, samples=16,
+                                  lo: float = 0.5, hi: float = 8.0, spacing: str = "linear", refine: int = 8, threshold: float = 0.5,
+                                  fill: float = 0.0, return_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """``query_view_first_hit`` against the predictions kept by ``remember``: the same march, every probe asked in the first remembered
+        prediction (``order`` as ``query_view_keys``) whose camera sees it, in one ``mlp.view_keys_march_depths`` launch.  Returns
+        ``query_view_first_hit``'s dictionary - flag bit 2: no prediction saw some evaluated probe - plus "view_march_key": the position in
+        the order of the prediction the ray's LAST probe asked, 255 = none.  ``IdhError`` when nothing is remembered or when B differs."""
+        from .mlp import view_keys_march_depths
+
+        if (size is None) == (rays is None):
+            raise _lib.IdhError("query_view_first_hit_keys takes exactly one of size=(h, w) and rays=(B,N,2)")
+        ring, slots, prior = self._remembered(invK_b44.shape[0], order)
+        depth, pred, flags, step, points, key = view_keys_march_depths(self.binary_mlp, ring.feat, 0, ring.feat.shape[-1], slots, invK_b44,
+                                                                       world_T_cam_b44, ring.cam_T_world, ring.K, size, rays, prior, samples, lo, hi,
+                                                                       spacing, refine, threshold,
+                                                                       self.thresholder if thresholder is None else thresholder, fill, return_points)
+        return {"view_march_depths": depth, "view_march_logits": pred, "view_march_flags": flags, "view_march_hit_step": step,
+                "view_march_points": points, "view_march_key": key}
+
     def _plan(self, B, K, C, H, W, enc_shapes: Sequence[Sequence[int]], device, head: Optional[str] = None, head_ch: int = 0,
               images: Optional[torch.Tensor] = None, scales: int = nhwc.ALL_SCALES):
         """``scales``: bit i = the plan builds the decoder's output_i result (part of the plan key: the full plan is built on first demand).

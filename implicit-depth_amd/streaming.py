@@ -238,11 +238,13 @@ class StreamingSession:
         order = nearest_keys_first(T_host.double().numpy(), [self._ring_poses[s] for s in slots])
         return [slots[i] for i in order]
 
-    def _view_search(self, world_T_cam, invK: torch.Tensor, size, rays, thresholder, fill: float):
+    def _live_view(self, world_T_cam, invK: torch.Tensor, rays):
+        """What the ray queries in the live camera share: the checks, the pose on the device, ``invK`` with a batch axis, and either the
+        order of the remembered keys (``query_keyframes`` > 1) or the carried prior's inputs.  Returns (T (1,4,4), invK (1,4,4), order | None,
+        prior_inputs | None)."""
         if self._key is None:
             raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
         _lib.require_cuda_f32(invK, rays)
-        k = self._key
         T = torch.as_tensor(world_T_cam.detach().cpu().numpy() if isinstance(world_T_cam, torch.Tensor) else np.asarray(world_T_cam))
         if tuple(T.shape) != (4, 4):
             raise _lib.IdhError(f"world_T_cam {tuple(T.shape)} must be (4,4)")
@@ -251,12 +253,19 @@ class StreamingSession:
         if invK.dim() == 2:
             invK = invK[None]
         if self.query_keyframes > 1:
-            with torch.inference_mode():
-                return self.hot.query_view_depths_keys(invK, T, size=size, rays=rays, order=self._key_order(T_host), thresholder=thresholder, fill=fill,
-                                                       return_points=True)
+            return T, invK, self._key_order(T_host), None
         pi = None
         if self.use_prior and self._prior is not None:
             pi = {"prior_prediction": self._prior[0][:, :1], "prior_cam_T_world": self._prior[1]}
+        return T, invK, None, pi
+
+    def _view_search(self, world_T_cam, invK: torch.Tensor, size, rays, thresholder, fill: float):
+        T, invK, order, pi = self._live_view(world_T_cam, invK, rays)
+        k = self._key
+        if order is not None:
+            with torch.inference_mode():
+                return self.hot.query_view_depths_keys(invK, T, size=size, rays=rays, order=order, thresholder=thresholder, fill=fill,
+                                                       return_points=True)
         with torch.inference_mode():
             return self.hot.query_view_depths(invK, T, k["cam_T_world_b44"], k["K_s0_b44"], size=size, rays=rays, prior_inputs=pi,
                                               thresholder=thresholder, fill=fill, return_points=True)
@@ -278,6 +287,38 @@ class StreamingSession:
         "view_search_depths" (1,N) is the z-depth in the live camera, "view_search_points" (1,N,3) the WORLD hit points.  Unlike
         ``raycast``, the carried prior (``use_prior``) is sampled per probe: the probes move across the keyframe's image."""
         return self._view_search(world_T_cam, invK, None, rays, thresholder, fill)
+
+    def _view_march(self, world_T_cam, invK: torch.Tensor, size, rays, thresholder, fill: float, march: dict):
+        T, invK, order, pi = self._live_view(world_T_cam, invK, rays)
+        k = self._key
+        if order is not None:
+            with torch.inference_mode():
+                return self.hot.query_view_first_hit_keys(invK, T, size=size, rays=rays, order=order, thresholder=thresholder, fill=fill,
+                                                          return_points=True, **march)
+        with torch.inference_mode():
+            return self.hot.query_view_first_hit(invK, T, k["cam_T_world_b44"], k["K_s0_b44"], size=size, rays=rays, prior_inputs=pi,
+                                                 thresholder=thresholder, fill=fill, return_points=True, **march)
+
+    def first_hit_for_view(self, world_T_cam, invK: torch.Tensor, size: Sequence[int], thresholder=None, fill: float = 0.0, samples=16,
+                           lo: float = 0.5, hi: float = 8.0, spacing: str = "linear", refine: int = 8) -> Dict[str, Optional[torch.Tensor]]:
+        """``depth_for_view`` without its one-crossing assumption, also on the frames where ``step`` returned None: every pixel's ray of the
+        LIVE camera probes the shared depths ``samples`` (a float32 vector, or n with ``lo`` / ``hi`` / ``spacing``) in turn until the
+        first probe that is behind the surface and bisects ``refine`` steps inside that bracket (``HotPath.query_view_first_hit``, one
+        launch; with ``query_keyframes`` > 1 ``query_view_first_hit_keys`` against the remembered predictions, nearest pose first).  Where a
+        live ray enters the region hidden from the keyframe, leaves it and enters it again, ``depth_for_view`` may return either crossing;
+        this returns the first one, at the resolution of the samples.  Returns ``HotPath.query_view_first_hit``'s dictionary with
+        "view_march_points" (1,1,h,w,3) WORLD points; "view_march_flags" == 3 marks the bracketed pixels whose probes all fell inside the
+        keyframe's view, "view_march_hit_step" == 255 those without a hit."""
+        return self._view_march(world_T_cam, invK, tuple(size), None, thresholder, fill,
+                                dict(samples=samples, lo=lo, hi=hi, spacing=spacing, refine=refine))
+
+    def raycast_first_hit(self, rays: torch.Tensor, world_T_cam, invK: torch.Tensor, thresholder=None, fill: float = 0.0, samples=16,
+                          lo: float = 0.5, hi: float = 8.0, spacing: str = "linear", refine: int = 8) -> Dict[str, Optional[torch.Tensor]]:
+        """The hit test from the LIVE screen that returns the FIRST surface along the ray: ``first_hit_for_view`` at ``rays`` (1,N,2), (x, y)
+        in pixel-centre units of the camera at ``world_T_cam`` / ``invK`` as in ``raycast_view``.  "view_march_depths" (1,N) is the z-depth in
+        the live camera, "view_march_points" (1,N,3) the WORLD hit points."""
+        return self._view_march(world_T_cam, invK, None, rays, thresholder, fill,
+                                dict(samples=samples, lo=lo, hi=hi, spacing=spacing, refine=refine))
 
     def raycast(self, rays: torch.Tensor, thresholder=None) -> Dict[str, torch.Tensor]:
         """The hit test: where rays (1,N,2) - (x, y) in pixel-centre units of the keyframe's scale-0 map - meet the scene, against the LAST

@@ -438,6 +438,55 @@ int idh_binary_mlp_view_keys_search_fwd(const float *feat_ring, int feat_cs, int
                                         float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128, int iters,
                                         float lo, float hi, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill,
                                         float *depth, float *last_logits, unsigned char *flags, float *points, unsigned char *key, void *stream);
+/* First-hit depth in a moving camera, in one launch (view_march_k): the FIRST depth along a ray of the view at which the probe is behind the
+ * surface, where idh_binary_mlp_view_search_fwd assumes the one crossing that the reference's search (experiment_modules/bd_model.py:273-292)
+ * may assume along the rays of its own camera.  Along a ray of another camera the occlusion seen from the keyframe can be entered, left and
+ * entered again, and the ray can leave the keyframe's image part way: bisection then converges on whichever crossing its midpoints fall into.
+ * Rays (grid or list form), cameras, prior, network, thresholds and `fill` are idh_binary_mlp_view_search_fwd's; lo / hi / iters are replaced by
+ *   march_depths: DEVICE pointer to n_march fp32 samples shared by all rays, 1 <= n_march <= 255.  PRECONDITION, not checked (the host entry
+ *                 point cannot read them): finite, positive, strictly increasing
+ *   refine:       R >= 0 bisection steps inside the bracket
+ * A probe at the view's z-depth q IS one pixel of idh_binary_mlp_view_fwd on rendered = q: steps 1 - 3 of idh_binary_mlp_view_search_fwd (world
+ * point by BackprojectDepth, utils/geometry_utils.py:55-63; Project3D, :77-89; validity; nearest prior texel, bd_model.py:405-409; logit = `fill`
+ * at an invalid probe, which reads nothing; thr keyed by the probe's keyframe z), verbatim.  A probe is BEHIND when logit < thr, IN FRONT otherwise.
+ * Per ray:
+ *   march:  probe q_s = march_depths[s], s = 0, 1, ..., and stop at the first s* that is behind.
+ *           no s*:    depth = march_depths[n_march-1], flags = bit 1
+ *           s* == 0:  depth = march_depths[0], flags = bit 0, no refinement
+ *           else:     lo = q_{s*-1}, hi = q_{s*}, flags = bits 0 and 1
+ *   refine: R steps at the query (hi + lo) * 0.5f: behind -> hi = query, in front -> lo = query; depth = (hi + lo) * 0.5f after the last step
+ *           (bd_model.py:286-290) - with R == 0 the midpoint of the bracket
+ *   flag bit 2: some probe the ray EVALUATED was invalid.  Probes a ray never reaches do not exist: they set no flag and read no memory.
+ *   `fill` goes through `<`: a `fill` below every threshold makes "outside the keyframe's view" a hit; positive, +inf or NaN marches on.
+ * Outputs, (B,h,w) or (B,N): depth; last_logits = the logit of the ray's last evaluated probe; optional (NULL: not written) flags (uint8),
+ * hit_step (uint8: s*, 255 = none), points (...,3) = the world point of `depth` by the expressions of the probes.
+ * By construction the outputs carry the bits of at most n_march + R launches of idh_binary_mlp_view_fwd on per-ray maps rendered = q with the
+ * rule above applied in fp32 between them.  A 16-ray tile skips the gather and the MLP of a step at which none of its unfinished rays has a
+ * valid probe, and stops when all of its rays are finished.
+ * fp32 only.  IDH_EINVAL: the conditions of idh_binary_mlp_view_search_fwd that apply (all but those on iters, lo, hi), n_march <= 0 or > 255,
+ * refine < 0, a NULL or misaligned march_depths.  IDH_EUNSUPPORTED: the parent's limits.  B == 0 or an empty grid / list: IDH_OK, no launch.
+ * Everything is checked on the host before the device is touched. */
+int idh_binary_mlp_view_march_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, int h, int w, const float *rays_bn2, int N,
+                                  const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44, const float *key_K_44,
+                                  const float *prior_pred_b1hw, const float *prior_cam_T_world_44, const float *prior_K_44, int has_prior,
+                                  float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128,
+                                  const float *march_depths, int n_march, int refine, float threshold, const float *bins, const float *thr_logits,
+                                  int n_bins, float fill, float *depth, float *last_logits, unsigned char *flags, unsigned char *hit_step,
+                                  float *points, void *stream);
+/* First-hit depth in a moving camera against several remembered keyframes, in one launch (view_keys_march_k): idh_binary_mlp_view_march_fwd's
+ * rule with every probe one pixel of idh_binary_mlp_view_keys_fwd on rendered = q - every probe selects the first key in which it is valid,
+ * exactly as idh_binary_mlp_view_keys_search_fwd does (Project3D per key, utils/geometry_utils.py:77-89).  thr is keyed by z_sel, by z_0 (key
+ * key_slots[0]) when no key is valid; flag bit 2: no key was valid at some evaluated probe.  Outputs as idh_binary_mlp_view_march_fwd's plus
+ * optional key (uint8): the sel of the ray's last evaluated probe, 255 = none.
+ * IDH_EINVAL / IDH_EUNSUPPORTED: the conditions of both parents.  B == 0 or an empty grid / list: IDH_OK, no launch. */
+int idh_binary_mlp_view_keys_march_fwd(const float *feat_ring, int feat_cs, int Cf, int B, int H, int W, long long key_stride, int n_slots,
+                                       const int *key_slots, int M, int h, int w, const float *rays_bn2, int N, const float *invK_44,
+                                       const float *world_T_cam_44, const float *key_cam_T_world_s44, const float *key_K_s44,
+                                       const float *prior_pred_sb1hw, const float *prior_cam_T_world_s44, const float *prior_K_s44, int has_prior,
+                                       float prior_const, const float *w1f_packed, const float *w2_packed, const float *vecs6x128,
+                                       const float *march_depths, int n_march, int refine, float threshold, const float *bins,
+                                       const float *thr_logits, int n_bins, float fill, float *depth, float *last_logits, unsigned char *flags,
+                                       unsigned char *hit_step, float *points, unsigned char *key, void *stream);
 /* World points -> rays of a view, as Project3D (reference utils/geometry_utils.py:77-89): P = K cam_T_world (fma dots, m = 0..3),
  * c = P[:3] (X, 1) as fma(P0, X0, fma(P1, X1, fma(P2, X2, P3))), depth = max(c_z, 1e-5), (u, v) = c_xy / depth.
  *   points_bn3 (B,N,3); cam_T_world_44, K_44 (B,4,4), K at the resolution H x W the rays are to be in
