@@ -114,6 +114,31 @@ class Bank(C.Structure):
 
 BANK_MAX_SLOTS, BANK_MAX_VIEWS = 64, 1024  # IDH_BANK_MAX_*
 
+
+class NormalsArgs(C.Structure):
+    """ctypes mirror of ``idh_normals_args`` (include/idh_geometry.h, surface normals from depth)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_b1hw", C.c_void_p), ("invK_b44", C.c_void_p), ("world_R_cam_b33", C.c_void_p),
+                ("flags_b1hw", C.c_void_p), ("normals_b3hw", C.c_void_p), ("valid_b1hw", C.c_void_p), ("smoothing_std", C.c_float),
+                ("kernel_size", C.c_int32), ("orient", C.c_int32), ("need", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(NormalsArgs)
+
+
+class PatchNormalsArgs(C.Structure):
+    """ctypes mirror of ``idh_patch_normals_args`` (include/idh_geometry.h)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("points_bn93", C.c_void_p), ("cam_centre_b3", C.c_void_p), ("flags_bn9", C.c_void_p),
+                ("normals_bn3", C.c_void_p), ("valid_bn", C.c_void_p), ("orient", C.c_int32), ("need", C.c_int32), ("B", C.c_int32),
+                ("N", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PatchNormalsArgs)
+
+
 RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
@@ -253,6 +278,10 @@ _SIGS = {
                                                      C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int,
                                                      C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_int,
                                                      C.c_float, f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, C.c_void_p]),
+    "idh_sizeof_normals_args": (C.c_size_t, []),
+    "idh_sizeof_patch_normals_args": (C.c_size_t, []),
+    "idh_depth_normals_fwd": (C.c_int, [C.POINTER(NormalsArgs), C.c_void_p]),
+    "idh_patch_normals_fwd": (C.c_int, [C.POINTER(PatchNormalsArgs), C.c_void_p]),
     "idh_project_points_fwd": (C.c_int, [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, C.c_void_p]),
     "idh_cost_volume_dot_fwd": (
         C.c_int,
@@ -284,7 +313,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
@@ -299,7 +328,9 @@ def lib():
             raise IdhError(f"{LIB_PATH}: sizeof(idh_composite_args) = {h.idh_sizeof_composite_args()} in the library, {C.sizeof(CompositeArgs)} in this binding")
         for what, got, mirror in (("idh_ingest_color_args", h.idh_sizeof_ingest_color_args(), IngestColorArgs),
                                   ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs),
-                                  ("idh_bank", h.idh_sizeof_bank(), Bank)):
+                                  ("idh_bank", h.idh_sizeof_bank(), Bank),
+                                  ("idh_normals_args", h.idh_sizeof_normals_args(), NormalsArgs),
+                                  ("idh_patch_normals_args", h.idh_sizeof_patch_normals_args(), PatchNormalsArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

@@ -97,14 +97,27 @@ def _check_native_stem(model: nn.Module) -> None:
                             "pool_only=True) stem (backbone.stem_is_native_eligible)")
 
 
-def convert(model: nn.Module, math: str = None, native_matching_stem: bool = False) -> nn.Module:
+def convert_normal_generator(ref: nn.Module) -> nn.Module:
+    from .geometry import NormalGenerator
+
+    return NormalGenerator(ref.height, ref.width, ref.kernel_size, ref.std).to(_device(ref))
+
+
+def convert(model: nn.Module, math: str = None, native_matching_stem: bool = False, native_normals: bool = False) -> nn.Module:
     """In-place: replace ``cost_volume``, ``cost_volume_net``, ``depth_decoder`` and (BDModel)
     ``binary_mlp`` of a reference model.  Idempotent.  ``math``: None keeps the default (fp32 MFMA); "f16x3" selects the split-precision
     kernels for this model's convs (and, for "f16x3", its MLP feature volume and BinaryMLP).  ``native_matching_stem``: additionally check
     that the matching encoder's ResNet18 stem can run on the native kernels (``IdhError`` if not); its modules and state dict are left
-    as they are."""
+    as they are.  ``native_normals``: additionally replace ``compute_normals`` (DepthModel's ``NormalGenerator``, depth_model.py:191) by
+    ``geometry.NormalGenerator`` of the same height, width, kernel size and std, so that the reference's own ``step`` produces
+    ``normals_pred_b3hw`` / ``normals_b3hw`` on the fused kernel, without kornia; a model without that attribute is left as it is."""
     if native_matching_stem:
         _check_native_stem(model)
+    if native_normals and hasattr(model, "compute_normals"):
+        from .geometry import NormalGenerator
+
+        if not isinstance(model.compute_normals, NormalGenerator):
+            model.compute_normals = convert_normal_generator(model.compute_normals)
     if not isinstance(model.cost_volume, cv.CostVolumeManager):
         model.cost_volume = convert_cost_volume(model.cost_volume)
     if not isinstance(model.cost_volume_net, net.CVEncoder):

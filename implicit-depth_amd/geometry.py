@@ -4,9 +4,20 @@ The fused kernels do the back-projection / projection arithmetic themselves; the
 exist so that a drop-in ``CostVolumeManager`` exposes the same ``state_dict`` buffers as the
 reference (``backprojector.pix_coords_13N``, ``projector.eps`` — SURVEY.md §5 checkpoint
 row; reference utils/geometry_utils.py:22-89) and loads reference checkpoints unchanged.
+
+``NormalGenerator`` is not a stand-in: it is the reference's module (utils/geometry_utils.py:92-138) on one fused kernel
+(csrc/normals.hip, include/idh_geometry.h).  ``depth_normals`` is the same kernel with its options (rotation into world
+space, orientation towards the camera, a validity map from per-pixel flags); ``patch_normals`` the sparse form for 3x3 patches of points.
+There is no CPU fallback.
 """
+from typing import Optional, Tuple
+
 import torch
 from torch import nn
+
+from . import _lib
+
+KERNEL_SIZES = (1, 3, 5, 7)
 
 
 class BackprojectDepth(nn.Module):
@@ -22,3 +33,108 @@ class Project3D(nn.Module):
     def __init__(self, eps: float = 1e-5):
         super().__init__()
         self.register_buffer("eps", torch.tensor(eps).view(1, 1, 1))
+
+
+def _flags(name, t, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.IdhError(f"{name} must be a tensor on the MI355X (there is no CPU fallback)")
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+        raise _lib.IdhError(f"{name} must be uint8 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def depth_normals(depth_b1hw: torch.Tensor, invK_b44: torch.Tensor, *, kernel_size: int = 5, std: float = 2.0,
+                  world_R_cam: Optional[torch.Tensor] = None, orient: bool = False, flags: Optional[torch.Tensor] = None,
+                  need: int = 3) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Surface normals (B,3,H,W) of a depth map (B,1,H,W) as the reference's ``NormalGenerator.forward`` computes them
+    (utils/geometry_utils.py:121-138; contract: include/idh_geometry.h), in one launch.  ``invK_b44`` (B,4,4): only ``[:3,:3]`` is read.
+    With everything else at its default the result is the reference's, in camera space, pointing away from the camera on a fronto-parallel
+    plane.  ``world_R_cam`` (B,3,3) rotates the stored normal; ``orient`` negates it where it points away from the camera (``n . p > 0``);
+    ``flags`` uint8 (B,1,H,W) with ``need``: a pixel is valid iff every depth its normal read - a ``(2 (k // 2) + 3)^2`` footprint under
+    the border maps - has ``flags == need``, invalid pixels hold (0,0,0).  Returns ``(normals, valid)``: ``valid`` uint8 (B,1,H,W), or
+    None without ``flags``."""
+    _lib.require_cuda_f32(depth_b1hw, invK_b44, world_R_cam)
+    if depth_b1hw.dim() != 4 or depth_b1hw.shape[1] != 1:
+        raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} must be (B,1,H,W)")
+    B, _, H, W = depth_b1hw.shape
+    if tuple(invK_b44.shape) != (B, 4, 4):
+        raise _lib.IdhError(f"invK {tuple(invK_b44.shape)} must be ({B},4,4)")
+    if int(kernel_size) not in KERNEL_SIZES:
+        raise _lib.IdhError(f"kernel_size must be one of {KERNEL_SIZES}, got {kernel_size}")
+    depth, invK = depth_b1hw.contiguous(), invK_b44.contiguous()
+    keep = [depth, invK]
+    a = _lib.NormalsArgs()
+    a.depth_b1hw, a.invK_b44 = depth.data_ptr(), invK.data_ptr()
+    a.smoothing_std, a.kernel_size, a.orient, a.need = float(std), int(kernel_size), int(bool(orient)), int(need)
+    a.B, a.H, a.W = B, H, W
+    if world_R_cam is not None:
+        if tuple(world_R_cam.shape) != (B, 3, 3):
+            raise _lib.IdhError(f"world_R_cam {tuple(world_R_cam.shape)} must be ({B},3,3)")
+        rot = world_R_cam.contiguous()
+        keep.append(rot)
+        a.world_R_cam_b33 = rot.data_ptr()
+    out = torch.empty(B, 3, H, W, device=depth.device)
+    valid = None
+    if flags is not None:
+        f = _flags("flags", flags, (B, 1, H, W))
+        keep.append(f)
+        valid = torch.empty(B, 1, H, W, dtype=torch.uint8, device=depth.device)
+        a.flags_b1hw, a.valid_b1hw = f.data_ptr(), valid.data_ptr()
+    a.normals_b3hw = out.data_ptr()
+    if B == 0:  # nothing to launch (an empty tensor has no storage to point at)
+        return out, valid
+    _lib.check(_lib.lib().idh_depth_normals_fwd(a, _lib.stream_ptr()), "idh_depth_normals_fwd")
+    return out, valid
+
+
+def patch_normals(points_bn93: torch.Tensor, *, cam_centre: Optional[torch.Tensor] = None, orient: bool = False,
+                  flags: Optional[torch.Tensor] = None, need: int = 3) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Normals (B,N,3) at the centres of 3x3 patches of points (B,N,9,3), row-major: the reference's gradient, cross product and
+    normalisation (utils/geometry_utils.py:129-138) through the device function ``depth_normals`` uses.  ``orient`` negates a normal where
+    it points along ``centre point - cam_centre`` (``cam_centre`` (B,3), required then); ``flags`` uint8 (B,N,9) with ``need``: a query is
+    valid iff all nine flags equal ``need``, invalid ones hold (0,0,0).  Returns ``(normals, valid)``: ``valid`` uint8 (B,N), or None."""
+    _lib.require_cuda_f32(points_bn93, cam_centre)
+    if points_bn93.dim() != 4 or tuple(points_bn93.shape[2:]) != (9, 3):
+        raise _lib.IdhError(f"points {tuple(points_bn93.shape)} must be (B,N,9,3)")
+    B, N = points_bn93.shape[:2]
+    pts = points_bn93.contiguous()
+    keep = [pts]
+    a = _lib.PatchNormalsArgs()
+    a.points_bn93, a.orient, a.need, a.B, a.N = pts.data_ptr(), int(bool(orient)), int(need), B, N
+    if orient:
+        if cam_centre is None or tuple(cam_centre.shape) != (B, 3):
+            raise _lib.IdhError(f"orient needs cam_centre ({B},3)")
+        cc = cam_centre.contiguous()
+        keep.append(cc)
+        a.cam_centre_b3 = cc.data_ptr()
+    out = torch.empty(B, N, 3, device=pts.device)
+    valid = None
+    if flags is not None:
+        f = _flags("flags", flags, (B, N, 9))
+        keep.append(f)
+        valid = torch.empty(B, N, dtype=torch.uint8, device=pts.device)
+        a.flags_bn9, a.valid_bn = f.data_ptr(), valid.data_ptr()
+    a.normals_bn3 = out.data_ptr()
+    if B == 0 or N == 0:
+        return out, valid
+    _lib.check(_lib.lib().idh_patch_normals_fwd(a, _lib.stream_ptr()), "idh_patch_normals_fwd")
+    return out, valid
+
+
+class NormalGenerator(nn.Module):
+    """The reference's ``NormalGenerator`` (utils/geometry_utils.py:92-138): same constructor, same ``backproject.pix_coords_13N`` buffer
+    in the state dict, ``forward(depth_b1hw, invK_b44) -> (B,3,H,W)`` - on the fused kernel, without kornia."""
+
+    def __init__(self, height: int, width: int, smoothing_kernel_size: int = 5, smoothing_kernel_std: float = 2.0):
+        super().__init__()
+        if int(smoothing_kernel_size) not in KERNEL_SIZES:
+            raise _lib.IdhError(f"smoothing_kernel_size must be one of {KERNEL_SIZES}, got {smoothing_kernel_size}")
+        self.height, self.width = int(height), int(width)
+        self.backproject = BackprojectDepth(self.height, self.width)
+        self.kernel_size, self.std = int(smoothing_kernel_size), float(smoothing_kernel_std)
+
+    def forward(self, depth_b1hw: torch.Tensor, invK_b44: torch.Tensor) -> torch.Tensor:
+        _lib.require_cuda_f32(depth_b1hw, invK_b44)
+        if tuple(depth_b1hw.shape[-2:]) != (self.height, self.width):
+            raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} must be (B,1,{self.height},{self.width})")
+        return depth_normals(depth_b1hw, invK_b44, kernel_size=self.kernel_size, std=self.std)[0]

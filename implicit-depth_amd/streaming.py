@@ -40,6 +40,14 @@ def nearest_keys_first(live_world_T_cam, key_poses_newest_first) -> list:
     return sorted(range(len(dist)), key=lambda i: (dist[i], i))
 
 
+def patch_rays(rays: torch.Tensor, step: float = 1.0) -> torch.Tensor:
+    """(B,9N,2): every ray (x, y) of ``rays`` (B,N,2) with its eight neighbours ``step`` pixels apart, patch-major; inside a patch row-major
+    (y - step first, x - step first), so index 4 is the ray itself - exactly: its offset is 0."""
+    o = torch.tensor([-1.0, 0.0, 1.0], device=rays.device, dtype=rays.dtype) * float(step)
+    off = torch.stack([o.repeat(3), o.repeat_interleave(3)], -1)  # (9,2): x runs fastest
+    return (rays[:, :, None, :] + off).reshape(rays.shape[0], -1, 2)
+
+
 class StreamingSession:
     """``model``: a reference ``BDModel`` / ``DepthModel`` (converted in place by ``dropin.hot_path_of``; its ``encoder`` is the image
     encoder) or a ``HotPath`` with a ``matching_model`` (then pass ``image_encoder``).  The matching encoder's stem must be eligible for
@@ -319,6 +327,52 @@ class StreamingSession:
         the live camera, "view_march_points" (1,N,3) the WORLD hit points."""
         return self._view_march(world_T_cam, invK, None, rays, thresholder, fill,
                                 dict(samples=samples, lo=lo, hi=hi, spacing=spacing, refine=refine))
+
+    def normals_for_view(self, world_T_cam, invK: torch.Tensor, size: Sequence[int], thresholder=None, fill: float = 0.0,
+                         smoothing_kernel_size: int = 5, smoothing_kernel_std: float = 2.0,
+                         first_hit: Optional[dict] = None) -> Dict[str, Optional[torch.Tensor]]:
+        """The orientation of the surface in the LIVE camera, also on the frames where ``step`` returned None: ``depth_for_view`` - or, with
+        ``first_hit`` a dictionary of ``first_hit_for_view``'s march arguments (``samples``, ``lo``, ``hi``, ``spacing``, ``refine``; ``{}`` for
+        its defaults), that search - followed by ``geometry.depth_normals`` on its depth map with the search's flags (``need = 3``: a normal
+        is valid iff every depth in its footprint is a trustworthy one, so ``fill`` never enters a valid normal), the rotation of
+        ``world_T_cam`` and ``orient=True``.  Returns the search's dictionary plus "view_normals" (1,3,h,w): unit normals in WORLD space that
+        face the live camera, (0,0,0) where "view_normals_valid" (1,1,h,w) uint8 is 0.  ``smoothing_kernel_size`` in {1,3,5,7} and
+        ``smoothing_kernel_std`` are the reference ``NormalGenerator``'s (utils/geometry_utils.py:92-138)."""
+        from .geometry import depth_normals
+
+        if first_hit is None:
+            out, pre = self.depth_for_view(world_T_cam, invK, size, thresholder, fill), "view_search"
+        else:
+            out, pre = self.first_hit_for_view(world_T_cam, invK, size, thresholder, fill, **first_hit), "view_march"
+        T, invK, _, _ = self._live_view(world_T_cam, invK, None)
+        with torch.inference_mode():
+            normals, valid = depth_normals(out[pre + "_depths"], invK, kernel_size=smoothing_kernel_size, std=smoothing_kernel_std,
+                                           world_R_cam=T[:, :3, :3], orient=True, flags=out[pre + "_flags"], need=3)
+        out["view_normals"], out["view_normals_valid"] = normals, valid
+        return out
+
+    def raycast_view_normals(self, rays: torch.Tensor, world_T_cam, invK: torch.Tensor, step: float = 1.0, thresholder=None,
+                             fill: float = 0.0) -> Dict[str, Optional[torch.Tensor]]:
+        """The hit test from the LIVE screen with the orientation of the surface at the hit: every ray of ``rays`` (1,N,2) becomes a 3x3
+        patch of rays ``step`` pixels apart (``patch_rays``: (1,9N,2), patch-major, row-major inside a patch), ONE ``raycast_view`` launch
+        answers all of them, and ``geometry.patch_normals`` turns each patch's nine WORLD points and flags into "view_normals" (1,N,3) -
+        facing the live camera - and "view_normals_valid" (1,N) uint8 (all nine rays bracketed, flags == 3; else (0,0,0)).  The other
+        entries are ``raycast_view``'s for the centre rays, sliced out of the 9N answers.  Building an anchor pose from point and normal is
+        the caller's."""
+        from .geometry import patch_normals
+
+        _lib.require_cuda_f32(rays)
+        if rays.dim() != 3 or rays.shape[0] != 1 or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays {tuple(rays.shape)} must be (1,N,2)")
+        N = rays.shape[1]
+        res = self._view_search(world_T_cam, invK, None, patch_rays(rays, step), thresholder, fill)
+        T, _, _, _ = self._live_view(world_T_cam, invK, rays)
+        with torch.inference_mode():
+            normals, valid = patch_normals(res["view_search_points"].view(1, N, 9, 3), cam_centre=T[:, :3, 3], orient=True,
+                                           flags=res["view_search_flags"].view(1, N, 9), need=3)
+        out = {k: (v if v is None else v.view(1, N, 9, *v.shape[2:])[:, :, 4].contiguous()) for k, v in res.items()}
+        out["view_normals"], out["view_normals_valid"] = normals, valid
+        return out
 
     def raycast(self, rays: torch.Tensor, thresholder=None) -> Dict[str, torch.Tensor]:
         """The hit test: where rays (1,N,2) - (x, y) in pixel-centre units of the keyframe's scale-0 map - meet the scene, against the LAST
