@@ -139,6 +139,22 @@ class PatchNormalsArgs(C.Structure):
         self.struct_size = C.sizeof(PatchNormalsArgs)
 
 
+class RasterShadedArgs(C.Structure):
+    """ctypes mirror of ``idh_raster_shaded_args`` (include/idh_raster.h, shaded mesh render)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("verts_v3", C.c_void_p), ("faces_f3", C.c_void_p), ("cam_T_world_b44", C.c_void_p), ("K_b44", C.c_void_p),
+                ("colors_v4", C.c_void_p), ("attrs_vc", C.c_void_p), ("depth_b1hw", C.c_void_p), ("pix_to_face_bhw", C.c_void_p),
+                ("bary_bhw3", C.c_void_p), ("attr_out_bhwc", C.c_void_p), ("rgba_bhw4", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("ambient", C.c_float), ("empty_depth", C.c_float), ("V", C.c_int32), ("F", C.c_int32),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(RasterShadedArgs)
+
+
+RASTER_MAX_ATTRS = 16  # channels of idh_raster_shaded_args.attrs_vc
+
 RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
@@ -241,6 +257,9 @@ _SIGS = {
     "idh_raster_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_void_p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "idh_vertex_predictions_fwd": (C.c_int, [f32p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, C.c_void_p]),
     "idh_vertex_occlusion_changes_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "idh_sizeof_raster_shaded_args": (C.c_size_t, []),
+    "idh_raster_shaded_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "idh_raster_shaded_fwd": (C.c_int, [C.POINTER(RasterShadedArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -313,7 +332,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
@@ -330,7 +349,8 @@ def lib():
                                   ("idh_ingest_depth_args", h.idh_sizeof_ingest_depth_args(), IngestDepthArgs),
                                   ("idh_bank", h.idh_sizeof_bank(), Bank),
                                   ("idh_normals_args", h.idh_sizeof_normals_args(), NormalsArgs),
-                                  ("idh_patch_normals_args", h.idh_sizeof_patch_normals_args(), PatchNormalsArgs)):
+                                  ("idh_patch_normals_args", h.idh_sizeof_patch_normals_args(), PatchNormalsArgs),
+                                  ("idh_raster_shaded_args", h.idh_sizeof_raster_shaded_args(), RasterShadedArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

@@ -4,10 +4,14 @@
 ``MeshDepthRasterizer`` renders the query plane of a ``temporal_eval`` window (test_bd.py:172-181) and the scene's ground-truth mesh
 (:362), and samples a prediction at every projected ground-truth vertex (:360-388).  ``load_ply`` reads the mesh.  Semantics of the render:
 include/idh_raster.h and DESIGN.md §4.8 — pixel (i, j) looks along the ray through (j + 0.5, i + 0.5), the nearest z > 0 wins, -1 where
-nothing is hit, triangles crossing z = 0 are drawn for their part in front of the camera."""
+nothing is hit, triangles crossing z = 0 are drawn for their part in front of the camera.
+
+``render_shaded`` / ``AssetRenderer`` (csrc/raster_shade.hip) render an asset for the live AR loop with the same geometry:
+the same depth bit for bit, plus lit RGBA from vertex colours, the visible face, its barycentrics and interpolated per-vertex attributes."""
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -29,11 +33,13 @@ def _ply_type(name, path):
         raise ValueError(f"{path}: unknown PLY property type {name!r}") from None
 
 
-def load_ply(path) -> Tuple[torch.Tensor, torch.Tensor]:
+def load_ply(path, return_colors: bool = False):
     """(verts float32 (V,3), faces int64 (F,3)) of an ASCII or binary-little-endian PLY file, as pytorch3d.io.load_ply returns them
-    (binary_metrics_utils.py:299).  Extra vertex properties (ScanNet meshes carry uchar colours), scalar properties beside the face
-    list (e.g. ``uchar flags``) and extra scalar-only elements are skipped; the face list may have any integer count and index type.
-    Triangles only.  Not supported (ValueError): big-endian files, list properties outside the face element, more than one list per face."""
+    (binary_metrics_utils.py:299).  Extra vertex properties, scalar properties beside the face list (e.g. ``uchar flags``) and extra
+    scalar-only elements are skipped; the face list may have any integer count and index type.  With ``return_colors`` a third value
+    follows: the vertices' ``red``, ``green``, ``blue`` and ``alpha`` (255 when the file has none) as uint8 (V,4), as ScanNet meshes
+    carry them and ``render_shaded`` takes them, or None when the file has no colours.  Triangles only.  Not supported (ValueError):
+    big-endian files, list properties outside the face element, more than one list per face, colours that are not uchar."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -60,7 +66,7 @@ def load_ply(path) -> Tuple[torch.Tensor, torch.Tensor]:
         raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii and binary_little_endian are)")
     tokens = data[body:].split() if fmt == "ascii" else None
     at = 0 if fmt == "ascii" else body
-    verts = faces = None
+    verts = faces = colors = None
     for name, count, props in elements:
         lists = [p for p in props if len(p) == 3]
         if lists and (name != "face" or len(lists) > 1):
@@ -104,6 +110,13 @@ def load_ply(path) -> Tuple[torch.Tensor, torch.Tensor]:
             if not all(k in cols for k in "xyz"):
                 raise ValueError(f"{path}: vertex element without x, y, z")
             verts = np.stack([np.asarray(cols[k], dtype=np.float32) for k in "xyz"], 1)
+            if return_colors and all(k in cols for k in ("red", "green", "blue")):
+                names = ("red", "green", "blue") + (("alpha",) if "alpha" in cols else ())
+                if any(t != "u1" for n, t in (q for q in props if len(q) == 2) if n in names):
+                    raise ValueError(f"{path}: vertex colours must be uchar")
+                colors = np.full((count, 4), 255, np.uint8)
+                for j, k in enumerate(names):
+                    colors[:, j] = np.asarray(cols[k]).astype(np.uint8)
         elif name == "face" and lists:
             if (np.asarray(cols["#n"]) != 3).any():
                 raise ValueError(f"{path}: only triangle faces are supported")
@@ -114,7 +127,10 @@ def load_ply(path) -> Tuple[torch.Tensor, torch.Tensor]:
         faces = np.zeros((0, 3), np.int64)
     if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
         raise ValueError(f"{path}: face index outside the {len(verts)} vertices")
-    return torch.from_numpy(np.ascontiguousarray(verts)), torch.from_numpy(np.ascontiguousarray(faces))
+    pair = torch.from_numpy(np.ascontiguousarray(verts)), torch.from_numpy(np.ascontiguousarray(faces))
+    if return_colors:
+        return pair + (None if colors is None else torch.from_numpy(colors),)
+    return pair
 
 
 def plane_faces(size: int = PLANE_SIZE) -> torch.Tensor:
@@ -163,6 +179,107 @@ def render_depth(verts, faces, cam_T_world_b44, K_b44, height, width) -> torch.T
     _lib.check(_lib.lib().idh_raster_depth_fwd(_lib.ptr(v) if V else None, V, _lib.ptr(f32) if F else None, F, T.data_ptr(), K.data_ptr(), B,
                                                height, width, out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr()), "idh_raster_depth_fwd")
     return out
+
+
+def render_shaded(verts, faces, cam_T_world_b44, K_b44, height, width, *, colors=None, attrs=None, ambient: float = 0.3,
+                  empty_depth: float = -1.0, return_faces: bool = False, return_bary: bool = False) -> Dict[str, torch.Tensor]:
+    """The mesh in B cameras with everything a compositor or a user's own shader needs, in one call (idh_raster_shaded_fwd, DESIGN.md
+    §4.19).  ``verts`` (V,3) float32 and ``faces`` (F,3) integer as for ``render_depth`` (int32 faces are used as they are).  Returns
+
+    * ``"depth"`` (B,1,height,width): ``render_depth``'s values bit for bit, ``empty_depth`` where nothing is hit;
+    * ``"rgba"`` (B,height,width,4) uint8 when ``colors`` (V,4) uint8 is given: the vertex colours interpolated over the visible face
+      and lit by a headlight at the camera on the face's own normal (``ambient`` in [0, 1]; 1 = unlit), alpha interpolated and 0 where
+      nothing is hit: ``compositing.composite_mask(..., virtual_rgba=...)`` takes it as it is;
+    * ``"attrs"`` (B,height,width,C) when ``attrs`` (V,C) float32, 1 <= C <= 16, is given: the user's own per-vertex quantities
+      (normals, UVs, labels) interpolated perspective-correctly, zeros where nothing is hit;
+    * ``"pix_to_face"`` (B,height,width) int32, -1 where nothing is hit (``return_faces``), and ``"bary"`` (B,height,width,3), the
+      barycentric weights of the face's three vertices at the hit point (``return_bary``).
+
+    Among faces at exactly the same depth the lowest index wins; two calls return the same bits.  There is no CPU fallback."""
+    _lib.require_cuda_f32(verts, cam_T_world_b44, K_b44, attrs)
+    if cam_T_world_b44.dim() != 3 or tuple(cam_T_world_b44.shape[1:]) != (4, 4) or tuple(K_b44.shape) != tuple(cam_T_world_b44.shape):
+        raise _lib.IdhError(f"render_shaded: cam_T_world {tuple(cam_T_world_b44.shape)} and K {tuple(K_b44.shape)} must both be (B,4,4)")
+    if not faces.is_cuda:
+        raise _lib.IdhError("render_shaded: faces must be on the GPU; there is no CPU fallback")
+    B, V, F = cam_T_world_b44.shape[0], verts.shape[0], faces.shape[0]
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point:
+        raise _lib.IdhError(f"render_shaded: vertices {tuple(verts.shape)} must be (V,3) and faces {tuple(faces.shape)} (F,3) integers")
+    if colors is not None and (not colors.is_cuda or colors.dtype != torch.uint8 or tuple(colors.shape) != (V, 4)):
+        raise _lib.IdhError(f"render_shaded: colors must be a uint8 ({V},4) tensor on the GPU (got {colors.dtype} {tuple(colors.shape)} on {colors.device})")
+    if attrs is not None and (attrs.dim() != 2 or attrs.shape[0] != V or not 1 <= attrs.shape[1] <= _lib.RASTER_MAX_ATTRS):
+        raise _lib.IdhError(f"render_shaded: attrs {tuple(attrs.shape)} must be ({V},C) with 1 <= C <= {_lib.RASTER_MAX_ATTRS}")
+    dev = verts.device
+    f32 = faces.to(torch.int32).contiguous()  # no copy when they already are
+    v, T, K = verts.contiguous(), cam_T_world_b44.contiguous(), K_b44.contiguous()
+    col = None if colors is None else colors.contiguous()
+    att = None if attrs is None else attrs.contiguous()
+    C_ = 0 if att is None else att.shape[1]
+    out = {"depth": torch.empty(B, 1, height, width, device=dev)}
+    if col is not None:
+        out["rgba"] = torch.empty(B, height, width, 4, device=dev, dtype=torch.uint8)
+    if att is not None:
+        out["attrs"] = torch.empty(B, height, width, C_, device=dev)
+    if return_faces:
+        out["pix_to_face"] = torch.empty(B, height, width, device=dev, dtype=torch.int32)
+    if return_bary:
+        out["bary"] = torch.empty(B, height, width, 3, device=dev)
+    L = _lib.lib()
+    nbytes = L.idh_raster_shaded_workspace_bytes(B, V, F, height, width)
+    ws = torch.empty(max(nbytes, 256), device=dev, dtype=torch.uint8)
+    a = _lib.RasterShadedArgs()
+    a.verts_v3, a.faces_f3 = (_lib.ptr(v) if V else None), (_lib.ptr(f32) if F else None)
+    a.cam_T_world_b44, a.K_b44, a.colors_v4, a.attrs_vc = T.data_ptr(), K.data_ptr(), _lib.ptr(col), _lib.ptr(att)
+    a.depth_b1hw, a.pix_to_face_bhw, a.bary_bhw3 = out["depth"].data_ptr(), _lib.ptr(out.get("pix_to_face")), _lib.ptr(out.get("bary"))
+    a.attr_out_bhwc, a.rgba_bhw4 = _lib.ptr(out.get("attrs")), _lib.ptr(out.get("rgba"))
+    a.workspace, a.workspace_bytes, a.ambient, a.empty_depth = ws.data_ptr(), nbytes, float(ambient), float(empty_depth)
+    a.V, a.F, a.B, a.H, a.W, a.C = V, F, B, int(height), int(width), C_
+    _lib.check(L.idh_raster_shaded_fwd(C.byref(a), _lib.stream_ptr()), "idh_raster_shaded_fwd")
+    return out
+
+
+def _pose_f64(name, T) -> np.ndarray:
+    T = np.asarray(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise _lib.IdhError(f"{name} {T.shape} must be (4,4)")
+    return T
+
+
+class AssetRenderer:
+    """A virtual asset kept on the GPU and rendered into a moving camera: the producer of the ``asset_depth`` / ``asset_rgba`` pair of
+    the live AR loop, which the reference reads from files rendered off line.  ``verts`` (V,3) in the asset's own
+    frame, ``faces`` (F,3) (their int32 copy is made once), ``colors`` (V,4) uint8 or None (then only depth is rendered).
+    ``world_T_asset`` places the asset in the world (default: identity); ``place`` moves it - e.g. onto the hit point of
+    ``StreamingSession.raycast_view``.  The vertices are never rewritten: every render forms
+    ``cam_T_mesh = float32(inv(world_T_cam) @ world_T_asset)`` in float64 on the host."""
+
+    def __init__(self, verts, faces, colors=None, world_T_asset=None, ambient: float = 0.3, device="cuda"):
+        self.verts, faces = _mesh(verts, faces, device)
+        self.faces = faces.to(torch.int32)
+        self.colors = None if colors is None else torch.as_tensor(colors).to(device=self.verts.device).contiguous()
+        if self.colors is not None and (self.colors.dtype != torch.uint8 or tuple(self.colors.shape) != (self.verts.shape[0], 4)):
+            raise _lib.IdhError(f"AssetRenderer: colors must be uint8 ({self.verts.shape[0]},4), got {self.colors.dtype} {tuple(self.colors.shape)}")
+        self.ambient = float(ambient)
+        self.world_T_asset = np.eye(4)
+        if world_T_asset is not None:
+            self.place(world_T_asset)
+
+    def place(self, world_T_asset) -> None:
+        """Move the asset: ``world_T_asset`` is a (4,4) array or tensor."""
+        self.world_T_asset = _pose_f64("world_T_asset", world_T_asset)
+
+    def cam_T_mesh(self, world_T_cam) -> torch.Tensor:
+        """(1,4,4) float32 on the asset's device: the asset's frame to the camera at ``world_T_cam``, formed in float64."""
+        T = np.linalg.inv(_pose_f64("world_T_cam", world_T_cam)) @ self.world_T_asset
+        return torch.from_numpy(T.astype(np.float32))[None].to(self.verts.device)
+
+    def render(self, world_T_cam, K, size, empty_depth: float = -1.0, **kw) -> Dict[str, torch.Tensor]:
+        """``render_shaded`` of the asset in the one camera at ``world_T_cam`` ((4,4) array or tensor) with intrinsics ``K`` ((4,4) or
+        (1,4,4), at ``size`` = (height, width)).  Keyword arguments (``attrs``, ``return_faces``, ``return_bary``) are passed on."""
+        K = torch.as_tensor(K).to(device=self.verts.device, dtype=torch.float32)
+        if K.dim() == 2:
+            K = K[None]
+        return render_shaded(self.verts, self.faces, self.cam_T_mesh(world_T_cam), K, int(size[0]), int(size[1]), colors=self.colors,
+                             ambient=self.ambient, empty_depth=empty_depth, **kw)
 
 
 def vertex_predictions(verts, cam_T_world_b44, K_b44, pred_11hw, depth_11hw, tolerance=DEPTH_TOLERANCE) -> torch.Tensor:

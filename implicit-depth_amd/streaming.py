@@ -240,6 +240,39 @@ class StreamingSession:
         with torch.inference_mode():
             return self.hot.query_view(rendered_depth, invK, T, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi, fill=fill)
 
+    def composite_asset(self, image_u8: torch.Tensor, asset, world_T_cam, K: torch.Tensor, *, query_size: Sequence[int] = None,
+                        fill: float = -20.0, fade=None, bgr: bool = False, return_parts: bool = False):
+        """The whole live frame, also on the frames where ``step`` returned None: the camera image ``image_u8`` (1,H,W,3) uint8 with
+        ``asset`` - a ``raster.AssetRenderer`` - drawn into it at the live pose ``world_T_cam`` ((4,4) array or tensor), hidden where
+        the scene is in front of it.  ``K`` ((4,4) or (1,4,4)) is the live camera's intrinsics at the image's H x W.  The asset is rendered
+        once at ``query_size`` (default ``compositing.MODEL_SIZE``) for its depth - with the first two rows of ``K`` scaled by w / W and
+        h / H, which is exact under the half-integer pixel centres the rasteriser and the view query share - and once at H x W for its
+        RGBA; then ``occlusion_for_view(depth, world_T_cam, inv(K_query), fill)`` and
+        ``compositing.composite_mask(image_u8, view_pred, virtual_rgba=rgba, fade=fade, bgr=bgr)``.  ``fill`` is the logit of the pixels
+        the keyframe cannot answer (-20: the asset stays visible there).  Returns the (1,H,W,3) uint8 frame; with ``return_parts`` a
+        dictionary with "frame", "asset_depth" (1,1,h,w; -1 where the asset is not), "asset_rgba" (1,H,W,4) and the view query's entries."""
+        from . import compositing
+
+        if self._key is None:
+            raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dim() != 4 or image_u8.shape[0] != 1 or image_u8.shape[-1] != 3:
+            raise _lib.IdhError("composite_asset: image_u8 must be one (1,H,W,3) uint8 frame on the GPU")
+        if getattr(asset, "colors", None) is None:
+            raise _lib.IdhError("composite_asset: the asset has no vertex colours (AssetRenderer(colors=...))")
+        H, W = int(image_u8.shape[1]), int(image_u8.shape[2])
+        h, w = (int(s) for s in (compositing.MODEL_SIZE if query_size is None else query_size))
+        K = torch.as_tensor(K).to(device=image_u8.device, dtype=torch.float32).reshape(-1, 4, 4)[:1]
+        K_query = K.clone()
+        K_query[:, 0] *= w / W
+        K_query[:, 1] *= h / H
+        depth = asset.render(world_T_cam, K_query, (h, w))["depth"]  # -1 where the asset is not: no positive depth, so `fill` there
+        rgba = asset.render(world_T_cam, K, (H, W))["rgba"]
+        v = self.occlusion_for_view(depth, world_T_cam, torch.linalg.inv(K_query), fill=fill)
+        frame = compositing.composite_mask(image_u8, v["view_pred"], virtual_rgba=rgba, fade=fade, bgr=bgr)
+        if return_parts:
+            return {**v, "frame": frame, "asset_depth": depth, "asset_rgba": rgba}
+        return frame
+
     def _key_order(self, T_host: torch.Tensor) -> list:
         """Ring slots of the remembered predictions, nearest pose to the live camera first (``nearest_keys_first``; host arithmetic)."""
         slots = self.hot._ring.slots_newest_first()

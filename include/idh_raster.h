@@ -1,5 +1,6 @@
 /*
  * idh_raster.h — depth-only mesh rasterisation and the vertex bookkeeping of the temporal evaluation (added without an ABI version change: nothing existing moved).
+ * The shaded render of an asset in a live camera - depth, winning face, barycentrics, attributes, lit RGBA - is at the end of the file.
  *
  * Under --temporal_eval the reference (test_bd.py:109-116, 157-183, 214-236; utils/binary_metrics_utils.py:247-388) renders a
  * 1024 x 1024-vertex plane and the scene's ground-truth mesh into every frame with pytorch3d's CUDA rasteriser, samples the
@@ -65,6 +66,63 @@ int idh_vertex_predictions_fwd(const float *verts_v3, int V, const float *cam_T_
  * *half_units_out (one int64 on the device) = 2 * sum over t, v of |p[t+1,v] - p[t,v]| ignoring pairs with an unknown: the flips
  * counted exactly in units of 0.5.  T < 2 or V == 0 gives 0. */
 int idh_vertex_occlusion_changes_fwd(const float *hist_tv, int T, int V, long long *half_units_out, void *stream);
+
+/* ---- shaded render: depth, winning face, barycentrics, interpolated attributes and lit RGBA in one call (additive: idh_version()
+ * stays as it is; this surface is versioned through idh_raster_shaded_args.struct_size; csrc/raster_shade.hip) --------
+ *
+ * Geometry, culls and the edge rule are exactly those of idh_raster_depth_fwd above.  Visibility is resolved on one 64-bit key per pixel,
+ *   key = ((uint64)float_bits(z) << 32) | face_index,        empty: float_bits(+inf) << 32 | 0xffffffff,
+ * with a 64-bit unsigned atomic minimum.  z is the fp32 value idh_raster_depth_fwd computes for that face and pixel, so the upper word of
+ * the final key is, bit for bit, that entry point's depth; among faces with the same fp32 z at a pixel the lowest face index wins.  No
+ * output depends on the order in which faces arrive: two renders are bit-identical.
+ *
+ * The shade pass, one lane per pixel, then redoes the triangle setup of the winning face alone.  With camera-space corners A, B, C
+ * (vertices face[0], face[1], face[2]), the pixel's ray d = ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1) and the plane normal N signed so
+ * that N.A > 0, all in fp32 without contraction:
+ *   e0 = d.(B x C), e1 = d.(C x A), e2 = d.(A x B)            (the edge functions of the coverage test, same expressions)
+ *   s = e0 + e1 + e2;  w_i = e_i / s  if s > 0, else w = (1/3, 1/3, 1/3)
+ * These are the barycentrics of the 3D hit point (perspective-correct: no 1 / z correction is involved in camera space).
+ *   depth        upper key word; `empty_depth` where nothing is hit
+ *   pix_to_face  lower key word; -1 where nothing is hit
+ *   bary         w_0, w_1, w_2; zeros where nothing is hit
+ *   attr_out[c]  w_0 * a0[c] + w_1 * a1[c] + w_2 * a2[c], summed in this order, a_i = attrs_vc[face[i]]; zeros where nothing is hit
+ *   rgba         per channel v = w_0 * (float)c0 + w_1 * (float)c1 + w_2 * (float)c2 from colors_v4[face[i]]; R, G and B are multiplied by
+ *                ambient + (1 - ambient) * lam, lam = d.N / sqrtf((N.N) * (d.d))  (a headlight at the camera on the face's own normal,
+ *                two-sided; ambient = 1 is unlit); alpha is not lit; stored as (uint8)(fminf(fmaxf(v, 0), 255) + 0.5f).
+ *                (0, 0, 0, 0) where nothing is hit: alpha 0 is "no asset" for idh_composite_fwd's virtual_rgba_bHW4. */
+typedef struct idh_raster_shaded_args {
+    int64_t struct_size;          /* sizeof(idh_raster_shaded_args) of the caller's header (must be >= the library's) */
+    const float *verts_v3;        /* (V,3) fp32, the space cam_T_world maps from */
+    const int32_t *faces_f3;      /* (F,3); may be NULL when F == 0 (every pixel is then empty) */
+    const float *cam_T_world_b44; /* (B,4,4) row-major */
+    const float *K_b44;           /* (B,4,4) */
+    const uint8_t *colors_v4;     /* (V,4) RGBA per vertex, or NULL */
+    const float *attrs_vc;        /* (V,C) fp32 per vertex, or NULL */
+    float *depth_b1hw;            /* outputs: each may be NULL (not written), at least one must be given */
+    int32_t *pix_to_face_bhw;     /* (B,H,W) */
+    float *bary_bhw3;             /* (B,H,W,3) */
+    float *attr_out_bhwc;         /* (B,H,W,C); needs attrs_vc */
+    uint8_t *rgba_bhw4;           /* (B,H,W,4); needs colors_v4 */
+    void *workspace;              /* 256-byte aligned, idh_raster_shaded_workspace_bytes(B, V, F, H, W) */
+    int64_t workspace_bytes;
+    float ambient;                /* in [0, 1] */
+    float empty_depth;            /* written to depth where nothing is hit (idh_raster_depth_fwd writes -1) */
+    int32_t V, F, B, H, W, C;     /* C: channels of attrs_vc, 1..16 (0 without attrs_vc) */
+} idh_raster_shaded_args;
+
+/* sizeof(idh_raster_shaded_args) as compiled into the library (bindings assert their mirror matches). */
+size_t idh_sizeof_raster_shaded_args(void);
+
+/* Bytes of workspace (256-byte aligned): what idh_raster_workspace_bytes(B, V, F) counts plus the key plane, 8 B per pixel and camera.
+ * 0 for bad arguments (a negative count, H <= 0, W <= 0). */
+size_t idh_raster_shaded_workspace_bytes(int B, int V, int F, int H, int W);
+
+/* Validated on the host before anything is launched.
+ * IDH_EINVAL: args NULL, struct_size short, B < 0, V < 0, F < 0, H <= 0, W <= 0, H * W >= 2^31, C < 0 or C > 16, attrs_vc with C == 0,
+ * ambient not finite or outside [0, 1]; then (B > 0) a null verts (V > 0) / faces (F > 0) / cam_T_world / K, no output requested,
+ * attr_out without attrs_vc, rgba without colors_v4; IDH_EWORKSPACE: workspace null, misaligned or short;
+ * IDH_EUNSUPPORTED: B > 65535 or B * H * W >= 2^31.  B == 0 is IDH_OK. */
+int idh_raster_shaded_fwd(const idh_raster_shaded_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
