@@ -155,6 +155,19 @@ class RasterShadedArgs(C.Structure):
 
 RASTER_MAX_ATTRS = 16  # channels of idh_raster_shaded_args.attrs_vc
 
+
+class DepthWarpArgs(C.Structure):
+    """ctypes mirror of ``idh_depth_warp_args`` (include/idh_raster.h, depth reprojection)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_m1hw", C.c_void_p), ("src_invK_m44", C.c_void_p), ("cam_T_src_bm44", C.c_void_p),
+                ("K_b44", C.c_void_p), ("depth_b1hw", C.c_void_p), ("source_bhw", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("tear_ratio", C.c_float), ("empty_depth", C.c_float), ("B", C.c_int32), ("M", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(DepthWarpArgs)
+
 RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
@@ -260,6 +273,9 @@ _SIGS = {
     "idh_sizeof_raster_shaded_args": (C.c_size_t, []),
     "idh_raster_shaded_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "idh_raster_shaded_fwd": (C.c_int, [C.POINTER(RasterShadedArgs), C.c_void_p]),
+    "idh_sizeof_depth_warp_args": (C.c_size_t, []),
+    "idh_depth_warp_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "idh_depth_warp_fwd": (C.c_int, [C.POINTER(DepthWarpArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -332,7 +348,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd, idh_depth_warp_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
@@ -350,7 +366,8 @@ def lib():
                                   ("idh_bank", h.idh_sizeof_bank(), Bank),
                                   ("idh_normals_args", h.idh_sizeof_normals_args(), NormalsArgs),
                                   ("idh_patch_normals_args", h.idh_sizeof_patch_normals_args(), PatchNormalsArgs),
-                                  ("idh_raster_shaded_args", h.idh_sizeof_raster_shaded_args(), RasterShadedArgs)):
+                                  ("idh_raster_shaded_args", h.idh_sizeof_raster_shaded_args(), RasterShadedArgs),
+                                  ("idh_depth_warp_args", h.idh_sizeof_depth_warp_args(), DepthWarpArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

@@ -1,5 +1,5 @@
-// What the two entry points of the mesh rasteriser share (raster.hip: depth only; raster_shade.hip: depth + winning face, then a
-// deferred shade pass): the camera, the per-triangle setup, the edge tests and the two-level face pass.  The passes are templates over
+// What the entry points of the mesh rasteriser share (raster.hip: depth only; raster_shade.hip: depth + winning face, then a
+// deferred shade pass; depth_warp.hip: depth maps drawn as implicit meshes, with its own passes over the device functions here): the camera, the per-triangle setup, the edge tests and the two-level face pass.  The passes are templates over
 // a per-pixel SINK, the one place where the two differ: what a hit (pixel, z, face) does to the z-buffer.
 //
 //   raster_vertex_k   world -> camera -> screen, once per vertex and camera.
@@ -15,7 +15,7 @@
 // edge (negated when that swaps the operands): the difference keeps full precision for the small far triangles whose P and Q are nearly
 // parallel, and the two triangles of a shared edge get exactly negated normals.  Built with -ffp-contract=off.
 //
-// Everything sits in an anonymous namespace: each of the two sources gets its own copy, as every other kernel file of the library does.
+// Everything sits in an anonymous namespace: each source that includes it gets its own copy, as every other kernel file of the library does.
 #ifndef IDH_RASTER_COMMON_H_
 #define IDH_RASTER_COMMON_H_
 
@@ -90,13 +90,11 @@ __device__ __forceinline__ V3 edge_normal(V3 P, int ip, V3 Q, int iq) {
     return swap ? V3{-n.x, -n.y, -n.z} : n;
 }
 
-// false: the face draws nothing
-__device__ __forceinline__ bool tri_setup(const float4 *__restrict__ cam, const float2 *__restrict__ scr, const int *__restrict__ face, int V,
-                                          int H, int W, Tri &t) {
-    const int ia = face[0], ib = face[1], ic = face[2];
-    if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
-    const float4 a4 = cam[ia], b4 = cam[ib], c4 = cam[ic];
-    const V3 A{a4.x, a4.y, a4.z}, B{b4.x, b4.y, b4.z}, C{c4.x, c4.y, c4.z};
+// The two halves of a triangle's setup, for callers that hold the corners in registers (depth_warp.hip: the faces of a depth map are
+// implicit).  tri_setup_corners: camera-space corners A, B, C with vertex numbers ia, ib, ic (they only order the shared edges); false:
+// the face draws nothing; a face that straddles z = 0 leaves with the whole image as its box.  tri_setup_box: the box of a face wholly
+// in front of the camera from its corners' screen positions; false: no pixel centre inside.
+__device__ __forceinline__ bool tri_setup_corners(V3 A, int ia, V3 B, int ib, V3 C, int ic, int H, int W, Tri &t) {
     if (!(finite3(A) && finite3(B) && finite3(C))) return false;
     const int front = (A.z > 0.f) + (B.z > 0.f) + (C.z > 0.f);
     if (front == 0) return false;
@@ -110,11 +108,11 @@ __device__ __forceinline__ bool tri_setup(const float4 *__restrict__ cam, const 
     t.n1 = scale(edge_normal(C, ic, A, ia), s);
     t.n2 = scale(edge_normal(A, ia, B, ib), s);
     t.straddles = front != 3;
-    if (t.straddles) {  // its projection is not the triangle of its projected corners: test the whole image
-        t.x0 = 0, t.x1 = W - 1, t.y0 = 0, t.y1 = H - 1;
-        return true;
-    }
-    const float2 pa = scr[ia], pb = scr[ib], pc = scr[ic];
+    if (t.straddles) t.x0 = 0, t.x1 = W - 1, t.y0 = 0, t.y1 = H - 1;  // its projection is not the triangle of its projected corners: test the whole image
+    return true;
+}
+
+__device__ __forceinline__ bool tri_setup_box(float2 pa, float2 pb, float2 pc, int H, int W, Tri &t) {
     const float u0 = fminf(pa.x, fminf(pb.x, pc.x)), u1 = fmaxf(pa.x, fmaxf(pb.x, pc.x));
     const float v0 = fminf(pa.y, fminf(pb.y, pc.y)), v1 = fmaxf(pa.y, fmaxf(pb.y, pc.y));
     // pixel centres j + 0.5 inside [u0 - pad, u1 + pad], clamped to the image in float (the ends may be infinite)
@@ -123,6 +121,17 @@ __device__ __forceinline__ bool tri_setup(const float4 *__restrict__ cam, const 
     t.y0 = (int)fminf(fmaxf(ceilf(v0 - 0.5f - kBoxPad), 0.f), (float)H);
     t.y1 = (int)fmaxf(fminf(floorf(v1 - 0.5f + kBoxPad), (float)(H - 1)), -1.f);
     return t.x1 >= t.x0 && t.y1 >= t.y0;
+}
+
+// false: the face draws nothing
+__device__ __forceinline__ bool tri_setup(const float4 *__restrict__ cam, const float2 *__restrict__ scr, const int *__restrict__ face, int V,
+                                          int H, int W, Tri &t) {
+    const int ia = face[0], ib = face[1], ic = face[2];
+    if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
+    const float4 a4 = cam[ia], b4 = cam[ib], c4 = cam[ic];
+    if (!tri_setup_corners(V3{a4.x, a4.y, a4.z}, ia, V3{b4.x, b4.y, b4.z}, ib, V3{c4.x, c4.y, c4.z}, ic, H, W, t)) return false;
+    if (t.straddles) return true;
+    return tri_setup_box(scr[ia], scr[ib], scr[ic], H, W, t);
 }
 
 // The ray test of one pixel.  A Sink is a small value type with
@@ -139,6 +148,19 @@ __device__ __forceinline__ void shade(const Tri &t, const Cam &c, int x, int y, 
         if (den > 0.f && z > 0.f && z < INFINITY) sink.hit((size_t)y * W + x, z, face);
     }
 }
+
+// The z-buffer that also names the winner (raster_shade.hip, depth_warp.hip): key = (float_bits(z) << 32) | id.  z > 0, so the unsigned
+// order of the upper word is the float order; the lower word breaks ties towards the lowest id.  One 64-bit atomicMin per hit
+// (global_atomic_umin_x2 on gfx950, no compare-and-swap loop) picks the same winner whatever the order of arrival.
+constexpr unsigned long long kEmptyKey = ((unsigned long long)kInfBits << 32) | 0xffffffffull;
+
+struct KeySink {
+    unsigned long long *keys;
+    __device__ __forceinline__ KeySink camera(size_t first_pixel) const { return {keys + first_pixel}; }
+    __device__ __forceinline__ void hit(size_t pixel, float z, unsigned face) const {
+        atomicMin(keys + pixel, ((unsigned long long)__float_as_uint(z) << 32) | face);
+    }
+};
 
 template <class Sink>
 struct RasterArgs {

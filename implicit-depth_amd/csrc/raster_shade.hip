@@ -8,9 +8,8 @@
 //   shaded_resolve_k   deferred shading, one lane per pixel: triangle setup of the winning face alone, barycentrics from the edge
 //                      functions of the coverage test, then whichever outputs were requested.
 //
-// Key: (float_bits(z) << 32) | face.  z > 0, so the unsigned order of the upper word is the float order; the lower word breaks ties
-// towards the lowest face index.  One 64-bit atomicMin per hit (global_atomic_umin_x2 on gfx950, no compare-and-swap loop) picks the
-// same winner whatever the order of arrival.  Nothing per-face is kept in memory: the shade pass recomputes what it needs from the
+// Key: (float_bits(z) << 32) | face, resolved by KeySink (raster_common.h): the nearest hit wins, the lowest face index among equal
+// depths, whatever the order of arrival.  Nothing per-face is kept in memory: the shade pass recomputes what it needs from the
 // transformed-vertex buffers of the vertex pass, which are still in the workspace.
 #include <math.h>
 
@@ -22,16 +21,7 @@
 
 namespace {
 
-constexpr unsigned long long kEmptyKey = ((unsigned long long)kInfBits << 32) | 0xffffffffull;
 constexpr int kMaxAttrs = 16;
-
-struct KeySink {
-    unsigned long long *keys;
-    __device__ __forceinline__ KeySink camera(size_t first_pixel) const { return {keys + first_pixel}; }
-    __device__ __forceinline__ void hit(size_t pixel, float z, unsigned face) const {
-        atomicMin(keys + pixel, ((unsigned long long)__float_as_uint(z) << 32) | face);
-    }
-};
 
 __global__ __launch_bounds__(256) void shaded_fill_k(unsigned long long *__restrict__ keys, long long n, unsigned *__restrict__ qcount, int B) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;

@@ -282,6 +282,76 @@ class AssetRenderer:
                              ambient=self.ambient, empty_depth=empty_depth, **kw)
 
 
+def warp_depth(depth_m1hw, src_invK_m44, cam_T_src_bm44, K_b44, height, width, *, tear_ratio: float = 1.1, empty_depth: float = -1.0,
+               return_source: bool = False) -> Dict[str, torch.Tensor]:
+    """M depth maps ``depth_m1hw`` (M,1,h,w) - predictions of a ``DepthModel``, lidar frames, a ``BDModel``'s ``infer_depth`` result -
+    warped into B cameras in one call (idh_depth_warp_fwd).  ``src_invK_m44`` (M,4,4): the sources' inverse intrinsics
+    at h x w; ``cam_T_src_bm44`` (B,M,4,4): source camera frame to target camera frame (``relative_poses`` forms it in float64);
+    ``K_b44`` (B,4,4): the targets' intrinsics at ``height`` x ``width``.  Every map is a triangulated surface over its pixel centres
+    (include/idh_raster.h states the vertices and the two faces of a quad); a face whose three source depths are not all finite and
+    positive, or whose largest exceeds ``tear_ratio`` (>= 1; ``inf`` never tears) times its smallest, is not drawn.  Returns
+
+    * ``"depth"`` (B,1,height,width): the z in the target camera of the nearest surface any of the M sources remembers,
+      ``empty_depth`` where none saw anything;
+    * ``"source"`` (B,height,width) int32 with ``return_source``: ``m * 2 (h-1) (w-1) + face`` of the winner (``decode_source``), -1
+      where empty; the lowest among exactly equal depths.
+
+    Two calls return the same bits.  There is no CPU fallback."""
+    _lib.require_cuda_f32(depth_m1hw, src_invK_m44, cam_T_src_bm44, K_b44)
+    if depth_m1hw.dim() != 4 or depth_m1hw.shape[1] != 1:
+        raise _lib.IdhError(f"warp_depth: depth {tuple(depth_m1hw.shape)} must be (M,1,h,w)")
+    M, _, h, w = depth_m1hw.shape
+    if tuple(src_invK_m44.shape) != (M, 4, 4):
+        raise _lib.IdhError(f"warp_depth: src_invK {tuple(src_invK_m44.shape)} must be ({M},4,4)")
+    if cam_T_src_bm44.dim() != 4 or tuple(cam_T_src_bm44.shape[1:]) != (M, 4, 4):
+        raise _lib.IdhError(f"warp_depth: cam_T_src {tuple(cam_T_src_bm44.shape)} must be (B,{M},4,4)")
+    B = cam_T_src_bm44.shape[0]
+    if tuple(K_b44.shape) != (B, 4, 4):
+        raise _lib.IdhError(f"warp_depth: K {tuple(K_b44.shape)} must be ({B},4,4)")
+    height, width = int(height), int(width)
+    d, iK, T, K = depth_m1hw.contiguous(), src_invK_m44.contiguous(), cam_T_src_bm44.contiguous(), K_b44.contiguous()
+    L = _lib.lib()
+    a = _lib.DepthWarpArgs()
+    a.B, a.M, a.h, a.w, a.H, a.W = B, M, h, w, height, width
+    a.tear_ratio, a.empty_depth = float(tear_ratio), float(empty_depth)
+    nbytes = L.idh_depth_warp_workspace_bytes(B, M, h, w, height, width)
+    if nbytes == 0:
+        raise _lib.IdhError(f"warp_depth: B = {B}, M = {M}, height = {height} and width = {width} must be positive and the sources "
+                            f"({h} x {w}) at least 2 x 2")
+    out = {"depth": torch.empty(B, 1, height, width, device=d.device)}
+    if return_source:
+        out["source"] = torch.empty(B, height, width, device=d.device, dtype=torch.int32)
+    ws = torch.empty(nbytes, device=d.device, dtype=torch.uint8)
+    a.depth_m1hw, a.src_invK_m44, a.cam_T_src_bm44, a.K_b44 = d.data_ptr(), iK.data_ptr(), T.data_ptr(), K.data_ptr()
+    a.depth_b1hw, a.source_bhw, a.workspace, a.workspace_bytes = out["depth"].data_ptr(), _lib.ptr(out.get("source")), ws.data_ptr(), nbytes
+    _lib.check(L.idh_depth_warp_fwd(C.byref(a), _lib.stream_ptr()), "idh_depth_warp_fwd")
+    return out
+
+
+def decode_source(source, h: int, w: int):
+    """``(m, i, j, upper)`` of ``warp_depth``'s ``"source"`` ids for sources of h x w pixels (a tensor gives int64 tensors, anything
+    else int64 arrays): the source map, the quad's top-left vertex (row i, column j) and whether the face is the quad's second one,
+    (v01, v10, v11), or its first, (v00, v10, v01).  All four are -1 where the id is -1 (nothing was hit)."""
+    h, w = int(h), int(w)
+    if h < 2 or w < 2:
+        raise _lib.IdhError(f"decode_source: sources of {h} x {w} pixels have no faces")
+    F = 2 * (h - 1) * (w - 1)
+    s, where = (source.long(), torch.where) if isinstance(source, torch.Tensor) else (np.asarray(source, dtype=np.int64), np.where)
+    empty = s < 0
+    m, face = s // F, s % F
+    q = face // 2
+    parts = (m, q // (w - 1), q % (w - 1), face % 2)
+    return tuple(where(empty, -1, p) for p in parts)
+
+
+def relative_poses(world_T_cam_targets, world_T_src_sources) -> torch.Tensor:
+    """(B,M,4,4) float32 on the host: ``float32(inv(world_T_cam[b]) @ world_T_src[m])`` formed in float64, as ``AssetRenderer.cam_T_mesh``
+    does.  Both arguments are sequences of (4,4) arrays or tensors."""
+    tgt = [np.linalg.inv(_pose_f64("world_T_cam", T)) for T in world_T_cam_targets]
+    src = [_pose_f64("world_T_src", T) for T in world_T_src_sources]
+    return torch.from_numpy(np.stack([np.stack([t @ s for s in src]) for t in tgt]).astype(np.float32))
+
+
 def vertex_predictions(verts, cam_T_world_b44, K_b44, pred_11hw, depth_11hw, tolerance=DEPTH_TOLERANCE) -> torch.Tensor:
     """(V,) the prediction sampled at each projected vertex, -1 where the vertex is behind the camera, off the image, hidden
     (``depth_11hw`` is the mesh's own render) or the prediction is not positive (binary_metrics_utils.py:364-386)."""

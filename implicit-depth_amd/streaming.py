@@ -57,7 +57,9 @@ class StreamingSession:
     last one, as ever.  N in [2, 16]: every prediction is remembered (``HotPath.remember``, with its own ``sigmoid(pred_0[:, :1])`` and
     camera as its prior under ``use_prior``) and a live pixel is asked in the first of the last N whose camera sees it, nearest pose
     first (``nearest_keys_first``); the dictionaries gain "view_key" / "view_search_key".  ``reset()`` empties that ring; like the last
-    prediction it survives a tracking-lost code."""
+    prediction it survives a tracking-lost code.  The same number bounds the ring of depth maps (``remember_depth``: a ``DepthModel``'s
+    predictions, pushed by ``step``; lidar frames or an inferred depth, pushed by the caller) that ``warped_depth_for_view`` draws into
+    a live camera and the depth route of ``composite_asset`` composites against."""
 
     def __init__(self, model: nn.Module, num_source_views: Optional[int] = None, buffer_size: Optional[int] = None, mode: str = "keyframe",
                  config=keyframes.DVMVS_Config, image_encoder: Optional[nn.Module] = None, math: Optional[str] = None,
@@ -112,6 +114,9 @@ class StreamingSession:
         # and so do the priors remembered with its predictions, while the single-key queries drop theirs there; reset() empties it.
         self.query_keyframes = int(query_keyframes)
         self._ring_poses: Dict[int, np.ndarray] = {}  # ring slot -> that prediction's world_T_cam on the host
+        # the last query_keyframes depth maps (remember_depth), newest first: (depth (1,1,h,w), world_T_cam float64 (4,4), invK (1,4,4)).
+        # What warped_depth_for_view draws; a DepthModel's predictions are pushed by step(), lidar or an inferred depth by the caller.
+        self._depth_ring: list = []
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -119,6 +124,7 @@ class StreamingSession:
                                                self.buffer.optimal_R_score)
         self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
         self._key = None
+        self._depth_ring = []
         if self.query_keyframes > 1:
             self.hot.forget()
             self._ring_poses = {}
@@ -187,6 +193,8 @@ class StreamingSession:
                     self._ring_poses[slot] = np.array(pose, dtype=np.float64)
                 if query_points is not None:
                     out.update(self.query_points(query_points))
+            elif "depth_pred_s0_b1hw" in out:  # a DepthModel: its prediction is what the frames between keyframes can be answered from
+                self.remember_depth(out["depth_pred_s0_b1hw"], pose, cur_data["invK_s0_b44"])
         if "prior_mask" in out:
             cur_data["prior_mask"] = out.pop("prior_mask")  # as fused_forward: run_mlp_val stores it on the inputs (bd_model.py:431)
         return out, code
@@ -250,10 +258,17 @@ class StreamingSession:
         RGBA; then ``occlusion_for_view(depth, world_T_cam, inv(K_query), fill)`` and
         ``compositing.composite_mask(image_u8, view_pred, virtual_rgba=rgba, fade=fade, bgr=bgr)``.  ``fill`` is the logit of the pixels
         the keyframe cannot answer (-20: the asset stays visible there).  Returns the (1,H,W,3) uint8 frame; with ``return_parts`` a
-        dictionary with "frame", "asset_depth" (1,1,h,w; -1 where the asset is not), "asset_rgba" (1,H,W,4) and the view query's entries."""
+        dictionary with "frame", "asset_depth" (1,1,h,w; -1 where the asset is not), "asset_rgba" (1,H,W,4) and the view query's entries.
+
+        A session without an occlusion MLP (a ``DepthModel``) takes the depth route (inference/composite.py:104-134): the asset's depth
+        and RGBA in one render at H x W, ``warped_depth_for_view`` at ``query_size`` with ``WARP_FAR`` where no remembered map saw
+        anything (the asset stays visible there), then ``compositing.composite_depth(image_u8, warped, virtual_depth=asset depth,
+        virtual_rgba=rgba, fade=fade, bgr=bgr)``.  ``fill`` is not used; "asset_depth" is then (1,1,H,W) and the parts hold
+        ``warped_depth_for_view``'s entries."""
         from . import compositing
 
-        if self._key is None:
+        depth_route = self.hot.binary_mlp is None  # a DepthModel: no occlusion MLP to ask, its remembered depth maps are warped instead
+        if (not self._depth_ring) if depth_route else (self._key is None):
             raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
         if not isinstance(image_u8, torch.Tensor) or image_u8.dim() != 4 or image_u8.shape[0] != 1 or image_u8.shape[-1] != 3:
             raise _lib.IdhError("composite_asset: image_u8 must be one (1,H,W,3) uint8 frame on the GPU")
@@ -265,6 +280,14 @@ class StreamingSession:
         K_query = K.clone()
         K_query[:, 0] *= w / W
         K_query[:, 1] *= h / H
+        if depth_route:
+            full = asset.render(world_T_cam, K, (H, W))  # composite_depth compares at the image's resolution
+            v = self.warped_depth_for_view(world_T_cam, K_query, (h, w), empty_depth=self.WARP_FAR)
+            frame = compositing.composite_depth(image_u8, v["view_warp_depth"], virtual_depth=full["depth"][:, 0], virtual_rgba=full["rgba"],
+                                                fade=fade, bgr=bgr)
+            if return_parts:
+                return {**v, "frame": frame, "asset_depth": full["depth"], "asset_rgba": full["rgba"]}
+            return frame
         depth = asset.render(world_T_cam, K_query, (h, w))["depth"]  # -1 where the asset is not: no positive depth, so `fill` there
         rgba = asset.render(world_T_cam, K, (H, W))["rgba"]
         v = self.occlusion_for_view(depth, world_T_cam, torch.linalg.inv(K_query), fill=fill)
@@ -272,6 +295,49 @@ class StreamingSession:
         if return_parts:
             return {**v, "frame": frame, "asset_depth": depth, "asset_rgba": rgba}
         return frame
+
+    WARP_FAR = 1.0e4  # metres: the depth composite_asset's depth route gives the pixels no remembered map covers
+
+    def remember_depth(self, depth_11hw: torch.Tensor, world_T_cam, invK: torch.Tensor) -> None:
+        """Push a depth map (1,1,h,w) onto the ring of the last ``query_keyframes`` maps ``warped_depth_for_view`` draws: the camera that
+        saw it at ``world_T_cam`` ((4,4) array or tensor) with inverse intrinsics ``invK`` ((4,4) or (1,4,4), at h x w).  ``step`` calls
+        this with a ``DepthModel``'s ``depth_pred_s0_b1hw``; a caller pushes a lidar frame or a ``BDModel``'s inferred depth.  Taps that
+        are not finite and positive are holes.  The map is copied; all maps of the ring have one size.  ``reset()`` empties the ring."""
+        from .raster import _pose_f64
+
+        _lib.require_cuda_f32(depth_11hw, invK)
+        if depth_11hw.dim() != 4 or tuple(depth_11hw.shape[:2]) != (1, 1) or depth_11hw.shape[2] < 2 or depth_11hw.shape[3] < 2:
+            raise _lib.IdhError(f"remember_depth: depth {tuple(depth_11hw.shape)} must be (1,1,h,w) with h, w >= 2")
+        if self._depth_ring and self._depth_ring[0][0].shape != depth_11hw.shape:
+            raise _lib.IdhError(f"remember_depth: the ring holds maps of {tuple(self._depth_ring[0][0].shape)}, got {tuple(depth_11hw.shape)}")
+        invK = invK.reshape(-1, 4, 4)
+        if invK.shape[0] != 1:
+            raise _lib.IdhError("remember_depth: invK must be (4,4) or (1,4,4)")
+        pose = _pose_f64("world_T_cam", world_T_cam)
+        self._depth_ring.insert(0, (depth_11hw.detach().clone(), pose, invK.detach().clone()))
+        del self._depth_ring[self.query_keyframes:]
+
+    def warped_depth_for_view(self, world_T_cam, K: torch.Tensor, size: Sequence[int], tear_ratio: float = 1.1, empty_depth: float = -1.0,
+                              return_source: bool = False) -> Dict[str, torch.Tensor]:
+        """The remembered depth maps in the LIVE camera, also on the frames where ``step`` returned None: every map of the ring drawn as a
+        triangulated surface, torn where neighbouring taps differ by more than ``tear_ratio``, into the ``size`` = (H, W) image of the
+        camera at ``world_T_cam`` ((4,4) array or tensor) with intrinsics ``K`` ((4,4) or (1,4,4), at H x W) - ``raster.warp_depth``, one
+        call for all maps.  Returns "view_warp_depth" (1,1,H,W): the depth of the nearest remembered surface, ``empty_depth`` where
+        "view_warp_valid" (1,1,H,W) bool is False (no map saw anything there); with ``return_source`` "view_warp_source" (1,H,W) int32
+        (``raster.decode_source``; source 0 is the newest map).  No network runs and nothing is searched: one pass over the maps' pixels."""
+        from . import raster
+
+        if not self._depth_ring:
+            raise _lib.IdhError("no prediction has been made in this sequence yet and no depth map was remembered (remember_depth)")
+        depth = torch.cat([d for d, _, _ in self._depth_ring])
+        invK = torch.cat([k for _, _, k in self._depth_ring])
+        T = raster.relative_poses([world_T_cam], [p for _, p, _ in self._depth_ring]).to(depth.device)
+        K = torch.as_tensor(K).to(device=depth.device, dtype=torch.float32).reshape(-1, 4, 4)[:1]
+        out = raster.warp_depth(depth, invK, T, K, int(size[0]), int(size[1]), tear_ratio=tear_ratio, empty_depth=empty_depth, return_source=True)
+        res = {"view_warp_depth": out["depth"], "view_warp_valid": (out["source"] >= 0)[:, None]}
+        if return_source:
+            res["view_warp_source"] = out["source"]
+        return res
 
     def _key_order(self, T_host: torch.Tensor) -> list:
         """Ring slots of the remembered predictions, nearest pose to the live camera first (``nearest_keys_first``; host arithmetic)."""

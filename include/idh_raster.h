@@ -1,6 +1,7 @@
 /*
  * idh_raster.h — depth-only mesh rasterisation and the vertex bookkeeping of the temporal evaluation (added without an ABI version change: nothing existing moved).
- * The shaded render of an asset in a live camera - depth, winning face, barycentrics, attributes, lit RGBA - is at the end of the file.
+ * The shaded render of an asset in a live camera - depth, winning face, barycentrics, attributes, lit RGBA - follows, and the warp of
+ * keyframe depth maps into a live camera is at the end of the file.
  *
  * Under --temporal_eval the reference (test_bd.py:109-116, 157-183, 214-236; utils/binary_metrics_utils.py:247-388) renders a
  * 1024 x 1024-vertex plane and the scene's ground-truth mesh into every frame with pytorch3d's CUDA rasteriser, samples the
@@ -123,6 +124,56 @@ size_t idh_raster_shaded_workspace_bytes(int B, int V, int F, int H, int W);
  * attr_out without attrs_vc, rgba without colors_v4; IDH_EWORKSPACE: workspace null, misaligned or short;
  * IDH_EUNSUPPORTED: B > 65535 or B * H * W >= 2^31.  B == 0 is IDH_OK. */
 int idh_raster_shaded_fwd(const idh_raster_shaded_args *args, void *stream);
+
+/* ---- depth reprojection: M keyframe depth maps warped into B live cameras (additive: idh_version() stays as it is; versioned through
+ * idh_depth_warp_args.struct_size; csrc/depth_warp.hip) -------------------------------------------------------------
+ *
+ * The depth path of the reference's compositor (inference/composite.py:104-134: the `predicted_depth` and `lidar` methods, fed with
+ * depth_pred_s0_b1hw of the regression baseline or a sensor's map) takes a depth map in the camera it composites into.  This entry
+ * point moves maps predicted or measured at keyframes into the camera of any frame between them.
+ *
+ * Each source map m (h x w, inverse intrinsics src_invK[m]) is a triangulated surface:
+ *   - vertex (i, j) = depth[m, i, j] * src_invK[m][:3,:3] (j + 0.5, i + 0.5, 1)   (BackprojectDepth, utils/geometry_utils.py:39,60-61),
+ *     taken into target camera b by cam_T_src[b, m]; it is valid when its depth is finite and > 0;
+ *   - quad q = i * (w - 1) + j, 0 <= i < h - 1, 0 <= j < w - 1, with corners v00 = (i, j), v01 = (i, j + 1), v10 = (i + 1, j),
+ *     v11 = (i + 1, j + 1) gives face 2q = (v00, v10, v01) and face 2q + 1 = (v01, v10, v11); vertex numbers i * w + j order shared edges;
+ *   - a face draws when its three vertices are valid and zmax <= zmin * tear_ratio over its three SOURCE depths (one fp32 multiply and
+ *     one compare); tear_ratio = +inf never tears;
+ *   - everything else is idh_raster_depth_fwd's rule: the ray / plane intersection in the target camera's space, >= 0 is inside, both
+ *     windings, a face crossing z = 0 is drawn for its front part.
+ * All M sources of a target go into one z-buffer of 64-bit keys (float_bits(z) << 32) | (m * 2 (h - 1) (w - 1) + face), resolved with
+ * a 64-bit unsigned atomic minimum:
+ *   depth   the smallest target-camera z over all faces of all sources; `empty_depth` where nothing is hit
+ *   source  m * 2 (h - 1) (w - 1) + face of the winner, the lowest among equal depths; -1 where nothing is hit
+ * Two calls return the same bits.  Where pixel centres fall exactly on mesh vertices (the identity pose, an integer zoom) coverage is
+ * decided by rounding and single-pixel holes can appear. */
+typedef struct idh_depth_warp_args {
+    int64_t struct_size;         /* sizeof(idh_depth_warp_args) of the caller's header (must be >= the library's) */
+    const float *depth_m1hw;     /* (M,1,h,w) source depth maps */
+    const float *src_invK_m44;   /* (M,4,4) inverse intrinsics of the sources at h x w, row-major */
+    const float *cam_T_src_bm44; /* (B,M,4,4) source camera frame -> target camera frame */
+    const float *K_b44;          /* (B,4,4) target intrinsics at H x W */
+    float *depth_b1hw;           /* out (B,1,H,W) */
+    int32_t *source_bhw;         /* out (B,H,W), or NULL */
+    void *workspace;             /* 256-byte aligned, idh_depth_warp_workspace_bytes(B, M, h, w, H, W) */
+    int64_t workspace_bytes;
+    float tear_ratio;            /* >= 1; +inf: the rubber sheet */
+    float empty_depth;           /* written to depth where nothing is hit */
+    int32_t B, M, h, w, H, W;
+} idh_depth_warp_args;
+
+/* sizeof(idh_depth_warp_args) as compiled into the library (bindings assert their mirror matches). */
+size_t idh_sizeof_depth_warp_args(void);
+
+/* Bytes of workspace (256-byte aligned): 4 B per face and (target, source) pair for the queue of large faces, 8 B per target pixel for
+ * the key plane.  0 for bad sizes (any <= 0, h < 2, w < 2). */
+size_t idh_depth_warp_workspace_bytes(int B, int M, int h, int w, int H, int W);
+
+/* Validated on the host before anything is launched.
+ * IDH_EINVAL: args NULL, struct_size short, B, M, H or W <= 0, h < 2, w < 2, tear_ratio < 1 or NaN, a null
+ * input or depth_b1hw; IDH_EUNSUPPORTED: h * w >= 2^30, M * 2 (h - 1) (w - 1) >= 2^31, B * H * W >= 2^31, B * M > 65535;
+ * IDH_EWORKSPACE: workspace null, misaligned or short (the code every entry point of the library gives a short workspace). */
+int idh_depth_warp_fwd(const idh_depth_warp_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
