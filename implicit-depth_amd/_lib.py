@@ -168,6 +168,46 @@ class DepthWarpArgs(C.Structure):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(DepthWarpArgs)
 
+
+class TsdfVolume(C.Structure):
+    """ctypes mirror of ``idh_tsdf_volume`` (include/idh_fusion.h, TSDF fusion)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("values", C.c_void_p), ("block_flags", C.c_void_p), ("block_flag_bytes", C.c_int64),
+                ("origin", C.c_float * 3), ("voxel_size", C.c_float), ("trunc_voxels", C.c_float), ("Nz", C.c_int32), ("Ny", C.c_int32),
+                ("Nx", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfVolume)
+
+
+class TsdfIntegrateArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_integrate_args`` (include/idh_fusion.h)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("volume", TsdfVolume), ("depth_m1hw", C.c_void_p), ("K_m44", C.c_void_p),
+                ("cam_T_world_m44", C.c_void_p), ("max_weight", C.c_float), ("M", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfIntegrateArgs)
+
+
+class TsdfRaycastArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_raycast_args`` (include/idh_fusion.h)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("volume", TsdfVolume), ("world_T_cam_b44", C.c_void_p), ("invK_b44", C.c_void_p),
+                ("depth_b1hw", C.c_void_p), ("flags_bhw", C.c_void_p), ("normals_b3hw", C.c_void_p), ("near", C.c_float),
+                ("step_voxels", C.c_float), ("empty_depth", C.c_float), ("max_steps", C.c_int32), ("world_normals", C.c_int32),
+                ("skip", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfRaycastArgs)
+
+
+TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
+TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
+
 RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1  # IDH_RESIZE_*
 INGEST_MAX_RATIO = 8  # IDH_INGEST_MAX_RATIO
 
@@ -276,6 +316,14 @@ _SIGS = {
     "idh_sizeof_depth_warp_args": (C.c_size_t, []),
     "idh_depth_warp_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "idh_depth_warp_fwd": (C.c_int, [C.POINTER(DepthWarpArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_volume": (C.c_size_t, []),
+    "idh_sizeof_tsdf_integrate_args": (C.c_size_t, []),
+    "idh_sizeof_tsdf_raycast_args": (C.c_size_t, []),
+    "idh_tsdf_block_flag_bytes": (C.c_size_t, [C.c_int] * 3),
+    "idh_tsdf_reset_fwd": (C.c_int, [C.POINTER(TsdfVolume), C.c_void_p]),
+    "idh_tsdf_flags_fwd": (C.c_int, [C.POINTER(TsdfVolume), C.c_void_p]),
+    "idh_tsdf_integrate_fwd": (C.c_int, [C.POINTER(TsdfIntegrateArgs), C.c_void_p]),
+    "idh_tsdf_raycast_fwd": (C.c_int, [C.POINTER(TsdfRaycastArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -348,7 +396,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd, idh_depth_warp_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd, idh_depth_warp_fwd, idh_tsdf_integrate_fwd, idh_tsdf_raycast_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
@@ -367,7 +415,10 @@ def lib():
                                   ("idh_normals_args", h.idh_sizeof_normals_args(), NormalsArgs),
                                   ("idh_patch_normals_args", h.idh_sizeof_patch_normals_args(), PatchNormalsArgs),
                                   ("idh_raster_shaded_args", h.idh_sizeof_raster_shaded_args(), RasterShadedArgs),
-                                  ("idh_depth_warp_args", h.idh_sizeof_depth_warp_args(), DepthWarpArgs)):
+                                  ("idh_depth_warp_args", h.idh_sizeof_depth_warp_args(), DepthWarpArgs),
+                                  ("idh_tsdf_volume", h.idh_sizeof_tsdf_volume(), TsdfVolume),
+                                  ("idh_tsdf_integrate_args", h.idh_sizeof_tsdf_integrate_args(), TsdfIntegrateArgs),
+                                  ("idh_tsdf_raycast_args", h.idh_sizeof_tsdf_raycast_args(), TsdfRaycastArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

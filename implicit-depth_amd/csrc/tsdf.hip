@@ -1,0 +1,378 @@
+// TSDF fusion (include/idh_fusion.h): depth maps averaged into a dense truncated signed distance volume, and the fused
+// surface ray-cast into live cameras.  The header states the arithmetic; this file follows it expression by expression.
+//
+//   tsdf_reset_k      every voxel to {1, 0}, every block flag to 0.
+//   tsdf_flags_k      block flags from the values of a volume made elsewhere (after a clear).
+//   tsdf_integrate_k  one lane per voxel, a wave along x; the M cameras are wave-uniform (scalar loads), the voxel's {T, W} pair stays in
+//                     registers over the M maps: one 8-byte load at the first map that touches it, one 8-byte store at the end.
+//   tsdf_raycast_k<SKIP, NORMALS>  one lane per pixel, an 8 x 8-pixel tile per wave.  A sample reads its eight corners as four 16-byte
+//                     loads: the x-neighbours {T0, W0, T1, W1} are adjacent in memory (8-byte aligned, which the global loads of gfx950
+//                     take).  SKIP clips the lattice range to the volume's box and jumps blocks whose flag is 0.
+//
+// Block flags.  A lane's row is 64 consecutive x, so the eight lanes of an aligned group share one block along x: the group's first lane
+// stores for the group (one ballot), and a touched voxel on a block's low face also stores for the block before it (the + 1 apron).
+// Only the value 1 is ever stored between resets, so concurrent stores need no atomic.
+#include <math.h>
+
+#include "../../include/idh_fusion.h"
+#include "idh_common.h"
+
+namespace {
+
+typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));  // two neighbouring {T, W} pairs: 8-byte aligned, one 16-byte load
+
+struct Vol {
+    float *values;
+    uint8_t *flags;
+    float ox, oy, oz, v, trunc;
+    int Nx, Ny, Nz, nbx, nby, nbz;
+};
+
+__host__ __device__ inline int tsdf_blocks(int n) { return (n + 6) / 8; }  // 8-cell blocks over n - 1 cells
+
+__device__ __forceinline__ bool valid_depth(float d) { return d > 0.f && d < INFINITY; }  // false for NaN
+
+__global__ __launch_bounds__(256) void tsdf_reset_k(float2 *__restrict__ values, long long n, uint8_t *__restrict__ flags, long long nb) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i < n) values[i] = make_float2(1.f, 0.f);
+    if (i < nb) flags[i] = 0;
+}
+
+// flags of the blocks whose cells read a voxel of block column bx (already resolved along x) at row y, slice z
+__device__ __forceinline__ void mark_yz(const Vol &V, int bx, int y, int z) {
+    if (bx < 0 || bx >= V.nbx) return;
+    const int by1 = y >> 3, bz1 = z >> 3;
+    const int by0 = (y & 7) == 0 && y > 0 ? by1 - 1 : by1, bz0 = (z & 7) == 0 && z > 0 ? bz1 - 1 : bz1;
+    for (int bz = bz0; bz <= bz1; ++bz)
+        for (int by = by0; by <= by1; ++by)
+            if (bz < V.nbz && by < V.nby) V.flags[((size_t)bz * V.nby + by) * V.nbx + bx] = 1;
+}
+
+// `seen`: this lane's voxel (x, y, z) has W > 0.  Called by every lane of the wave (x = 64-aligned base + lane).
+__device__ __forceinline__ void mark_blocks(const Vol &V, bool seen, int x, int y, int z) {
+    const unsigned long long mask = __ballot(seen);
+    const int lane = threadIdx.x & 63;
+    if ((lane & 7) != 0) return;
+    if ((mask >> lane) & 0xffull) mark_yz(V, x >> 3, y, z);
+    if (seen && x > 0) mark_yz(V, (x >> 3) - 1, y, z);
+}
+
+__global__ __launch_bounds__(256) void tsdf_flags_k(const Vol V) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
+    if (y >= V.Ny) return;  // whole wave
+    bool seen = false;
+    if (x < V.Nx) seen = V.values[2 * (((size_t)z * V.Ny + y) * V.Nx + x) + 1] > 0.f;
+    mark_blocks(V, seen, x, y, z);
+}
+
+struct IntegrateArgs {
+    Vol V;
+    const float *depth, *K, *T;
+    float max_weight;
+    int M, h, w;
+};
+
+__global__ __launch_bounds__(256) void tsdf_integrate_k(const IntegrateArgs a) {
+    const Vol &V = a.V;
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
+    if (y >= V.Ny) return;  // whole wave
+    const bool live = x < V.Nx;
+    const float px = V.ox + V.v * (float)x, py = V.oy + V.v * (float)y, pz = V.oz + V.v * (float)z;
+    float2 *cell = reinterpret_cast<float2 *>(V.values) + (((size_t)z * V.Ny + y) * V.Nx + (live ? x : 0));
+    float T = 1.f, W = 0.f;
+    bool touched = false;
+    const float fw = (float)a.w, fh = (float)a.h;
+    for (int m = 0; m < a.M; ++m) {
+        const float *E = a.T + m * 16, *K = a.K + m * 16;  // wave-uniform
+        const float cz = ((E[8] * px + E[9] * py) + E[10] * pz) + E[11];
+        if (!(live && cz > 0.f)) continue;
+        const float cx = ((E[0] * px + E[1] * py) + E[2] * pz) + E[3];
+        const float cy = ((E[4] * px + E[5] * py) + E[6] * pz) + E[7];
+        const float u = K[0] * (cx / cz) + K[2], v = K[5] * (cy / cz) + K[6];
+        if (!(u >= 0.f && u < fw && v >= 0.f && v < fh)) continue;  // also refuses NaN
+        const int j = (int)floorf(u), i = (int)floorf(v);
+        const float d = a.depth[((size_t)m * a.h + i) * a.w + j];
+        if (!valid_depth(d)) continue;
+        const float sdf = d - cz;
+        if (sdf < -V.trunc) continue;
+        const float s = fminf(1.f, sdf / V.trunc);
+        if (!touched) {
+            const float2 tw = *cell;
+            T = tw.x, W = tw.y;
+            touched = true;
+        }
+        T = (W * T + s) / (W + 1.f);
+        W = fminf(W + 1.f, a.max_weight);
+    }
+    if (touched) *cell = make_float2(T, W);
+    mark_blocks(V, touched, x, y, z);  // a touched voxel has W >= 1
+}
+
+struct RaycastArgs {
+    Vol V;
+    const float *world_T_cam, *invK;
+    float *depth, *normals;
+    uint8_t *flags;
+    float near, step_voxels, empty_depth;
+    int max_steps, world_normals, B, H, W;
+};
+
+// the eight corners of the cell at floor(g): false when the cell is outside the volume or a corner has W == 0
+struct Corners {
+    f4a8 a, b, c, d;  // rows (y, z) = (0,0), (1,0), (0,1), (1,1); each {T_x0, W_x0, T_x1, W_x1}
+    float rx, ry, rz;
+};
+
+__device__ __forceinline__ bool cell_of(const Vol &V, float gx, float gy, float gz, float &fx, float &fy, float &fz) {
+    fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+    return fx >= 0.f && fx <= (float)(V.Nx - 2) && fy >= 0.f && fy <= (float)(V.Ny - 2) && fz >= 0.f && fz <= (float)(V.Nz - 2);  // false for NaN
+}
+
+__device__ __forceinline__ bool load_corners(const Vol &V, float gx, float gy, float gz, float fx, float fy, float fz, Corners &c) {
+    const int x = (int)fx, y = (int)fy, z = (int)fz;
+    const size_t row = (size_t)V.Nx * 2, slice = row * V.Ny;
+    const float *p = V.values + ((size_t)z * V.Ny + y) * row + (size_t)x * 2;
+    c.a = *reinterpret_cast<const f4a8 *>(p);
+    c.b = *reinterpret_cast<const f4a8 *>(p + row);
+    c.c = *reinterpret_cast<const f4a8 *>(p + slice);
+    c.d = *reinterpret_cast<const f4a8 *>(p + slice + row);
+    c.rx = gx - fx, c.ry = gy - fy, c.rz = gz - fz;
+    return c.a.y > 0.f && c.a.w > 0.f && c.b.y > 0.f && c.b.w > 0.f && c.c.y > 0.f && c.c.w > 0.f && c.d.y > 0.f && c.d.w > 0.f;
+}
+
+__device__ __forceinline__ float lerp(float a, float b, float r) { return a + r * (b - a); }
+
+__device__ __forceinline__ float trilinear(const Corners &c) {
+    const float a00 = lerp(c.a.x, c.a.z, c.rx), a10 = lerp(c.b.x, c.b.z, c.rx), a01 = lerp(c.c.x, c.c.z, c.rx), a11 = lerp(c.d.x, c.d.z, c.rx);
+    return lerp(lerp(a00, a10, c.ry), lerp(a01, a11, c.ry), c.rz);
+}
+
+template <bool SKIP, bool NORMALS>
+__global__ __launch_bounds__(256) void tsdf_raycast_k(const RaycastArgs a) {
+    const Vol &V = a.V;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), i = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3), b = blockIdx.z;
+    if (i >= a.H || j >= a.W) return;
+    const float *E = a.world_T_cam + b * 16, *iK = a.invK + b * 16;
+    const float u = (float)j + 0.5f, v = (float)i + 0.5f;
+    const float qx = (iK[0] * u + iK[1] * v) + iK[2], qy = (iK[4] * u + iK[5] * v) + iK[6], qz = (iK[8] * u + iK[9] * v) + iK[10];
+    const float n = sqrtf((qx * qx + qy * qy) + qz * qz);
+    const float dcx = qx / n, dcy = qy / n, dcz = qz / n;
+    const float dx = (E[0] * dcx + E[1] * dcy) + E[2] * dcz, dy = (E[4] * dcx + E[5] * dcy) + E[6] * dcz, dz = (E[8] * dcx + E[9] * dcy) + E[10] * dcz;
+    const float ogx = (E[3] - V.ox) / V.v, ogy = (E[7] - V.oy) / V.v, ogz = (E[11] - V.oz) / V.v;
+    const float dgx = dx / V.v, dgy = dy / V.v, dgz = dz / V.v;
+    const float step = a.step_voxels * V.v, near = a.near;
+
+    int k = 0, k_last = a.max_steps - 1;
+    if (SKIP) {
+        // The lattice range that can hold a known sample: the slab test against the box of cells [0, N - 1), widened by kMargin voxels
+        // and two samples - far more than the fp32 error of g, so every sample left out is out of the volume.
+        const float kMargin = 0.01f;
+        const float og[3] = {ogx, ogy, ogz}, dg[3] = {dgx, dgy, dgz}, hi[3] = {(float)(V.Nx - 1), (float)(V.Ny - 1), (float)(V.Nz - 1)};
+        float t_in = -INFINITY, t_out = INFINITY;
+        bool never = false;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            if (dg[ax] == 0.f) {
+                never |= !(og[ax] >= 0.f && og[ax] < hi[ax]);  // g is og at every sample
+            } else {
+                const float t1 = (-kMargin - og[ax]) / dg[ax], t2 = ((hi[ax] + kMargin) - og[ax]) / dg[ax];
+                t_in = fmaxf(t_in, fminf(t1, t2));
+                t_out = fminf(t_out, fmaxf(t1, t2));
+            }
+        }
+        const float top = (float)a.max_steps;
+        const float k0 = fminf(fmaxf(floorf((t_in - near) / step) - 2.f, 0.f), top);          // NaN -> 0
+        const float k1 = fmaxf(fminf(ceilf((t_out - near) / step) + 2.f, top - 1.f), -1.f);  // NaN -> max_steps - 1
+        k = never ? a.max_steps : (int)k0;
+        k_last = (int)k1;
+    }
+
+    int known_count = 0, hit_k = -1, cur_block = -1;
+    unsigned cur_flag = 1;
+    bool prev_known = false;
+    float f_prev = 0.f, t_star = 0.f;
+    while (k <= k_last) {
+        const float t = near + (float)k * step;
+        const float gx = ogx + t * dgx, gy = ogy + t * dgy, gz = ogz + t * dgz;
+        float fx, fy, fz, f = 0.f;
+        bool known = cell_of(V, gx, gy, gz, fx, fy, fz);
+        Corners c;
+        if (SKIP && known) {
+            const int bx = (int)fx >> 3, by = (int)fy >> 3, bz = (int)fz >> 3;
+            const int block = (bz * V.nby + by) * V.nbx + bx;
+            // (fetching the corners together with a new block's flag, so that the flag's latency is not in front of theirs, was measured:
+            // no faster where blocks are flagged, 18 % slower where they are not - profiles/tsdf/README.md)
+            if (block != cur_block) cur_block = block, cur_flag = V.flags[block];
+            if (!cur_flag) {
+                // Nothing in this block is known: leave it.  t_exit is where the ray leaves the block shrunk by kMargin; the samples up
+                // to two before it lie inside the block (g is monotone in k on every axis, in fp32 too), so they are not known either.
+                const float kMargin = 0.01f;
+                const float lo[3] = {(float)(bx * 8), (float)(by * 8), (float)(bz * 8)}, og[3] = {ogx, ogy, ogz}, dg[3] = {dgx, dgy, dgz};
+                float t_exit = INFINITY;
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    if (dg[ax] > 0.f) t_exit = fminf(t_exit, ((lo[ax] + (8.f - kMargin)) - og[ax]) / dg[ax]);
+                    if (dg[ax] < 0.f) t_exit = fminf(t_exit, ((lo[ax] + kMargin) - og[ax]) / dg[ax]);
+                }
+                const float kn = fminf(fmaxf(floorf((t_exit - near) / step) - 1.f, (float)(k + 1)), (float)(k_last + 1));  // NaN -> k + 1
+                k = (int)kn;
+                prev_known = false;
+                continue;
+            }
+        }
+        if (known) known = load_corners(V, gx, gy, gz, fx, fy, fz, c);
+        if (known) {
+            f = trilinear(c);
+            ++known_count;
+            if (prev_known && f_prev > 0.f && f <= 0.f) {
+                const float t_prev = near + (float)(k - 1) * step;
+                t_star = t_prev + step * (f_prev / (f_prev - f));
+                hit_k = k;
+                break;
+            }
+        }
+        prev_known = known, f_prev = f;
+        ++k;
+    }
+
+    const int total = hit_k >= 0 ? hit_k + 1 : a.max_steps;
+    unsigned flags = hit_k >= 0 ? IDH_TSDF_HIT : 0u;
+    if (known_count == 0) flags |= IDH_TSDF_NONE_KNOWN;
+    else if (known_count < total) flags |= IDH_TSDF_SOME_KNOWN;
+    const size_t pix = ((size_t)b * a.H + i) * a.W + j, plane = (size_t)a.H * a.W;
+    a.depth[pix] = hit_k >= 0 ? t_star * dcz : a.empty_depth;
+    if (NORMALS) {
+        float nx = 0.f, ny = 0.f, nz = 0.f;
+        if (hit_k >= 0) {
+            const float gx = ogx + t_star * dgx, gy = ogy + t_star * dgy, gz = ogz + t_star * dgz;
+            float fx, fy, fz;
+            Corners c;
+            bool ok = cell_of(V, gx, gy, gz, fx, fy, fz);
+            if (ok) ok = load_corners(V, gx, gy, gz, fx, fy, fz, c);
+            if (ok) {
+                // rows: a = (y0,z0), b = (y1,z0), c = (y0,z1), d = (y1,z1); .x / .z are T at x0 / x1
+                const float Gx = lerp(lerp(c.a.z - c.a.x, c.b.z - c.b.x, c.ry), lerp(c.c.z - c.c.x, c.d.z - c.d.x, c.ry), c.rz);
+                const float Gy = lerp(lerp(c.b.x - c.a.x, c.b.z - c.a.z, c.rx), lerp(c.d.x - c.c.x, c.d.z - c.c.z, c.rx), c.rz);
+                const float Gz = lerp(lerp(c.c.x - c.a.x, c.c.z - c.a.z, c.rx), lerp(c.d.x - c.b.x, c.d.z - c.b.z, c.rx), c.ry);
+                const float len = sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz);
+                ok = len > 0.f;
+                if (ok) {
+                    float wx = Gx / len, wy = Gy / len, wz = Gz / len;
+                    if ((wx * dx + wy * dy) + wz * dz > 0.f) wx = -wx, wy = -wy, wz = -wz;
+                    if (a.world_normals) {
+                        nx = wx, ny = wy, nz = wz;
+                    } else {  // R^T N
+                        nx = (E[0] * wx + E[4] * wy) + E[8] * wz;
+                        ny = (E[1] * wx + E[5] * wy) + E[9] * wz;
+                        nz = (E[2] * wx + E[6] * wy) + E[10] * wz;
+                    }
+                }
+            }
+            if (!ok) flags |= IDH_TSDF_NO_NORMAL;
+        }
+        float *o = a.normals + (size_t)b * 3 * plane + (size_t)i * a.W + j;
+        o[0] = nx, o[plane] = ny, o[2 * plane] = nz;
+    }
+    a.flags[pix] = (uint8_t)flags;
+}
+
+bool finite_pos(float x) { return x > 0.f && x < INFINITY; }
+
+// the volume's conditions, in the header's order
+int check_volume(const idh_tsdf_volume &e, Vol &V) {
+    if (e.struct_size < (int64_t)sizeof(idh_tsdf_volume)) return IDH_EINVAL;
+    if (e.Nz < 2 || e.Ny < 2 || e.Nx < 2) return IDH_EINVAL;
+    if (!finite_pos(e.voxel_size) || !finite_pos(e.trunc_voxels)) return IDH_EINVAL;
+    for (int i = 0; i < 3; ++i)
+        if (!(fabsf(e.origin[i]) < INFINITY)) return IDH_EINVAL;
+    if (!e.values) return IDH_EINVAL;
+    if ((long long)e.Nz * e.Ny * e.Nx >= (1ll << 31) || e.Nz > 65535 || e.Ny > 262140) return IDH_EUNSUPPORTED;
+    if (!e.block_flags || e.block_flag_bytes < 0 || (size_t)e.block_flag_bytes < idh_tsdf_block_flag_bytes(e.Nz, e.Ny, e.Nx)) return IDH_EWORKSPACE;
+    V.values = e.values, V.flags = e.block_flags;
+    V.ox = e.origin[0], V.oy = e.origin[1], V.oz = e.origin[2];
+    V.v = e.voxel_size, V.trunc = e.trunc_voxels * e.voxel_size;
+    V.Nx = e.Nx, V.Ny = e.Ny, V.Nz = e.Nz;
+    V.nbx = tsdf_blocks(e.Nx), V.nby = tsdf_blocks(e.Ny), V.nbz = tsdf_blocks(e.Nz);
+    return IDH_OK;
+}
+
+dim3 voxel_grid(const Vol &V) { return dim3(idh_cdiv(V.Nx, 64), idh_cdiv(V.Ny, 4), V.Nz); }
+
+int clear_volume(const Vol &V, bool values, hipStream_t st) {
+    const long long n = values ? (long long)V.Nx * V.Ny * V.Nz : 0, nb = (long long)V.nbx * V.nby * V.nbz;
+    hipLaunchKernelGGL(tsdf_reset_k, dim3(idh_cdiv(n > nb ? n : nb, 256)), dim3(256), 0, st, reinterpret_cast<float2 *>(V.values), n, V.flags, nb);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t idh_sizeof_tsdf_volume(void) { return sizeof(idh_tsdf_volume); }
+extern "C" size_t idh_sizeof_tsdf_integrate_args(void) { return sizeof(idh_tsdf_integrate_args); }
+extern "C" size_t idh_sizeof_tsdf_raycast_args(void) { return sizeof(idh_tsdf_raycast_args); }
+
+extern "C" size_t idh_tsdf_block_flag_bytes(int Nz, int Ny, int Nx) {
+    if (Nz < 2 || Ny < 2 || Nx < 2) return 0;
+    return (size_t)tsdf_blocks(Nz) * (size_t)tsdf_blocks(Ny) * (size_t)tsdf_blocks(Nx);
+}
+
+extern "C" int idh_tsdf_reset_fwd(const idh_tsdf_volume *vol, void *stream) {
+    if (!vol) return IDH_EINVAL;
+    Vol V;
+    if (const int rc = check_volume(*vol, V)) return rc;
+    return clear_volume(V, true, idh_stream(stream));
+}
+
+extern "C" int idh_tsdf_flags_fwd(const idh_tsdf_volume *vol, void *stream) {
+    if (!vol) return IDH_EINVAL;
+    Vol V;
+    if (const int rc = check_volume(*vol, V)) return rc;
+    hipStream_t st = idh_stream(stream);
+    if (const int rc = clear_volume(V, false, st)) return rc;
+    hipLaunchKernelGGL(tsdf_flags_k, voxel_grid(V), dim3(64, 4), 0, st, V);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" int idh_tsdf_integrate_fwd(const idh_tsdf_integrate_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_integrate_args)) return IDH_EINVAL;
+    const idh_tsdf_integrate_args &e = *args;
+    if (e.M <= 0 || e.h <= 0 || e.w <= 0) return IDH_EINVAL;
+    if (!(e.max_weight >= 1.f && e.max_weight < INFINITY)) return IDH_EINVAL;
+    if (!e.depth_m1hw || !e.K_m44 || !e.cam_T_world_m44) return IDH_EINVAL;
+    IntegrateArgs a;
+    if (const int rc = check_volume(e.volume, a.V)) return rc;
+    if (e.M > IDH_TSDF_MAX_MAPS || (long long)e.M * e.h * e.w >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    a.depth = e.depth_m1hw, a.K = e.K_m44, a.T = e.cam_T_world_m44;
+    a.max_weight = e.max_weight, a.M = e.M, a.h = e.h, a.w = e.w;
+    hipLaunchKernelGGL(tsdf_integrate_k, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" int idh_tsdf_raycast_fwd(const idh_tsdf_raycast_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_raycast_args)) return IDH_EINVAL;
+    const idh_tsdf_raycast_args &e = *args;
+    if (e.B <= 0 || e.H <= 0 || e.W <= 0 || e.max_steps <= 0) return IDH_EINVAL;
+    if (!(e.step_voxels > 0.f && e.step_voxels <= 1.f)) return IDH_EINVAL;  // also refuses NaN
+    if (!(e.near >= 0.f && e.near < INFINITY) || e.empty_depth != e.empty_depth) return IDH_EINVAL;
+    if (!e.world_T_cam_b44 || !e.invK_b44 || !e.depth_b1hw || !e.flags_bhw) return IDH_EINVAL;
+    RaycastArgs a;
+    if (const int rc = check_volume(e.volume, a.V)) return rc;
+    if (e.B > IDH_TSDF_MAX_CAMERAS || (long long)e.B * e.H * e.W >= (1ll << 31) || e.max_steps > IDH_TSDF_MAX_STEPS) return IDH_EUNSUPPORTED;
+    a.world_T_cam = e.world_T_cam_b44, a.invK = e.invK_b44, a.depth = e.depth_b1hw, a.normals = e.normals_b3hw, a.flags = e.flags_bhw;
+    a.near = e.near, a.step_voxels = e.step_voxels, a.empty_depth = e.empty_depth;
+    a.max_steps = e.max_steps, a.world_normals = e.world_normals, a.B = e.B, a.H = e.H, a.W = e.W;
+    const dim3 grid(idh_cdiv(e.W, 16), idh_cdiv(e.H, 16), e.B);
+    hipStream_t st = idh_stream(stream);
+    if (e.skip) {
+        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<true, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tsdf_raycast_k<true, false>), grid, dim3(256), 0, st, a);
+    } else {
+        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<false, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tsdf_raycast_k<false, false>), grid, dim3(256), 0, st, a);
+    }
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}

@@ -59,7 +59,8 @@ class StreamingSession:
     first (``nearest_keys_first``); the dictionaries gain "view_key" / "view_search_key".  ``reset()`` empties that ring; like the last
     prediction it survives a tracking-lost code.  The same number bounds the ring of depth maps (``remember_depth``: a ``DepthModel``'s
     predictions, pushed by ``step``; lidar frames or an inferred depth, pushed by the caller) that ``warped_depth_for_view`` draws into
-    a live camera and the depth route of ``composite_asset`` composites against."""
+    a live camera and the depth route of ``composite_asset`` composites against.  ``start_fusion`` adds a memory that is not bounded by
+    that ring: every remembered map is also averaged into a TSDF volume (``fusion.TSDFVolume``) that ``fused_depth_for_view`` ray-casts."""
 
     def __init__(self, model: nn.Module, num_source_views: Optional[int] = None, buffer_size: Optional[int] = None, mode: str = "keyframe",
                  config=keyframes.DVMVS_Config, image_encoder: Optional[nn.Module] = None, math: Optional[str] = None,
@@ -117,6 +118,9 @@ class StreamingSession:
         # the last query_keyframes depth maps (remember_depth), newest first: (depth (1,1,h,w), world_T_cam float64 (4,4), invK (1,4,4)).
         # What warped_depth_for_view draws; a DepthModel's predictions are pushed by step(), lidar or an inferred depth by the caller.
         self._depth_ring: list = []
+        self._fusion: Optional[dict] = None  # start_fusion's arguments; the volume is made when the first map arrives
+        self._volume = None                  # fusion.TSDFVolume
+        self._fused_maps = 0                 # maps integrated since start_fusion / reset
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -125,6 +129,9 @@ class StreamingSession:
         self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
         self._key = None
         self._depth_ring = []
+        self._fused_maps = 0
+        if self._volume is not None:
+            self._volume.reset()  # (with origin=None the next first map centres the grid again)
         if self.query_keyframes > 1:
             self.hot.forget()
             self._ring_poses = {}
@@ -249,7 +256,7 @@ class StreamingSession:
             return self.hot.query_view(rendered_depth, invK, T, k["cam_T_world_b44"], k["K_s0_b44"], prior_inputs=pi, fill=fill)
 
     def composite_asset(self, image_u8: torch.Tensor, asset, world_T_cam, K: torch.Tensor, *, query_size: Sequence[int] = None,
-                        fill: float = -20.0, fade=None, bgr: bool = False, return_parts: bool = False):
+                        fill: float = -20.0, fade=None, bgr: bool = False, return_parts: bool = False, depth_source: Optional[str] = None):
         """The whole live frame, also on the frames where ``step`` returned None: the camera image ``image_u8`` (1,H,W,3) uint8 with
         ``asset`` - a ``raster.AssetRenderer`` - drawn into it at the live pose ``world_T_cam`` ((4,4) array or tensor), hidden where
         the scene is in front of it.  ``K`` ((4,4) or (1,4,4)) is the live camera's intrinsics at the image's H x W.  The asset is rendered
@@ -264,11 +271,20 @@ class StreamingSession:
         and RGBA in one render at H x W, ``warped_depth_for_view`` at ``query_size`` with ``WARP_FAR`` where no remembered map saw
         anything (the asset stays visible there), then ``compositing.composite_depth(image_u8, warped, virtual_depth=asset depth,
         virtual_rgba=rgba, fade=fade, bgr=bgr)``.  ``fill`` is not used; "asset_depth" is then (1,1,H,W) and the parts hold
-        ``warped_depth_for_view``'s entries."""
+        ``warped_depth_for_view``'s entries.
+
+        ``depth_source="fused"`` (any session after ``start_fusion``, a ``BDModel``'s fed with inferred depths included) takes the depth
+        route against the fused volume: ``fused_depth_for_view`` at ``query_size`` with ``WARP_FAR`` where no surface is hit; the parts
+        hold its entries.  ``None`` is the behaviour described above."""
         from . import compositing
 
-        depth_route = self.hot.binary_mlp is None  # a DepthModel: no occlusion MLP to ask, its remembered depth maps are warped instead
-        if (not self._depth_ring) if depth_route else (self._key is None):
+        if depth_source not in (None, "fused"):
+            raise _lib.IdhError(f"composite_asset: depth_source must be None or 'fused', got {depth_source!r}")
+        fused = depth_source == "fused"
+        depth_route = fused or self.hot.binary_mlp is None  # a DepthModel: no occlusion MLP to ask, its remembered depth maps are warped instead
+        if fused and self._fusion is None:
+            raise _lib.IdhError("composite_asset(depth_source='fused') needs start_fusion()")
+        if (self._fused_maps == 0) if fused else (not self._depth_ring) if depth_route else (self._key is None):
             raise _lib.IdhError("no prediction has been made in this sequence yet (step() returned None so far)")
         if not isinstance(image_u8, torch.Tensor) or image_u8.dim() != 4 or image_u8.shape[0] != 1 or image_u8.shape[-1] != 3:
             raise _lib.IdhError("composite_asset: image_u8 must be one (1,H,W,3) uint8 frame on the GPU")
@@ -282,8 +298,11 @@ class StreamingSession:
         K_query[:, 1] *= h / H
         if depth_route:
             full = asset.render(world_T_cam, K, (H, W))  # composite_depth compares at the image's resolution
-            v = self.warped_depth_for_view(world_T_cam, K_query, (h, w), empty_depth=self.WARP_FAR)
-            frame = compositing.composite_depth(image_u8, v["view_warp_depth"], virtual_depth=full["depth"][:, 0], virtual_rgba=full["rgba"],
+            if fused:
+                v = self.fused_depth_for_view(world_T_cam, torch.linalg.inv(K_query), (h, w), empty_depth=self.WARP_FAR)
+            else:
+                v = self.warped_depth_for_view(world_T_cam, K_query, (h, w), empty_depth=self.WARP_FAR)
+            frame = compositing.composite_depth(image_u8, v["view_fused_depth" if fused else "view_warp_depth"], virtual_depth=full["depth"][:, 0], virtual_rgba=full["rgba"],
                                                 fade=fade, bgr=bgr)
             if return_parts:
                 return {**v, "frame": frame, "asset_depth": full["depth"], "asset_rgba": full["rgba"]}
@@ -316,6 +335,67 @@ class StreamingSession:
         pose = _pose_f64("world_T_cam", world_T_cam)
         self._depth_ring.insert(0, (depth_11hw.detach().clone(), pose, invK.detach().clone()))
         del self._depth_ring[self.query_keyframes:]
+        if self._fusion is not None:
+            self._fuse(self._depth_ring[0][0], pose, invK)
+
+    def start_fusion(self, voxel_size: float = 0.04, dims: Sequence[int] = (96, 256, 256), origin=None, trunc_voxels: float = 3.0,
+                     max_weight: float = 64.0) -> None:
+        """From now on ``remember_depth`` - which ``step`` calls with a ``DepthModel``'s predictions - also averages the map it pushes
+        into a TSDF volume of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres (``fusion.TSDFVolume``), which
+        ``fused_depth_for_view`` ray-casts: maps are combined, holes one map left are filled by another, and a map that has left the ring
+        is still in the volume.  ``origin``: the world (x, y, z) of voxel (0,0,0)'s centre; None centres the grid on the camera position
+        of the first map integrated.  ``reset()`` empties the volume and keeps its storage.  Calling it again starts a new volume."""
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 2 or not float(voxel_size) > 0:
+            raise _lib.IdhError(f"start_fusion: dims {dims} must be three sizes >= 2 and voxel_size {voxel_size} positive")
+        self._fusion = dict(voxel_size=float(voxel_size), dims=dims, origin=None if origin is None else tuple(float(o) for o in origin),
+                            trunc_voxels=float(trunc_voxels), max_weight=float(max_weight))
+        self._volume, self._fused_maps = None, 0
+
+    def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor) -> None:
+        from .fusion import TSDFVolume
+
+        f = self._fusion
+        if self._fused_maps == 0:
+            origin = f["origin"]
+            if origin is None:  # the camera sits at the centre of the grid
+                nz, ny, nx = f["dims"]
+                origin = tuple(pose[:3, 3] - f["voxel_size"] * 0.5 * (np.array([nx, ny, nz], dtype=np.float64) - 1.0))
+            if self._volume is None:
+                self._volume = TSDFVolume(f["dims"], f["voxel_size"], origin, f["trunc_voxels"], f["max_weight"], device=depth_11hw.device)
+            self._volume.origin = tuple(float(o) for o in origin)
+        cam_T_world = torch.from_numpy(np.linalg.inv(pose).astype(np.float32))[None]  # inverted in float64 on the host
+        self._volume.integrate(depth_11hw, torch.linalg.inv(invK_144), cam_T_world)
+        self._fused_maps += 1
+
+    @property
+    def fusion_volume(self):
+        """The ``fusion.TSDFVolume`` of ``start_fusion`` (None before the first map)."""
+        return self._volume
+
+    def fused_depth_for_view(self, world_T_cam, invK: torch.Tensor, size: Sequence[int], near: float = 0.25, far: float = 8.0,
+                             step_voxels: float = 1.0, empty_depth: float = -1.0, return_normals: bool = False) -> Dict[str, torch.Tensor]:
+        """The fused surface in the LIVE camera, also on the frames where ``step`` returned None: the volume of ``start_fusion`` ray-cast
+        into the ``size`` = (H, W) image of the camera at ``world_T_cam`` ((4,4) array or tensor; taken to float32 from float64 on the
+        host) with inverse intrinsics ``invK`` ((4,4) or (1,4,4), at H x W) - ``TSDFVolume.raycast``, one launch.  Returns
+        "view_fused_depth" (1,1,H,W): the camera's z of the first surface between ``near`` and ``far`` metres along each pixel's ray,
+        ``empty_depth`` where "view_fused_valid" (1,1,H,W) bool is False; "view_fused_flags" (1,H,W) uint8 (``fusion.FLAG_*``: a ray
+        without a hit crossed only unobserved space, partly observed space, or - flags 0 - observed free space); with
+        ``return_normals`` "view_fused_normals" (1,3,H,W), unit normals in WORLD space that face the camera, zero where there is none."""
+        from .raster import _pose_f64
+
+        if self._fusion is None:
+            raise _lib.IdhError("fused_depth_for_view needs start_fusion()")
+        if self._fused_maps == 0:
+            raise _lib.IdhError("no prediction has been made in this sequence yet and no depth map was remembered (remember_depth)")
+        _lib.require_cuda_f32(invK)
+        T = torch.from_numpy(_pose_f64("world_T_cam", world_T_cam).astype(np.float32))[None]
+        out = self._volume.raycast(T, invK.reshape(-1, 4, 4)[:1], (int(size[0]), int(size[1])), near=near, far=far, step_voxels=step_voxels,
+                                   empty_depth=empty_depth, return_normals=return_normals, world_normals=True)
+        res = {"view_fused_depth": out["depth"], "view_fused_valid": ((out["flags"] & 1) != 0)[:, None], "view_fused_flags": out["flags"]}
+        if return_normals:
+            res["view_fused_normals"] = out["normals"]
+        return res
 
     def warped_depth_for_view(self, world_T_cam, K: torch.Tensor, size: Sequence[int], tear_ratio: float = 1.1, empty_depth: float = -1.0,
                               return_source: bool = False) -> Dict[str, torch.Tensor]:

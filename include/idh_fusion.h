@@ -1,0 +1,154 @@
+/*
+ * idh_fusion.h — TSDF fusion of depth maps and the ray cast of the fused surface into live cameras (additive: idh_version() stays as it
+ * is; every struct is versioned through its struct_size; csrc/tsdf.hip).
+ *
+ * The depth warp of idh_raster.h draws remembered maps as separate sheets under one z-buffer: maps are not combined, holes stay holes
+ * and the memory is as long as the ring.  Here every map is averaged into a truncated signed distance volume (Curless and Levoy) - the
+ * step the reference's workflow takes off line with open3d ("for mesh fusion") before --temporal_eval - and a live camera ray-casts it.
+ *
+ * Conventions shared with the rest of the library: OpenCV intrinsics fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]; pixel
+ * (row i, column j) has its centre at (j + 0.5, i + 0.5), the convention of BackprojectDepth (utils/geometry_utils.py:39,60-61), so the
+ * pixel that holds image point (px, py) is (floor(py), floor(px)); device pointers, dense fp32, caller-owned storage, `stream` a
+ * hipStream_t, asynchronous, IDH_OK or a negative IDH_E* code.  Arguments are validated on the host before anything is launched.
+ * All device arithmetic is fp32 without contraction, in the order written below.
+ *
+ * The volume
+ *   dims (Nz, Ny, Nx), axis-aligned with the world; voxel (x, y, z) has its centre at origin + voxel_size * (x, y, z);
+ *   values (Nz, Ny, Nx, 2) fp32, x fastest among voxels: the pair {T, W} - truncated signed distance in units of the truncation
+ *   distance, in [-1, 1], and the number of observations.  An empty volume holds {1, 0} everywhere.
+ *   trunc = trunc_voxels * voxel_size (one fp32 multiply).
+ *   block_flags: one byte per 8 x 8 x 8 block of CELLS (cell (x, y, z) is the cube between voxels (x..x+1, y..y+1, z..z+1); an axis of
+ *   N voxels has N - 1 cells and (N + 6) / 8 blocks, the last one partial), (NBz, NBy, NBx), x fastest.  The guarantee: a block whose
+ *   byte is 0 has W == 0 at EVERY voxel any of its cells reads (its 8 x 8 x 8 cells read 9 x 9 x 9 voxels) - no sample inside it is
+ *   known.  This is a superset of "some voxel there has W > 0 and T < 1": the ray cast's flag bits 2 and 4 count known samples, and
+ *   observed free space (W > 0, T == 1) is known, so only blocks without any observation can be jumped without changing a bit.
+ *   Bytes are set by idh_tsdf_integrate_fwd, rebuilt by idh_tsdf_flags_fwd, cleared by idh_tsdf_reset_fwd alone.
+ */
+#ifndef IDH_FUSION_H_
+#define IDH_FUSION_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "idh.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+#if defined(__GNUC__) || defined(__clang__)
+#pragma GCC visibility push(default)
+#endif
+
+#define IDH_TSDF_MAX_MAPS 16      /* M of one integrate call: pipeline.MAX_RING_CAPACITY */
+#define IDH_TSDF_MAX_CAMERAS 128  /* B of one ray cast */
+#define IDH_TSDF_MAX_STEPS 65536  /* max_steps of one ray cast (the range clip of `skip` is exact up to this lattice length) */
+
+#define IDH_TSDF_HIT 1          /* flags: a surface crossing was found */
+#define IDH_TSDF_NONE_KNOWN 2   /* no sample up to the end was known */
+#define IDH_TSDF_SOME_KNOWN 4   /* some but not all samples up to the end were known */
+#define IDH_TSDF_NO_NORMAL 8    /* a hit whose cell is not known or whose gradient is zero (only with normals_b3hw) */
+
+typedef struct idh_tsdf_volume {
+    int64_t struct_size;       /* sizeof(idh_tsdf_volume) of the caller's header (must be >= the library's) */
+    float *values;             /* (Nz,Ny,Nx,2) {T, W} */
+    uint8_t *block_flags;      /* idh_tsdf_block_flag_bytes(Nz, Ny, Nx) bytes */
+    int64_t block_flag_bytes;  /* what the caller allocated */
+    float origin[3];           /* world (x, y, z) of the centre of voxel (0,0,0) */
+    float voxel_size;          /* > 0, finite */
+    float trunc_voxels;        /* > 0, finite */
+    int32_t Nz, Ny, Nx;        /* each >= 2; Nz * Ny * Nx < 2^31 */
+} idh_tsdf_volume;
+
+typedef struct idh_tsdf_integrate_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *depth_m1hw;       /* (M,1,h,w) */
+    const float *K_m44;            /* (M,4,4) intrinsics at h x w, row-major */
+    const float *cam_T_world_m44;  /* (M,4,4) */
+    float max_weight;              /* >= 1, finite */
+    int32_t M, h, w;
+} idh_tsdf_integrate_args;
+
+typedef struct idh_tsdf_raycast_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *world_T_cam_b44;  /* (B,4,4) */
+    const float *invK_b44;         /* (B,4,4) inverse intrinsics at H x W */
+    float *depth_b1hw;             /* out (B,1,H,W) */
+    uint8_t *flags_bhw;            /* out (B,H,W) */
+    float *normals_b3hw;           /* out (B,3,H,W), or NULL */
+    float near;                    /* >= 0, finite: t of sample 0 */
+    float step_voxels;             /* in (0, 1] */
+    float empty_depth;             /* written to depth where there is no hit */
+    int32_t max_steps;             /* 1 .. IDH_TSDF_MAX_STEPS */
+    int32_t world_normals;         /* 0: normals in the camera's frame, 1: in the world's */
+    int32_t skip;                  /* 0: the plain march over every sample, 1: range clip and block jumps (same bits) */
+    int32_t B, H, W;
+} idh_tsdf_raycast_args;
+
+/* sizeof(...) as compiled into the library (bindings assert their mirrors match). */
+size_t idh_sizeof_tsdf_volume(void);
+size_t idh_sizeof_tsdf_integrate_args(void);
+size_t idh_sizeof_tsdf_raycast_args(void);
+
+/* Bytes of the block flags of a (Nz, Ny, Nx) volume: ((Nz + 6) / 8) * ((Ny + 6) / 8) * ((Nx + 6) / 8).  0 if a dim is < 2. */
+size_t idh_tsdf_block_flag_bytes(int Nz, int Ny, int Nx);
+
+/* What every entry point below checks of its volume, in this order.
+ * IDH_EINVAL: struct_size short, a dim < 2, voxel_size or trunc_voxels not finite and > 0, an origin component not finite, values NULL;
+ * IDH_EUNSUPPORTED: Nz * Ny * Nx >= 2^31, Nz > 65535 or Ny > 262140 (the launch grid's limits);
+ * IDH_EWORKSPACE: block_flags NULL or block_flag_bytes < idh_tsdf_block_flag_bytes(Nz, Ny, Nx) - the caller-owned side storage is
+ * answered like a short workspace everywhere else in the library. */
+
+/* Every voxel to {1, 0}, every block flag to 0.  IDH_EINVAL also for vol == NULL. */
+int idh_tsdf_reset_fwd(const idh_tsdf_volume *vol, void *stream);
+
+/* Rebuild the block flags from the values (for a pair tensor made elsewhere): a block's byte is 1 iff W > 0 at some voxel its cells read. */
+int idh_tsdf_flags_fwd(const idh_tsdf_volume *vol, void *stream);
+
+/* M depth maps into the volume, one launch, one lane per voxel.  Per voxel (x, y, z), for m = 0 .. M - 1 in this order:
+ *   p = origin + voxel_size * (x, y, z)                                  (per component: one multiply, one add)
+ *   c = R p + t from cam_T_world[m]: c.x = ((r00 p.x + r01 p.y) + r02 p.z) + t.x, likewise y, z;   skip unless c.z > 0
+ *   px = fx * (c.x / c.z) + cx,  py = fy * (c.y / c.z) + cy;  tap (i, j) = (floor(py), floor(px));
+ *   skip unless 0 <= px < w and 0 <= py < h and d = depth[m, i, j] is finite and > 0                (the validity rule of the warp)
+ *   sdf = d - c.z   (projective, along the camera's z);  skip if sdf < -trunc;  s = min(1, sdf / trunc)
+ *   T <- (W * T + s) / (W + 1);   W <- min(W + 1, max_weight)
+ * The lane keeps {T, W} in registers over the M maps: it loads them when the first map touches the voxel and stores them once; a
+ * voxel no map touches reads and writes nothing of the volume.  So two calls return the same bits, and one call with M maps equals M
+ * calls with one map each, bit for bit.  Flags of the blocks a touched voxel belongs to are set to 1 (plain byte stores of one value).
+ * IDH_EINVAL: args NULL, struct_size short, M, h or w <= 0, max_weight < 1 or not finite, a null input; the volume's conditions;
+ * IDH_EUNSUPPORTED: M > IDH_TSDF_MAX_MAPS, h * w >= 2^31 / M. */
+int idh_tsdf_integrate_fwd(const idh_tsdf_integrate_args *args, void *stream);
+
+/* The fused surface in B cameras, one launch, one lane per pixel, 8 x 8-pixel tiles per wave.  Per pixel (i, j) of camera b:
+ *   q = invK[:3,:3] (j + 0.5, i + 0.5, 1): q.x = (k00 u + k01 v) + k02, ...;  n = sqrt((q.x q.x + q.y q.y) + q.z q.z);  dc = q / n
+ *   dir = R dc (as c above, without t), o = t from world_T_cam;   og = (o - origin) / voxel_size,  dg = dir / voxel_size  (per component)
+ *   step = step_voxels * voxel_size;  sample k = 0 .. max_steps - 1:  t_k = near + (float)k * step,  g = og + t_k * dg,  cell = floor(g)
+ *   the sample is KNOWN when 0 <= cell <= N - 2 on the three axes and the eight voxels cell + {0,1}^3 all have W > 0; then with
+ *   r = g - cell:  along x  a_yz = T_yz0 + r.x * (T_yz1 - T_yz0),  then y  b_z = a_0z + r.y * (a_1z - a_0z),  then z  f = b_0 + r.z * (b_1 - b_0)
+ *   HIT: the first k >= 1 with samples k - 1 and k known, f_{k-1} > 0 and f_k <= 0:
+ *        t* = t_{k-1} + step * (f_{k-1} / (f_{k-1} - f_k));   depth = t* * dc.z   (the camera's z of the point; no further refinement)
+ *   A ray that starts behind a surface, or enters one from unobserved space, does not hit there and marches on.
+ *   flags: IDH_TSDF_HIT; with "the end" = the hit's k (samples 0 .. k) or max_steps (all samples): IDH_TSDF_NONE_KNOWN when none of them
+ *   was known, IDH_TSDF_SOME_KNOWN when some but not all were; no hit and neither bit: the ray crossed observed free space only.
+ *   depth = empty_depth when there is no hit.
+ *   normals (optional): at a hit, g* = og + t* dg and its cell; if that cell is known, the gradient of the interpolant there,
+ *        G.x = lerp_z(lerp_y(T001 - T000, T011 - T010), lerp_y(T101 - T100, T111 - T110))   (Tzyx; lerp(a, b) = a + r (b - a)),
+ *        G.y = lerp_z(lerp_x(T010 - T000, T011 - T001), lerp_x(T110 - T100, T111 - T101)),
+ *        G.z = lerp_y(lerp_x(T100 - T000, T101 - T001), lerp_x(T110 - T010, T111 - T011)),
+ *        N = G / sqrt((G.x G.x + G.y G.y) + G.z G.z), negated if N . dir > 0 (towards the camera); world_normals == 0 stores R^T N.
+ *        Zero, with IDH_TSDF_NO_NORMAL set, when the cell is not known or G is zero; zero where there is no hit.
+ * skip: the lattice range is clipped to the volume's box and blocks whose flag is 0 are jumped to the first lattice sample that may
+ * lie past them; every sample left out is one the plain march finds not known, so both marches return the same bits.
+ * IDH_EINVAL: args NULL, struct_size short, B, H or W <= 0, max_steps <= 0, step_voxels outside (0, 1] or NaN, near < 0 or not finite,
+ * empty_depth NaN, a null world_T_cam / invK / depth / flags; the volume's conditions;
+ * IDH_EUNSUPPORTED: B > IDH_TSDF_MAX_CAMERAS, B * H * W >= 2^31, max_steps > IDH_TSDF_MAX_STEPS. */
+int idh_tsdf_raycast_fwd(const idh_tsdf_raycast_args *args, void *stream);
+
+#if defined(__GNUC__) || defined(__clang__)
+#pragma GCC visibility pop
+#endif
+#ifdef __cplusplus
+}
+#endif
+#endif /* IDH_FUSION_H_ */
