@@ -7,7 +7,7 @@ own ``to_fast()`` precedent (reference ``test_bd.py:80-81``).
 """
 __version__ = "0.1.0"
 
-_EXPORTS = {"MeshDepthRasterizer": "raster", "TSDFVolume": "fusion", "load_ply": "raster", "AssetRenderer": "raster", "TemporalEvaluator": "evaluation", "temporal_final_metrics": "evaluation",
+_EXPORTS = {"MeshDepthRasterizer": "raster", "TSDFVolume": "fusion", "load_ply": "raster", "save_ply": "raster", "AssetRenderer": "raster", "TemporalEvaluator": "evaluation", "temporal_final_metrics": "evaluation",
             "FrameIngest": "ingest", "load_color": "ingest", "load_depth": "ingest", "intrinsics_pyramid": "ingest",
             "StreamingSession": "streaming", "FeatureBank": "feature_bank", "KeyframeBuffer": "keyframes"}
 

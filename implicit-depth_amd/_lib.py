@@ -205,6 +205,18 @@ class TsdfRaycastArgs(C.Structure):
         self.struct_size = C.sizeof(TsdfRaycastArgs)
 
 
+class TsdfMeshArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_mesh_args`` (include/idh_fusion.h, mesh extraction)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("volume", TsdfVolume), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("totals", C.c_void_p), ("verts_v3", C.c_void_p), ("faces_f3", C.c_void_p), ("weights_v", C.c_void_p),
+                ("vert_capacity", C.c_int64), ("face_capacity", C.c_int64), ("min_weight", C.c_float), ("use_block_flags", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfMeshArgs)
+
+
 TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
 TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
 
@@ -324,6 +336,10 @@ _SIGS = {
     "idh_tsdf_flags_fwd": (C.c_int, [C.POINTER(TsdfVolume), C.c_void_p]),
     "idh_tsdf_integrate_fwd": (C.c_int, [C.POINTER(TsdfIntegrateArgs), C.c_void_p]),
     "idh_tsdf_raycast_fwd": (C.c_int, [C.POINTER(TsdfRaycastArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_mesh_args": (C.c_size_t, []),
+    "idh_tsdf_mesh_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "idh_tsdf_mesh_count_fwd": (C.c_int, [C.POINTER(TsdfMeshArgs), C.c_void_p]),
+    "idh_tsdf_mesh_emit_fwd": (C.c_int, [C.POINTER(TsdfMeshArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -396,7 +412,7 @@ def lib():
         for name, (res, args) in _all_sigs().items():
             try:
                 fn = getattr(h, name)
-            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd, idh_depth_warp_fwd, idh_tsdf_integrate_fwd, idh_tsdf_raycast_fwd) are found missing here
+            except AttributeError:  # entry points added without an ABI bump (additive: idh_binary_mlp_rays_fwd, idh_project_points_fwd, idh_binary_mlp_rays_search_fwd, idh_binary_mlp_view_fwd, idh_binary_mlp_view_search_fwd, idh_binary_mlp_view_keys_fwd, idh_binary_mlp_view_keys_search_fwd, idh_binary_mlp_view_march_fwd, idh_binary_mlp_view_keys_march_fwd, idh_depth_normals_fwd, idh_patch_normals_fwd, idh_raster_shaded_fwd, idh_depth_warp_fwd, idh_tsdf_integrate_fwd, idh_tsdf_raycast_fwd, idh_tsdf_mesh_count_fwd) are found missing here
                 raise IdhError(f"{LIB_PATH} does not export {name}: it was built from an older tree; rebuild with `python implicit-depth_amd/build.py --force`") from None
             fn.restype = res
             fn.argtypes = args
@@ -418,7 +434,8 @@ def lib():
                                   ("idh_depth_warp_args", h.idh_sizeof_depth_warp_args(), DepthWarpArgs),
                                   ("idh_tsdf_volume", h.idh_sizeof_tsdf_volume(), TsdfVolume),
                                   ("idh_tsdf_integrate_args", h.idh_sizeof_tsdf_integrate_args(), TsdfIntegrateArgs),
-                                  ("idh_tsdf_raycast_args", h.idh_sizeof_tsdf_raycast_args(), TsdfRaycastArgs)):
+                                  ("idh_tsdf_raycast_args", h.idh_sizeof_tsdf_raycast_args(), TsdfRaycastArgs),
+                                  ("idh_tsdf_mesh_args", h.idh_sizeof_tsdf_mesh_args(), TsdfMeshArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

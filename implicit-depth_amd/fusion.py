@@ -3,7 +3,9 @@
 ``raster.warp_depth`` draws remembered depth maps as separate sheets: the nearest one wins, holes stay holes, and a map that has left
 the ring is forgotten.  ``TSDFVolume`` averages every map into a dense truncated signed distance grid (Curless and Levoy) - the step
 the reference's workflow takes off line with open3d before ``--temporal_eval`` - and ``raycast`` returns the fused surface in any camera.
-There is no CPU fallback: the tensors live on the GPU and both halves are HIP kernels."""
+``extract_mesh`` turns the volume into an indexed triangle mesh (marching cubes, csrc/tsdf_mesh.hip) that the mesh
+consumers of ``raster`` and ``evaluation`` take as it is.  There is no CPU fallback: the tensors live on the GPU and every step is a
+HIP kernel."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +18,7 @@ import torch
 from . import _lib
 
 FLAG_HIT, FLAG_NONE_KNOWN, FLAG_SOME_KNOWN, FLAG_NO_NORMAL = _lib.TSDF_HIT, _lib.TSDF_NONE_KNOWN, _lib.TSDF_SOME_KNOWN, _lib.TSDF_NO_NORMAL
+MESH_USE_BLOCK_FLAGS = True  # extract_mesh's default: skip blocks no map has touched (same tensors either way; DESIGN.md §4.22 has the timings)
 
 
 def _mats(name, t, device) -> torch.Tensor:
@@ -86,6 +89,9 @@ class TSDFVolume:
         return raycast_volume(self, world_T_cam_b44, invK_b44, size, near=near, step_voxels=step_voxels, max_steps=int(math.ceil((far - near) / step)),
                               empty_depth=empty_depth, return_normals=return_normals, world_normals=world_normals, skip=skip)
 
+    def extract_mesh(self, min_weight: float = 0.0, return_weights: bool = False, use_block_flags: bool = MESH_USE_BLOCK_FLAGS) -> Dict[str, torch.Tensor]:
+        return extract_mesh(self, min_weight, return_weights, use_block_flags)
+
 
 def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44) -> None:
     """Average M depth maps (M,1,h,w) into ``volume`` in one launch (idh_tsdf_integrate_fwd): ``K_m44`` their intrinsics at h x w,
@@ -139,4 +145,67 @@ def raycast_volume(volume: TSDFVolume, world_T_cam_b44, invK_b44, size: Sequence
     a.near, a.step_voxels, a.empty_depth, a.max_steps = float(near), float(step_voxels), float(empty_depth), int(max_steps)
     a.world_normals, a.skip, a.B, a.H, a.W = int(bool(world_normals)), int(bool(skip)), B, H, W
     _lib.check(_lib.lib().idh_tsdf_raycast_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_raycast_fwd")
+    return out
+
+
+def _mesh_args(volume: TSDFVolume, workspace: torch.Tensor, min_weight: float, use_block_flags: bool) -> "_lib.TsdfMeshArgs":
+    a = _lib.TsdfMeshArgs()
+    a.volume = volume._struct()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    a.min_weight, a.use_block_flags = float(min_weight), int(bool(use_block_flags))
+    return a
+
+
+def mesh_count(volume: TSDFVolume, min_weight: float = 0.0, use_block_flags: bool = MESH_USE_BLOCK_FLAGS):
+    """The first half of ``extract_mesh`` (idh_tsdf_mesh_count_fwd): classify every cell and scan the counts.  Returns ``(workspace,
+    totals)``: the uint8 workspace ``mesh_emit`` reads and the int32 device tensor ``{V, F}``; nothing is read back to the host."""
+    nbytes = _lib.lib().idh_tsdf_mesh_workspace_bytes(*volume.dims)
+    if nbytes == 0:
+        raise _lib.IdhError(f"extract_mesh: a volume of {volume.dims} has more than 2^28 voxels")
+    dev = volume.values.device
+    workspace, totals = torch.empty(nbytes, device=dev, dtype=torch.uint8), torch.empty(2, device=dev, dtype=torch.int32)
+    a = _mesh_args(volume, workspace, min_weight, use_block_flags)
+    a.totals = totals.data_ptr()
+    _lib.check(_lib.lib().idh_tsdf_mesh_count_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_mesh_count_fwd")
+    return workspace, totals
+
+
+def mesh_emit(volume: TSDFVolume, workspace: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, weights: Optional[torch.Tensor] = None,
+              min_weight: float = 0.0, vert_capacity: Optional[int] = None, face_capacity: Optional[int] = None) -> None:
+    """The second half (idh_tsdf_mesh_emit_fwd): the first ``vert_capacity`` vertices into ``verts`` (rows, 3) float32 (and ``weights``
+    (rows,)), the first ``face_capacity`` faces into ``faces`` (rows, 3) int32, after ``mesh_count`` on the same volume.  The capacities
+    default to the tensors' rows and may not exceed them; nothing is written past them whatever the totals are."""
+    _lib.require_cuda_f32(verts, weights)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or not faces.is_cuda:
+        raise _lib.IdhError(f"mesh_emit: verts {tuple(verts.shape)} must be (V,3) float32 and faces {tuple(faces.shape)} {faces.dtype} (F,3) int32 on the GPU")
+    if not (verts.is_contiguous() and faces.is_contiguous() and (weights is None or weights.is_contiguous())):
+        raise _lib.IdhError("mesh_emit: the outputs must be contiguous")
+    vcap = verts.shape[0] if vert_capacity is None else int(vert_capacity)
+    fcap = faces.shape[0] if face_capacity is None else int(face_capacity)
+    if vcap > verts.shape[0] or fcap > faces.shape[0] or (weights is not None and (weights.dim() != 1 or vcap > weights.shape[0])):
+        raise _lib.IdhError(f"mesh_emit: capacities ({vcap}, {fcap}) exceed the tensors' rows")
+    a = _mesh_args(volume, workspace, min_weight, False)
+    # a tensor of no rows may have a null pointer: the C call wants an address even when it stores nothing there
+    a.verts_v3, a.faces_f3, a.weights_v = verts.data_ptr() or workspace.data_ptr(), faces.data_ptr() or workspace.data_ptr(), _lib.ptr(weights)
+    a.vert_capacity, a.face_capacity = vcap, fcap
+    _lib.check(_lib.lib().idh_tsdf_mesh_emit_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_mesh_emit_fwd")
+
+
+def extract_mesh(volume: TSDFVolume, min_weight: float = 0.0, return_weights: bool = False,
+                 use_block_flags: bool = MESH_USE_BLOCK_FLAGS) -> Dict[str, torch.Tensor]:
+    """The fused surface as an indexed triangle mesh: marching cubes over the cells whose eight voxels have ``W > min_weight``, a voxel
+    being inside where ``T <= 0`` (include/idh_fusion.h states vertex positions, orders and orientation).  Returns ``"verts"`` (V,3)
+    float32 in the world, ``"faces"`` (F,3) int32 with normals towards free space - what ``MeshDepthRasterizer.load_gt_mesh(verts=,
+    faces=)``, ``raster.render_depth``, ``render_shaded`` and ``save_ply`` take - and with ``return_weights`` ``"weights"`` (V,), the
+    observation count interpolated like the position.  Order and bits are deterministic.  Two groups of launches with one host read of the
+    two totals between them; an empty result has shapes (0,3).  ``use_block_flags`` skips the blocks no map has touched and changes no
+    bit."""
+    workspace, totals = mesh_count(volume, min_weight, use_block_flags)
+    V, F = totals.tolist()  # the one host read
+    dev = volume.values.device
+    out = {"verts": torch.empty(V, 3, device=dev), "faces": torch.empty(F, 3, device=dev, dtype=torch.int32)}
+    if return_weights:
+        out["weights"] = torch.empty(V, device=dev)
+    if V or F:
+        mesh_emit(volume, workspace, out["verts"], out["faces"], out.get("weights"), min_weight)
     return out

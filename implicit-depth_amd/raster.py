@@ -133,6 +133,42 @@ def load_ply(path, return_colors: bool = False):
     return pair
 
 
+def save_ply(path, verts, faces, colors=None) -> None:
+    """Write a triangle mesh as binary little-endian PLY that ``load_ply`` reads back exactly: ``verts`` (V,3) stored as float32,
+    ``faces`` (F,3) of any integer type stored as ``uchar`` count + ``int`` indices, ``colors`` (V,3) or (V,4) uint8 stored as
+    ``red green blue [alpha]`` uchar (the layout of ScanNet's meshes).  Tensors (GPU ones included) or arrays."""
+    def host(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+    v, f = host(verts), host(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError(f"save_ply: verts {v.shape} must be (V,3) and faces {f.shape} {f.dtype} an integer (F,3)")
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"save_ply: face index outside the {len(v)} vertices")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    names = ()
+    if colors is not None:
+        c = host(colors)
+        if c.dtype != np.uint8 or c.ndim != 2 or c.shape[0] != len(v) or c.shape[1] not in (3, 4):
+            raise ValueError(f"save_ply: colors {c.shape} {c.dtype} must be uint8 ({len(v)},3) or ({len(v)},4)")
+        names = ("red", "green", "blue", "alpha")[:c.shape[1]]
+        fields += [(n, "u1") for n in names]
+    vrec = np.empty(len(v), dtype=np.dtype(fields))
+    for j, k in enumerate("xyz"):
+        vrec[k] = v[:, j]
+    for j, k in enumerate(names):
+        vrec[k] = c[:, j]
+    frec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    frec["n"], frec["i"] = 3, f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y", "property float z"]
+    header += [f"property uchar {n}" for n in names]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vrec.tobytes())
+        out.write(frec.tobytes())
+
+
 def plane_faces(size: int = PLANE_SIZE) -> torch.Tensor:
     """The (2 (size-1)^2, 3) int64 faces of the size x size vertex grid in the order of the reference's double loop
     (binary_metrics_utils.py:315-323): for idx = h * size + w, (idx, idx + size + 1, idx + size) then (idx, idx + 1, idx + 1 + size)."""

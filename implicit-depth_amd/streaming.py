@@ -397,6 +397,17 @@ class StreamingSession:
             res["view_fused_normals"] = out["normals"]
         return res
 
+    def fused_mesh(self, min_weight: float = 0.0) -> Dict[str, torch.Tensor]:
+        """The session's own reconstruction as a triangle mesh: ``fusion.extract_mesh`` of the volume of ``start_fusion`` - "verts"
+        (V,3) float32 in the world, "faces" (F,3) int32, normals towards free space - as ``MeshDepthRasterizer.load_gt_mesh(verts=,
+        faces=)``, ``evaluation.TemporalEvaluator``, ``raster.render_shaded`` and ``raster.save_ply`` take them.  ``min_weight`` keeps
+        the cells whose eight voxels were observed more often than that."""
+        if self._fusion is None:
+            raise _lib.IdhError("fused_mesh needs start_fusion()")
+        if self._fused_maps == 0:
+            raise _lib.IdhError("no prediction has been made in this sequence yet and no depth map was remembered (remember_depth)")
+        return self._volume.extract_mesh(min_weight=min_weight)
+
     def warped_depth_for_view(self, world_T_cam, K: torch.Tensor, size: Sequence[int], tear_ratio: float = 1.1, empty_depth: float = -1.0,
                               return_source: bool = False) -> Dict[str, torch.Tensor]:
         """The remembered depth maps in the LIVE camera, also on the frames where ``step`` returned None: every map of the ring drawn as a

@@ -1,6 +1,7 @@
 /*
- * idh_fusion.h — TSDF fusion of depth maps and the ray cast of the fused surface into live cameras (additive: idh_version() stays as it
- * is; every struct is versioned through its struct_size; csrc/tsdf.hip).
+ * idh_fusion.h — TSDF fusion of depth maps, the ray cast of the fused surface into live cameras and its extraction as a triangle mesh
+ * (additive: idh_version() stays as it is; every struct is versioned through its struct_size; csrc/tsdf.hip, csrc/tsdf_mesh.hip,
+ * DESIGN.md §4.21, §4.22).
  *
  * The depth warp of idh_raster.h draws remembered maps as separate sheets under one z-buffer: maps are not combined, holes stay holes
  * and the memory is as long as the ring.  Here every map is averaged into a truncated signed distance volume (Curless and Levoy) - the
@@ -144,6 +145,59 @@ int idh_tsdf_integrate_fwd(const idh_tsdf_integrate_args *args, void *stream);
  * empty_depth NaN, a null world_T_cam / invK / depth / flags; the volume's conditions;
  * IDH_EUNSUPPORTED: B > IDH_TSDF_MAX_CAMERAS, B * H * W >= 2^31, max_steps > IDH_TSDF_MAX_STEPS. */
 int idh_tsdf_raycast_fwd(const idh_tsdf_raycast_args *args, void *stream);
+
+/* ---- Mesh extraction: marching cubes over the volume to an indexed triangle mesh (csrc/tsdf_mesh.hip) ----------
+ *
+ * Voxel values are compared as stored; no arithmetic decides topology.
+ *   A voxel is INSIDE when T <= 0 (the ray cast's f_{k-1} > 0, f_k <= 0) and KNOWN when W > min_weight (min_weight = 0: the ray cast's
+ *   W > 0).  A cell is KNOWN when its eight voxels are, and EMITTED when it is known and its case is neither 0 nor 255.
+ *   Corner c = dx + 2 dy + 4 dz of a cell; case bit c is set when corner c is inside.  Cube edge e = 4 * axis + j, axis 0/1/2 = x/y/z,
+ *   j = first + 2 * second of the edge's lower corner's two other coordinates in x < y < z order.  The grid edge from voxel a to
+ *   a + axis is OWNED by a.  The triangles of a case come from the table csrc/mc_table.h, generated by tools/gen_mc_table.py.
+ * Vertices.  One on every owned edge with exactly one endpoint inside that at least one emitted cell contains (no orphans, none
+ *   missing), ordered by ascending linear index of the owner ((z * Ny + y) * Nx + x), then axis.  With a the owner and b = a + axis:
+ *     r = T_a / (T_a - T_b)                                     (the denominator cannot be zero)
+ *     along the axis   origin + voxel_size * ((float)idx + r);   the other two   origin + voxel_size * (float)idx
+ *     weights (optional)   W_a + r * (W_b - W_a)
+ * Faces.  int32 triples of vertex indices, ordered by ascending linear index of the cell, then table order.  The right-hand normal
+ *   (v1 - v0) x (v2 - v0) points to the positive (free-space) side: a closed surface around an inside region has positive signed volume.
+ *   Degenerate triangles (a vertex at r = 0 or r = 1) are kept.
+ * Order and bits are deterministic: two extractions return equal arrays.
+ *
+ * Two calls.  idh_tsdf_mesh_count_fwd classifies every cell, scans the per-voxel vertex and triangle counts (a three-phase scan:
+ * per-workgroup sums, a scan of the sums, the bases added back; no workgroup waits on another) and leaves the totals {V, F} in
+ * `totals` and what the second call needs in `workspace`.  The caller reads the totals, allocates, and idh_tsdf_mesh_emit_fwd - same
+ * volume, min_weight and workspace - writes the first vert_capacity vertices and the first face_capacity faces: every store is guarded
+ * by the capacities, so a stale total cannot write out of bounds.
+ * use_block_flags: cells of a block whose flag is 0 are not read (none of them is known); the arrays are the same either way. */
+typedef struct idh_tsdf_mesh_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    void *workspace;          /* idh_tsdf_mesh_workspace_bytes(Nz, Ny, Nx) bytes, 16-byte aligned */
+    int64_t workspace_bytes;  /* what the caller allocated */
+    int32_t *totals;          /* count: out, 2 x int32 {V, F} on the device; emit: not read */
+    float *verts_v3;          /* emit: out (vert_capacity, 3); count: not read */
+    int32_t *faces_f3;        /* emit: out (face_capacity, 3); count: not read */
+    float *weights_v;         /* emit: out (vert_capacity), or NULL */
+    int64_t vert_capacity;    /* >= 0 */
+    int64_t face_capacity;    /* >= 0 */
+    float min_weight;         /* >= 0 */
+    int32_t use_block_flags;  /* 0: every cell is read; 1: blocks whose flag is 0 are skipped (same arrays) */
+} idh_tsdf_mesh_args;
+
+size_t idh_sizeof_tsdf_mesh_args(void);
+
+/* With n = Nz * Ny * Nx rounded up to a multiple of 4 and p_1 = ceil(n / 1024), p_{k+1} = ceil(p_k / 1024) while p_k > 1024:
+ * 8 n + 8 (p_1 + p_2 + ...) bytes - four bytes of {case, vertex on x, y, z} and a four-byte vertex base per voxel, and the scan's
+ * partial sums.  0 if a dim is < 2 or Nz * Ny * Nx > 2^28. */
+size_t idh_tsdf_mesh_workspace_bytes(int Nz, int Ny, int Nx);
+
+/* Both calls - IDH_EINVAL: args NULL, struct_size short, min_weight negative or NaN, a null output (count: totals; emit: verts_v3 or
+ * faces_f3), a negative capacity (emit); the volume's conditions; IDH_EUNSUPPORTED: Nz * Ny * Nx > 2^28 (int32 indices cannot overflow
+ * at five triangles per cell); IDH_EWORKSPACE: workspace NULL or workspace_bytes < idh_tsdf_mesh_workspace_bytes(Nz, Ny, Nx);
+ * IDH_EINVAL: workspace not 16-byte aligned. */
+int idh_tsdf_mesh_count_fwd(const idh_tsdf_mesh_args *args, void *stream);
+int idh_tsdf_mesh_emit_fwd(const idh_tsdf_mesh_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
