@@ -1728,7 +1728,9 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 break;
             }
             case IDH_OP_UPSAMPLE2_NEAREST: {
-                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0) return IDH_EINVAL;
+                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 ||
+                    s.cs < s.Cin || op.out_cs < s.Cin)
+                    return IDH_EINVAL;
                 const long long tot = (long long)op.N * 4 * s.H * s.W * (s.Cin >> 2);
                 int grid = idh_cdiv(tot, 256);
                 if (grid > 8192) grid = 8192;
@@ -1771,7 +1773,7 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 break;
             }
             case IDH_OP_NHWC_TO_NCHW: {
-                if (!s.in || !op.out || op.N <= 0 || op.N > 65535) return IDH_EINVAL;
+                if (!s.in || !op.out || op.N <= 0 || op.N > 65535 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 || s.cs < s.Cin) return IDH_EINVAL;
                 const int HW = s.H * s.W;
                 IDH_LAUNCH(export_nchw_k, dim3(idh_cdiv(HW, 64), idh_cdiv(s.Cin, 32), op.N), dim3(256), 0, st, s.in,
                                    op.out, s.Cin, HW, s.cs);
@@ -1779,7 +1781,8 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 break;
             }
             case IDH_OP_POINTWISE_HEAD: {
-                if (!s.in || !s.w || !op.out || (s.Cin & 3) || (s.cs & 3)) return IDH_EINVAL;
+                if (!s.in || !s.w || !op.out || (s.Cin & 3) || (s.cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 || s.cs < s.Cin)
+                    return IDH_EINVAL;
                 const long long M = (long long)op.N * s.H * s.W;
                 int grid = idh_cdiv(M, 256);
                 if (grid > 8192) grid = 8192;
@@ -1831,7 +1834,9 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
                 break;
             }
             case IDH_OP_COPY: {
-                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0) return IDH_EINVAL;
+                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 ||
+                    s.cs < s.Cin || op.out_cs < s.Cin)
+                    return IDH_EINVAL;
                 const long long npix = (long long)op.N * s.H * s.W;
                 int grid = idh_cdiv(npix * (s.Cin >> 2), 256);
                 if (grid > 8192) grid = 8192;
@@ -1842,7 +1847,7 @@ extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
             case IDH_OP_INSTNORM: {
                 const int C = s.Cin, HW = s.H * s.W;
                 if (!s.in || !op.ws || C <= 0 || (C & 3) || 256 % (C >> 2) || (s.cs & 3) || (op.out && (op.out_cs & 3)) ||
-                    op.N <= 0 || op.N > 65535)
+                    op.N <= 0 || op.N > 65535 || s.H <= 0 || s.W <= 0)  // (H W = 0: a zero-sized statistics grid)
                     return IDH_EINVAL;
                 const int nchunks = idh_cdiv(HW, kInChunk);
                 // C >= 64: the chunk is summed as 1024 / (C/4) rows at either block size (bit-identical statistics at every batch size)

@@ -29,15 +29,20 @@ enum {
     IDH_OP_UPSAMPLE2 = 2,   /* bilinear x2, align_corners=False (generic_utils.py:94-103).  32-bit element indices since ABI 104:
                                N*H*W*C/4 (input channel quads) and the same count of the output must stay below 2^31 - i.e. inputs
                                under 32 GiB - else IDH_EUNSUPPORTED (no 64-bit-index variant is kept; split the batch) */
-    IDH_OP_NCHW_TO_NHWC = 3,/* strided layout import: (N,C,H,W) -> NHWC slice                */
-    IDH_OP_NHWC_TO_NCHW = 4,/* strided layout export: NHWC slice -> (N,C,H,W)                */
+    IDH_OP_NCHW_TO_NHWC = 3,/* strided layout import: (N,C,H,W) dense -> NHWC slice of channel stride out_cs, any channel count;
+                               0 < N <= 65535, H, W, Cin > 0, else IDH_EINVAL.  Up to 8 consecutive imports with one non-zero group id share a
+                               grid; a member of more than 4096 blocks (64 pixels x 32 channels each) keeps its own */
+    IDH_OP_NHWC_TO_NCHW = 4,/* strided layout export: NHWC slice -> (N,C,H,W) dense.  src[0].in / .cs / .H / .W / .Cin = the slice, any channel count;
+                               0 < N <= 65535, H, W, Cin > 0, cs >= Cin, else IDH_EINVAL */
     IDH_OP_SPLITK_REDUCE = 5,/* RESERVED, never accepted: idh_run_ops / idh_count_launches answer IDH_EINVAL for it.  The sum of the
                                 split-K partials (+ bias + residual + activation) is implicit in an IDH_OP_CONV with split_k > 1, which
                                 launches its own reduce (one grid for all split members of a group); the number stays taken */
     IDH_OP_POINTWISE_HEAD = 6,/* 1x1 conv to 1 channel (DepthDecoderPP heads, networks.py:158-161); ws != NULL: a second
-                                 (N,1,H,W) output = exp(out), the depth map of depth_model.py:425-433 */
-    IDH_OP_COPY = 9,        /* channel-strided NHWC -> NHWC slice copy */
-    IDH_OP_UPSAMPLE2_NEAREST = 8, /* nearest x2 (SkipDecoder, networks_fast.py:43) */
+                                 (N,1,H,W) output = exp(out), the depth map of depth_model.py:425-433.  src[0].w = Cin floats, bias = 1 float or
+                                 NULL; N, H, W, Cin > 0, Cin and cs multiples of 4, cs >= Cin, else IDH_EINVAL */
+    IDH_OP_COPY = 9,        /* channel-strided NHWC -> NHWC slice copy.  N, H, W, Cin > 0, Cin / cs / out_cs multiples of 4, cs >= Cin and
+                               out_cs >= Cin (a narrower stride would make pixels overlap), else IDH_EINVAL */
+    IDH_OP_UPSAMPLE2_NEAREST = 8, /* nearest x2 (SkipDecoder, networks_fast.py:43); the rules of IDH_OP_COPY */
     IDH_OP_POINTWISE_NCHW = 10, /* 1x1 conv 64 -> 128 read straight from a dense (N,64,H,W) tensor into an NHWC slice: the first
                                    layer of the matching-encoder head (networks.py:279) without a layout-import pass;
                                    src[0].w = idh_pack_conv_weight(128, 64, 1); other widths: IDH_EUNSUPPORTED */
@@ -57,7 +62,7 @@ enum {
                                out_cs), channels [0, 64) written, 16-byte aligned, out_cs >= 64 and a multiple of 4; Cout = 64; Ho = floor(ceil(H/2) / 2),
                                Wo likewise.  bias / res / ws / act unused */
     IDH_OP_INSTNORM = 7     /* nn.InstanceNorm2d (no affine, eps 1e-5) [+ LeakyReLU] on NHWC; matching-encoder
-                               head networks.py:279-283.  ws: N*(ceil(HW/1024)+1)*2*C floats (chunk partials + mean/rstd);
+                               head networks.py:279-283.  0 < N <= 65535, H, W > 0, Cin a multiple of 4 with (Cin / 4) | 256, else IDH_EINVAL.  ws: N*(ceil(HW/1024)+1)*2*C floats (chunk partials + mean/rstd);
                                out == NULL: statistics only — float[N][2][C] at ws + N*ceil(HW/1024)*2*C, for a
                                consumer convolution that normalises on load (idh_conv_src.norm) */
 };
