@@ -31,6 +31,9 @@
 // view_march_k / view_keys_march_k are view_search_k / view_keys_search_k with the bracket found instead of assumed: every ray probes the
 // shared samples march_depths[0 .. n_march-1] in turn until the first probe that is behind the surface, then bisects `refine` steps inside
 // [previous sample, that sample].  Rays of a tile finish at different steps: a finished ray rides along as an invalid probe with its state frozen.
+#include <algorithm>
+#include <cfloat>
+#include <tuple>
 #include <type_traits>
 
 #include "idh_common.h"
@@ -40,6 +43,7 @@ namespace {
 
 using namespace idh_mlp;
 
+// (the host value-initialises an argument block and sets its fields by name - set_* in the host section: what a mode does not name is zero or null)
 struct RayArgs {
     const float *feat;   // NHWC rows, B*H*W x cs
     const float *rays;   // B,N,2
@@ -76,7 +80,7 @@ struct RayArgs {
 
 // view_keys_k / view_keys_search_k: `feat`, `key_cTw`, `key_K`, `prior`, `prior_cTw`, `prior_K` are rings indexed by slot - the features of
 // slot s start at feat + s * key_stride, the matrices are (n_slots,B,4,4), the prior maps (n_slots,B,1,H,W).  A separate struct: the four
-// single-key kernels keep their argument block as it is.
+// single-key kernels keep their argument block as it is.  On the host keys_args checks and fills these fields; set_common reads key_stride.
 constexpr int kMaxKeys = 16;
 struct KeysArgs : RayArgs {
     long long key_stride;     // floats between the feature blocks of two slots
@@ -636,16 +640,24 @@ __global__ __launch_bounds__(256) void project_points_k(const float *__restrict_
 
 }  // namespace
 
-// Work partition of one launch (host side, also what tests/ray_query_ref.py restates for its persistent-loop case):
-// an item is 16 rays x one run of samples.  While the ray tiles alone do not give every SIMD of the device (256 CUs x 4) a wave, the S
-// samples of a tile are cut into runs of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256
-// per sample), so N = 4096 rays x 64 samples run on 1024 waves instead of 256.  The search (S = 1) has one item per tile: its iterations are
-// dependent, so there is nothing to split.
-// view_keys_k / view_keys_search_k (KeysArgs): the same tile partition, one item per tile, M (B + 1) x 24 floats of cameras in LDS.
-// view_march_k / view_keys_march_k (MarchArgs / KeysMarchArgs): as their search parents, S = 1 and so one item per tile.
-template <class Args>
-static int ray_mlp_launch(Args a, void *stream, int mode = kSamples) {
-    constexpr bool keys = std::is_base_of<KeysArgs, Args>::value;
+// ---- host side ----
+// An entry point is the rules that apply to it, in the order that decides which code wins - argument errors (IDH_EINVAL), the empty call
+// (IDH_OK), missing and misaligned pointers (IDH_EINVAL), sizes (IDH_EUNSUPPORTED) -, then its argument block, value-initialised and filled by
+// name, then ray_mlp_launch<mode>.  A rule is one helper for every entry point that has it; what one has on its own stands in its body.
+constexpr bool mode_view(int m) { return m >= kView; }  // the rays come from another camera: cameras in LDS, grid = (W, H)
+constexpr bool mode_keys(int m) { return m == kViewKeys || m == kViewKeysSearch || m == kViewKeysMarch; }  // (kKeys of ray_body)
+
+// The kernels, in the order of the modes' enum; the argument struct of a mode is what its kernel takes
+constexpr auto kRayKernels = std::make_tuple(ray_mlp_k, ray_search_k, view_mlp_k, view_search_k, view_keys_k, view_keys_search_k, view_march_k, view_keys_march_k);
+static_assert(std::tuple_size<decltype(kRayKernels)>::value == kRayModes, "one kernel per mode");
+
+// Work partition of one launch (also what tests/ray_query_ref.py restates for its persistent-loop case): an item is 16 rays x one run of
+// samples.  While the ray tiles alone do not give every SIMD of the device (256 CUs x 4) a wave, the S samples of a tile are cut into runs
+// of at least kMinChunk (a run repeats the gather and the W1f product: 128 - 512 MFMAs against 256 per sample), so N = 4096 rays x 64
+// samples run on 1024 waves instead of 256.  Every mode but kSamples has S = 1 and so one item per tile: its evaluations are dependent,
+// there is nothing to split.  The kernel and the cameras' share of LDS follow from the mode: B x 48 floats for one key, (M + 1) B x 24 for M.
+template <int kMode, class Args>
+static int ray_mlp_launch(Args a, void *stream) {
     constexpr int kSimds = 256 * 4, kMinChunk = 8;
     const long long tiles = ((long long)a.M + 15) / 16;
     int nchunk = 1;
@@ -663,49 +675,125 @@ static int ray_mlp_launch(Args a, void *stream, int mode = kSamples) {
     long long grid = (items + waves - 1) / waves;
     if (grid > 256) grid = 256;
     const int cblocks = (a.Cf + 15) >> 4;
-    size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) +
-                       6 * kHidden * sizeof(float) + (mode == kView || mode == kViewSearch || mode == kViewMarch ? (size_t)a.nb * kCamFloats * sizeof(float) : 0) +
-                       (keys ? (size_t)a.nb * kKeyCamFloats * sizeof(float) : 0);
-    static IdhDeviceOnce attr_set[kRayModes];
-    void (*kernel)(const Args);
-    if constexpr (keys) lds += (size_t)a.nkeys * a.nb * kKeyCamFloats * sizeof(float);
-    if constexpr (std::is_same<Args, KeysMarchArgs>::value) {
-        kernel = view_keys_march_k;
-    } else if constexpr (std::is_same<Args, MarchArgs>::value) {
-        kernel = view_march_k;
-    } else if constexpr (keys) {
-        kernel = mode == kViewKeysSearch ? view_keys_search_k : view_keys_k;
-    } else {
-        kernel = mode == kViewSearch ? view_search_k : mode == kView ? view_mlp_k : mode == kSearch ? ray_search_k : ray_mlp_k;
-    }
-    if (attr_set[mode].first()) {
+    size_t lds = ((size_t)kNS * kNS * 64 + (cblocks <= kW1LdsMaxBlocks ? (size_t)cblocks * kNS * 64 : 0)) * sizeof(f32x4) + 6 * kHidden * sizeof(float);
+    if constexpr (mode_keys(kMode)) lds += (size_t)(a.nkeys + 1) * a.nb * kKeyCamFloats * sizeof(float);
+    else if constexpr (mode_view(kMode)) lds += (size_t)a.nb * kCamFloats * sizeof(float);
+    constexpr void (*kernel)(const Args) = std::get<kMode>(kRayKernels);  // (RayArgs, KeysArgs, MarchArgs or KeysMarchArgs: no other compiles)
+    static IdhDeviceOnce attr_set;
+    if (attr_set.first()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return IDH_ELAUNCH;
-        attr_set[mode].mark();
+        attr_set.mark();
     }
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(waves * 64), lds, idh_stream(stream), a);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }
 
+// ---- the rules ----
+using Ptrs = std::initializer_list<const void *>;
+static bool any_null(Ptrs ps) { return std::any_of(ps.begin(), ps.end(), [](const void *p) { return !p; }); }
+static bool any_misaligned(Ptrs ps) { return std::any_of(ps.begin(), ps.end(), [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }); }
+// the feature map and its shapes
+static bool feat_bad(int B, int H, int W, int Cf, int feat_cs) { return B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf; }
+// the constant threshold (n_bins = 0) or the tables of the per-depth Thresholder
+static bool threshold_bad(float threshold, const float *bins, const float *thr_logits, int n_bins) {
+    return n_bins < 0 || (n_bins == 0 ? !(threshold > 0.f) || !(threshold < 1.f) : !bins || !thr_logits);
+}
+// the bracket of a search in another camera: finite, 0 < lo < hi (NaN fails every comparison); idh_binary_mlp_rays_search_fwd asks hi > lo alone
+static bool bracket_bad(float lo, float hi) { return !(lo > 0.f) || !(hi > lo) || !(lo <= FLT_MAX) || !(hi <= FLT_MAX); }
+// the cameras of a view entry point (rings of them, with several keys); a prior map comes with its cameras and a prior-enabled network
+struct ViewCams { const float *invK, *wTc, *key_cTw, *key_K, *prior_cTw, *prior_K; };
+static bool prior_map_bad(const float *prior, int has_prior, const ViewCams &c) { return prior && (!has_prior || !c.prior_cTw || !c.prior_K); }
+// the pointers every view entry point requires, and those it wants 4-byte aligned; `req` (required) and `opt` are the entry point's own
+static bool view_ptrs_bad(const float *feat, const ViewCams &c, const float *prior, const float *w1f, const float *w2, const float *vecs, Ptrs req, Ptrs opt) {
+    return any_null({feat, c.invK, c.wTc, c.key_cTw, c.key_K, w1f, w2, vecs}) || any_null(req) ||
+           any_misaligned({feat, c.invK, c.wTc, c.key_cTw, c.key_K, prior, c.prior_cTw, c.prior_K}) || any_misaligned(req) || any_misaligned(opt);
+}
+// where the rays of a view come from: `rays` (B,N,2), or null - the pixel centres of its h x w grid; the dense modes have vP x vh x vw pixels
+struct RaySource { long long Nq; int vP, vh, vw; bool bad, empty; };
+static RaySource ray_source(const float *rays, int N, int h, int w) {
+    if (rays) return {N, 1, 1, N, N < 0, N == 0};
+    return {(long long)h * w, 1, h, w, h < 0 || w < 0, h == 0 || w == 0};
+}
+// rays (a tile rounds their number up to 16) and texels are indexed with ints (Nq first: B * Nq stays inside 64 bits; it can be large only
+// with a grid, the dense modes bound P * h before they form it); the cameras of every batch element of a view sit in LDS
+template <int kMode>
+static int size_limits(int B, long long Nq, int H, int W) {
+    if (Nq >= (1ll << 31) || (long long)B * Nq >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    return mode_view(kMode) && B > kViewMaxBatch ? IDH_EUNSUPPORTED : IDH_OK;
+}
+// the multi-key entry points, between the pointers and the sizes: the order of the keys and the ring's geometry.  IDH_OK: k's own fields are filled in
+static int keys_args(KeysArgs &k, long long key_stride, int n_slots, const int *key_slots, int M, int B, int H, int W, int feat_cs) {
+    if (!key_slots || M <= 0 || n_slots <= 0 || key_stride < 0) return IDH_EINVAL;
+    if (M > kMaxKeys) return IDH_EUNSUPPORTED;
+    for (int m = 0; m < M; ++m) {
+        if (key_slots[m] < 0 || key_slots[m] >= n_slots) return IDH_EINVAL;
+        for (int o = 0; o < m; ++o)
+            if (key_slots[o] == key_slots[m]) return IDH_EINVAL;
+    }
+    if (n_slots > 1 && key_stride < (long long)B * H * W * feat_cs) return IDH_EINVAL;
+    if ((long long)M * B > kViewMaxBatch || (long long)n_slots * B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    k.key_stride = key_stride, k.nkeys = M;
+    std::copy(key_slots, key_slots + M, k.key_slots);
+    return IDH_OK;
+}
+// the march entry points, among their argument errors
+static int march_args_ok(const float *march_depths, int n_march, int refine) {
+    if (n_march <= 0 || n_march > 255 || refine < 0 || !march_depths || (reinterpret_cast<uintptr_t>(march_depths) & 3)) return IDH_EINVAL;
+    return refine > (1 << 30) ? IDH_EUNSUPPORTED : IDH_OK;  // (n_march + refine stays an int)
+}
+
+// ---- the argument block: `Args a{}` leaves every field zero or null, these name what the modes share ----
+// every mode: the feature map (rows of a ring's slots lie key_stride apart), the prior, the weights, and one sample per ray in one item
+template <class Args>
+static void set_common(Args &a, const float *feat, int feat_cs, int Cf, int H, int W, const float *prior, int has_prior, float prior_const,
+                       const float *w1f, const float *w2, const float *vecs) {
+    a.feat = feat, a.cs = feat_cs, a.Cf = Cf, a.H = H, a.W = W;
+    a.prior = prior, a.has_prior = has_prior, a.prior_const = prior_const;
+    a.w1f = w1f, a.w2 = w2, a.vecs = vecs;
+    a.S = a.ray_step = a.nchunk = a.s_chunk = 1;
+    long long key_stride = 0;
+    if constexpr (std::is_base_of<KeysArgs, Args>::value) key_stride = a.key_stride;
+    a.feat_unaligned = ((feat_cs & 3) || (key_stride & 3) || (reinterpret_cast<uintptr_t>(feat) & 15)) ? 1 : 0;
+}
+// the B x Nq rays of the launch, of N per batch element, in pixel-centre units of a grid_w x grid_h grid
+static void set_rays(RayArgs &a, const float *rays, int B, long long Nq, int N, int grid_w, int grid_h) {
+    a.rays = rays, a.M = (int)((long long)B * Nq), a.Nq = (int)Nq, a.N = N;
+    a.grid_w = (float)grid_w, a.grid_h = (float)grid_h;
+}
+// the view modes (after set_common): rays from `src` on the keyframe's own grid, and the cameras
+static void set_view(RayArgs &a, const float *rays, int B, const RaySource &src, const ViewCams &c, float fill) {
+    set_rays(a, rays, B, src.Nq, (int)src.Nq, a.W, a.H);
+    a.invK = c.invK, a.wTc = c.wTc, a.key_cTw = c.key_cTw, a.key_K = c.key_K, a.prior_cTw = c.prior_cTw, a.prior_K = c.prior_K;
+    a.nb = B, a.vP = src.vP, a.vh = src.vh, a.vw = src.vw, a.fill = fill;
+}
+static void set_threshold(RayArgs &a, float threshold, const float *bins, const float *thr_logits, int n_bins) {
+    a.thr_logit = n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f;
+    a.bins = bins, a.thr_logits = thr_logits, a.n_bins = n_bins;
+}
+// `out`: the logits; what the other three hold depends on the mode (RayArgs)
+static void set_outputs(RayArgs &a, float *out, float *sdepth, unsigned char *flags, float *points) {
+    a.out = out, a.sdepth = sdepth, a.flags = flags, a.points = points;
+}
+
 extern "C" int idh_binary_mlp_rays_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, const float *rays_bn2,
                                        const float *depth_bns, const float *prior_bns, int has_prior, float prior_const, int N, int S,
                                        int ray_step, int grid_w, int grid_h, const float *w1f_packed, const float *w2_packed,
                                        const float *vecs6x128, float *out_bqs, void *stream) {
-    if (B < 0 || N < 0 || S <= 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || ray_step < 1 || grid_w <= 0 || grid_h <= 0)
-        return IDH_EINVAL;
+    if (feat_bad(B, H, W, Cf, feat_cs) || N < 0 || S <= 0 || ray_step < 1 || grid_w <= 0 || grid_h <= 0) return IDH_EINVAL;
     if (B == 0 || N == 0) return IDH_OK;
-    if (!feat_nhwc || !rays_bn2 || !depth_bns || !w1f_packed || !w2_packed || !vecs6x128 || !out_bqs) return IDH_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(feat_nhwc) & 3) || (reinterpret_cast<uintptr_t>(rays_bn2) & 3) || (reinterpret_cast<uintptr_t>(depth_bns) & 3) ||
-        (reinterpret_cast<uintptr_t>(prior_bns) & 3) || (reinterpret_cast<uintptr_t>(out_bqs) & 3))
+    if (any_null({feat_nhwc, rays_bn2, depth_bns, w1f_packed, w2_packed, vecs6x128, out_bqs}) ||
+        any_misaligned({feat_nhwc, rays_bn2, depth_bns, prior_bns, out_bqs}))  // (its data pointers alone)
         return IDH_EINVAL;
     const int Nq = (int)(((long long)N + ray_step - 1) / ray_step);
-    const long long M = (long long)B * Nq;
-    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31) || (M + 15) / 16 * ((S + 7) / 8) >= (1ll << 30)) return IDH_EUNSUPPORTED;
-    RayArgs a{feat_nhwc, rays_bn2, depth_bns, prior_bns, w1f_packed, w2_packed, vecs6x128, out_bqs, (int)M, Nq, N, S, ray_step, H, W, feat_cs, Cf,
-              (float)grid_w, (float)grid_h, has_prior, prior_const, 0, 1, S};
-    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    return ray_mlp_launch(a, stream);
+    if (const int rc = size_limits<kSamples>(B, Nq, H, W)) return rc;
+    if (((long long)B * Nq + 15) / 16 * ((S + 7) / 8) >= (1ll << 30)) return IDH_EUNSUPPORTED;  // the items of the launch
+    RayArgs a{};
+    set_common(a, feat_nhwc, feat_cs, Cf, H, W, prior_bns, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_rays(a, rays_bn2, B, Nq, N, grid_w, grid_h);
+    a.depth = depth_bns, a.S = S, a.ray_step = ray_step, a.out = out_bqs;
+    return ray_mlp_launch<kSamples>(a, stream);
 }
 
 // Depth and hit point per ray by binary search (reference BDModel.forward(infer_depth=True), bd_model.py:273-292, at the rays of
@@ -716,24 +804,22 @@ extern "C" int idh_binary_mlp_rays_search_fwd(const float *feat_nhwc, int feat_c
                                               float threshold, const float *bins, const float *thr_logits, int n_bins, const float *invK_44,
                                               const float *world_T_cam_44, float *depth_bn, float *last_logits_bn, unsigned char *flags_bn,
                                               float *points_bn3, void *stream) {
-    if (B < 0 || N < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || grid_w <= 0 || grid_h <= 0 || iters <= 0 || !(hi > lo) || n_bins < 0)
+    if (feat_bad(B, H, W, Cf, feat_cs) || N < 0 || grid_w <= 0 || grid_h <= 0 || iters <= 0 || !(hi > lo) ||
+        threshold_bad(threshold, bins, thr_logits, n_bins) || (points_bn3 && !invK_44))
         return IDH_EINVAL;
-    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
-    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
-    if (points_bn3 && !invK_44) return IDH_EINVAL;
     if (B == 0 || N == 0) return IDH_OK;
-    if (!feat_nhwc || !rays_bn2 || !w1f_packed || !w2_packed || !vecs6x128 || !depth_bn || !last_logits_bn) return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)prior_bn, (const void *)bins, (const void *)thr_logits,
-                          (const void *)invK_44, (const void *)world_T_cam_44, (const void *)depth_bn, (const void *)last_logits_bn, (const void *)points_bn3})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    const long long M = (long long)B * N;
-    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    RayArgs a{feat_nhwc, rays_bn2, nullptr, prior_bn, w1f_packed, w2_packed, vecs6x128, last_logits_bn, (int)M, N, N, 1, 1, H, W, feat_cs, Cf,
-              (float)grid_w, (float)grid_h, has_prior, prior_const, 0, 1, 1,
-              iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth_bn, flags_bn, points_bn3, invK_44,
-              world_T_cam_44};
-    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    return ray_mlp_launch(a, stream, kSearch);
+    if (any_null({feat_nhwc, rays_bn2, w1f_packed, w2_packed, vecs6x128, depth_bn, last_logits_bn}) ||
+        any_misaligned({feat_nhwc, rays_bn2, prior_bn, bins, thr_logits, invK_44, world_T_cam_44, depth_bn, last_logits_bn, points_bn3}))
+        return IDH_EINVAL;
+    if (const int rc = size_limits<kSearch>(B, N, H, W)) return rc;
+    RayArgs a{};
+    set_common(a, feat_nhwc, feat_cs, Cf, H, W, prior_bn, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_rays(a, rays_bn2, B, N, N, grid_w, grid_h);
+    a.iters = iters, a.lo = lo, a.hi = hi;
+    set_threshold(a, threshold, bins, thr_logits, n_bins);
+    a.invK = invK_44, a.wTc = world_T_cam_44;
+    set_outputs(a, last_logits_bn, depth_bn, flags_bn, points_bn3);
+    return ray_mlp_launch<kSearch>(a, stream);
 }
 
 // Dense occlusion in another camera: every pixel of rendered (B,P,h,w) is back-projected in its own view, projected into the keyframe's
@@ -744,26 +830,21 @@ extern "C" int idh_binary_mlp_view_fwd(const float *feat_nhwc, int feat_cs, int 
                                        const float *prior_K_44, int has_prior, float prior_const, const float *w1f_packed, const float *w2_packed,
                                        const float *vecs6x128, float fill, float *logits_bphw, unsigned char *valid_bphw, float *view_depth_bphw,
                                        float *view_points_bphw3, void *stream) {
-    if (B < 0 || P < 0 || h < 0 || w < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf) return IDH_EINVAL;
-    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44};
+    if (feat_bad(B, H, W, Cf, feat_cs) || P < 0 || h < 0 || w < 0 || prior_map_bad(prior_pred_b1hw, has_prior, cams)) return IDH_EINVAL;
     if (B == 0 || P == 0 || h == 0 || w == 0) return IDH_OK;
-    if (!feat_nhwc || !rendered_bphw || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 ||
-        !logits_bphw)
+    if (view_ptrs_bad(feat_nhwc, cams, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, {rendered_bphw, logits_bphw},
+                      {view_depth_bphw, view_points_bphw3}))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_nhwc, (const void *)rendered_bphw, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
-                          (const void *)prior_K_44, (const void *)logits_bphw, (const void *)view_depth_bphw, (const void *)view_points_bphw3})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
     if ((long long)P * h >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (the product below stays inside 64 bits)
-    const long long Nq = (long long)P * h * w, M = (long long)B * Nq;
-    if (M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
-    RayArgs a{feat_nhwc, nullptr, rendered_bphw, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, logits_bphw, (int)M, (int)Nq, (int)Nq, 1, 1, H, W,
-              feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
-              0, 0.f, 0.f, 0.f, nullptr, nullptr, 0, view_depth_bphw, valid_bphw, view_points_bphw3, invK_44, world_T_cam_44,
-              key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, P, h, w, fill};
-    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    return ray_mlp_launch(a, stream, kView);
+    const RaySource src{(long long)P * h * w, P, h, w};
+    if (const int rc = size_limits<kView>(B, src.Nq, H, W)) return rc;
+    RayArgs a{};
+    set_common(a, feat_nhwc, feat_cs, Cf, H, W, prior_pred_b1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, nullptr, B, src, cams, fill);
+    a.depth = rendered_bphw;
+    set_outputs(a, logits_bphw, view_depth_bphw, valid_bphw, view_points_bphw3);
+    return ray_mlp_launch<kView>(a, stream);
 }
 
 // Depth along the rays of another camera: the search of idh_binary_mlp_rays_search_fwd with every step one pixel of idh_binary_mlp_view_fwd at
@@ -775,50 +856,22 @@ extern "C" int idh_binary_mlp_view_search_fwd(const float *feat_nhwc, int feat_c
                                               const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi, float threshold,
                                               const float *bins, const float *thr_logits, int n_bins, float fill, float *depth, float *last_logits,
                                               unsigned char *flags, float *points, void *stream) {
-    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || iters <= 0 || n_bins < 0) return IDH_EINVAL;
-    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
-    const float fmax = 3.4028234663852886e38f;
-    if (!(lo > 0.f) || !(hi > lo) || !(lo <= fmax) || !(hi <= fmax)) return IDH_EINVAL;  // (NaN fails every comparison)
-    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
-    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
-    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
-    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
-    if (!feat_nhwc || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth || !last_logits)
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44};
+    const RaySource src = ray_source(rays_bn2, N, h, w);
+    if (feat_bad(B, H, W, Cf, feat_cs) || src.bad || iters <= 0 || bracket_bad(lo, hi) || threshold_bad(threshold, bins, thr_logits, n_bins) ||
+        prior_map_bad(prior_pred_b1hw, has_prior, cams))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
-                          (const void *)prior_K_44, (const void *)bins, (const void *)thr_logits, (const void *)depth, (const void *)last_logits,
-                          (const void *)points})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, M = (long long)B * Nq;
-    if (Nq >= (1ll << 31) || M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
-    RayArgs a{feat_nhwc, rays_bn2, nullptr, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)M, (int)Nq, (int)Nq, 1, 1, H, W,
-              feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
-              iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags, points, invK_44,
-              world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, 1, rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
-    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    return ray_mlp_launch(a, stream, kViewSearch);
-}
-
-// The checks the two multi-key entry points add to their parents': the order of the keys and the ring's geometry.  IDH_OK: k is filled in.
-static int keys_args(KeysArgs &k, long long key_stride, int n_slots, const int *key_slots, int M, int B, int H, int W, int feat_cs,
-                     const float *feat) {
-    if (!key_slots || M <= 0 || n_slots <= 0 || key_stride < 0) return IDH_EINVAL;
-    if (M > kMaxKeys) return IDH_EUNSUPPORTED;
-    for (int m = 0; m < M; ++m) {
-        if (key_slots[m] < 0 || key_slots[m] >= n_slots) return IDH_EINVAL;
-        for (int o = 0; o < m; ++o)
-            if (key_slots[o] == key_slots[m]) return IDH_EINVAL;
-    }
-    if (n_slots > 1 && key_stride < (long long)B * H * W * feat_cs) return IDH_EINVAL;
-    if ((long long)M * B > kViewMaxBatch || (long long)n_slots * B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    k.key_stride = key_stride;
-    k.nkeys = M;
-    for (int m = 0; m < kMaxKeys; ++m) k.key_slots[m] = m < M ? key_slots[m] : 0;
-    k.keyout = nullptr;
-    k.feat_unaligned = ((feat_cs & 3) || (key_stride & 3) || (reinterpret_cast<uintptr_t>(feat) & 15)) ? 1 : 0;
-    return IDH_OK;
+    if (B == 0 || src.empty) return IDH_OK;
+    if (view_ptrs_bad(feat_nhwc, cams, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, {depth, last_logits}, {rays_bn2, bins, thr_logits, points}))
+        return IDH_EINVAL;
+    if (const int rc = size_limits<kViewSearch>(B, src.Nq, H, W)) return rc;
+    RayArgs a{};
+    set_common(a, feat_nhwc, feat_cs, Cf, H, W, prior_pred_b1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, rays_bn2, B, src, cams, fill);
+    a.iters = iters, a.lo = lo, a.hi = hi;
+    set_threshold(a, threshold, bins, thr_logits, n_bins);
+    set_outputs(a, last_logits, depth, flags, points);
+    return ray_mlp_launch<kViewSearch>(a, stream);
 }
 
 // Dense occlusion in another camera against M remembered keyframes: idh_binary_mlp_view_fwd with the projection looped over the keys and the
@@ -830,29 +883,22 @@ extern "C" int idh_binary_mlp_view_keys_fwd(const float *feat_ring, int feat_cs,
                                             int has_prior, float prior_const, const float *w1f_packed, const float *w2_packed,
                                             const float *vecs6x128, float fill, float *logits_bphw, unsigned char *key_bphw,
                                             float *view_depth_bphw, float *view_points_bphw3, void *stream) {
-    if (B < 0 || P < 0 || h < 0 || w < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf) return IDH_EINVAL;
-    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44};
+    if (feat_bad(B, H, W, Cf, feat_cs) || P < 0 || h < 0 || w < 0 || prior_map_bad(prior_pred_sb1hw, has_prior, cams)) return IDH_EINVAL;
     if (B == 0 || P == 0 || h == 0 || w == 0) return IDH_OK;
-    if (!feat_ring || !rendered_bphw || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed ||
-        !vecs6x128 || !logits_bphw)
+    if (view_ptrs_bad(feat_ring, cams, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, {rendered_bphw, logits_bphw},
+                      {view_depth_bphw, view_points_bphw3}))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_ring, (const void *)rendered_bphw, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
-                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)logits_bphw, (const void *)view_depth_bphw,
-                          (const void *)view_points_bphw3})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    KeysArgs k{};
-    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
+    KeysArgs a{};
+    if (const int rc = keys_args(a, key_stride, n_slots, key_slots, M, B, H, W, feat_cs)) return rc;
     if ((long long)P * h >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (the product below stays inside 64 bits)
-    const long long Nq = (long long)P * h * w, Mr = (long long)B * Nq;
-    if (Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
-    const int unaligned = k.feat_unaligned;
-    static_cast<RayArgs &>(k) = RayArgs{feat_ring, nullptr, rendered_bphw, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, logits_bphw, (int)Mr,
-                                        (int)Nq, (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
-                                        0, 0.f, 0.f, 0.f, nullptr, nullptr, 0, view_depth_bphw, key_bphw, view_points_bphw3, invK_44, world_T_cam_44,
-                                        key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, P, h, w, fill};
-    return ray_mlp_launch(k, stream, kViewKeys);
+    const RaySource src{(long long)P * h * w, P, h, w};
+    if (const int rc = size_limits<kViewKeys>(B, src.Nq, H, W)) return rc;
+    set_common(a, feat_ring, feat_cs, Cf, H, W, prior_pred_sb1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, nullptr, B, src, cams, fill);
+    a.depth = rendered_bphw;
+    set_outputs(a, logits_bphw, view_depth_bphw, key_bphw, view_points_bphw3);  // (view_keys_k writes the key to `flags`)
+    return ray_mlp_launch<kViewKeys>(a, stream);
 }
 
 // Depth along the rays of another camera against M remembered keyframes: idh_binary_mlp_view_search_fwd with every step one pixel of
@@ -865,46 +911,28 @@ extern "C" int idh_binary_mlp_view_keys_search_fwd(const float *feat_ring, int f
                                                    const float *w2_packed, const float *vecs6x128, int iters, float lo, float hi, float threshold,
                                                    const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
                                                    float *last_logits, unsigned char *flags, float *points, unsigned char *key, void *stream) {
-    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || iters <= 0 || n_bins < 0) return IDH_EINVAL;
-    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
-    const float fmax = 3.4028234663852886e38f;
-    if (!(lo > 0.f) || !(hi > lo) || !(lo <= fmax) || !(hi <= fmax)) return IDH_EINVAL;  // (NaN fails every comparison)
-    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
-    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
-    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
-    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
-    if (!feat_ring || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth ||
-        !last_logits)
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44};
+    const RaySource src = ray_source(rays_bn2, N, h, w);
+    if (feat_bad(B, H, W, Cf, feat_cs) || src.bad || iters <= 0 || bracket_bad(lo, hi) || threshold_bad(threshold, bins, thr_logits, n_bins) ||
+        prior_map_bad(prior_pred_sb1hw, has_prior, cams))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_ring, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
-                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)bins, (const void *)thr_logits,
-                          (const void *)depth, (const void *)last_logits, (const void *)points})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    KeysArgs k{};
-    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
-    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, Mr = (long long)B * Nq;
-    if (Nq >= (1ll << 31) || Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
-    const int unaligned = k.feat_unaligned;
-    static_cast<RayArgs &>(k) = RayArgs{feat_ring, rays_bn2, nullptr, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)Mr, (int)Nq,
-                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
-                                        iters, lo, hi, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
-                                        points, invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, 1,
-                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
-    k.keyout = key;
-    return ray_mlp_launch(k, stream, kViewKeysSearch);
+    if (B == 0 || src.empty) return IDH_OK;
+    if (view_ptrs_bad(feat_ring, cams, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, {depth, last_logits}, {rays_bn2, bins, thr_logits, points}))
+        return IDH_EINVAL;
+    KeysArgs a{};
+    if (const int rc = keys_args(a, key_stride, n_slots, key_slots, M, B, H, W, feat_cs)) return rc;
+    if (const int rc = size_limits<kViewKeysSearch>(B, src.Nq, H, W)) return rc;
+    set_common(a, feat_ring, feat_cs, Cf, H, W, prior_pred_sb1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, rays_bn2, B, src, cams, fill);
+    a.iters = iters, a.lo = lo, a.hi = hi;
+    set_threshold(a, threshold, bins, thr_logits, n_bins);
+    set_outputs(a, last_logits, depth, flags, points);
+    a.keyout = key;
+    return ray_mlp_launch<kViewKeysSearch>(a, stream);
 }
 
 // First-hit depth along the rays of another camera: the samples march_depths[0 .. n_march-1] in turn until the first probe that is behind, then
 // `refine` steps of idh_binary_mlp_view_search_fwd's rule inside the bracket, in one launch (view_march_k).  include/idh.h states the rule.
-// The checks the two march entry points add to their search parents' (those apply without iters / lo / hi).
-static int march_args_ok(const float *march_depths, int n_march, int refine) {
-    if (n_march <= 0 || n_march > 255 || refine < 0 || !march_depths || (reinterpret_cast<uintptr_t>(march_depths) & 3)) return IDH_EINVAL;
-    if (refine > (1 << 30)) return IDH_EUNSUPPORTED;  // (n_march + refine stays an int)
-    return IDH_OK;
-}
-
 extern "C" int idh_binary_mlp_view_march_fwd(const float *feat_nhwc, int feat_cs, int Cf, int B, int H, int W, int h, int w, const float *rays_bn2,
                                              int N, const float *invK_44, const float *world_T_cam_44, const float *key_cam_T_world_44,
                                              const float *key_K_44, const float *prior_pred_b1hw, const float *prior_cam_T_world_44,
@@ -912,35 +940,22 @@ extern "C" int idh_binary_mlp_view_march_fwd(const float *feat_nhwc, int feat_cs
                                              const float *w2_packed, const float *vecs6x128, const float *march_depths, int n_march, int refine,
                                              float threshold, const float *bins, const float *thr_logits, int n_bins, float fill, float *depth,
                                              float *last_logits, unsigned char *flags, unsigned char *hit_step, float *points, void *stream) {
-    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || n_bins < 0) return IDH_EINVAL;
-    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44};
+    const RaySource src = ray_source(rays_bn2, N, h, w);
+    if (feat_bad(B, H, W, Cf, feat_cs) || n_bins < 0 || src.bad) return IDH_EINVAL;
     if (const int rc = march_args_ok(march_depths, n_march, refine)) return rc;
-    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
-    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
-    if (prior_pred_b1hw && (!has_prior || !prior_cam_T_world_44 || !prior_K_44)) return IDH_EINVAL;
-    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
-    if (!feat_nhwc || !invK_44 || !world_T_cam_44 || !key_cam_T_world_44 || !key_K_44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth || !last_logits)
+    if (threshold_bad(threshold, bins, thr_logits, n_bins) || prior_map_bad(prior_pred_b1hw, has_prior, cams)) return IDH_EINVAL;
+    if (B == 0 || src.empty) return IDH_OK;
+    if (view_ptrs_bad(feat_nhwc, cams, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, {depth, last_logits}, {rays_bn2, bins, thr_logits, points}))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_nhwc, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_44, (const void *)key_K_44, (const void *)prior_pred_b1hw, (const void *)prior_cam_T_world_44,
-                          (const void *)prior_K_44, (const void *)bins, (const void *)thr_logits, (const void *)depth, (const void *)last_logits,
-                          (const void *)points})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, M = (long long)B * Nq;
-    if (Nq >= (1ll << 31) || M >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;  // the cameras of every batch element sit in LDS
+    if (const int rc = size_limits<kViewMarch>(B, src.Nq, H, W)) return rc;
     MarchArgs a{};
-    static_cast<RayArgs &>(a) = RayArgs{feat_nhwc, rays_bn2, nullptr, prior_pred_b1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)M, (int)Nq,
-                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, 0, 1, 1,
-                                        0, 0.f, 0.f, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
-                                        points, invK_44, world_T_cam_44, key_cam_T_world_44, key_K_44, prior_cam_T_world_44, prior_K_44, B, 1,
-                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
-    a.feat_unaligned = ((feat_cs & 3) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15)) ? 1 : 0;
-    a.march_depths = march_depths;
-    a.n_march = n_march;
-    a.refine = refine;
-    a.hit_step = hit_step;
-    return ray_mlp_launch(a, stream, kViewMarch);
+    set_common(a, feat_nhwc, feat_cs, Cf, H, W, prior_pred_b1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, rays_bn2, B, src, cams, fill);
+    set_threshold(a, threshold, bins, thr_logits, n_bins);
+    a.march_depths = march_depths, a.n_march = n_march, a.refine = refine, a.hit_step = hit_step;
+    set_outputs(a, last_logits, depth, flags, points);
+    return ray_mlp_launch<kViewMarch>(a, stream);
 }
 
 // The same against M remembered keyframes: every probe selects its own key, as in idh_binary_mlp_view_keys_search_fwd (view_keys_march_k).
@@ -953,38 +968,24 @@ extern "C" int idh_binary_mlp_view_keys_march_fwd(const float *feat_ring, int fe
                                                   int refine, float threshold, const float *bins, const float *thr_logits, int n_bins, float fill,
                                                   float *depth, float *last_logits, unsigned char *flags, unsigned char *hit_step, float *points,
                                                   unsigned char *key, void *stream) {
-    if (B < 0 || H <= 0 || W <= 0 || Cf <= 0 || (Cf & 3) || feat_cs < Cf || n_bins < 0) return IDH_EINVAL;
-    if (rays_bn2 ? N < 0 : (h < 0 || w < 0)) return IDH_EINVAL;
+    const ViewCams cams{invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44};
+    const RaySource src = ray_source(rays_bn2, N, h, w);
+    if (feat_bad(B, H, W, Cf, feat_cs) || n_bins < 0 || src.bad) return IDH_EINVAL;
     if (const int rc = march_args_ok(march_depths, n_march, refine)) return rc;
-    if (n_bins == 0 && (!(threshold > 0.f) || !(threshold < 1.f))) return IDH_EINVAL;
-    if (n_bins > 0 && (!bins || !thr_logits)) return IDH_EINVAL;
-    if (prior_pred_sb1hw && (!has_prior || !prior_cam_T_world_s44 || !prior_K_s44)) return IDH_EINVAL;
-    if (B == 0 || (rays_bn2 ? N == 0 : (h == 0 || w == 0))) return IDH_OK;
-    if (!feat_ring || !invK_44 || !world_T_cam_44 || !key_cam_T_world_s44 || !key_K_s44 || !w1f_packed || !w2_packed || !vecs6x128 || !depth ||
-        !last_logits)
+    if (threshold_bad(threshold, bins, thr_logits, n_bins) || prior_map_bad(prior_pred_sb1hw, has_prior, cams)) return IDH_EINVAL;
+    if (B == 0 || src.empty) return IDH_OK;
+    if (view_ptrs_bad(feat_ring, cams, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, {depth, last_logits}, {rays_bn2, bins, thr_logits, points}))
         return IDH_EINVAL;
-    for (const void *p : {(const void *)feat_ring, (const void *)rays_bn2, (const void *)invK_44, (const void *)world_T_cam_44,
-                          (const void *)key_cam_T_world_s44, (const void *)key_K_s44, (const void *)prior_pred_sb1hw,
-                          (const void *)prior_cam_T_world_s44, (const void *)prior_K_s44, (const void *)bins, (const void *)thr_logits,
-                          (const void *)depth, (const void *)last_logits, (const void *)points})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return IDH_EINVAL;
-    KeysMarchArgs k{};
-    if (const int rc = keys_args(k, key_stride, n_slots, key_slots, M, B, H, W, feat_cs, feat_ring)) return rc;
-    const long long Nq = rays_bn2 ? (long long)N : (long long)h * w, Mr = (long long)B * Nq;
-    if (Nq >= (1ll << 31) || Mr >= (1ll << 31) - 16 || (long long)B * H * W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    if (B > kViewMaxBatch) return IDH_EUNSUPPORTED;
-    const int unaligned = k.feat_unaligned;
-    static_cast<RayArgs &>(k) = RayArgs{feat_ring, rays_bn2, nullptr, prior_pred_sb1hw, w1f_packed, w2_packed, vecs6x128, last_logits, (int)Mr, (int)Nq,
-                                        (int)Nq, 1, 1, H, W, feat_cs, Cf, (float)W, (float)H, has_prior, prior_const, unaligned, 1, 1,
-                                        0, 0.f, 0.f, n_bins == 0 ? logf(threshold / (1.f - threshold)) : 0.f, bins, thr_logits, n_bins, depth, flags,
-                                        points, invK_44, world_T_cam_44, key_cam_T_world_s44, key_K_s44, prior_cam_T_world_s44, prior_K_s44, B, 1,
-                                        rays_bn2 ? 1 : h, rays_bn2 ? (int)Nq : w, fill};
-    k.keyout = key;
-    k.march_depths = march_depths;
-    k.n_march = n_march;
-    k.refine = refine;
-    k.hit_step = hit_step;
-    return ray_mlp_launch(k, stream, kViewKeysMarch);
+    KeysMarchArgs a{};
+    if (const int rc = keys_args(a, key_stride, n_slots, key_slots, M, B, H, W, feat_cs)) return rc;
+    if (const int rc = size_limits<kViewKeysMarch>(B, src.Nq, H, W)) return rc;
+    set_common(a, feat_ring, feat_cs, Cf, H, W, prior_pred_sb1hw, has_prior, prior_const, w1f_packed, w2_packed, vecs6x128);
+    set_view(a, rays_bn2, B, src, cams, fill);
+    set_threshold(a, threshold, bins, thr_logits, n_bins);
+    a.march_depths = march_depths, a.n_march = n_march, a.refine = refine, a.hit_step = hit_step;
+    set_outputs(a, last_logits, depth, flags, points);
+    a.keyout = key;
+    return ray_mlp_launch<kViewKeysMarch>(a, stream);
 }
 
 extern "C" int idh_project_points_fwd(const float *points_bn3, const float *cam_T_world_44, const float *K_44, int B, int N, int H, int W,

@@ -7,6 +7,8 @@
 """
 from __future__ import annotations
 
+import ctypes
+import types
 from typing import Dict, List, Optional
 
 import torch
@@ -101,6 +103,13 @@ def _thresholder_tables(thresholder, dev):
     if bins.dim() != 1 or thr.shape != bins.shape or not bool(((thr > 0) & (thr < 1)).all()):
         raise _lib.IdhError("thresholder needs 1-D bins / thresholds of equal length with thresholds in (0, 1)")
     return bins, torch.log(thr / (1 - thr)).contiguous()
+
+
+def _threshold_args(threshold, thresholder, dev):
+    """(threshold, bins, thr_logits, n_bins) as the ray and view search entry points take them, and the tables, to be held until the launch is
+    enqueued."""
+    bins, thr_logits = _thresholder_tables(thresholder, dev)
+    return (threshold, _lib.ptr(bins), _lib.ptr(thr_logits), 0 if bins is None else bins.numel()), (bins, thr_logits)
 
 
 def infer_depth(net, feat_nhwc: torch.Tensor, feat_c0: int, n_feat: int, prior_b1hw: Optional[torch.Tensor] = None,
@@ -226,7 +235,7 @@ def ray_depths(net, feat_view, rays: torch.Tensor, prior=None, grid=None, iters:
             raise _lib.IdhError(f"invK / world_T_cam must be ({B}, 4, 4), got {tuple(m.shape)}")
     gh, gw = (H, W) if grid is None else (int(grid[0]), int(grid[1]))
     w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
-    bins, thr_logits = _thresholder_tables(thresholder, rays.device)
+    thr, _tables = _threshold_args(threshold, thresholder, rays.device)
     r = rays.contiguous()  # alive until enqueued
     pt = prior_t.contiguous() if prior_t is not None else None
     iK = invK.contiguous() if invK is not None else None
@@ -238,8 +247,7 @@ def ray_depths(net, feat_view, rays: torch.Tensor, prior=None, grid=None, iters:
     _lib.check(
         _lib.lib().idh_binary_mlp_rays_search_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, r.data_ptr(), _lib.ptr(pt), int(net.use_prior),
                                                   -1.0 if prior is None or prior_t is not None else float(prior), N, gw, gh, w1p.data_ptr(),
-                                                  w2p.data_ptr(), vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
-                                                  0 if bins is None else bins.numel(), _lib.ptr(iK), _lib.ptr(wT), depth.data_ptr(),
+                                                  w2p.data_ptr(), vecs.data_ptr(), iters, lo, hi, *thr, _lib.ptr(iK), _lib.ptr(wT), depth.data_ptr(),
                                                   logits.data_ptr(), hit.data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
         "idh_binary_mlp_rays_search_fwd")
     return depth, logits, hit, points
@@ -276,6 +284,95 @@ def project_points(points_bn3: torch.Tensor, cam_T_world: torch.Tensor, K: torch
     return rays, depth, valid.view(torch.bool), prior  # the kernel writes 0 / 1: reinterpreted, no conversion pass
 
 
+MAX_VIEW_KEYS, MAX_VIEW_KEY_CAMERAS = 16, 128  # idh_binary_mlp_view_keys_fwd: M <= 16, M * B <= 128
+
+
+def _view_query(net, entry, public, feat_view, ring, cams, prior, rendered=None, size=None, rays=None, refine=None, return_points=False, planes=1):
+    """The host side the ``view_*`` wrappers share: every check that is made before the C call ``entry``, in one order, and the arguments
+    all of them pass.  ``feat_view``: the keyframe's ``nhwc.View``, or None with ``ring`` = (feat_ring, feat_c0, n_feat, key_slots);
+    ``cams``: (invK, world_T_cam, key_cam_T_world, key_K_s0) - the last two are rings with ``ring``; ``prior`` as ``view_logits``; the rays
+    are the pixels of ``rendered`` (B,P,h,w), or exactly one of ``size`` and ``rays`` (``public`` names the wrapper in that message).
+    Returns a namespace: ``head`` (feat, feat_cs, Cf, B, H, W [, key_stride, n_slots, key_slots, M]), ``source`` (rendered, P, h, w) |
+    (h, w, rays, N), ``cams`` (the matrices, the prior map and its cameras, has_prior, prior_const, the packed weights) - three runs of
+    the C argument list -, the outputs ``a`` / ``b`` (two float maps of the rays' shape) and ``points`` | None, views of ONE allocation,
+    ``u8`` (planes, *shape) bytes, ``dev``, and ``keep``: the contiguous copies, alive as long as the namespace is."""
+    if mlp_math_of(net) != "fp32":
+        raise _lib.IdhError(f"ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of {entry}; set mlp_math = 'fp32'")
+    if rendered is None and (size is None) == (rays is None):
+        raise _lib.IdhError(f"{public} takes exactly one of size=(h, w) and rays=(B,N,2)")
+    if refine is not None and int(refine) < 0:
+        raise _lib.IdhError(f"refine must be >= 0, got {refine}")
+    pmap = prior if isinstance(prior, (tuple, list)) else None
+    mats = list(cams) + ([pmap[1], pmap[2]] if pmap is not None else [])
+    feat_t = feat_view.buf if ring is None else ring[0]
+    _lib.require_cuda_f32(feat_t, rendered, rays, *mats, pmap[0] if pmap is not None else None)
+    if ring is None:
+        B, H, W, cs, Cf, feat_ptr = feat_view.N, feat_view.H, feat_view.W, feat_view.cs, feat_view.C, feat_view.ptr
+        for m in mats:
+            if m is None or tuple(m.shape) != (B, 4, 4):
+                raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
+        prior_shape, prior_name = (B, 1, H, W), "prior prediction"
+    else:
+        feat_ring, feat_c0, Cf, key_slots = ring
+        if feat_ring.dim() != 5 or not feat_ring.is_contiguous():
+            raise _lib.IdhError(f"the feature ring must be a dense (n_slots, B, H, W, C) tensor, got {tuple(feat_ring.shape)}")
+        n_slots, B, H, W, cs = feat_ring.shape
+        if feat_c0 < 0 or Cf <= 0 or feat_c0 + Cf > cs:
+            raise _lib.IdhError(f"channels [{feat_c0}, {feat_c0 + Cf}) are not inside the ring's {cs}")
+        feat_ptr = feat_ring.data_ptr() + 4 * feat_c0
+        for m in mats[:2]:
+            if tuple(m.shape) != (B, 4, 4):
+                raise _lib.IdhError(f"invK / world_T_cam must be ({B}, 4, 4), got {tuple(m.shape)}")
+        for m in mats[2:]:
+            if tuple(m.shape) != (n_slots, B, 4, 4):
+                raise _lib.IdhError(f"the camera rings must be ({n_slots}, {B}, 4, 4), got {tuple(m.shape)}")
+        prior_shape, prior_name = (n_slots, B, 1, H, W), "prior ring"
+    if rendered is not None:
+        if rendered.dim() != 4 or rendered.shape[0] != B:
+            raise _lib.IdhError(f"rendered depth must be ({B}, P, h, w), got {tuple(rendered.shape)}")
+        shape = tuple(rendered.shape)
+    elif rays is not None:
+        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
+            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
+        shape = (B, rays.shape[1])
+    else:
+        h, w = int(size[0]), int(size[1])
+        if h < 0 or w < 0:
+            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
+        shape = (B, 1, h, w)
+    if prior is not None and not net.use_prior:
+        raise _lib.IdhError("prior given to a network built with use_prior=False")
+    if pmap is not None and tuple(pmap[0].shape) != prior_shape:
+        raise _lib.IdhError(f"{prior_name} {tuple(pmap[0].shape)} must be ({', '.join(str(d) for d in prior_shape)})")
+    head = (feat_ptr, cs, Cf, B, H, W)
+    if ring is not None:
+        slots = [int(k) for k in key_slots]
+        if not slots or len(set(slots)) != len(slots) or any(k < 0 or k >= n_slots for k in slots):
+            raise _lib.IdhError(f"key_slots must be a non-empty list of distinct slots in [0, {n_slots}), got {slots}")
+        if len(slots) > MAX_VIEW_KEYS or len(slots) * B > MAX_VIEW_KEY_CAMERAS:
+            raise _lib.IdhError(f"{entry} takes at most {MAX_VIEW_KEYS} keys and {MAX_VIEW_KEY_CAMERAS} key cameras (keys x batch), got {len(slots)} x {B} (IDH_EUNSUPPORTED)")
+        head += (B * H * W * cs, n_slots, (ctypes.c_int * len(slots))(*slots), len(slots))
+    w1p, w2p, vecs = _prepared(net.mlps["s0"], Cf, net.use_prior, "fp32")
+    keep = [m.contiguous() for m in mats]  # alive until enqueued
+    src = rendered if rendered is not None else rays
+    src = src.contiguous() if src is not None else None
+    pp = pmap[0].contiguous() if pmap is not None else None
+    q = types.SimpleNamespace(head=head, dev=feat_t.device, keep=(keep, src, pp, w1p, w2p, vecs))
+    if rendered is not None:
+        q.source = (src.data_ptr(),) + shape[1:]
+    else:
+        q.source = (0, 0, src.data_ptr(), shape[1]) if rays is not None else shape[2:] + (None, 0)
+    q.cams = (keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp), keep[4].data_ptr() if pp is not None else None,
+              keep[5].data_ptr() if pp is not None else None, int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior),
+              w1p.data_ptr(), w2p.data_ptr(), vecs.data_ptr())
+    n = torch.Size(shape).numel()
+    buf = torch.empty((5 if return_points else 2) * n, device=q.dev)  # one allocation for the float outputs, as project_points
+    q.a, q.b = buf[:n].view(shape), buf[n: 2 * n].view(shape)
+    q.points = buf[2 * n:].view(*shape, 3) if return_points else None
+    q.u8 = torch.empty((planes,) + shape, device=q.dev, dtype=torch.uint8)
+    return q
+
+
 def view_logits(net, feat_view, rendered_bphw: torch.Tensor, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, key_cam_T_world_b44: torch.Tensor,
                 key_K_s0_b44: torch.Tensor, prior=None, fill: float = 0.0, return_points: bool = False):
     """Dense occlusion in another camera on ``idh_binary_mlp_view_fwd``: every pixel of ``rendered_bphw`` (B,P,h,w) - an asset's depth in
@@ -287,40 +384,13 @@ def view_logits(net, feat_view, rendered_bphw: torch.Tensor, invK_b44: torch.Ten
     A pixel is valid when its depth is finite and positive and the point lies in front of the keyframe camera and inside its image;
     the others hold ``fill``.  Returns (logits (B,P,h,w), valid (B,P,h,w) bool, view_depth (B,P,h,w): the keyframe z, points (B,P,h,w,3)
     world points | None)."""
-    if mlp_math_of(net) != "fp32":
-        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_fwd; set mlp_math = 'fp32'")
-    pmap = prior if isinstance(prior, (tuple, list)) else None
-    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
-    _lib.require_cuda_f32(feat_view.buf, rendered_bphw, *mats, pmap[0] if pmap is not None else None)
-    B, H, W = feat_view.N, feat_view.H, feat_view.W
-    if rendered_bphw.dim() != 4 or rendered_bphw.shape[0] != B:
-        raise _lib.IdhError(f"rendered depth must be ({B}, P, h, w), got {tuple(rendered_bphw.shape)}")
-    _, P, h, w = rendered_bphw.shape
-    for m in mats:
-        if m is None or tuple(m.shape) != (B, 4, 4):
-            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
-    if prior is not None and not net.use_prior:
-        raise _lib.IdhError("prior given to a network built with use_prior=False")
-    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
-        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
-    dev = rendered_bphw.device
-    rd, keep = rendered_bphw.contiguous(), [m.contiguous() for m in mats]  # alive until enqueued
-    pp = pmap[0].contiguous() if pmap is not None else None
-    n = B * P * h * w
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    logits, depth = buf[:n].view(B, P, h, w), buf[n: 2 * n].view(B, P, h, w)
-    points = buf[2 * n:].view(B, P, h, w, 3) if return_points else None
-    valid = torch.empty(B, P, h, w, device=dev, dtype=torch.uint8)
+    q = _view_query(net, "idh_binary_mlp_view_fwd", "view_logits", feat_view, None, (invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44),
+                    prior, rendered=rendered_bphw, return_points=return_points)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, rd.data_ptr(), P, h, w, keep[0].data_ptr(),
-                                           keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
-                                           keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
-                                           int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
-                                           w2p.data_ptr(), vecs.data_ptr(), float(fill), logits.data_ptr(), valid.data_ptr(), depth.data_ptr(),
-                                           _lib.ptr(points), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_fwd(*q.head, *q.source, *q.cams, float(fill), q.a.data_ptr(), q.u8.data_ptr(), q.b.data_ptr(), _lib.ptr(q.points),
+                                           _lib.stream_ptr()),
         "idh_binary_mlp_view_fwd")
-    return logits, valid.view(torch.bool), depth, points  # the kernel writes 0 / 1: reinterpreted, no conversion pass
+    return q.a, q.u8[0].view(torch.bool), q.b, q.points  # the kernel writes 0 / 1: reinterpreted, no conversion pass
 
 
 def view_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, key_cam_T_world_b44: torch.Tensor, key_K_s0_b44: torch.Tensor,
@@ -336,88 +406,14 @@ def view_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: torch.T
     Returns (depth (B,1,h,w) | (B,N), logits of the last step, flags uint8: bit 0 = ``hi`` moved, bit 1 = ``lo`` moved, bit 2 = some probe
     was invalid, world points (...,3) | None).  The MLP answers occlusion as seen from the keyframe: the depth is where the view's ray
     crosses into the region hidden from the keyframe - the surface as far as both cameras see the same side of it."""
-    if mlp_math_of(net) != "fp32":
-        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_search_fwd; set mlp_math = 'fp32'")
-    if (size is None) == (rays is None):
-        raise _lib.IdhError("view_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
-    pmap = prior if isinstance(prior, (tuple, list)) else None
-    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
-    _lib.require_cuda_f32(feat_view.buf, rays, *mats, pmap[0] if pmap is not None else None)
-    B, H, W = feat_view.N, feat_view.H, feat_view.W
-    for m in mats:
-        if m is None or tuple(m.shape) != (B, 4, 4):
-            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
-    if rays is not None:
-        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
-            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
-        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
-    else:
-        h, w = int(size[0]), int(size[1])
-        if h < 0 or w < 0:
-            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
-        N, shape = h * w, (B, 1, h, w)
-    if prior is not None and not net.use_prior:
-        raise _lib.IdhError("prior given to a network built with use_prior=False")
-    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
-        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
-    dev = feat_view.buf.device
-    bins, thr_logits = _thresholder_tables(thresholder, dev)
-    keep = [m.contiguous() for m in mats]  # alive until enqueued
-    r = rays.contiguous() if rays is not None else None
-    pp = pmap[0].contiguous() if pmap is not None else None
-    n = B * N
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
-    points = buf[2 * n:].view(*shape, 3) if return_points else None
-    flags = torch.empty(shape, device=dev, dtype=torch.uint8)
+    q = _view_query(net, "idh_binary_mlp_view_search_fwd", "view_depths", feat_view, None, (invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44),
+                    prior, size=size, rays=rays, return_points=return_points)
+    thr, _tables = _threshold_args(threshold, thresholder, q.dev)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_search_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, h, w, _lib.ptr(r), N if r is not None else 0,
-                                                  keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
-                                                  keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
-                                                  int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
-                                                  w2p.data_ptr(), vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
-                                                  0 if bins is None else bins.numel(), float(fill), depth.data_ptr(), logits.data_ptr(),
-                                                  flags.data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_search_fwd(*q.head, *q.source, *q.cams, iters, lo, hi, *thr, float(fill), q.a.data_ptr(), q.b.data_ptr(),
+                                                  q.u8.data_ptr(), _lib.ptr(q.points), _lib.stream_ptr()),
         "idh_binary_mlp_view_search_fwd")
-    return depth, logits, flags, points
-
-
-MAX_VIEW_KEYS, MAX_VIEW_KEY_CAMERAS = 16, 128  # idh_binary_mlp_view_keys_fwd: M <= 16, M * B <= 128
-
-
-def _view_keys_common(net, what, feat_ring, feat_c0, n_feat, key_slots, invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior):
-    """The checks and arguments the two multi-key wrappers share: (B, H, W, n_slots, slots array, M, matrices kept alive, prior map | None)."""
-    if mlp_math_of(net) != "fp32":
-        raise _lib.IdhError(f"ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of {what}; set mlp_math = 'fp32'")
-    pmap = prior if isinstance(prior, (tuple, list)) else None
-    _lib.require_cuda_f32(feat_ring, invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, *(pmap if pmap is not None else ()))
-    if feat_ring.dim() != 5 or not feat_ring.is_contiguous():
-        raise _lib.IdhError(f"the feature ring must be a dense (n_slots, B, H, W, C) tensor, got {tuple(feat_ring.shape)}")
-    n_slots, B, H, W, cs = feat_ring.shape
-    if feat_c0 < 0 or n_feat <= 0 or feat_c0 + n_feat > cs:
-        raise _lib.IdhError(f"channels [{feat_c0}, {feat_c0 + n_feat}) are not inside the ring's {cs}")
-    for m in (invK_b44, world_T_cam_b44):
-        if tuple(m.shape) != (B, 4, 4):
-            raise _lib.IdhError(f"invK / world_T_cam must be ({B}, 4, 4), got {tuple(m.shape)}")
-    rings = [key_cam_T_world_sb44, key_K_s0_sb44] + ([pmap[1], pmap[2]] if pmap is not None else [])
-    for m in rings:
-        if tuple(m.shape) != (n_slots, B, 4, 4):
-            raise _lib.IdhError(f"the camera rings must be ({n_slots}, {B}, 4, 4), got {tuple(m.shape)}")
-    if prior is not None and not net.use_prior:
-        raise _lib.IdhError("prior given to a network built with use_prior=False")
-    if pmap is not None and tuple(pmap[0].shape) != (n_slots, B, 1, H, W):
-        raise _lib.IdhError(f"prior ring {tuple(pmap[0].shape)} must be ({n_slots}, {B}, 1, {H}, {W})")
-    slots = [int(k) for k in key_slots]
-    if not slots or len(set(slots)) != len(slots) or any(k < 0 or k >= n_slots for k in slots):
-        raise _lib.IdhError(f"key_slots must be a non-empty list of distinct slots in [0, {n_slots}), got {slots}")
-    if len(slots) > MAX_VIEW_KEYS or len(slots) * B > MAX_VIEW_KEY_CAMERAS:
-        raise _lib.IdhError(f"{what} takes at most {MAX_VIEW_KEYS} keys and {MAX_VIEW_KEY_CAMERAS} key cameras (keys x batch), got {len(slots)} x {B} (IDH_EUNSUPPORTED)")
-    import ctypes as C
-
-    keep = [m.contiguous() for m in [invK_b44, world_T_cam_b44] + rings]  # alive until enqueued
-    pp = pmap[0].contiguous() if pmap is not None else None
-    return B, H, W, n_slots, (C.c_int * len(slots))(*slots), len(slots), keep, pp
+    return q.a, q.b, q.u8[0], q.points
 
 
 def view_keys_logits(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, rendered_bphw: torch.Tensor, invK_b44: torch.Tensor,
@@ -430,31 +426,13 @@ def view_keys_logits(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, ke
     prior_K (n_slots,B,4,4)) - the selected key's own prior is sampled.  Returns (logits (B,P,h,w), ``fill`` where no key is valid, key
     (B,P,h,w) uint8: the position in ``key_slots`` of the selected key, 255 = none, view_depth (B,P,h,w): z in the selected key (in the
     first key where none is valid), points (B,P,h,w,3) | None)."""
-    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_fwd", feat_ring, feat_c0, n_feat, key_slots, invK_b44,
-                                                              world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
-    _lib.require_cuda_f32(rendered_bphw)
-    if rendered_bphw.dim() != 4 or rendered_bphw.shape[0] != B:
-        raise _lib.IdhError(f"rendered depth must be ({B}, P, h, w), got {tuple(rendered_bphw.shape)}")
-    _, P, h, w = rendered_bphw.shape
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
-    dev = rendered_bphw.device
-    rd = rendered_bphw.contiguous()
-    n = B * P * h * w
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    logits, depth = buf[:n].view(B, P, h, w), buf[n: 2 * n].view(B, P, h, w)
-    points = buf[2 * n:].view(B, P, h, w, 3) if return_points else None
-    key = torch.empty(B, P, h, w, device=dev, dtype=torch.uint8)
-    cs = feat_ring.shape[-1]
+    q = _view_query(net, "idh_binary_mlp_view_keys_fwd", "view_keys_logits", None, (feat_ring, feat_c0, n_feat, key_slots),
+                    (invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44), prior, rendered=rendered_bphw, return_points=return_points)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_keys_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
-                                                rd.data_ptr(), P, h, w, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(),
-                                                keep[3].data_ptr(), _lib.ptr(pp), keep[4].data_ptr() if pp is not None else None,
-                                                keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
-                                                -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
-                                                vecs.data_ptr(), float(fill), logits.data_ptr(), key.data_ptr(), depth.data_ptr(),
-                                                _lib.ptr(points), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_keys_fwd(*q.head, *q.source, *q.cams, float(fill), q.a.data_ptr(), q.u8.data_ptr(), q.b.data_ptr(),
+                                                _lib.ptr(q.points), _lib.stream_ptr()),
         "idh_binary_mlp_view_keys_fwd")
-    return logits, key, depth, points
+    return q.a, q.u8[0], q.b, q.points
 
 
 def view_keys_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor,
@@ -466,42 +444,14 @@ def view_keys_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, ke
     is looked up at the probe's depth in the selected key (in the first key where none is valid).  Ring arguments as ``view_keys_logits``,
     the others as ``view_depths``.  Returns (depth, logits of the last step, flags uint8 - bit 2: no key was valid at some probe -, world
     points | None, key uint8: the position in ``key_slots`` of the key the LAST step selected, 255 = none)."""
-    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_search_fwd", feat_ring, feat_c0, n_feat, key_slots,
-                                                              invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
-    if (size is None) == (rays is None):
-        raise _lib.IdhError("view_keys_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
-    _lib.require_cuda_f32(rays)
-    if rays is not None:
-        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
-            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
-        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
-    else:
-        h, w = int(size[0]), int(size[1])
-        if h < 0 or w < 0:
-            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
-        N, shape = h * w, (B, 1, h, w)
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
-    dev = feat_ring.device
-    bins, thr_logits = _thresholder_tables(thresholder, dev)
-    r = rays.contiguous() if rays is not None else None
-    n = B * N
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
-    points = buf[2 * n:].view(*shape, 3) if return_points else None
-    flags = torch.empty((2,) + tuple(shape), device=dev, dtype=torch.uint8)
-    cs = feat_ring.shape[-1]
+    q = _view_query(net, "idh_binary_mlp_view_keys_search_fwd", "view_keys_depths", None, (feat_ring, feat_c0, n_feat, key_slots),
+                    (invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44), prior, size=size, rays=rays, return_points=return_points, planes=2)
+    thr, _tables = _threshold_args(threshold, thresholder, q.dev)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_keys_search_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
-                                                       h, w, _lib.ptr(r), N if r is not None else 0, keep[0].data_ptr(), keep[1].data_ptr(),
-                                                       keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
-                                                       keep[4].data_ptr() if pp is not None else None,
-                                                       keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
-                                                       -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
-                                                       vecs.data_ptr(), iters, lo, hi, threshold, _lib.ptr(bins), _lib.ptr(thr_logits),
-                                                       0 if bins is None else bins.numel(), float(fill), depth.data_ptr(), logits.data_ptr(),
-                                                       flags[0].data_ptr(), _lib.ptr(points), flags[1].data_ptr(), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_keys_search_fwd(*q.head, *q.source, *q.cams, iters, lo, hi, *thr, float(fill), q.a.data_ptr(), q.b.data_ptr(),
+                                                       q.u8[0].data_ptr(), _lib.ptr(q.points), q.u8[1].data_ptr(), _lib.stream_ptr()),
         "idh_binary_mlp_view_keys_search_fwd")
-    return depth, logits, flags[0], points, flags[1]
+    return q.a, q.b, q.u8[0], q.points, q.u8[1]
 
 
 MAX_MARCH_SAMPLES = 255  # idh_binary_mlp_view_march_fwd: hit_step is a byte, 255 = none
@@ -577,54 +527,15 @@ def view_march_depths(net, feat_view, invK_b44: torch.Tensor, world_T_cam_b44: t
     Returns (depth (B,1,h,w) | (B,N), logits of each ray's last probe, flags uint8: 3 = bracketed, 1 = behind at the first sample (depth is
     that sample), 2 = no hit (depth is the last sample), bit 2 = some evaluated probe was invalid, hit_step uint8: the first sample that was
     behind, 255 = none, world points (...,3) | None)."""
-    if mlp_math_of(net) != "fp32":
-        raise _lib.IdhError("ray queries are fp32 only (IDH_EUNSUPPORTED): there is no f16x3 form of idh_binary_mlp_view_march_fwd; set mlp_math = 'fp32'")
-    if (size is None) == (rays is None):
-        raise _lib.IdhError("view_march_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
-    if int(refine) < 0:
-        raise _lib.IdhError(f"refine must be >= 0, got {refine}")
-    pmap = prior if isinstance(prior, (tuple, list)) else None
-    mats = [invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44] + ([pmap[1], pmap[2]] if pmap is not None else [])
-    _lib.require_cuda_f32(feat_view.buf, rays, *mats, pmap[0] if pmap is not None else None)
-    B, H, W = feat_view.N, feat_view.H, feat_view.W
-    for m in mats:
-        if m is None or tuple(m.shape) != (B, 4, 4):
-            raise _lib.IdhError(f"invK / world_T_cam / key_cam_T_world / key_K_s0 (and the prior's) must be ({B}, 4, 4)")
-    if rays is not None:
-        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
-            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
-        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
-    else:
-        h, w = int(size[0]), int(size[1])
-        if h < 0 or w < 0:
-            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
-        N, shape = h * w, (B, 1, h, w)
-    if prior is not None and not net.use_prior:
-        raise _lib.IdhError("prior given to a network built with use_prior=False")
-    if pmap is not None and tuple(pmap[0].shape) != (B, 1, H, W):
-        raise _lib.IdhError(f"prior prediction {tuple(pmap[0].shape)} must be ({B}, 1, {H}, {W})")
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], feat_view.C, net.use_prior, "fp32")
-    dev = feat_view.buf.device
-    md = _march_depths(samples, lo, hi, spacing, dev)
-    bins, thr_logits = _thresholder_tables(thresholder, dev)
-    keep = [m.contiguous() for m in mats]  # alive until enqueued
-    r = rays.contiguous() if rays is not None else None
-    pp = pmap[0].contiguous() if pmap is not None else None
-    n = B * N
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
-    points = buf[2 * n:].view(*shape, 3) if return_points else None
-    flags = torch.empty((2,) + tuple(shape), device=dev, dtype=torch.uint8)
+    q = _view_query(net, "idh_binary_mlp_view_march_fwd", "view_march_depths", feat_view, None, (invK_b44, world_T_cam_b44, key_cam_T_world_b44, key_K_s0_b44),
+                    prior, size=size, rays=rays, refine=refine, return_points=return_points, planes=2)
+    md = _march_depths(samples, lo, hi, spacing, q.dev)
+    thr, _tables = _threshold_args(threshold, thresholder, q.dev)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_march_fwd(feat_view.ptr, feat_view.cs, feat_view.C, B, H, W, h, w, _lib.ptr(r), N if r is not None else 0,
-                                                 keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
-                                                 keep[4].data_ptr() if pp is not None else None, keep[5].data_ptr() if pp is not None else None,
-                                                 int(net.use_prior), -1.0 if prior is None or pmap is not None else float(prior), w1p.data_ptr(),
-                                                 w2p.data_ptr(), vecs.data_ptr(), md.data_ptr(), md.numel(), int(refine), threshold, _lib.ptr(bins),
-                                                 _lib.ptr(thr_logits), 0 if bins is None else bins.numel(), float(fill), depth.data_ptr(),
-                                                 logits.data_ptr(), flags[0].data_ptr(), flags[1].data_ptr(), _lib.ptr(points), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_march_fwd(*q.head, *q.source, *q.cams, md.data_ptr(), md.numel(), int(refine), *thr, float(fill), q.a.data_ptr(),
+                                                 q.b.data_ptr(), q.u8[0].data_ptr(), q.u8[1].data_ptr(), _lib.ptr(q.points), _lib.stream_ptr()),
         "idh_binary_mlp_view_march_fwd")
-    return depth, logits, flags[0], flags[1], points
+    return q.a, q.b, q.u8[0], q.u8[1], q.points
 
 
 def view_keys_march_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: int, key_slots, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor,
@@ -636,46 +547,17 @@ def view_keys_march_depths(net, feat_ring: torch.Tensor, feat_c0: int, n_feat: i
     was valid at some evaluated probe.  Ring arguments as ``view_keys_logits``, the others as ``view_march_depths``.  Returns (depth, logits
     of the last probe, flags, hit_step, world points | None, key uint8: the position in ``key_slots`` of the key the ray's LAST evaluated
     probe selected, 255 = none)."""
-    B, H, W, n_slots, slots, M, keep, pp = _view_keys_common(net, "idh_binary_mlp_view_keys_march_fwd", feat_ring, feat_c0, n_feat, key_slots,
-                                                              invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44, prior)
-    if (size is None) == (rays is None):
-        raise _lib.IdhError("view_keys_march_depths takes exactly one of size=(h, w) and rays=(B,N,2)")
-    if int(refine) < 0:
-        raise _lib.IdhError(f"refine must be >= 0, got {refine}")
-    _lib.require_cuda_f32(rays)
-    if rays is not None:
-        if rays.dim() != 3 or rays.shape[0] != B or rays.shape[2] != 2:
-            raise _lib.IdhError(f"rays must be ({B}, N, 2), got {tuple(rays.shape)}")
-        h, w, N, shape = 0, 0, rays.shape[1], (B, rays.shape[1])
-    else:
-        h, w = int(size[0]), int(size[1])
-        if h < 0 or w < 0:
-            raise _lib.IdhError(f"size must be (h, w) >= 0, got {tuple(size)}")
-        N, shape = h * w, (B, 1, h, w)
-    w1p, w2p, vecs = _prepared(net.mlps["s0"], n_feat, net.use_prior, "fp32")
-    dev = feat_ring.device
-    md = _march_depths(samples, lo, hi, spacing, dev)
-    bins, thr_logits = _thresholder_tables(thresholder, dev)
-    r = rays.contiguous() if rays is not None else None
-    n = B * N
-    buf = torch.empty((5 if return_points else 2) * n, device=dev)  # one allocation for the float outputs, as project_points
-    depth, logits = buf[:n].view(shape), buf[n: 2 * n].view(shape)
-    points = buf[2 * n:].view(*shape, 3) if return_points else None
-    flags = torch.empty((3,) + tuple(shape), device=dev, dtype=torch.uint8)
-    cs = feat_ring.shape[-1]
+    q = _view_query(net, "idh_binary_mlp_view_keys_march_fwd", "view_keys_march_depths", None, (feat_ring, feat_c0, n_feat, key_slots),
+                    (invK_b44, world_T_cam_b44, key_cam_T_world_sb44, key_K_s0_sb44), prior, size=size, rays=rays, refine=refine,
+                    return_points=return_points, planes=3)
+    md = _march_depths(samples, lo, hi, spacing, q.dev)
+    thr, _tables = _threshold_args(threshold, thresholder, q.dev)
     _lib.check(
-        _lib.lib().idh_binary_mlp_view_keys_march_fwd(feat_ring.data_ptr() + 4 * feat_c0, cs, n_feat, B, H, W, B * H * W * cs, n_slots, slots, M,
-                                                      h, w, _lib.ptr(r), N if r is not None else 0, keep[0].data_ptr(), keep[1].data_ptr(),
-                                                      keep[2].data_ptr(), keep[3].data_ptr(), _lib.ptr(pp),
-                                                      keep[4].data_ptr() if pp is not None else None,
-                                                      keep[5].data_ptr() if pp is not None else None, int(net.use_prior),
-                                                      -1.0 if prior is None or pp is not None else float(prior), w1p.data_ptr(), w2p.data_ptr(),
-                                                      vecs.data_ptr(), md.data_ptr(), md.numel(), int(refine), threshold, _lib.ptr(bins),
-                                                      _lib.ptr(thr_logits), 0 if bins is None else bins.numel(), float(fill), depth.data_ptr(),
-                                                      logits.data_ptr(), flags[0].data_ptr(), flags[1].data_ptr(), _lib.ptr(points),
-                                                      flags[2].data_ptr(), _lib.stream_ptr()),
+        _lib.lib().idh_binary_mlp_view_keys_march_fwd(*q.head, *q.source, *q.cams, md.data_ptr(), md.numel(), int(refine), *thr, float(fill),
+                                                      q.a.data_ptr(), q.b.data_ptr(), q.u8[0].data_ptr(), q.u8[1].data_ptr(), _lib.ptr(q.points),
+                                                      q.u8[2].data_ptr(), _lib.stream_ptr()),
         "idh_binary_mlp_view_keys_march_fwd")
-    return depth, logits, flags[0], flags[1], points, flags[2]
+    return q.a, q.b, q.u8[0], q.u8[1], q.points, q.u8[2]
 
 
 def binary_mlp_forward(net, inputs: List[torch.Tensor], max_scale_only: bool = False) -> Dict[str, torch.Tensor]:

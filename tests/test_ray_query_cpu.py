@@ -136,6 +136,15 @@ def _rows():
         add("rays", Q.EINVAL, **{k: P + 2})  # not 4-byte aligned
     add("rays", Q.EUNSUPPORTED, B=1 << 16, N=1 << 16)  # B * Nq >= 2^31
     add("rays", Q.EUNSUPPORTED, B=1 << 12, H=1 << 10, W=1 << 10)  # B * H * W >= 2^31
+    add("rays", Q.EUNSUPPORTED, B=1 << 10, N=1 << 20, S=1 << 20)  # B * Nq fits, the work items of the launch do not
+    # which rule wins: shapes, then the empty call, then the pointers, then the sizes
+    add("rays", Q.EINVAL, B=0, Cf=62)
+    add("rays", Q.EINVAL, N=0, S=0)
+    add("rays", Q.OK, B=0, rays=P + 2)
+    add("rays", Q.OK, N=0, B=1 << 12, H=1 << 10, W=1 << 10)
+    add("rays", Q.EINVAL, feat=None, B=1 << 16, N=1 << 16)
+    add("rays", Q.EINVAL, out=P + 2, B=1 << 12, H=1 << 10, W=1 << 10)
+    add("rays", Q.EINVAL, ray_step=0, B=1 << 16, N=1 << 16)
     for k in ("points", "cam_T_world", "K", "rays", "depth", "valid"):
         add("proj", Q.EINVAL, **{k: None})
     for k in ("B", "N"):

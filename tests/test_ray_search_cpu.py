@@ -65,6 +65,18 @@ def _refusals():
     add(invK=None, points=None, wTc=None, B=0, code=OK)
     add(flags=None, points=None, B=0, code=OK)  # both optional outputs
     add(prior=None, B=0, code=OK)  # prior_const
+    # which rule wins: argument errors, then the empty call, then the pointers, then the sizes
+    add(B=0, iters=0)
+    add(B=0, threshold=0.0, n_bins=0)
+    add(N=0, bins=None)
+    add(N=0, invK=None)
+    add(B=0, rays=None, depth=None, code=OK)
+    add(N=0, B=1 << 11, H=1 << 10, W=1 << 10, code=OK)
+    add(feat=None, B=1 << 10, N=1 << 21)
+    add(points=P_(14) + 2, B=1 << 11, H=1 << 10, W=1 << 10)
+    add(hi=0.5, lo=8.0, B=1 << 10, N=1 << 21)
+    add(lo=0.0, B=0, code=OK)  # hi > lo is all this entry point asks of the bracket
+    add(lo=-1.0, hi=float("inf"), B=0, code=OK)
     return rs
 
 

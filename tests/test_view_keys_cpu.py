@@ -204,6 +204,15 @@ def _key_rows(add):
         add(VK.EINVAL, **dict(prior, **{k: None}))
     add(VK.EINVAL, **dict(prior, has_prior=0))
     add(VK.EUNSUPPORTED, B=129, M=1, key_slots=(0,), key_stride=129 * 5 * 7 * 64)
+    # which rule wins: the keys are looked at after the pointers and before the sizes, and each of their rules in its own order
+    add(VK.EINVAL, B=0, Cf=62)
+    add(VK.EINVAL, **dict(prior, has_prior=0, B=0))
+    add(VK.EINVAL, key_slots=None, B=129)
+    add(VK.EINVAL, n_slots=17, key_slots=tuple(range(17)), M=17, feat=P + 2)
+    add(VK.EINVAL, n_slots=17, key_slots=tuple(range(17)), M=17, key_stride=-4)
+    add(VK.EUNSUPPORTED, n_slots=17, key_slots=(0, 0) + tuple(range(2, 17)), M=17)  # too many keys, before they are read
+    add(VK.EINVAL, key_slots=(0, 1, 0), B=43, key_stride=43 * 5 * 7 * 64)
+    add(VK.EINVAL, key_stride=129 * 5 * 7 * 64 - 1, B=129)  # overlapping blocks, before M * B
 
 
 def _dense_rows():

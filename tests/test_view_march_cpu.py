@@ -207,6 +207,18 @@ def _rows():
     add(V.OK, B=0)
     add(V.OK, n_march=1, refine=0, B=0)
     add(V.OK, n_march=255, refine=0, h=0)
+    # which rule wins: shapes, the march, the thresholds and the prior rule, then the empty call, then the pointers, then the sizes
+    add(V.EUNSUPPORTED, refine=(1 << 30) + 1)
+    add(V.EUNSUPPORTED, refine=(1 << 30) + 1, threshold=0.0)
+    add(V.EUNSUPPORTED, refine=(1 << 30) + 1, B=0)
+    add(V.EINVAL, refine=(1 << 30) + 1, n_bins=-1)
+    add(V.EINVAL, refine=(1 << 30) + 1, n_march=0)
+    add(V.EINVAL, B=0, threshold=0.0)
+    add(V.EINVAL, h=0, prior_pred=P, prior_cam_T_world=P, prior_K=P, has_prior=0)
+    add(V.OK, h=0, B=129)
+    add(V.OK, w=0, depth=P + 2)
+    add(V.EINVAL, feat=None, B=129)
+    add(V.EINVAL, points=P + 2, B=8, h=1 << 14, w=1 << 14)
     # the parents' that apply
     for k in ("feat", "invK", "world_T_cam", "key_cam_T_world", "key_K", "w1f", "w2", "vecs", "depth", "last_logits"):
         add(V.EINVAL, **{k: None})
@@ -258,6 +270,9 @@ def _keys_rows():
     add(V.EUNSUPPORTED, key_slots=tuple(range(17)), M=17, n_slots=17)
     add(V.EUNSUPPORTED, key_slots=tuple(range(16)), M=16, n_slots=16, B=9)  # M * B > 128
     add(V.OK, key_slots=None, B=0)
+    add(V.EINVAL, key_slots=None, B=129)  # the keys are looked at before the sizes ...
+    add(V.EINVAL, key_slots=tuple(range(17)), M=17, n_slots=17, feat=P + 2)  # ... and after the pointers
+    add(V.EUNSUPPORTED, key_slots=None, refine=(1 << 30) + 1)
     return rs
 
 

@@ -147,6 +147,15 @@ def _rows():
     add(V.EUNSUPPORTED, B=8, P=1 << 8, h=1 << 10, w=1 << 10)  # B * P * h * w >= 2^31
     add(V.EUNSUPPORTED, B=1 << 12, H=1 << 10, W=1 << 10)  # B * H * W >= 2^31
     add(V.EUNSUPPORTED, B=129)  # the cameras of one launch sit in LDS
+    # which rule wins: shapes and the prior rule, then the empty call, then the pointers, then the sizes
+    add(V.EINVAL, B=0, Cf=62)
+    add(V.EINVAL, **dict(prior, has_prior=0, h=0))
+    add(V.OK, w=0, B=129)
+    add(V.OK, P=0, rendered=P + 2)
+    add(V.OK, P=1 << 16, h=1 << 16, w=0)
+    add(V.EINVAL, feat=None, B=129)
+    add(V.EINVAL, logits=P + 2, B=1, P=1 << 16, h=1 << 16)
+    add(V.EINVAL, H=0, B=129)
     return rs
 
 

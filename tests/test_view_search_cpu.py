@@ -182,6 +182,17 @@ def _rows():
     add(V.EUNSUPPORTED, B=4, rays=P, N=1 << 29)
     add(V.EUNSUPPORTED, B=1 << 12, H=1 << 10, W=1 << 10)  # B * H * W >= 2^31
     add(V.EUNSUPPORTED, B=129)  # the cameras of one launch sit in LDS
+    # which rule wins: argument errors, then the empty call, then the pointers, then the sizes
+    add(V.EINVAL, B=0, iters=0)
+    add(V.EINVAL, h=0, threshold=1.0)
+    add(V.EINVAL, w=0, lo=0.0)
+    add(V.EINVAL, **dict(prior, has_prior=0, B=0))
+    add(V.EINVAL, rays=P, N=0, n_bins=3)
+    add(V.OK, h=0, B=129)
+    add(V.OK, B=0, depth=P + 2)
+    add(V.EINVAL, feat=None, B=129)
+    add(V.EINVAL, points=P + 2, B=8, h=1 << 14, w=1 << 14)
+    add(V.EINVAL, hi=INF, B=1 << 12, H=1 << 10, W=1 << 10)
     return rs
 
 
