@@ -217,6 +217,38 @@ class TsdfMeshArgs(C.Structure):
         self.struct_size = C.sizeof(TsdfMeshArgs)
 
 
+class TsdfIntegrateColorArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_integrate_color_args`` (include/idh_fusion.h, TSDF colour)."""
+
+    _fields_ = TsdfIntegrateArgs._fields_ + [("colors_zyx4", C.c_void_p), ("color_mhw3", C.c_void_p), ("color_K_m44", C.c_void_p),
+                                             ("hc", C.c_int32), ("wc", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfIntegrateColorArgs)
+
+
+class TsdfRaycastColorArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_raycast_color_args`` (include/idh_fusion.h)."""
+
+    _fields_ = TsdfRaycastArgs._fields_ + [("colors_zyx4", C.c_void_p), ("rgba_bhw4", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfRaycastColorArgs)
+
+
+class TsdfMeshColorsArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_mesh_colors_args`` (include/idh_fusion.h)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("mesh", TsdfMeshArgs), ("colors_zyx4", C.c_void_p), ("rgba_v4", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfMeshColorsArgs)
+        self.mesh.struct_size = C.sizeof(TsdfMeshArgs)
+
+
 TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
 TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
 
@@ -340,6 +372,12 @@ _SIGS = {
     "idh_tsdf_mesh_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "idh_tsdf_mesh_count_fwd": (C.c_int, [C.POINTER(TsdfMeshArgs), C.c_void_p]),
     "idh_tsdf_mesh_emit_fwd": (C.c_int, [C.POINTER(TsdfMeshArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_integrate_color_args": (C.c_size_t, []),
+    "idh_sizeof_tsdf_raycast_color_args": (C.c_size_t, []),
+    "idh_sizeof_tsdf_mesh_colors_args": (C.c_size_t, []),
+    "idh_tsdf_integrate_color_fwd": (C.c_int, [C.POINTER(TsdfIntegrateColorArgs), C.c_void_p]),
+    "idh_tsdf_raycast_color_fwd": (C.c_int, [C.POINTER(TsdfRaycastColorArgs), C.c_void_p]),
+    "idh_tsdf_mesh_colors_fwd": (C.c_int, [C.POINTER(TsdfMeshColorsArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -435,7 +473,10 @@ def lib():
                                   ("idh_tsdf_volume", h.idh_sizeof_tsdf_volume(), TsdfVolume),
                                   ("idh_tsdf_integrate_args", h.idh_sizeof_tsdf_integrate_args(), TsdfIntegrateArgs),
                                   ("idh_tsdf_raycast_args", h.idh_sizeof_tsdf_raycast_args(), TsdfRaycastArgs),
-                                  ("idh_tsdf_mesh_args", h.idh_sizeof_tsdf_mesh_args(), TsdfMeshArgs)):
+                                  ("idh_tsdf_mesh_args", h.idh_sizeof_tsdf_mesh_args(), TsdfMeshArgs),
+                                  ("idh_tsdf_integrate_color_args", h.idh_sizeof_tsdf_integrate_color_args(), TsdfIntegrateColorArgs),
+                                  ("idh_tsdf_raycast_color_args", h.idh_sizeof_tsdf_raycast_color_args(), TsdfRaycastColorArgs),
+                                  ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

@@ -5,9 +5,15 @@
 //   tsdf_flags_k      block flags from the values of a volume made elsewhere (after a clear).
 //   tsdf_integrate_k  one lane per voxel, a wave along x; the M cameras are wave-uniform (scalar loads), the voxel's {T, W} pair stays in
 //                     registers over the M maps: one 8-byte load at the first map that touches it, one 8-byte store at the end.
-//   tsdf_raycast_k<SKIP, NORMALS>  one lane per pixel, an 8 x 8-pixel tile per wave.  A sample reads its eight corners as four 16-byte
+//                     With IntegrateColorArgs the same kernel also averages a camera frame's tap into the voxel's {R, G, B, Wc} quad
+//                     (one 16-byte load and store per coloured voxel, three byte gathers per coloured voxel and map).
+//   tsdf_raycast_k<SKIP, NORMALS, Args>  one lane per pixel, an 8 x 8-pixel tile per wave.  A sample reads its eight corners as four 16-byte
 //                     loads: the x-neighbours {T0, W0, T1, W1} are adjacent in memory (8-byte aligned, which the global loads of gfx950
-//                     take).  SKIP clips the lattice range to the volume's box and jumps blocks whose flag is 0.
+//                     take).  SKIP clips the lattice range to the volume's box and jumps blocks whose flag is 0.  With RaycastColorArgs
+//                     also the hit's colour: eight 16-byte loads of {R, G, B, Wc} once per pixel, after the march.
+//
+// The colour variants are instantiations on an argument struct derived from the plain one: the plain instantiations keep
+// their kernel arguments and their code.
 //
 // Block flags.  A lane's row is 64 consecutive x, so the eight lanes of an aligned group share one block along x: the group's first lane
 // stores for the group (one ballot), and a touched voxel on a block's low face also stores for the block before it (the + 1 apron).
@@ -54,13 +60,25 @@ __global__ __launch_bounds__(256) void tsdf_flags_k(const Vol V) {
 }
 
 struct IntegrateArgs {
+    static constexpr bool kColor = false;
     Vol V;
     const float *depth, *K, *T;
     float max_weight;
     int M, h, w;
 };
 
-__global__ __launch_bounds__(256) void tsdf_integrate_k(const IntegrateArgs a) {
+// the colour variant's arguments come after the plain ones, so the plain instantiation's kernel arguments are what they were
+struct IntegrateColorArgs : IntegrateArgs {
+    static constexpr bool kColor = true;
+    float4 *colors;
+    const uint8_t *frames;
+    const float *Kc;
+    int hc, wc;
+};
+
+template <class Args>
+__global__ __launch_bounds__(256) void tsdf_integrate_k(const Args a) {
+    constexpr bool COLOR = Args::kColor;
     const Vol &V = a.V;
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
     if (y >= V.Ny) return;  // whole wave
@@ -70,6 +88,8 @@ __global__ __launch_bounds__(256) void tsdf_integrate_k(const IntegrateArgs a) {
     float T = 1.f, W = 0.f;
     bool touched = false;
     const float fw = (float)a.w, fh = (float)a.h;
+    float4 col = make_float4(0.f, 0.f, 0.f, 0.f);  // {R, G, B, Wc}
+    bool coloured = false;
     for (int m = 0; m < a.M; ++m) {
         const float *E = a.T + m * 16, *K = a.K + m * 16;  // wave-uniform
         const float cz = ((E[8] * px + E[9] * py) + E[10] * pz) + E[11];
@@ -91,12 +111,30 @@ __global__ __launch_bounds__(256) void tsdf_integrate_k(const IntegrateArgs a) {
         }
         T = (W * T + s) / (W + 1.f);
         W = fminf(W + 1.f, a.max_weight);
+        if constexpr (COLOR) {
+            if (!(sdf <= V.trunc)) continue;  // free space in front of the band
+            const float *Kc = a.Kc + m * 16;
+            const float qx = Kc[0] * (cx / cz) + Kc[2], qy = Kc[5] * (cy / cz) + Kc[6];
+            if (!(qx >= 0.f && qx < (float)a.wc && qy >= 0.f && qy < (float)a.hc)) continue;
+            const uint8_t *tap = a.frames + (((size_t)m * a.hc + (int)floorf(qy)) * a.wc + (int)floorf(qx)) * 3;
+            const float r = (float)tap[0], g = (float)tap[1], b = (float)tap[2];
+            float4 *quad = a.colors + (((size_t)z * V.Ny + y) * V.Nx + x);
+            if (!coloured) col = *quad, coloured = true;
+            col.x = (col.w * col.x + r) / (col.w + 1.f);
+            col.y = (col.w * col.y + g) / (col.w + 1.f);
+            col.z = (col.w * col.z + b) / (col.w + 1.f);
+            col.w = fminf(col.w + 1.f, a.max_weight);
+        }
     }
     if (touched) *cell = make_float2(T, W);
+    if constexpr (COLOR) {
+        if (coloured) a.colors[((size_t)z * V.Ny + y) * V.Nx + x] = col;
+    }
     mark_blocks(V, touched, x, y, z);  // a touched voxel has W >= 1
 }
 
 struct RaycastArgs {
+    static constexpr bool kColor = false;
     Vol V;
     const float *world_T_cam, *invK;
     float *depth, *normals;
@@ -104,6 +142,14 @@ struct RaycastArgs {
     float near, step_voxels, empty_depth;
     int max_steps, world_normals, B, H, W;
 };
+
+struct RaycastColorArgs : RaycastArgs {  // as IntegrateColorArgs: the plain arguments first
+    static constexpr bool kColor = true;
+    const float4 *colors;
+    uint8_t *rgba;
+};
+
+__device__ __forceinline__ unsigned channel_byte(float c) { return (unsigned)(int)(fminf(fmaxf(c, 0.f), 255.f) + 0.5f); }
 
 // the eight corners of the cell at floor(g): false when the cell is outside the volume or a corner has W == 0
 struct Corners {
@@ -135,8 +181,9 @@ __device__ __forceinline__ float trilinear(const Corners &c) {
     return lerp(lerp(a00, a10, c.ry), lerp(a01, a11, c.ry), c.rz);
 }
 
-template <bool SKIP, bool NORMALS>
-__global__ __launch_bounds__(256) void tsdf_raycast_k(const RaycastArgs a) {
+template <bool SKIP, bool NORMALS, class Args>
+__global__ __launch_bounds__(256) void tsdf_raycast_k(const Args a) {
+    constexpr bool COLOR = Args::kColor;
     const Vol &V = a.V;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int j = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), i = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3), b = blockIdx.z;
@@ -263,6 +310,30 @@ __global__ __launch_bounds__(256) void tsdf_raycast_k(const RaycastArgs a) {
         o[0] = nx, o[plane] = ny, o[2 * plane] = nz;
     }
     a.flags[pix] = (uint8_t)flags;
+    if constexpr (COLOR) {
+        // once per pixel, outside the march: the coloured corners of the hit's cell, weighted trilinearly and renormalised
+        unsigned rgba = 0u;
+        if (hit_k >= 0) {
+            const float gx = ogx + t_star * dgx, gy = ogy + t_star * dgy, gz = ogz + t_star * dgz;
+            float fx, fy, fz;
+            if (cell_of(V, gx, gy, gz, fx, fy, fz)) {
+                const float rx = gx - fx, ry = gy - fy, rz = gz - fz;
+                const size_t row = (size_t)V.Nx, slice = row * V.Ny;
+                const float4 *p = a.colors + ((size_t)(int)fz * slice + (size_t)(int)fy * row + (size_t)(int)fx);
+                float nr = 0.f, ng = 0.f, nb = 0.f, den = 0.f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const int ex = c & 1, ey = (c >> 1) & 1, ez = c >> 2;
+                    const float4 q = p[ex + ey * row + ez * slice];
+                    if (!(q.w > 0.f)) continue;
+                    const float w = ((ex ? rx : 1.f - rx) * (ey ? ry : 1.f - ry)) * (ez ? rz : 1.f - rz);
+                    nr += w * q.x, ng += w * q.y, nb += w * q.z, den += w;
+                }
+                if (den > 0.f) rgba = channel_byte(nr / den) | channel_byte(ng / den) << 8 | channel_byte(nb / den) << 16 | 255u << 24;
+            }
+        }
+        reinterpret_cast<unsigned *>(a.rgba)[pix] = rgba;  // bytes R, G, B, A in memory order
+    }
 }
 
 dim3 voxel_grid(const Vol &V) { return dim3(idh_cdiv(V.Nx, 64), idh_cdiv(V.Ny, 4), V.Nz); }
@@ -279,6 +350,8 @@ int clear_volume(const Vol &V, bool values, hipStream_t st) {
 extern "C" size_t idh_sizeof_tsdf_volume(void) { return sizeof(idh_tsdf_volume); }
 extern "C" size_t idh_sizeof_tsdf_integrate_args(void) { return sizeof(idh_tsdf_integrate_args); }
 extern "C" size_t idh_sizeof_tsdf_raycast_args(void) { return sizeof(idh_tsdf_raycast_args); }
+extern "C" size_t idh_sizeof_tsdf_integrate_color_args(void) { return sizeof(idh_tsdf_integrate_color_args); }
+extern "C" size_t idh_sizeof_tsdf_raycast_color_args(void) { return sizeof(idh_tsdf_raycast_color_args); }
 
 extern "C" size_t idh_tsdf_block_flag_bytes(int Nz, int Ny, int Nx) {
     if (Nz < 2 || Ny < 2 || Nx < 2) return 0;
@@ -314,33 +387,74 @@ extern "C" int idh_tsdf_integrate_fwd(const idh_tsdf_integrate_args *args, void 
     if (e.M > IDH_TSDF_MAX_MAPS || (long long)e.M * e.h * e.w >= (1ll << 31)) return IDH_EUNSUPPORTED;
     a.depth = e.depth_m1hw, a.K = e.K_m44, a.T = e.cam_T_world_m44;
     a.max_weight = e.max_weight, a.M = e.M, a.h = e.h, a.w = e.w;
-    hipLaunchKernelGGL(tsdf_integrate_k, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
+    hipLaunchKernelGGL(tsdf_integrate_k<IntegrateArgs>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }
 
-extern "C" int idh_tsdf_raycast_fwd(const idh_tsdf_raycast_args *args, void *stream) {
-    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_raycast_args)) return IDH_EINVAL;
-    const idh_tsdf_raycast_args &e = *args;
+extern "C" int idh_tsdf_integrate_color_fwd(const idh_tsdf_integrate_color_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_integrate_color_args)) return IDH_EINVAL;
+    const idh_tsdf_integrate_color_args &e = *args;
+    if (e.M <= 0 || e.h <= 0 || e.w <= 0 || e.hc <= 0 || e.wc <= 0) return IDH_EINVAL;
+    if (!(e.max_weight >= 1.f && e.max_weight < INFINITY)) return IDH_EINVAL;
+    if (!e.depth_m1hw || !e.K_m44 || !e.cam_T_world_m44 || !e.colors_zyx4 || !e.color_mhw3 || !e.color_K_m44) return IDH_EINVAL;
+    if ((uintptr_t)e.colors_zyx4 & 15u) return IDH_EINVAL;
+    IntegrateColorArgs a;
+    if (const int rc = check_volume(e.volume, a.V)) return rc;
+    if (e.M > IDH_TSDF_MAX_MAPS || (long long)e.M * e.h * e.w >= (1ll << 31) || (long long)e.M * e.hc * e.wc >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    a.depth = e.depth_m1hw, a.K = e.K_m44, a.T = e.cam_T_world_m44;
+    a.max_weight = e.max_weight, a.M = e.M, a.h = e.h, a.w = e.w;
+    a.colors = reinterpret_cast<float4 *>(e.colors_zyx4), a.frames = e.color_mhw3, a.Kc = e.color_K_m44, a.hc = e.hc, a.wc = e.wc;
+    hipLaunchKernelGGL(tsdf_integrate_k<IntegrateColorArgs>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+namespace {
+
+// what both ray casts check and set, in the header's order (the colour call's own pointers are checked by its entry point in between)
+template <class E>
+int raycast_check_inputs(const E &e) {
     if (e.B <= 0 || e.H <= 0 || e.W <= 0 || e.max_steps <= 0) return IDH_EINVAL;
     if (!(e.step_voxels > 0.f && e.step_voxels <= 1.f)) return IDH_EINVAL;  // also refuses NaN
     if (!(e.near >= 0.f && e.near < INFINITY) || e.empty_depth != e.empty_depth) return IDH_EINVAL;
     if (!e.world_T_cam_b44 || !e.invK_b44 || !e.depth_b1hw || !e.flags_bhw) return IDH_EINVAL;
-    RaycastArgs a;
+    return IDH_OK;
+}
+
+template <class E, class A>
+int raycast_launch(const E &e, A &a, hipStream_t st) {
     if (const int rc = check_volume(e.volume, a.V)) return rc;
     if (e.B > IDH_TSDF_MAX_CAMERAS || (long long)e.B * e.H * e.W >= (1ll << 31) || e.max_steps > IDH_TSDF_MAX_STEPS) return IDH_EUNSUPPORTED;
     a.world_T_cam = e.world_T_cam_b44, a.invK = e.invK_b44, a.depth = e.depth_b1hw, a.normals = e.normals_b3hw, a.flags = e.flags_bhw;
     a.near = e.near, a.step_voxels = e.step_voxels, a.empty_depth = e.empty_depth;
     a.max_steps = e.max_steps, a.world_normals = e.world_normals, a.B = e.B, a.H = e.H, a.W = e.W;
     const dim3 grid(idh_cdiv(e.W, 16), idh_cdiv(e.H, 16), e.B);
-    hipStream_t st = idh_stream(stream);
     if (e.skip) {
-        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<true, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tsdf_raycast_k<true, false>), grid, dim3(256), 0, st, a);
+        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<true, true, A>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tsdf_raycast_k<true, false, A>), grid, dim3(256), 0, st, a);
     } else {
-        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tsdf_raycast_k<false, false>), grid, dim3(256), 0, st, a);
+        if (e.normals_b3hw) hipLaunchKernelGGL((tsdf_raycast_k<false, true, A>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tsdf_raycast_k<false, false, A>), grid, dim3(256), 0, st, a);
     }
     IDH_CHECK_LAUNCH();
     return IDH_OK;
+}
+
+}  // namespace
+
+extern "C" int idh_tsdf_raycast_fwd(const idh_tsdf_raycast_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_raycast_args)) return IDH_EINVAL;
+    if (const int rc = raycast_check_inputs(*args)) return rc;
+    RaycastArgs a;
+    return raycast_launch(*args, a, idh_stream(stream));
+}
+
+extern "C" int idh_tsdf_raycast_color_fwd(const idh_tsdf_raycast_color_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_raycast_color_args)) return IDH_EINVAL;
+    if (const int rc = raycast_check_inputs(*args)) return rc;
+    if (!args->colors_zyx4 || !args->rgba_bhw4 || ((uintptr_t)args->colors_zyx4 & 15u)) return IDH_EINVAL;
+    RaycastColorArgs a;
+    a.colors = reinterpret_cast<const float4 *>(args->colors_zyx4), a.rgba = args->rgba_bhw4;
+    return raycast_launch(*args, a, idh_stream(stream));
 }

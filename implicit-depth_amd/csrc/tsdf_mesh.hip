@@ -22,6 +22,9 @@
 //                               workgroup, add the chunk's base and write faces, whose indices are vertex_base[owner] + the rank of
 //                               the axis among the owner's vertex bytes.  Every store is guarded by the capacities.
 //
+//   colours: mesh_colors_k      C'. the vertex half of C over again: the owner's and the far endpoint's {R, G, B, Wc} quads (16-byte
+//                               loads) interpolated with the vertex's r and stored as one 4-byte word at the vertex's index.
+//
 // Every kernel is one pass over independent chunks: no workgroup waits on another.
 #include "tsdf_common.h"
 
@@ -228,6 +231,53 @@ __global__ __launch_bounds__(256) void mesh_emit_k(const EmitArgs a) {
     }
 }
 
+struct ColorsArgs {
+    Vol V;
+    const unsigned *info;
+    const int32_t *vbase;
+    const u64 *base;
+    const float4 *colors;  // {R, G, B, Wc} per voxel
+    unsigned *rgba;        // one word per vertex: bytes R, G, B, A in memory order
+    long long n4, vcap;
+};
+
+__device__ __forceinline__ unsigned channel_byte(float c) { return (unsigned)(int)(fminf(fmaxf(c, 0.f), 255.f) + 0.5f); }
+__device__ __forceinline__ unsigned pack_rgba(float r, float g, float b) { return channel_byte(r) | channel_byte(g) << 8 | channel_byte(b) << 16 | 255u << 24; }
+
+// The vertex half of mesh_emit_k over again, for the colours: same chunks, same four voxels per lane, same vertex indices.
+__global__ __launch_bounds__(256) void mesh_colors_k(const ColorsArgs a) {
+    const Vol &V = a.V;
+    if (blockIdx.x + 1 < gridDim.x && (unsigned)a.base[blockIdx.x + 1] == (unsigned)a.base[blockIdx.x]) return;  // a chunk without a vertex
+    const long long i0 = blockIdx.x * (long long)kChunk + threadIdx.x * kItems;
+    if (i0 >= a.n4) return;
+    const uint4 w = reinterpret_cast<const uint4 *>(a.info)[i0 >> 2];
+    if (((w.x | w.y | w.z | w.w) >> 8) == 0u) return;  // nothing owned
+    const int4 vb = reinterpret_cast<const int4 *>(a.vbase)[i0 >> 2];
+    const long long row = V.Nx, slice = row * V.Ny;
+    const float2 *values = reinterpret_cast<const float2 *>(V.values);
+    for (int k = 0; k < kItems; ++k) {
+        const unsigned word = k == 0 ? w.x : k == 1 ? w.y : k == 2 ? w.z : w.w;
+        if (!(word >> 8)) continue;
+        const long long i = i0 + k;
+        const float Ta = values[i].x;
+        const float4 ca = a.colors[i];
+        long long vi = k == 0 ? vb.x : k == 1 ? vb.y : k == 2 ? vb.z : vb.w;
+        for (int axis = 0; axis < 3; ++axis) {
+            if (!((word >> (8 + 8 * axis)) & 1u)) continue;
+            const long long j = i + (axis == 0 ? 1 : axis == 1 ? row : slice);
+            const float Tb = values[j].x;
+            const float4 cb = a.colors[j];
+            const float r = Ta / (Ta - Tb);
+            unsigned out = 0u;
+            if (ca.w > 0.f && cb.w > 0.f) out = pack_rgba(ca.x + r * (cb.x - ca.x), ca.y + r * (cb.y - ca.y), ca.z + r * (cb.z - ca.z));
+            else if (ca.w > 0.f) out = pack_rgba(ca.x, ca.y, ca.z);
+            else if (cb.w > 0.f) out = pack_rgba(cb.x, cb.y, cb.z);
+            if (vi < a.vcap) a.rgba[vi] = out;
+            ++vi;
+        }
+    }
+}
+
 struct MeshLayout {
     long long n, n4;
     int levels;              // levels of partial sums, >= 1; the last one has at most kChunk entries
@@ -254,13 +304,13 @@ bool mesh_layout(int Nz, int Ny, int Nx, MeshLayout &L) {
     return p <= kChunk;
 }
 
-// what both calls check, in the header's order
-int check_mesh(const idh_tsdf_mesh_args *args, bool emit, Vol &V, MeshLayout &L) {
+// what the calls check, in the header's order; `outputs`: the call has its non-null outputs
+int check_mesh(const idh_tsdf_mesh_args *args, bool outputs, bool bad_capacity, Vol &V, MeshLayout &L) {
     if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_mesh_args)) return IDH_EINVAL;
     const idh_tsdf_mesh_args &e = *args;
     if (!(e.min_weight >= 0.f)) return IDH_EINVAL;  // also refuses NaN
-    if (emit ? (!e.verts_v3 || !e.faces_f3) : !e.totals) return IDH_EINVAL;
-    if (emit && (e.vert_capacity < 0 || e.face_capacity < 0)) return IDH_EINVAL;
+    if (!outputs) return IDH_EINVAL;
+    if (bad_capacity) return IDH_EINVAL;
     if (const int rc = check_volume(e.volume, V)) return rc;
     if (!mesh_layout(e.volume.Nz, e.volume.Ny, e.volume.Nx, L)) return IDH_EUNSUPPORTED;
     if (!e.workspace || e.workspace_bytes < 0 || (size_t)e.workspace_bytes < L.bytes) return IDH_EWORKSPACE;
@@ -280,7 +330,7 @@ extern "C" size_t idh_tsdf_mesh_workspace_bytes(int Nz, int Ny, int Nx) {
 extern "C" int idh_tsdf_mesh_count_fwd(const idh_tsdf_mesh_args *args, void *stream) {
     Vol V;
     MeshLayout L;
-    if (const int rc = check_mesh(args, false, V, L)) return rc;
+    if (const int rc = check_mesh(args, args && args->totals, false, V, L)) return rc;
     hipStream_t st = idh_stream(stream);
     char *ws = static_cast<char *>(args->workspace);
     if (hipMemsetAsync(ws + L.info_off, 0, (size_t)L.n4 * 4, st) != hipSuccess) return IDH_ELAUNCH;
@@ -312,7 +362,7 @@ extern "C" int idh_tsdf_mesh_count_fwd(const idh_tsdf_mesh_args *args, void *str
 extern "C" int idh_tsdf_mesh_emit_fwd(const idh_tsdf_mesh_args *args, void *stream) {
     Vol V;
     MeshLayout L;
-    if (const int rc = check_mesh(args, true, V, L)) return rc;
+    if (const int rc = check_mesh(args, args && args->verts_v3 && args->faces_f3, args && (args->vert_capacity < 0 || args->face_capacity < 0), V, L)) return rc;
     if (args->vert_capacity == 0 && args->face_capacity == 0) return IDH_OK;
     char *ws = static_cast<char *>(args->workspace);
     EmitArgs a;
@@ -321,6 +371,27 @@ extern "C" int idh_tsdf_mesh_emit_fwd(const idh_tsdf_mesh_args *args, void *stre
     a.verts = args->verts_v3, a.weights = args->weights_v, a.faces = args->faces_f3;
     a.n4 = L.n4, a.vcap = args->vert_capacity, a.fcap = args->face_capacity;
     hipLaunchKernelGGL(mesh_emit_k, dim3((unsigned)L.p[0]), dim3(kThreads), 0, idh_stream(stream), a);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" size_t idh_sizeof_tsdf_mesh_colors_args(void) { return sizeof(idh_tsdf_mesh_colors_args); }
+
+extern "C" int idh_tsdf_mesh_colors_fwd(const idh_tsdf_mesh_colors_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_mesh_colors_args)) return IDH_EINVAL;
+    const idh_tsdf_mesh_args &m = args->mesh;
+    Vol V;
+    MeshLayout L;
+    if (const int rc = check_mesh(&m, args->colors_zyx4 && args->rgba_v4, m.vert_capacity < 0, V, L)) return rc;
+    if ((uintptr_t)args->colors_zyx4 & 15u) return IDH_EINVAL;
+    if (m.vert_capacity == 0) return IDH_OK;
+    char *ws = static_cast<char *>(m.workspace);
+    ColorsArgs a;
+    a.V = V, a.info = reinterpret_cast<const unsigned *>(ws + L.info_off), a.vbase = reinterpret_cast<const int32_t *>(ws + L.vbase_off);
+    a.base = reinterpret_cast<const u64 *>(ws + L.level_off[0]);
+    a.colors = reinterpret_cast<const float4 *>(args->colors_zyx4), a.rgba = reinterpret_cast<unsigned *>(args->rgba_v4);
+    a.n4 = L.n4, a.vcap = m.vert_capacity;
+    hipLaunchKernelGGL(mesh_colors_k, dim3((unsigned)L.p[0]), dim3(kThreads), 0, idh_stream(stream), a);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }

@@ -5,7 +5,11 @@ the ring is forgotten.  ``TSDFVolume`` averages every map into a dense truncated
 the reference's workflow takes off line with open3d before ``--temporal_eval`` - and ``raycast`` returns the fused surface in any camera.
 ``extract_mesh`` turns the volume into an indexed triangle mesh (marching cubes, csrc/tsdf_mesh.hip) that the mesh
 consumers of ``raster`` and ``evaluation`` take as it is.  There is no CPU fallback: the tensors live on the GPU and every step is a
-HIP kernel."""
+HIP kernel.
+
+Colour: a volume made with ``color=True`` also holds ``colors``, (Nz,Ny,Nx,4) float32 {R, G, B, Wc}; ``integrate_depth``
+then takes the camera frames that belong to the depth maps, ``raycast_volume(return_color=True)`` returns the surface's colour in the
+live camera and ``extract_mesh(return_colors=True)`` the colour of every vertex."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,10 +38,12 @@ class TSDFVolume:
     """A dense TSDF grid of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres, axis-aligned with the world; ``origin`` is the world
     (x, y, z) of the centre of voxel (0,0,0).  ``values`` is the (Nz,Ny,Nx,2) float32 tensor of {T, W} pairs - distance in units of the
     truncation ``trunc_voxels * voxel_size`` and observation count - ``{1, 0}`` when empty; ``block_flags`` the per-block bytes the ray
-    cast's empty-space skipping reads (include/idh_fusion.h says what they guarantee).  ``max_weight`` caps W."""
+    cast's empty-space skipping reads (include/idh_fusion.h says what they guarantee).  ``max_weight`` caps W.  With ``color=True``
+    ``colors`` is the (Nz,Ny,Nx,4) float32 tensor of {R, G, B, Wc} quads - channels in units of a uint8 channel and the number of colour
+    observations - all zero when empty; otherwise it is None."""
 
     def __init__(self, dims: Sequence[int], voxel_size: float, origin: Sequence[float], trunc_voxels: float = 3.0, max_weight: float = 64.0,
-                 device="cuda", _values: Optional[torch.Tensor] = None):
+                 device="cuda", _values: Optional[torch.Tensor] = None, color: bool = False, _colors: Optional[torch.Tensor] = None):
         self.dims = tuple(int(d) for d in dims)
         if len(self.dims) != 3:
             raise _lib.IdhError(f"TSDFVolume: dims {dims} must be (Nz, Ny, Nx)")
@@ -54,6 +60,14 @@ class TSDFVolume:
                 raise _lib.IdhError(f"TSDFVolume.from_values: values {tuple(_values.shape)} must be contiguous {(*self.dims, 2)}")
             self.values = _values
         self.block_flags = torch.empty(nbytes, device=self.values.device, dtype=torch.uint8)
+        self.colors: Optional[torch.Tensor] = None
+        if _colors is not None:
+            _lib.require_cuda_f32(_colors)
+            if tuple(_colors.shape) != (*self.dims, 4) or not _colors.is_contiguous() or _colors.device != self.values.device or _colors.data_ptr() % 16:
+                raise _lib.IdhError(f"TSDFVolume: colors {tuple(_colors.shape)} must be contiguous {(*self.dims, 4)}, 16-byte aligned, on the values' device")
+            self.colors = _colors
+        elif color:
+            self.colors = torch.zeros(*self.dims, 4, device=self.values.device, dtype=torch.float32)
         if _values is None:
             self.reset()
         else:
@@ -61,9 +75,10 @@ class TSDFVolume:
 
     @classmethod
     def from_values(cls, values: torch.Tensor, voxel_size: float, origin: Sequence[float], trunc_voxels: float = 3.0,
-                    max_weight: float = 64.0) -> "TSDFVolume":
-        """Adopt a (Nz,Ny,Nx,2) pair tensor made elsewhere (it is not copied) and rebuild the block flags from it (idh_tsdf_flags_fwd)."""
-        return cls(tuple(values.shape[:3]), voxel_size, origin, trunc_voxels, max_weight, device=values.device, _values=values)
+                    max_weight: float = 64.0, colors: Optional[torch.Tensor] = None) -> "TSDFVolume":
+        """Adopt a (Nz,Ny,Nx,2) pair tensor made elsewhere (it is not copied) and rebuild the block flags from it (idh_tsdf_flags_fwd);
+        ``colors`` adopts a (Nz,Ny,Nx,4) quad tensor the same way."""
+        return cls(tuple(values.shape[:3]), voxel_size, origin, trunc_voxels, max_weight, device=values.device, _values=values, _colors=colors)
 
     def _struct(self) -> "_lib.TsdfVolume":
         v = _lib.TsdfVolume()
@@ -74,29 +89,39 @@ class TSDFVolume:
         return v
 
     def reset(self) -> None:
-        """Every voxel back to {1, 0}, every block flag to 0; the storage is kept."""
+        """Every voxel back to {1, 0}, every block flag to 0, every colour quad to zero; the storage is kept."""
         _lib.check(_lib.lib().idh_tsdf_reset_fwd(C.byref(self._struct()), _lib.stream_ptr()), "idh_tsdf_reset_fwd")
+        if self.colors is not None:
+            self.colors.zero_()
 
-    def integrate(self, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44) -> None:
-        integrate_depth(self, depth_m1hw, K_m44, cam_T_world_m44)
+    def integrate(self, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None, color_K=None) -> None:
+        integrate_depth(self, depth_m1hw, K_m44, cam_T_world_m44, color_u8, color_K)
 
     def raycast(self, world_T_cam_b44, invK_b44, size: Sequence[int], near: float = 0.25, far: float = 8.0, step_voxels: float = 1.0,
-                empty_depth: float = -1.0, return_normals: bool = False, world_normals: bool = True, skip: bool = False) -> Dict[str, torch.Tensor]:
+                empty_depth: float = -1.0, return_normals: bool = False, world_normals: bool = True, skip: bool = False,
+                return_color: bool = False) -> Dict[str, torch.Tensor]:
         """``raycast_volume`` with ``max_steps = ceil((far - near) / (step_voxels * voxel_size))`` formed on the host."""
         step = float(np.float32(step_voxels) * np.float32(self.voxel_size))
         if not (step > 0 and far > near):
             raise _lib.IdhError(f"TSDFVolume.raycast: far = {far} must exceed near = {near} and the step be positive")
         return raycast_volume(self, world_T_cam_b44, invK_b44, size, near=near, step_voxels=step_voxels, max_steps=int(math.ceil((far - near) / step)),
-                              empty_depth=empty_depth, return_normals=return_normals, world_normals=world_normals, skip=skip)
+                              empty_depth=empty_depth, return_normals=return_normals, world_normals=world_normals, skip=skip, return_color=return_color)
 
-    def extract_mesh(self, min_weight: float = 0.0, return_weights: bool = False, use_block_flags: bool = MESH_USE_BLOCK_FLAGS) -> Dict[str, torch.Tensor]:
-        return extract_mesh(self, min_weight, return_weights, use_block_flags)
+    def extract_mesh(self, min_weight: float = 0.0, return_weights: bool = False, use_block_flags: bool = MESH_USE_BLOCK_FLAGS,
+                     return_colors: bool = False) -> Dict[str, torch.Tensor]:
+        return extract_mesh(self, min_weight, return_weights, use_block_flags, return_colors)
 
 
-def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44) -> None:
+def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None,
+                    color_K=None) -> None:
     """Average M depth maps (M,1,h,w) into ``volume`` in one launch (idh_tsdf_integrate_fwd): ``K_m44`` their intrinsics at h x w,
     ``cam_T_world_m44`` their poses ((4,4) or (M,4,4), tensors or arrays).  Taps that are not finite and positive are holes.  M is at most
-    ``pipeline.MAX_RING_CAPACITY``.  One call with M maps equals M calls with one map each, bit for bit."""
+    ``pipeline.MAX_RING_CAPACITY``.  One call with M maps equals M calls with one map each, bit for bit.
+
+    ``color_u8``: the M camera frames of the maps, uint8 (M,hc,wc,3) RGB on the GPU, averaged into ``volume.colors`` in the same launch
+    (idh_tsdf_integrate_color_fwd; ``values`` and ``block_flags`` get the same bits as without).  ``color_K`` their intrinsics at
+    hc x wc; None is allowed only when (hc, wc) == (h, w) and then means ``K_m44``.  Without ``color_u8`` the colours are left as they
+    are (depth-only maps)."""
     _lib.require_cuda_f32(depth_m1hw)
     if depth_m1hw.dim() != 4 or depth_m1hw.shape[1] != 1:
         raise _lib.IdhError(f"integrate_depth: depth {tuple(depth_m1hw.shape)} must be (M,1,h,w)")
@@ -105,16 +130,38 @@ def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_w
     d, K, T = depth_m1hw.contiguous(), _mats("K", K_m44, dev), _mats("cam_T_world", cam_T_world_m44, dev)
     if K.shape[0] != M or T.shape[0] != M:
         raise _lib.IdhError(f"integrate_depth: {M} maps need ({M},4,4) intrinsics and poses, got {tuple(K.shape)} and {tuple(T.shape)}")
-    a = _lib.TsdfIntegrateArgs()
+    if color_u8 is None and color_K is not None:
+        raise _lib.IdhError("integrate_depth: color_K without color_u8")
+    if color_u8 is not None:
+        if volume.colors is None:
+            raise _lib.IdhError("integrate_depth: colour frames for a volume without colors (TSDFVolume(..., color=True))")
+        if color_u8.dtype != torch.uint8 or not color_u8.is_cuda or color_u8.dim() != 4 or color_u8.shape[0] != M or color_u8.shape[3] != 3:
+            raise _lib.IdhError(f"integrate_depth: color_u8 {tuple(color_u8.shape)} {color_u8.dtype} must be uint8 ({M},hc,wc,3) on the GPU")
+        hc, wc = int(color_u8.shape[1]), int(color_u8.shape[2])
+        if color_K is None:
+            if (hc, wc) != (h, w):
+                raise _lib.IdhError(f"integrate_depth: frames of {(hc, wc)} for maps of {(h, w)} need color_K")
+            Kc = K
+        else:
+            Kc = _mats("color_K", color_K, dev)
+            if Kc.shape[0] != M:
+                raise _lib.IdhError(f"integrate_depth: {M} frames need ({M},4,4) color_K, got {tuple(Kc.shape)}")
+        frames = color_u8.contiguous()
+        a = _lib.TsdfIntegrateColorArgs()
+        a.colors_zyx4, a.color_mhw3, a.color_K_m44, a.hc, a.wc = volume.colors.data_ptr(), frames.data_ptr(), Kc.data_ptr(), hc, wc
+        fn, name = _lib.lib().idh_tsdf_integrate_color_fwd, "idh_tsdf_integrate_color_fwd"
+    else:
+        a = _lib.TsdfIntegrateArgs()
+        fn, name = _lib.lib().idh_tsdf_integrate_fwd, "idh_tsdf_integrate_fwd"
     a.volume = volume._struct()
     a.depth_m1hw, a.K_m44, a.cam_T_world_m44 = d.data_ptr(), K.data_ptr(), T.data_ptr()
     a.max_weight, a.M, a.h, a.w = volume.max_weight, M, h, w
-    _lib.check(_lib.lib().idh_tsdf_integrate_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_integrate_fwd")
+    _lib.check(fn(C.byref(a), _lib.stream_ptr()), name)
 
 
 def raycast_volume(volume: TSDFVolume, world_T_cam_b44, invK_b44, size: Sequence[int], *, near: float = 0.25, step_voxels: float = 1.0,
                    max_steps: int = 194, empty_depth: float = -1.0, return_normals: bool = False, world_normals: bool = True,
-                   skip: bool = False) -> Dict[str, torch.Tensor]:
+                   skip: bool = False, return_color: bool = False) -> Dict[str, torch.Tensor]:
     """The fused surface in B cameras in one launch (idh_tsdf_raycast_fwd).  ``world_T_cam_b44`` / ``invK_b44``: (4,4) or (B,4,4), the
     inverse intrinsics at ``size`` = (H, W).  Every pixel's ray is sampled at ``t_k = near + k * step_voxels * voxel_size``, k below
     ``max_steps``; the first sign change from positive to non-positive between two known samples is the hit.  Returns
@@ -123,7 +170,10 @@ def raycast_volume(volume: TSDFVolume, world_T_cam_b44, invK_b44, size: Sequence
     * ``"flags"`` (B,H,W) uint8: ``FLAG_HIT``, ``FLAG_NONE_KNOWN`` (nothing is known along the ray), ``FLAG_SOME_KNOWN`` (part of it is);
       0 is a ray through observed free space;
     * ``"normals"`` (B,3,H,W) with ``return_normals``: unit normals facing the camera, in the world's frame or (``world_normals=False``)
-      the camera's; zero where there is no hit or ``FLAG_NO_NORMAL`` is set.
+      the camera's; zero where there is no hit or ``FLAG_NO_NORMAL`` is set;
+    * ``"rgba"`` (B,H,W,4) uint8 with ``return_color`` (idh_tsdf_raycast_color_fwd, a volume with ``colors``; the layout of
+      ``render_shaded``'s "rgba"): the colour of the hit from the coloured corners of its cell, alpha 255; four zero bytes where there
+      is no hit or no coloured corner.  The other outputs keep their bits.
 
     ``skip=False`` (the default) marches every sample; ``skip=True`` clips the range to the volume and jumps unobserved blocks, and returns
     the same bits.  Measured, it is faster where most rays cross unobserved space and slower in a room that has been seen (DESIGN.md
@@ -138,13 +188,22 @@ def raycast_volume(volume: TSDFVolume, world_T_cam_b44, invK_b44, size: Sequence
     out = {"depth": torch.empty(B, 1, H, W, device=dev), "flags": torch.empty(B, H, W, device=dev, dtype=torch.uint8)}
     if return_normals:
         out["normals"] = torch.empty(B, 3, H, W, device=dev)
-    a = _lib.TsdfRaycastArgs()
+    if return_color:
+        if volume.colors is None:
+            raise _lib.IdhError("raycast_volume: return_color needs a volume with colors (TSDFVolume(..., color=True))")
+        out["rgba"] = torch.empty(B, H, W, 4, device=dev, dtype=torch.uint8)
+        a = _lib.TsdfRaycastColorArgs()
+        a.colors_zyx4, a.rgba_bhw4 = volume.colors.data_ptr(), out["rgba"].data_ptr()
+        fn, name = _lib.lib().idh_tsdf_raycast_color_fwd, "idh_tsdf_raycast_color_fwd"
+    else:
+        a = _lib.TsdfRaycastArgs()
+        fn, name = _lib.lib().idh_tsdf_raycast_fwd, "idh_tsdf_raycast_fwd"
     a.volume = volume._struct()
     a.world_T_cam_b44, a.invK_b44 = T.data_ptr(), iK.data_ptr()
     a.depth_b1hw, a.flags_bhw, a.normals_b3hw = out["depth"].data_ptr(), out["flags"].data_ptr(), _lib.ptr(out.get("normals"))
     a.near, a.step_voxels, a.empty_depth, a.max_steps = float(near), float(step_voxels), float(empty_depth), int(max_steps)
     a.world_normals, a.skip, a.B, a.H, a.W = int(bool(world_normals)), int(bool(skip)), B, H, W
-    _lib.check(_lib.lib().idh_tsdf_raycast_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_raycast_fwd")
+    _lib.check(fn(C.byref(a), _lib.stream_ptr()), name)
     return out
 
 
@@ -191,15 +250,36 @@ def mesh_emit(volume: TSDFVolume, workspace: torch.Tensor, verts: torch.Tensor, 
     _lib.check(_lib.lib().idh_tsdf_mesh_emit_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_mesh_emit_fwd")
 
 
+def mesh_colors(volume: TSDFVolume, workspace: torch.Tensor, rgba: torch.Tensor, min_weight: float = 0.0, vert_capacity: Optional[int] = None) -> None:
+    """The colours of ``mesh_emit``'s vertices (idh_tsdf_mesh_colors_fwd): the first ``vert_capacity`` of them into ``rgba`` (rows, 4)
+    uint8, after ``mesh_count`` on the same volume.  The capacity defaults to the tensor's rows and may not exceed them."""
+    if volume.colors is None:
+        raise _lib.IdhError("mesh_colors needs a volume with colors (TSDFVolume(..., color=True))")
+    if rgba.dim() != 2 or rgba.shape[1] != 4 or rgba.dtype != torch.uint8 or not rgba.is_cuda or not rgba.is_contiguous():
+        raise _lib.IdhError(f"mesh_colors: rgba {tuple(rgba.shape)} {rgba.dtype} must be contiguous (V,4) uint8 on the GPU")
+    vcap = rgba.shape[0] if vert_capacity is None else int(vert_capacity)
+    if vcap > rgba.shape[0]:
+        raise _lib.IdhError(f"mesh_colors: capacity {vcap} exceeds the tensor's rows")
+    a = _lib.TsdfMeshColorsArgs()
+    a.mesh = _mesh_args(volume, workspace, min_weight, False)
+    a.mesh.vert_capacity = vcap
+    a.colors_zyx4, a.rgba_v4 = volume.colors.data_ptr(), rgba.data_ptr() or workspace.data_ptr()
+    _lib.check(_lib.lib().idh_tsdf_mesh_colors_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_mesh_colors_fwd")
+
+
 def extract_mesh(volume: TSDFVolume, min_weight: float = 0.0, return_weights: bool = False,
-                 use_block_flags: bool = MESH_USE_BLOCK_FLAGS) -> Dict[str, torch.Tensor]:
+                 use_block_flags: bool = MESH_USE_BLOCK_FLAGS, return_colors: bool = False) -> Dict[str, torch.Tensor]:
     """The fused surface as an indexed triangle mesh: marching cubes over the cells whose eight voxels have ``W > min_weight``, a voxel
     being inside where ``T <= 0`` (include/idh_fusion.h states vertex positions, orders and orientation).  Returns ``"verts"`` (V,3)
     float32 in the world, ``"faces"`` (F,3) int32 with normals towards free space - what ``MeshDepthRasterizer.load_gt_mesh(verts=,
     faces=)``, ``raster.render_depth``, ``render_shaded`` and ``save_ply`` take - and with ``return_weights`` ``"weights"`` (V,), the
     observation count interpolated like the position.  Order and bits are deterministic.  Two groups of launches with one host read of the
     two totals between them; an empty result has shapes (0,3).  ``use_block_flags`` skips the blocks no map has touched and changes no
-    bit."""
+    bit.  With ``return_colors`` (a volume with ``colors``) ``"colors"`` (V,4) uint8 RGBA, what ``render_shaded(colors=)`` and
+    ``save_ply(colors=)`` take: the endpoints' colours interpolated like the position, alpha 0 where neither endpoint has one; (0,4)
+    for an empty mesh."""
+    if return_colors and volume.colors is None:
+        raise _lib.IdhError("extract_mesh: return_colors needs a volume with colors (TSDFVolume(..., color=True))")
     workspace, totals = mesh_count(volume, min_weight, use_block_flags)
     V, F = totals.tolist()  # the one host read
     dev = volume.values.device
@@ -208,4 +288,8 @@ def extract_mesh(volume: TSDFVolume, min_weight: float = 0.0, return_weights: bo
         out["weights"] = torch.empty(V, device=dev)
     if V or F:
         mesh_emit(volume, workspace, out["verts"], out["faces"], out.get("weights"), min_weight)
+    if return_colors:
+        out["colors"] = torch.empty(V, 4, device=dev, dtype=torch.uint8)
+        if V:
+            mesh_colors(volume, workspace, out["colors"], min_weight)
     return out

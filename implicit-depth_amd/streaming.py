@@ -137,14 +137,17 @@ class StreamingSession:
             self._ring_poses = {}
 
     def step(self, cur_data: Dict[str, torch.Tensor], world_T_cam=None, dist_to_last_valid=None, return_mask: bool = False,
-             infer_depth: bool = False, query_points: Optional[torch.Tensor] = None) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
+             infer_depth: bool = False, query_points: Optional[torch.Tensor] = None, frame_u8: Optional[torch.Tensor] = None,
+             frame_K: Optional[torch.Tensor] = None) -> Tuple[Optional[Dict[str, torch.Tensor]], int]:
         """``cur_data``: what ``FrameIngest`` returns for ONE frame (``image_b3hw``, ``world_T_cam_b44``, ``cam_T_world_b44``, ``K_s0/s1_b44``,
         ``invK_s0/s1_b44``; for a BDModel also ``rendered_depth``).  ``world_T_cam``: the same pose as a (4,4) host array, in the dtype the
         selection is to be computed in - the keyframe decision is taken on the host; without it the pose is read back from the device, which synchronises.
         Returns ``(outputs, code)``: the output dictionary of ``fused_forward`` when a prediction is due, else None - first frame, not enough
         motion, no pose, tracking lost, or fewer than K keyframes stored so far; ``code`` is the buffer's return code either way.
         ``query_points`` (1,N,3) world points: when a prediction is due, its outputs gain ``point_pred`` / ``point_valid`` / ``point_depth`` /
-        ``point_rays`` (``HotPath.query_points`` against this prediction); on the other frames ask ``session.query_points``."""
+        ``point_rays`` (``HotPath.query_points`` against this prediction); on the other frames ask ``session.query_points``.
+        ``frame_u8`` / ``frame_K``: the camera frame of this step, handed to the ``remember_depth`` a ``DepthModel``'s prediction goes to
+        (``start_fusion(color=True)``)."""
         image = cur_data["image_b3hw"]
         if image.dim() != 4 or image.shape[0] != 1:
             raise _lib.IdhError(f"step() takes one frame: image_b3hw must be (1,3,h,w), got {tuple(image.shape)}")
@@ -201,7 +204,7 @@ class StreamingSession:
                 if query_points is not None:
                     out.update(self.query_points(query_points))
             elif "depth_pred_s0_b1hw" in out:  # a DepthModel: its prediction is what the frames between keyframes can be answered from
-                self.remember_depth(out["depth_pred_s0_b1hw"], pose, cur_data["invK_s0_b44"])
+                self.remember_depth(out["depth_pred_s0_b1hw"], pose, cur_data["invK_s0_b44"], frame_u8=frame_u8, frame_K=frame_K)
         if "prior_mask" in out:
             cur_data["prior_mask"] = out.pop("prior_mask")  # as fused_forward: run_mlp_val stores it on the inputs (bd_model.py:431)
         return out, code
@@ -317,11 +320,15 @@ class StreamingSession:
 
     WARP_FAR = 1.0e4  # metres: the depth composite_asset's depth route gives the pixels no remembered map covers
 
-    def remember_depth(self, depth_11hw: torch.Tensor, world_T_cam, invK: torch.Tensor) -> None:
+    def remember_depth(self, depth_11hw: torch.Tensor, world_T_cam, invK: torch.Tensor, frame_u8: Optional[torch.Tensor] = None,
+                       frame_K: Optional[torch.Tensor] = None) -> None:
         """Push a depth map (1,1,h,w) onto the ring of the last ``query_keyframes`` maps ``warped_depth_for_view`` draws: the camera that
         saw it at ``world_T_cam`` ((4,4) array or tensor) with inverse intrinsics ``invK`` ((4,4) or (1,4,4), at h x w).  ``step`` calls
         this with a ``DepthModel``'s ``depth_pred_s0_b1hw``; a caller pushes a lidar frame or a ``BDModel``'s inferred depth.  Taps that
-        are not finite and positive are holes.  The map is copied; all maps of the ring have one size.  ``reset()`` empties the ring."""
+        are not finite and positive are holes.  The map is copied; all maps of the ring have one size.  ``reset()`` empties the ring.
+        ``frame_u8`` (1,Hf,Wf,3) uint8: the camera frame that belongs to the map, fused into the colours of the volume of
+        ``start_fusion(color=True)`` (it is not kept); ``frame_K`` its intrinsics ((4,4) or (1,4,4)) at Hf x Wf, None: the inverse of
+        ``invK`` with rows 0 and 1 scaled by Wf / w and Hf / h (``intrinsics_pyramid``'s rule)."""
         from .raster import _pose_f64
 
         _lib.require_cuda_f32(depth_11hw, invK)
@@ -333,26 +340,41 @@ class StreamingSession:
         if invK.shape[0] != 1:
             raise _lib.IdhError("remember_depth: invK must be (4,4) or (1,4,4)")
         pose = _pose_f64("world_T_cam", world_T_cam)
+        if frame_u8 is None and frame_K is not None:
+            raise _lib.IdhError("remember_depth: frame_K without frame_u8")
+        if frame_u8 is not None:
+            if self._fusion is None or not self._fusion["color"]:
+                raise _lib.IdhError("remember_depth: a frame needs start_fusion(color=True)")
+            if frame_u8.dtype != torch.uint8 or not frame_u8.is_cuda or frame_u8.dim() != 4 or frame_u8.shape[0] != 1 or frame_u8.shape[3] != 3:
+                raise _lib.IdhError(f"remember_depth: frame_u8 {tuple(frame_u8.shape)} {frame_u8.dtype} must be uint8 (1,Hf,Wf,3) on the GPU")
+            if frame_K is not None:
+                _lib.require_cuda_f32(frame_K)
+                frame_K = frame_K.reshape(-1, 4, 4)
+                if frame_K.shape[0] != 1:
+                    raise _lib.IdhError("remember_depth: frame_K must be (4,4) or (1,4,4)")
         self._depth_ring.insert(0, (depth_11hw.detach().clone(), pose, invK.detach().clone()))
         del self._depth_ring[self.query_keyframes:]
         if self._fusion is not None:
-            self._fuse(self._depth_ring[0][0], pose, invK)
+            self._fuse(self._depth_ring[0][0], pose, invK, frame_u8, frame_K)
 
     def start_fusion(self, voxel_size: float = 0.04, dims: Sequence[int] = (96, 256, 256), origin=None, trunc_voxels: float = 3.0,
-                     max_weight: float = 64.0) -> None:
+                     max_weight: float = 64.0, color: bool = False) -> None:
         """From now on ``remember_depth`` - which ``step`` calls with a ``DepthModel``'s predictions - also averages the map it pushes
         into a TSDF volume of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres (``fusion.TSDFVolume``), which
         ``fused_depth_for_view`` ray-casts: maps are combined, holes one map left are filled by another, and a map that has left the ring
         is still in the volume.  ``origin``: the world (x, y, z) of voxel (0,0,0)'s centre; None centres the grid on the camera position
-        of the first map integrated.  ``reset()`` empties the volume and keeps its storage.  Calling it again starts a new volume."""
+        of the first map integrated.  ``reset()`` empties the volume and keeps its storage.  Calling it again starts a new volume.
+        ``color=True`` gives the volume colours (16 more bytes per voxel): ``remember_depth`` and ``step`` then take the
+        camera frame of a map, ``fused_depth_for_view(return_color=True)`` and ``fused_mesh(return_colors=True)`` return them."""
         dims = tuple(int(d) for d in dims)
         if len(dims) != 3 or min(dims) < 2 or not float(voxel_size) > 0:
             raise _lib.IdhError(f"start_fusion: dims {dims} must be three sizes >= 2 and voxel_size {voxel_size} positive")
         self._fusion = dict(voxel_size=float(voxel_size), dims=dims, origin=None if origin is None else tuple(float(o) for o in origin),
-                            trunc_voxels=float(trunc_voxels), max_weight=float(max_weight))
+                            trunc_voxels=float(trunc_voxels), max_weight=float(max_weight), color=bool(color))
         self._volume, self._fused_maps = None, 0
 
-    def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor) -> None:
+    def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor, frame_u8: Optional[torch.Tensor] = None,
+              frame_K_144: Optional[torch.Tensor] = None) -> None:
         from .fusion import TSDFVolume
 
         f = self._fusion
@@ -362,10 +384,15 @@ class StreamingSession:
                 nz, ny, nx = f["dims"]
                 origin = tuple(pose[:3, 3] - f["voxel_size"] * 0.5 * (np.array([nx, ny, nz], dtype=np.float64) - 1.0))
             if self._volume is None:
-                self._volume = TSDFVolume(f["dims"], f["voxel_size"], origin, f["trunc_voxels"], f["max_weight"], device=depth_11hw.device)
+                self._volume = TSDFVolume(f["dims"], f["voxel_size"], origin, f["trunc_voxels"], f["max_weight"], device=depth_11hw.device, color=f["color"])
             self._volume.origin = tuple(float(o) for o in origin)
         cam_T_world = torch.from_numpy(np.linalg.inv(pose).astype(np.float32))[None]  # inverted in float64 on the host
-        self._volume.integrate(depth_11hw, torch.linalg.inv(invK_144), cam_T_world)
+        K = torch.linalg.inv(invK_144)
+        if frame_u8 is not None and frame_K_144 is None:
+            frame_K_144 = K.clone()
+            frame_K_144[:, 0] *= frame_u8.shape[2] / depth_11hw.shape[3]
+            frame_K_144[:, 1] *= frame_u8.shape[1] / depth_11hw.shape[2]
+        self._volume.integrate(depth_11hw, K, cam_T_world, frame_u8, frame_K_144)
         self._fused_maps += 1
 
     @property
@@ -374,39 +401,49 @@ class StreamingSession:
         return self._volume
 
     def fused_depth_for_view(self, world_T_cam, invK: torch.Tensor, size: Sequence[int], near: float = 0.25, far: float = 8.0,
-                             step_voxels: float = 1.0, empty_depth: float = -1.0, return_normals: bool = False) -> Dict[str, torch.Tensor]:
+                             step_voxels: float = 1.0, empty_depth: float = -1.0, return_normals: bool = False,
+                             return_color: bool = False) -> Dict[str, torch.Tensor]:
         """The fused surface in the LIVE camera, also on the frames where ``step`` returned None: the volume of ``start_fusion`` ray-cast
         into the ``size`` = (H, W) image of the camera at ``world_T_cam`` ((4,4) array or tensor; taken to float32 from float64 on the
         host) with inverse intrinsics ``invK`` ((4,4) or (1,4,4), at H x W) - ``TSDFVolume.raycast``, one launch.  Returns
         "view_fused_depth" (1,1,H,W): the camera's z of the first surface between ``near`` and ``far`` metres along each pixel's ray,
         ``empty_depth`` where "view_fused_valid" (1,1,H,W) bool is False; "view_fused_flags" (1,H,W) uint8 (``fusion.FLAG_*``: a ray
         without a hit crossed only unobserved space, partly observed space, or - flags 0 - observed free space); with
-        ``return_normals`` "view_fused_normals" (1,3,H,W), unit normals in WORLD space that face the camera, zero where there is none."""
+        ``return_normals`` "view_fused_normals" (1,3,H,W), unit normals in WORLD space that face the camera, zero where there is none;
+        with ``return_color`` (``start_fusion(color=True)``) "view_fused_rgba" (1,H,W,4) uint8, the surface's fused colour with alpha
+        255, four zero bytes where there is no hit or no colour."""
         from .raster import _pose_f64
 
         if self._fusion is None:
             raise _lib.IdhError("fused_depth_for_view needs start_fusion()")
+        if return_color and not self._fusion["color"]:
+            raise _lib.IdhError("fused_depth_for_view(return_color=True) needs start_fusion(color=True)")
         if self._fused_maps == 0:
             raise _lib.IdhError("no prediction has been made in this sequence yet and no depth map was remembered (remember_depth)")
         _lib.require_cuda_f32(invK)
         T = torch.from_numpy(_pose_f64("world_T_cam", world_T_cam).astype(np.float32))[None]
         out = self._volume.raycast(T, invK.reshape(-1, 4, 4)[:1], (int(size[0]), int(size[1])), near=near, far=far, step_voxels=step_voxels,
-                                   empty_depth=empty_depth, return_normals=return_normals, world_normals=True)
+                                   empty_depth=empty_depth, return_normals=return_normals, world_normals=True, return_color=return_color)
         res = {"view_fused_depth": out["depth"], "view_fused_valid": ((out["flags"] & 1) != 0)[:, None], "view_fused_flags": out["flags"]}
         if return_normals:
             res["view_fused_normals"] = out["normals"]
+        if return_color:
+            res["view_fused_rgba"] = out["rgba"]
         return res
 
-    def fused_mesh(self, min_weight: float = 0.0) -> Dict[str, torch.Tensor]:
+    def fused_mesh(self, min_weight: float = 0.0, return_colors: bool = False) -> Dict[str, torch.Tensor]:
         """The session's own reconstruction as a triangle mesh: ``fusion.extract_mesh`` of the volume of ``start_fusion`` - "verts"
         (V,3) float32 in the world, "faces" (F,3) int32, normals towards free space - as ``MeshDepthRasterizer.load_gt_mesh(verts=,
         faces=)``, ``evaluation.TemporalEvaluator``, ``raster.render_shaded`` and ``raster.save_ply`` take them.  ``min_weight`` keeps
-        the cells whose eight voxels were observed more often than that."""
+        the cells whose eight voxels were observed more often than that.  ``return_colors`` (``start_fusion(color=True)``) adds
+        "colors" (V,4) uint8, what ``render_shaded(colors=)`` and ``save_ply(colors=)`` take."""
         if self._fusion is None:
             raise _lib.IdhError("fused_mesh needs start_fusion()")
+        if return_colors and not self._fusion["color"]:
+            raise _lib.IdhError("fused_mesh(return_colors=True) needs start_fusion(color=True)")
         if self._fused_maps == 0:
             raise _lib.IdhError("no prediction has been made in this sequence yet and no depth map was remembered (remember_depth)")
-        return self._volume.extract_mesh(min_weight=min_weight)
+        return self._volume.extract_mesh(min_weight=min_weight, return_colors=return_colors)
 
     def warped_depth_for_view(self, world_T_cam, K: torch.Tensor, size: Sequence[int], tear_ratio: float = 1.1, empty_depth: float = -1.0,
                               return_source: bool = False) -> Dict[str, torch.Tensor]:

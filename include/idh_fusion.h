@@ -1,7 +1,7 @@
 /*
  * idh_fusion.h — TSDF fusion of depth maps, the ray cast of the fused surface into live cameras and its extraction as a triangle mesh
  * (additive: idh_version() stays as it is; every struct is versioned through its struct_size; csrc/tsdf.hip, csrc/tsdf_mesh.hip,
- * DESIGN.md §4.21, §4.22).
+ * DESIGN.md §4.21, §4.22, §4.23).
  *
  * The depth warp of idh_raster.h draws remembered maps as separate sheets under one z-buffer: maps are not combined, holes stay holes
  * and the memory is as long as the ring.  Here every map is averaged into a truncated signed distance volume (Curless and Levoy) - the
@@ -198,6 +198,96 @@ size_t idh_tsdf_mesh_workspace_bytes(int Nz, int Ny, int Nx);
  * IDH_EINVAL: workspace not 16-byte aligned. */
 int idh_tsdf_mesh_count_fwd(const idh_tsdf_mesh_args *args, void *stream);
 int idh_tsdf_mesh_emit_fwd(const idh_tsdf_mesh_args *args, void *stream);
+
+/* ---- Colour: camera frames fused next to the depth, ray-cast and meshed with the surface (csrc/tsdf.hip, csrc/tsdf_mesh.hip) ----
+ *
+ * colors (Nz, Ny, Nx, 4) fp32, caller-owned and laid out like `values`: the quad {R, G, B, Wc} per voxel, 16 bytes, 16-byte aligned -
+ * R, G, B in units of a uint8 channel (0 .. 255), Wc the number of colour observations.  The EMPTY state is all-zero bytes: a memset
+ * (hipMemsetAsync, tensor.zero_()) resets it; idh_tsdf_reset_fwd does not know the tensor and leaves it alone.  No entry point above
+ * reads or writes it: idh_tsdf_integrate_fwd on a coloured volume (lidar, depth-only maps) leaves `colors` as it is, so Wc <= W holds
+ * at every voxel of a volume filled through these calls with one max_weight.
+ * Frames are uint8 RGB (M, hc, wc, 3), the frame convention of idh_ingest.h and idh_composite.h, with intrinsics of their own. */
+typedef struct idh_tsdf_integrate_color_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *depth_m1hw;       /* (M,1,h,w) */
+    const float *K_m44;            /* (M,4,4) intrinsics at h x w, row-major */
+    const float *cam_T_world_m44;  /* (M,4,4) */
+    float max_weight;              /* >= 1, finite: caps W and Wc */
+    int32_t M, h, w;
+    float *colors_zyx4;            /* (Nz,Ny,Nx,4) {R, G, B, Wc}, 16-byte aligned */
+    const uint8_t *color_mhw3;     /* (M,hc,wc,3) RGB frames, frame m taken with depth map m */
+    const float *color_K_m44;      /* (M,4,4) intrinsics at hc x wc */
+    int32_t hc, wc;
+} idh_tsdf_integrate_color_args;
+
+typedef struct idh_tsdf_raycast_color_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *world_T_cam_b44;  /* the fields of idh_tsdf_raycast_args, with their meaning */
+    const float *invK_b44;
+    float *depth_b1hw;
+    uint8_t *flags_bhw;
+    float *normals_b3hw;           /* or NULL */
+    float near;
+    float step_voxels;
+    float empty_depth;
+    int32_t max_steps;
+    int32_t world_normals;
+    int32_t skip;
+    int32_t B, H, W;
+    const float *colors_zyx4;      /* (Nz,Ny,Nx,4), 16-byte aligned */
+    uint8_t *rgba_bhw4;            /* out (B,H,W,4): the layout of idh_raster_shaded_fwd's rgba */
+} idh_tsdf_raycast_color_args;
+
+typedef struct idh_tsdf_mesh_colors_args {
+    int64_t struct_size;
+    idh_tsdf_mesh_args mesh;       /* volume, min_weight and workspace of the count call before it; vert_capacity; the rest is not read */
+    const float *colors_zyx4;      /* (Nz,Ny,Nx,4), 16-byte aligned */
+    uint8_t *rgba_v4;              /* out (vert_capacity, 4) */
+} idh_tsdf_mesh_colors_args;
+
+size_t idh_sizeof_tsdf_integrate_color_args(void);
+size_t idh_sizeof_tsdf_raycast_color_args(void);
+size_t idh_sizeof_tsdf_mesh_colors_args(void);
+
+/* idh_tsdf_integrate_fwd with a colour frame per map, one launch, one lane per voxel.  For m = 0 .. M - 1 the {T, W} update of the
+ * voxel is exactly the one stated there; immediately after the voxel's {T, W} update for map m (so only where map m updated it):
+ *   skip the colour unless sdf <= trunc                               (free space in front of the band carries no colour)
+ *   qx = fxc * (c.x / c.z) + cxc,  qy = fyc * (c.y / c.z) + cyc       (color_K[m]; the quotients are those of px and py)
+ *   skip unless 0 <= qx < wc and 0 <= qy < hc;   tap (floor(qy), floor(qx)),  c = its three bytes converted to float
+ *   per channel   C <- (Wc * C + c) / (Wc + 1);   then   Wc <- min(Wc + 1, max_weight)
+ * The lane keeps {R, G, B, Wc} in registers over the M maps: one 16-byte load at the first map that colours the voxel, one 16-byte
+ * store at the end; a voxel no map colours reads and writes nothing of `colors`.
+ * Promises: `values` and `block_flags` after this call equal, bit for bit, what idh_tsdf_integrate_fwd leaves for the same maps; two
+ * calls return the same bits; one call with M maps equals M calls with one map each, bit for bit, colours included.
+ * Codes: those of idh_tsdf_integrate_fwd, and with its IDH_EINVAL conditions (before the volume's) also a null colors_zyx4, color_mhw3
+ * or color_K_m44, hc <= 0 or wc <= 0, colors_zyx4 not 16-byte aligned; with its IDH_EUNSUPPORTED conditions also hc * wc >= 2^31 / M. */
+int idh_tsdf_integrate_color_fwd(const idh_tsdf_integrate_color_args *args, void *stream);
+
+/* idh_tsdf_raycast_fwd with the surface's colour.  The march, depth, flags and normals are the ones stated there, bit for bit, with
+ * skip 0 and 1.  Colour is formed once per pixel, at the hit:
+ *   g* = og + t* dg, its cell and r = g* - cell, exactly as for the normals; if the cell is in range (0 <= cell <= N - 2 per axis),
+ *   over its corners c = 0 .. 7 (c = dx + 2 dy + 4 dz) in this order, only those with Wc > 0:
+ *     w = ((dx ? r.x : 1 - r.x) * (dy ? r.y : 1 - r.y)) * (dz ? r.z : 1 - r.z);   num += w * C (per channel);   den += w
+ *   den > 0: each channel (uint8)(int)(min(max(num / den, 0), 255) + 0.5f), alpha 255
+ *   no hit, a cell out of range or den == 0: the four bytes are 0.
+ * The known rule W > 0 plays no part in the colour and there is no new flag bit: alpha says whether there is a colour.
+ * Codes: those of idh_tsdf_raycast_fwd, and with its null checks (before the volume's conditions) IDH_EINVAL for a null colors_zyx4 or
+ * rgba_bhw4 or colors_zyx4 not 16-byte aligned. */
+int idh_tsdf_raycast_color_fwd(const idh_tsdf_raycast_color_args *args, void *stream);
+
+/* The colours of the vertices idh_tsdf_mesh_emit_fwd writes, after idh_tsdf_mesh_count_fwd on the same volume, min_weight and
+ * workspace (before or after the emit call; that call is not changed).  One pass over the workspace's chunks.  An owner a with a vertex
+ * on `axis` has the index it has in emit; with b = a + axis:
+ *   r = T_a / (T_a - T_b)                                             (the expression of emit)
+ *   both endpoints with Wc > 0:  C = C_a + r * (C_b - C_a) per channel;   one endpoint with Wc > 0: that endpoint's colour;
+ *   rounding and alpha as in the ray cast;   neither: four zero bytes.
+ * Every store is guarded by mesh.vert_capacity.
+ * Codes: IDH_EINVAL for args NULL or struct_size short; then those of the two mesh calls in their order, where the null outputs are
+ * colors_zyx4 and rgba_v4 (verts_v3, faces_f3 and totals are not read) and the capacity is vert_capacity; IDH_EINVAL also for
+ * colors_zyx4 not 16-byte aligned. */
+int idh_tsdf_mesh_colors_fwd(const idh_tsdf_mesh_colors_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
