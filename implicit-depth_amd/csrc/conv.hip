@@ -42,20 +42,6 @@ namespace {
 // so the K loop is branch-free.  Must cover the widest Cin_pad (host-checked).
 __device__ float g_zero_page[kZeroFloats];
 
-// idh_count_launches() replays idh_run_ops' launch decisions without launching anything
-thread_local bool t_dry_run = false;
-thread_local int t_launches = 0;
-#undef IDH_CHECK_LAUNCH
-#define IDH_CHECK_LAUNCH()                                              \
-    do {                                                                \
-        if (!t_dry_run && hipGetLastError() != hipSuccess) return IDH_ELAUNCH; \
-    } while (0)
-#define IDH_LAUNCH(...)                         \
-    do {                                        \
-        if (t_dry_run) ++t_launches;            \
-        else hipLaunchKernelGGL(__VA_ARGS__);   \
-    } while (0)
-
 template <int TM, int TN>
 __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, unsigned blk_in, unsigned nblk) {
     const int lane = threadIdx.x & 63;
@@ -323,7 +309,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const LdsConvArgs &la, unsigned
     const int nc0 = a.s[0].cblocks;
     const int nc1 = a.s[1].in ? a.s[1].cblocks : 0;
     // split boundaries in COST units, not chunks: a 3x3 chunk is 9 taps of MFMAs + one staging round, a 1x1 chunk one tap and (batched,
-    // lds_g1) a fraction of a round - about a ninth (measured flat between 4 and 9).  With equal weights the first split of a
+    // lds_g1) a fraction of a round - about a ninth (weights 3 ... 9 measured flat within 1 %: profiles/r05/experiments.md 3b).  With equal weights the first split of a
     // BasicBlock's conv2 + projection got all 3x3 chunks and the last ones only 1x1 chunks: the launch took as long as the unsplit 3x3 part.
     constexpr int kW3 = 9;
     const int w1 = S2 ? kW3 : 1;
@@ -1327,287 +1313,542 @@ __global__ __launch_bounds__(256) void level_k(const LevelArgs g) {
 
 inline int ceil16(int v) { return (v + 15) & ~15; }
 
-// A validated conv op, ready to launch: either the LDS-staged kernel (lds_rows = 8 / 4) or the
-// direct-fragment kernel (lds_rows = 0, tile tm x tn).
+// ---- host side: launching ---------------------------------------------------------------------------------------------
+// What a pass hands down its call chain.  dry: idh_count_launches' replay - every decision is taken and every launch counted, none is issued.
+struct RunCtx { hipStream_t st; bool dry; int launches; };
+template <typename T> struct as_declared { using type = T; };  // (keeps P deduced from the kernel alone: arguments convert to what it declares)
+
+// The one place a kernel of this file is launched (or, dry, counted)
+template <typename... P>
+int launch(RunCtx &ctx, void (*k)(P...), dim3 grid, dim3 block, size_t lds, const typename as_declared<P>::type &...args) {
+    ++ctx.launches;
+    if (ctx.dry) return IDH_OK;
+    void *argv[] = {const_cast<void *>(static_cast<const void *>(&args))...};
+    (void)hipLaunchKernel(reinterpret_cast<const void *>(k), grid, block, argv, lds, ctx.st);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+// ... and the one place a launcher of conv_split.hip / conv_wino.hip / conv_wino4.hip is called
+template <typename Call>
+int launch_ext(RunCtx &ctx, Call call) { return ++ctx.launches, ctx.dry ? IDH_OK : call(); }
+inline int consumed(int rc, int n) { return rc != IDH_OK ? rc : n; }  // what a run_<kind> returns: ops consumed, or the error
+
+// ---- host side: one conv ----------------------------------------------------------------------------------------------
+enum class ConvKernel { Direct, Lds, Split, Wino2, Wino4 };
+
+// A validated conv op, ready to launch.  `kernel` says which of the geometry fields mean something:
+//   Direct  conv_mfma_k<tm, tn>: a wave owns tm x tn sub-tiles of 16 pixels x 16 channels; `blocks` workgroups; la.c = a (for level_k)
+//   Lds     conv3x3_lds_k: tiles of `rows` (8 | 4) x 16 pixels x 16 nj channels (nj = 4 | 2 | 1); la = a + the tile grid; `blocks` workgroups
+//   Split   conv_split.hip: `rows` (16 | 8) tile rows, split_mode = IDH_SPLIT_*
+//   Wino2 / Wino4   conv_wino.hip / conv_wino4.hip: their launchers derive the geometry from a and n_img
 struct PreparedConv {
     ConvArgs a;
     LdsConvArgs la;
-    int lds_rows, tm, tn;  // lds_rows = 16: split-precision kernel, tm = IDH_SPLIT_* mode; 32: Winograd kernel, tn = tile rows; 36: Winograd F(4x4)
-    int n_img;
+    ConvKernel kernel;
+    int rows, nj, tm, tn, split_mode, n_img;
     unsigned blocks;
-    bool up;         // some source has fused x2-upsampled segments (LDS kernels only)
-    bool norm;       // source 0 is normalised on load (LDS kernels with 16-channel tiles only)
-    bool s2;         // source 1 is a 3x3 stride-2 projection (LDS kernels with 64- / 32-channel tiles)
-    int nj;          // LDS kernels: 16-channel output sub-tiles per workgroup (4, 2, 1)
+    // Lds loader flavour, at most one set.  up: some source has fused x2-upsampled segments (64-channel tiles only); norm: source 0 is normalised
+    // on load (16-channel tiles only); s2: source 1 is a 3x3 stride-2 projection (64- / 32-channel tiles)
+    bool up, norm, s2;
+    int level;       // LV_* when a level launch can host the op, else -1
     ReduceDesc red;  // valid when a.S > 1
 };
 
-int prep_conv(const idh_op &op, PreparedConv &pc) {
-    ConvArgs &a = pc.a;
-    a = ConvArgs{};
-    pc.up = false;
-    pc.norm = op.src[0].norm != nullptr;
-    pc.s2 = false;
-    pc.nj = 4;
-    int steps = 0;
-    for (int i = 0; i < 2; ++i) {
-        const idh_conv_src &s = op.src[i];
-        ConvSrc &d = a.s[i];
-        d.in = s.in;
-        if (!s.in) continue;
-        // the K loop reads whole 16-channel blocks: the buffer must be readable (and finite) up to
-        // ceil16(Cin) channels per pixel; packed weights are zero there.
-        if (!s.w || s.Cin <= 0 || s.cs < (s.up_in[0] ? s.up_c0 : ceil16(s.Cin)) || (s.cs & 3) || (s.ks != 1 && s.ks != 3) ||
-            (s.stride != 1 && s.stride != 2) || s.H <= 0 || s.W <= 0)
-            return IDH_EINVAL;
-        if (ceil16(s.Cin) > kZeroFloats) return IDH_EUNSUPPORTED;
-        const int pad = s.ks / 2;
-        if ((s.H + 2 * pad - s.ks) / s.stride + 1 != op.Ho || (s.W + 2 * pad - s.ks) / s.stride + 1 != op.Wo)
-            return IDH_EINVAL;
-        d.w = s.w; d.cs = s.cs; d.H = s.H; d.W = s.W; d.Cin = s.Cin; d.ks = s.ks; d.stride = s.stride;
-        d.pad_mode = s.pad_mode; d.cblocks = ceil16(s.Cin) / 16;
-        d.up_in[0] = s.up_in[0]; d.up_in[1] = s.up_in[1]; d.up_cs[0] = s.up_cs[0]; d.up_cs[1] = s.up_cs[1];
-        d.up_c0 = s.up_c0; d.up_C = s.up_C;
-        d.norm = s.norm; d.norm_slope = s.norm_slope; d.norm_act = s.norm_act;
-        if (s.norm && (i != 0 || s.up_in[0] || ((uintptr_t)s.norm & 15) || (s.Cin & 15))) return IDH_EUNSUPPORTED;
-        if (s.up_in[0]) {
-            const int nseg = s.up_in[1] ? 2 : 1;
-            if (s.up_c0 < 0 || (s.up_c0 & 15) || s.up_C <= 0 || (s.up_C & 15) || s.up_c0 + nseg * s.up_C != s.Cin || (s.H & 1) || (s.W & 1) ||
-                s.stride != 1 || (s.up_c0 > 0 && s.cs < s.up_c0) || s.up_cs[0] < s.up_C || (s.up_cs[0] & 3) ||
-                (nseg == 2 && (s.up_cs[1] < s.up_C || (s.up_cs[1] & 3))))
-                return IDH_EINVAL;
-            pc.up = true;
-        }
-        steps += s.ks * s.ks * d.cblocks;
-    }
-    if (!a.s[0].in || !op.out || op.Cout <= 0 || op.N <= 0) return IDH_EINVAL;
-    // vector epilogue: 4 consecutive channels per lane -> 16-byte aligned rows
-    if ((op.Cout & 3) || (op.out_cs & 3) || ((uintptr_t)op.out & 15) || (op.bias && ((uintptr_t)op.bias & 15)) ||
-        (op.res && ((op.res_cs & 3) || ((uintptr_t)op.res & 15))))
+// Step 1: validate source i and translate it into the kernels' form.  Returns the K steps it contributes (0: unused) or an error.
+int fill_source(const idh_op &op, int i, ConvSrc &d) {
+    const idh_conv_src &s = op.src[i];
+    d.in = s.in;
+    if (!s.in) return 0;
+    // the K loop reads whole 16-channel blocks: the buffer must be readable (and finite) up to
+    // ceil16(Cin) channels per pixel; packed weights are zero there.
+    if (!s.w || s.Cin <= 0 || s.cs < (s.up_in[0] ? s.up_c0 : ceil16(s.Cin)) || (s.cs & 3) || (s.ks != 1 && s.ks != 3) ||
+        (s.stride != 1 && s.stride != 2) || s.H <= 0 || s.W <= 0)
         return IDH_EINVAL;
-    a.bias = op.bias; a.res = op.res; a.out = op.out; a.ws = op.ws;
-    a.res_cs = op.res_cs; a.out_cs = op.out_cs; a.Ho = op.Ho; a.Wo = op.Wo; a.Cout = op.Cout;
-    a.Cout_pad = ceil16(op.Cout);
-    const long long M = (long long)op.N * op.Ho * op.Wo;
-    if (M >= (1ll << 31)) return IDH_EUNSUPPORTED;
-    a.M = (int)M; a.steps_total = steps; a.act = op.act; a.slope = op.slope;
-    a.S = op.split_k > 1 ? op.split_k : 1;
-    if (a.S > steps) a.S = steps;
-    // A lone 3x3 stride-2 conv (conv1 of a stride-2 BasicBlock) asked onto the LDS-staged kernel (tile_m 8 / 9): it runs as the kernel's
-    // stride-2 SECOND source (halo de-interleaved by column parity) behind an empty first source (no chunks: its loops do not execute,
-    // its descriptors have zero range).
-    if (a.s[0].ks == 3 && a.s[0].stride == 2 && !a.s[1].in && (op.tile_m == 8 || op.tile_m == 9) && a.s[0].pad_mode == IDH_PAD_ZEROS &&
-        !a.s[0].up_in[0] && !a.s[0].norm && op.Wo >= kLT_W && (op.Cout % 32) == 0 && (op.tile_n == 0 ? (op.Cout % 64) == 0 : op.tile_n == 2)) {
-        a.s[1] = a.s[0];
-        ConvSrc e{};
-        e.in = a.s[1].in; e.w = a.s[1].w; e.ks = 3; e.stride = 1; e.pad_mode = IDH_PAD_ZEROS;  // cblocks = H = W = cs = 0
-        a.s[0] = e;
+    if (ceil16(s.Cin) > kZeroFloats) return IDH_EUNSUPPORTED;
+    const int pad = s.ks / 2;
+    if ((s.H + 2 * pad - s.ks) / s.stride + 1 != op.Ho || (s.W + 2 * pad - s.ks) / s.stride + 1 != op.Wo)
+        return IDH_EINVAL;
+    d.w = s.w; d.cs = s.cs; d.H = s.H; d.W = s.W; d.Cin = s.Cin; d.ks = s.ks; d.stride = s.stride;
+    d.pad_mode = s.pad_mode; d.cblocks = ceil16(s.Cin) / 16;
+    d.up_in[0] = s.up_in[0]; d.up_in[1] = s.up_in[1]; d.up_cs[0] = s.up_cs[0]; d.up_cs[1] = s.up_cs[1];
+    d.up_c0 = s.up_c0; d.up_C = s.up_C;
+    d.norm = s.norm; d.norm_slope = s.norm_slope; d.norm_act = s.norm_act;
+    if (s.norm && (i != 0 || s.up_in[0] || ((uintptr_t)s.norm & 15) || (s.Cin & 15))) return IDH_EUNSUPPORTED;
+    if (s.up_in[0]) {
+        const int nseg = s.up_in[1] ? 2 : 1;
+        if (s.up_c0 < 0 || (s.up_c0 & 15) || s.up_C <= 0 || (s.up_C & 15) || s.up_c0 + nseg * s.up_C != s.Cin || (s.H & 1) || (s.W & 1) ||
+            s.stride != 1 || (s.up_c0 > 0 && s.cs < s.up_c0) || s.up_cs[0] < s.up_C || (s.up_cs[0] & 3) ||
+            (nseg == 2 && (s.up_cs[1] < s.up_C || (s.up_cs[1] & 3))))
+            return IDH_EINVAL;
     }
-    // LDS-staged kernel for the dominant shape family: tile_m 8 / 9 request the 8- / 4-row tile,
-    // 0 = auto (8-row)
-    // LDS kernels: tile_n = output sub-tiles of 16 channels per workgroup (0 = 4 -> 64 channels; 2; 1)
-    const int nj = (op.tile_m == 8 || op.tile_m == 9 || op.tile_m == 0) ? (op.tile_n == 0 ? 4 : op.tile_n) : 4;
-    const bool lds_ok = a.s[0].ks == 3 && a.s[0].stride == 1 && (nj == 4 || nj == 2 || nj == 1) && (op.Cout % (16 * nj)) == 0 &&
-                        (a.s[0].pad_mode == IDH_PAD_ZEROS || (a.s[0].pad_mode == IDH_PAD_REPLICATE && !a.s[1].in)) &&
-                        (!a.s[1].in || (a.s[1].ks == 1 && a.s[1].stride == 1) ||
-                         (a.s[1].ks == 3 && a.s[1].stride == 2 && a.s[1].pad_mode == IDH_PAD_ZEROS && !a.s[1].up_in[0] && !a.s[0].up_in[0] &&
-                          !op.src[0].norm && (nj == 4 || nj == 2))) &&
-                        op.Wo >= kLT_W;
-    pc.lds_rows = 0;
-    // the LDS kernels address source 0 with 32-bit byte offsets inside one image / the packed weights
-    const bool lds_fits = (long long)a.s[0].H * a.s[0].W * a.s[0].cs * 4 < (1ll << 31) && 9ll * a.s[0].cblocks * 4 * a.Cout_pad * 16 < (1ll << 31) &&
-                          (!a.s[1].in || ((long long)a.s[1].H * a.s[1].W * a.s[1].cs * 4 < (1ll << 31) && 9ll * a.s[1].cblocks * 4 * a.Cout_pad * 16 < (1ll << 31))) &&
-                          (long long)op.Ho * op.Wo * op.out_cs * 4 < (1ll << 31) && (!op.res || (long long)op.Ho * op.Wo * op.res_cs * 4 < (1ll << 31));
-    if (op.tile_m == IDH_TILE_WINO) {
-        // Winograd F(2x2,3x3) kernel (conv_wino.hip): src[0].w holds idh_pack_conv_weight_wino output
-        if (!wino_supported(a)) return IDH_EUNSUPPORTED;
-        pc.lds_rows = 32;
-        pc.tm = op.tile_m;
-        pc.tn = 0;
-        pc.n_img = op.N;
-        pc.blocks = 0;
-    } else if (op.tile_m == IDH_TILE_WINO4) {
-        // Winograd F(4x4,3x3) kernel (conv_wino4.hip): src[0].w holds idh_pack_conv_weight_wino4 output
-        if (!wino4_supported(a)) return IDH_EUNSUPPORTED;
-        pc.lds_rows = 36;
-        pc.tm = op.tile_m;
-        pc.tn = 0;
-        pc.n_img = op.N;
-        pc.blocks = 0;
-    } else if (op.tile_m == IDH_SPLIT_F16X3) {
-        // split-precision kernel (conv_split.hip): src[0].w holds idh_pack_conv_weight_split output
-        if (!lds_ok || a.s[0].pad_mode != IDH_PAD_ZEROS || (op.Cout % 64) || a.S != 1 || op.Wo < kSplitTile || op.Ho < 1 || (op.tile_n != 0 && op.tile_n != 8 && op.tile_n != 16))
-            return IDH_EUNSUPPORTED;
-        // second source: the kernel walks src[1] with source 0's H / W and reads ONE tap of weights per 16-channel chunk from the 1x1 panels of the
-        // blob - a 1x1 stride-1 projection of an output-sized plain tensor and nothing else (lds_ok also admits the LDS kernel's 3x3 stride-2 projection)
-        if (a.s[1].in && (a.s[1].ks != 1 || a.s[1].stride != 1 || a.s[1].H != op.Ho || a.s[1].W != op.Wo || a.s[1].up_in[0] || a.s[1].norm))
-            return IDH_EUNSUPPORTED;
-        a.NT = op.Cout / 64;
-        pc.lds_rows = 16;
-        pc.tm = op.tile_m;
-        pc.tn = op.tile_n == 8 ? 8 : 16;  // tile rows
-        pc.n_img = op.N;
-        pc.blocks = 0;
-    } else if (lds_ok && lds_fits && (op.tile_m == 8 || op.tile_m == 0 || op.tile_m == 9)) {
-        const int rows = op.tile_m == 9 ? 4 : 8;
-        const int chunks = a.s[0].cblocks + (a.s[1].in ? a.s[1].cblocks : 0);
-        if (a.S > chunks) a.S = chunks;
-        {   // the kernel draws the split boundaries in cost units (9 per 3x3 chunk, 1 per 1x1 chunk, conv3x3_lds_body): more splits than whole
-            // 3x3-chunk costs would leave some of them empty (all-zero partials written and reduced for nothing)
-            const int w1 = (a.s[1].in && a.s[1].ks == 3) ? 9 : 1;
-            const int T = 9 * a.s[0].cblocks + (a.s[1].in ? w1 * a.s[1].cblocks : 0);
-            const int smax = T / 9 > 1 ? T / 9 : 1;
-            if (a.S > smax) a.S = smax;
-        }
-        a.NT = op.Cout / (16 * nj);
-        pc.nj = nj;
-        pc.la = LdsConvArgs{a, (op.Wo + kLT_W - 1) / kLT_W, (op.Ho + rows - 1) / rows};
-        const long long blocks = (long long)a.S * op.N * pc.la.tiles_x * pc.la.tiles_y * a.NT;
-        if (blocks >= (1ll << 31)) return IDH_EUNSUPPORTED;
-        pc.blocks = (unsigned)blocks;
-        pc.lds_rows = rows;
-        pc.s2 = a.s[1].in && a.s[1].ks == 3;
-    } else {
-        int tm = op.tile_m, tn = op.tile_n;
-        if (tm == 8 || tm == 9) tm = 0;
-        const int nsub = a.Cout_pad / 16;
-        if (tn == 0) tn = (nsub % 4 == 0) ? 4 : (nsub % 2 == 0 ? 2 : 1);
-        if (tm == 0) tm = 4;
-        if ((tm != 1 && tm != 2 && tm != 4) || (tn != 1 && tn != 2 && tn != 4) || nsub % tn) return IDH_EINVAL;
-        a.MT = (int)((M + 16 * tm - 1) / (16 * tm));
-        a.NT = nsub / tn;
-        pc.tm = tm; pc.tn = tn;
-        const long long waves = (long long)a.MT * a.NT * a.S;
-        if ((waves + 3) / 4 >= (1ll << 31)) return IDH_EUNSUPPORTED;
-        pc.blocks = (unsigned)((waves + 3) / 4);
-    }
-    if (pc.up && ((pc.lds_rows != 8 && pc.lds_rows != 4) || pc.nj != 4)) return IDH_EUNSUPPORTED;  // fused upsampling lives in the 64-channel LDS loader
-    if (pc.norm && ((pc.lds_rows != 8 && pc.lds_rows != 4) || pc.nj != 1)) return IDH_EUNSUPPORTED;  // normalise-on-load: 16-channel LDS tiles
-    if (a.S > 1) {
-        if (!op.ws) return IDH_EWORKSPACE;
-        pc.red = ReduceDesc{op.ws, op.bias, op.res, op.out, a.M, op.Cout, a.Cout_pad, a.S, op.res_cs, op.out_cs, op.act, op.slope};
-    }
+    return s.ks * s.ks * d.cblocks;
+}
+
+// Step 2: the epilogue.  Vector stores: 4 consecutive channels per lane -> 16-byte aligned rows.
+int check_epilogue(const idh_op &op) {
+    if (!op.src[0].in || !op.out || op.Cout <= 0 || op.N <= 0 || (op.Cout & 3) || (op.out_cs & 3) || ((uintptr_t)op.out & 15) ||
+        (op.bias && ((uintptr_t)op.bias & 15)) || (op.res && ((op.res_cs & 3) || ((uintptr_t)op.res & 15))))
+        return IDH_EINVAL;
+    if ((long long)op.N * op.Ho * op.Wo >= (1ll << 31)) return IDH_EUNSUPPORTED;
     return IDH_OK;
 }
 
-int launch_conv(const PreparedConv &pc, hipStream_t st) {
-    if (pc.lds_rows == 16) {
-        if (t_dry_run) { ++t_launches; return IDH_OK; }
-        return launch_conv_split(pc.a, pc.n_img, pc.tm, pc.tn, st);
-    }
-    if (pc.lds_rows == 32) {
-        if (t_dry_run) { ++t_launches; return IDH_OK; }
-        return launch_conv_wino(pc.a, pc.n_img, pc.tn, st);
-    }
-    if (pc.lds_rows == 36) {
-        if (t_dry_run) { ++t_launches; return IDH_OK; }
-        return launch_conv_wino4(pc.a, pc.n_img, st);
-    }
-    if (pc.lds_rows == 8 && pc.up) IDH_LAUNCH(conv3x3_lds_up_k<2>, dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8 && pc.s2 && pc.nj == 4) IDH_LAUNCH((conv3x3_lds_k<2, false, 4, false, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8 && pc.s2) IDH_LAUNCH((conv3x3_lds_k<2, false, 2, false, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.s2 && pc.nj == 4) IDH_LAUNCH((conv3x3_lds_k<1, false, 4, false, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.s2) IDH_LAUNCH((conv3x3_lds_k<1, false, 2, false, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8 && pc.norm) IDH_LAUNCH((conv3x3_lds_k<2, false, 1, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.norm) IDH_LAUNCH((conv3x3_lds_k<1, false, 1, true>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8 && pc.nj == 2) IDH_LAUNCH((conv3x3_lds_k<2, false, 2>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8 && pc.nj == 1) IDH_LAUNCH((conv3x3_lds_k<2, false, 1>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.nj == 2) IDH_LAUNCH((conv3x3_lds_k<1, false, 2>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.nj == 1) IDH_LAUNCH((conv3x3_lds_k<1, false, 1>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 8) IDH_LAUNCH((conv3x3_lds_k<2, false>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4 && pc.up) IDH_LAUNCH(conv3x3_lds_up_k<1>, dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else if (pc.lds_rows == 4) IDH_LAUNCH((conv3x3_lds_k<1, false>), dim3(pc.blocks), dim3(256), 0, st, pc.la);
-    else {
-#define IDH_CASE(TM_, TN_) \
-    if (pc.tm == TM_ && pc.tn == TN_) IDH_LAUNCH((conv_mfma_k<TM_, TN_>), dim3(pc.blocks), dim3(256), 0, st, pc.a);
-        IDH_CASE(4, 4) IDH_CASE(2, 4) IDH_CASE(1, 4) IDH_CASE(4, 2) IDH_CASE(2, 2) IDH_CASE(1, 2) IDH_CASE(4, 1)
-        IDH_CASE(2, 1) IDH_CASE(1, 1)
-#undef IDH_CASE
-    }
-    IDH_CHECK_LAUNCH();
+// Step 3: a lone 3x3 stride-2 conv (conv1 of a stride-2 BasicBlock) asked onto the LDS-staged kernel (tile_m 8 / 9) runs as the kernel's
+// stride-2 SECOND source (halo de-interleaved by column parity) behind an empty first source (no chunks: its loops do not execute,
+// its descriptors have zero range).
+void lone_stride2_as_second_source(const idh_op &op, ConvArgs &a) {
+    if (!(a.s[0].ks == 3 && a.s[0].stride == 2 && !a.s[1].in && (op.tile_m == 8 || op.tile_m == 9) && a.s[0].pad_mode == IDH_PAD_ZEROS &&
+          !a.s[0].up_in[0] && !a.s[0].norm && op.Wo >= kLT_W && (op.Cout % 32) == 0 && (op.tile_n == 0 ? (op.Cout % 64) == 0 : op.tile_n == 2)))
+        return;
+    a.s[1] = a.s[0];
+    ConvSrc e{};
+    e.in = a.s[1].in; e.w = a.s[1].w; e.ks = 3; e.stride = 1; e.pad_mode = IDH_PAD_ZEROS;  // cblocks = H = W = cs = 0
+    a.s[0] = e;
+}
+
+// The shape family of the LDS-staged kernel with nj 16-channel sub-tiles per workgroup (the split-precision kernel shares it)
+bool lds_ok(const idh_op &op, const ConvArgs &a, int nj) {
+    return a.s[0].ks == 3 && a.s[0].stride == 1 && (nj == 4 || nj == 2 || nj == 1) && (op.Cout % (16 * nj)) == 0 &&
+           (a.s[0].pad_mode == IDH_PAD_ZEROS || (a.s[0].pad_mode == IDH_PAD_REPLICATE && !a.s[1].in)) &&
+           (!a.s[1].in || (a.s[1].ks == 1 && a.s[1].stride == 1) ||
+            (a.s[1].ks == 3 && a.s[1].stride == 2 && a.s[1].pad_mode == IDH_PAD_ZEROS && !a.s[1].up_in[0] && !a.s[0].up_in[0] &&
+             !op.src[0].norm && (nj == 4 || nj == 2))) &&
+           op.Wo >= kLT_W;
+}
+
+// The LDS kernels address a source with 32-bit byte offsets inside one image / the packed weights
+bool lds_fits(const idh_op &op, const ConvArgs &a) {
+    const auto src_fits = [&](const ConvSrc &s) { return (long long)s.H * s.W * s.cs * 4 < (1ll << 31) && 9ll * s.cblocks * 4 * a.Cout_pad * 16 < (1ll << 31); };
+    return src_fits(a.s[0]) && (!a.s[1].in || src_fits(a.s[1])) && (long long)op.Ho * op.Wo * op.out_cs * 4 < (1ll << 31) &&
+           (!op.res || (long long)op.Ho * op.Wo * op.res_cs * 4 < (1ll << 31));
+}
+
+// Step 4, one per kernel: refuse what the kernel does not cover, set the launch geometry.
+// Winograd F(2x2,3x3) / F(4x4,3x3) (conv_wino.hip / conv_wino4.hip): src[0].w holds idh_pack_conv_weight_wino / _wino4 output
+int choose_wino2(PreparedConv &pc) { return pc.kernel = ConvKernel::Wino2, wino_supported(pc.a) ? IDH_OK : IDH_EUNSUPPORTED; }
+int choose_wino4(PreparedConv &pc) { return pc.kernel = ConvKernel::Wino4, wino4_supported(pc.a) ? IDH_OK : IDH_EUNSUPPORTED; }
+
+// split precision (conv_split.hip): src[0].w holds idh_pack_conv_weight_split output
+int choose_split(const idh_op &op, PreparedConv &pc) {
+    ConvArgs &a = pc.a;
+    if (!lds_ok(op, a, 4) || a.s[0].pad_mode != IDH_PAD_ZEROS || (op.Cout % 64) || a.S != 1 || op.Wo < kSplitTile || op.Ho < 1 ||
+        (op.tile_n != 0 && op.tile_n != 8 && op.tile_n != 16))
+        return IDH_EUNSUPPORTED;
+    // second source: the kernel walks src[1] with source 0's H / W and reads ONE tap of weights per 16-channel chunk from the 1x1 panels of the
+    // blob - a 1x1 stride-1 projection of an output-sized plain tensor and nothing else (lds_ok also admits the LDS kernel's 3x3 stride-2 projection)
+    if (a.s[1].in && (a.s[1].ks != 1 || a.s[1].stride != 1 || a.s[1].H != op.Ho || a.s[1].W != op.Wo || a.s[1].up_in[0] || a.s[1].norm))
+        return IDH_EUNSUPPORTED;
+    a.NT = op.Cout / 64;
+    pc.kernel = ConvKernel::Split; pc.split_mode = op.tile_m; pc.rows = op.tile_n == 8 ? 8 : 16;
     return IDH_OK;
 }
 
-int launch_reduces(const PreparedConv *pcs, int n, hipStream_t st) {
-    ReduceGroupArgs g{};
-    unsigned cursor = 0;
-    for (int i = 0; i < n; ++i) {
-        if (pcs[i].a.S <= 1) continue;
-        g.start[g.n] = cursor;
-        g.d[g.n] = pcs[i].red;
-        cursor += (unsigned)idh_cdiv((long long)pcs[i].red.M * pcs[i].red.Cout, 256);
-        ++g.n;
-    }
-    if (g.n == 0) return IDH_OK;
-    g.start[g.n] = cursor;
-    IDH_LAUNCH(splitk_reduce_group_k, dim3(cursor), dim3(256), 0, st, g);
-    IDH_CHECK_LAUNCH();
+// Step 5 (LDS kernel): the kernel draws the split boundaries in cost units (9 per 3x3 chunk, 1 per 1x1 chunk, conv3x3_lds_body): more splits than
+// chunks, or than whole 3x3-chunk costs, would leave some of them empty (all-zero partials written and reduced for nothing)
+void clamp_lds_split(ConvArgs &a) {
+    const int nc1 = a.s[1].in ? a.s[1].cblocks : 0, w1 = a.s[1].ks == 3 ? 9 : 1;
+    const int T = 9 * a.s[0].cblocks + w1 * nc1;
+    a.S = std::min(a.S, std::min(a.s[0].cblocks + nc1, std::max(T / 9, 1)));
+}
+
+// LDS-staged kernel: tile_m 8 / 0 -> 8-row tiles, 9 -> 4-row tiles
+int choose_lds(const idh_op &op, PreparedConv &pc, int nj) {
+    ConvArgs &a = pc.a;
+    const int rows = op.tile_m == 9 ? 4 : 8;
+    clamp_lds_split(a);
+    a.NT = op.Cout / (16 * nj);
+    pc.la = LdsConvArgs{a, (op.Wo + kLT_W - 1) / kLT_W, (op.Ho + rows - 1) / rows};
+    const long long blocks = (long long)a.S * op.N * pc.la.tiles_x * pc.la.tiles_y * a.NT;
+    if (blocks >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    pc.kernel = ConvKernel::Lds; pc.blocks = (unsigned)blocks; pc.rows = rows; pc.nj = nj;
+    pc.s2 = a.s[1].in && a.s[1].ks == 3;
     return IDH_OK;
 }
 
-// Launch ops[i..j) — all convs of one dependency level that map to the 4-row LDS kernel — as one grid.
-int launch_group(const PreparedConv *pcs, int n, hipStream_t st) {
-    LdsGroupArgs g{};
-    unsigned cursor = 0;
-    g.n = n;
-    for (int i = 0; i < n; ++i) {
-        g.start[i] = cursor;
-        g.op[i] = pcs[i].la;
-        cursor += pcs[i].blocks;
-    }
-    g.start[n] = cursor;
-    bool any_up = false;
-    for (int i = 0; i < n; ++i) any_up = any_up || pcs[i].up;
-    if (any_up) IDH_LAUNCH((conv3x3_lds_group_k<1, true>), dim3(cursor), dim3(256), 0, st, g);
-    else if (pcs[0].nj == 2) IDH_LAUNCH((conv3x3_lds_group_k<1, false, 2>), dim3(cursor), dim3(256), 0, st, g);
-    else if (pcs[0].nj == 1) IDH_LAUNCH((conv3x3_lds_group_k<1, false, 1>), dim3(cursor), dim3(256), 0, st, g);
-    else IDH_LAUNCH((conv3x3_lds_group_k<1, false>), dim3(cursor), dim3(256), 0, st, g);
-    IDH_CHECK_LAUNCH();
-    return launch_reduces(pcs, n, st);
-}
-
-// Launch a heterogeneous level (see level_k): kinds[i] = LV_*, pcs[i] prepared (LV_UP2: only la.c's upsample fields).
-int launch_level(const PreparedConv *pcs, const int *kinds, int n, hipStream_t st) {
-    LevelArgs g{};
-    unsigned cursor = 0;
-    g.n = n;
-    for (int i = 0; i < n; ++i) {
-        g.start[i] = cursor;
-        g.kind[i] = kinds[i];
-        g.op[i] = pcs[i].la;
-        if (kinds[i] == LV_MFMA14) g.op[i].c = pcs[i].a;  // prep_conv fills la for the LDS kernels only
-        cursor += pcs[i].blocks;
-    }
-    g.start[n] = cursor;
-    bool wide = false;
-    for (int i = 0; i < n; ++i) wide = wide || kinds[i] == LV_LDS4;
-    if (wide) IDH_LAUNCH(level_k<true>, dim3(cursor), dim3(256), 0, st, g);
-    else IDH_LAUNCH(level_k<false>, dim3(cursor), dim3(256), 0, st, g);
-    IDH_CHECK_LAUNCH();
-    return launch_reduces(pcs, n, st);
+// direct kernel: tile_m x tile_n sub-tiles per wave, 0 = auto (a tile_m 8 / 9 request the LDS kernel does not cover lands here as auto)
+int choose_direct(const idh_op &op, PreparedConv &pc) {
+    ConvArgs &a = pc.a;
+    int tm = op.tile_m, tn = op.tile_n;
+    if (tm == 8 || tm == 9) tm = 0;
+    const int nsub = a.Cout_pad / 16;
+    if (tn == 0) tn = (nsub % 4 == 0) ? 4 : (nsub % 2 == 0 ? 2 : 1);
+    if (tm == 0) tm = 4;
+    if ((tm != 1 && tm != 2 && tm != 4) || (tn != 1 && tn != 2 && tn != 4) || nsub % tn) return IDH_EINVAL;
+    a.MT = (int)(((long long)a.M + 16 * tm - 1) / (16 * tm));
+    a.NT = nsub / tn;
+    const long long waves = (long long)a.MT * a.NT * a.S;
+    if ((waves + 3) / 4 >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    pc.kernel = ConvKernel::Direct; pc.blocks = (unsigned)((waves + 3) / 4); pc.tm = tm; pc.tn = tn;
+    pc.la.c = a;
+    return IDH_OK;
 }
 
 // Level-launch member kind of a prepared conv, or -1
 int level_kind(const PreparedConv &pc) {
     if (pc.up || pc.norm || pc.s2) return -1;
-    if (pc.lds_rows == 4 && pc.nj == 4) return LV_LDS4;
-    if (pc.lds_rows == 4 && pc.nj == 2) return LV_LDS2;
-    if (pc.lds_rows == 0 && pc.tm == 1 && pc.tn == 4) return LV_MFMA14;
+    if (pc.kernel == ConvKernel::Lds && pc.rows == 4 && pc.nj >= 2) return pc.nj == 4 ? LV_LDS4 : LV_LDS2;
+    if (pc.kernel == ConvKernel::Direct && pc.tm == 1 && pc.tn == 4) return LV_MFMA14;
     return -1;
 }
 
-int check_upsample(const idh_op &op) {
-    const idh_conv_src &s = op.src[0];
-    if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0) return IDH_EINVAL;
-    if ((long long)op.N * s.H * s.W * (s.Cin >> 2) >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (upsample2_body: 32-bit quad index)
+// The order of the steps decides which code a descriptor with two faults gets.
+int prep_conv(const idh_op &op, PreparedConv &pc) {
+    pc = PreparedConv{};
+    ConvArgs &a = pc.a;
+    int steps = 0;
+    for (int i = 0; i < 2; ++i) {
+        const int k = fill_source(op, i, a.s[i]);
+        if (k < 0) return k;
+        steps += k;
+    }
+    if (const int rc = check_epilogue(op)) return rc;
+    pc.up = a.s[0].up_in[0] || a.s[1].up_in[0]; pc.norm = op.src[0].norm != nullptr; pc.n_img = op.N;
+    a.bias = op.bias; a.res = op.res; a.out = op.out; a.ws = op.ws;
+    a.res_cs = op.res_cs; a.out_cs = op.out_cs; a.Ho = op.Ho; a.Wo = op.Wo; a.Cout = op.Cout;
+    a.Cout_pad = ceil16(op.Cout);
+    a.M = op.N * op.Ho * op.Wo; a.steps_total = steps; a.act = op.act; a.slope = op.slope;
+    a.S = std::min(op.split_k > 1 ? op.split_k : 1, steps);
+    lone_stride2_as_second_source(op, a);
+    // LDS kernels (tile_m 8 / 9 / 0): tile_n = output sub-tiles of 16 channels per workgroup (0 = 4 -> 64 channels; 2; 1)
+    const bool lds_asked = op.tile_m == 8 || op.tile_m == 9 || op.tile_m == 0;
+    const int nj = lds_asked && op.tile_n != 0 ? op.tile_n : 4;
+    int rc;
+    if (op.tile_m == IDH_TILE_WINO) rc = choose_wino2(pc);
+    else if (op.tile_m == IDH_TILE_WINO4) rc = choose_wino4(pc);
+    else if (op.tile_m == IDH_SPLIT_F16X3) rc = choose_split(op, pc);
+    else if (lds_asked && lds_ok(op, a, nj) && lds_fits(op, a)) rc = choose_lds(op, pc, nj);
+    else rc = choose_direct(op, pc);
+    if (rc != IDH_OK) return rc;
+    const bool lds = pc.kernel == ConvKernel::Lds;
+    if (pc.up && !(lds && pc.nj == 4)) return IDH_EUNSUPPORTED;    // fused upsampling lives in the 64-channel LDS loader
+    if (pc.norm && !(lds && pc.nj == 1)) return IDH_EUNSUPPORTED;  // normalise-on-load: 16-channel LDS tiles
+    if (a.S > 1) {
+        if (!op.ws) return IDH_EWORKSPACE;
+        pc.red = ReduceDesc{op.ws, op.bias, op.res, op.out, a.M, op.Cout, a.Cout_pad, a.S, op.res_cs, op.out_cs, op.act, op.slope};
+    }
+    pc.level = level_kind(pc);
     return IDH_OK;
 }
 
+// ---- host side: kernel tables -------------------------------------------------------------------------------------------
+// Every instantiation idh_run_ops can launch is an entry of one of these; nullptr = a combination prep_conv never produces.
+constexpr int tile_slot(int t) { return t == 4 ? 0 : t == 2 ? 1 : t == 1 ? 2 : -1; }  // 4 | 2 | 1 -> table index
+using DirectKernel = void (*)(const ConvArgs);
+const DirectKernel kDirectKernels[3][3] = {  // [tm 4 | 2 | 1][tn 4 | 2 | 1]
+    {conv_mfma_k<4, 4>, conv_mfma_k<4, 2>, conv_mfma_k<4, 1>},
+    {conv_mfma_k<2, 4>, conv_mfma_k<2, 2>, conv_mfma_k<2, 1>},
+    {conv_mfma_k<1, 4>, conv_mfma_k<1, 2>, conv_mfma_k<1, 1>}};
+enum { FL_PLAIN, FL_UP, FL_NORM, FL_S2 };
+using LdsKernel = void (*)(const LdsConvArgs);
+template <int RW>  // RW = tile rows / 4
+constexpr LdsKernel kLdsRow[3][4] = {  // [nj 4 | 2 | 1][flavour]
+    {conv3x3_lds_k<RW, false, 4>, conv3x3_lds_up_k<RW>, nullptr, conv3x3_lds_k<RW, false, 4, false, true>},
+    {conv3x3_lds_k<RW, false, 2>, nullptr, nullptr, conv3x3_lds_k<RW, false, 2, false, true>},
+    {conv3x3_lds_k<RW, false, 1>, nullptr, conv3x3_lds_k<RW, false, 1, true>, nullptr}};
+using GroupKernel = void (*)(const LdsGroupArgs);
+const GroupKernel kGroupKernels[3][2] = {  // [nj 4 | 2 | 1][some member has fused-upsample segments]
+    {conv3x3_lds_group_k<1, false, 4>, conv3x3_lds_group_k<1, true, 4>}, {conv3x3_lds_group_k<1, false, 2>, nullptr}, {conv3x3_lds_group_k<1, false, 1>, nullptr}};
+using LevelKernel = void (*)(const LevelArgs);
+const LevelKernel kLevelKernels[2] = {level_k<false>, level_k<true>};  // [some member is LV_LDS4]
+
+LdsKernel lds_kernel(const PreparedConv &pc) {
+    const int j = tile_slot(pc.nj), fl = pc.up ? FL_UP : pc.norm ? FL_NORM : pc.s2 ? FL_S2 : FL_PLAIN;
+    if ((pc.rows != 8 && pc.rows != 4) || j < 0 || pc.up + pc.norm + pc.s2 > 1) return nullptr;
+    return pc.rows == 8 ? kLdsRow<2>[j][fl] : kLdsRow<1>[j][fl];
+}
+
+int launch_conv(const PreparedConv &pc, RunCtx &ctx) {
+    const int m = tile_slot(pc.tm), n = tile_slot(pc.tn);
+    switch (pc.kernel) {
+        case ConvKernel::Split: return launch_ext(ctx, [&] { return launch_conv_split(pc.a, pc.n_img, pc.split_mode, pc.rows, ctx.st); });
+        case ConvKernel::Wino2: return launch_ext(ctx, [&] { return launch_conv_wino(pc.a, pc.n_img, 0, ctx.st); });  // (tile rows: fixed in the launcher)
+        case ConvKernel::Wino4: return launch_ext(ctx, [&] { return launch_conv_wino4(pc.a, pc.n_img, ctx.st); });
+        case ConvKernel::Lds: if (const LdsKernel k = lds_kernel(pc)) return launch(ctx, k, dim3(pc.blocks), dim3(256), 0, pc.la); break;
+        case ConvKernel::Direct: if (m >= 0 && n >= 0) return launch(ctx, kDirectKernels[m][n], dim3(pc.blocks), dim3(256), 0, pc.a); break;
+    }
+    return IDH_EUNSUPPORTED;  // (no such kernel: impossible after prep_conv)
+}
+
+// The split members' partials, summed by one grid
+int launch_reduces(const PreparedConv *pcs, int n, RunCtx &ctx) {
+    ReduceGroupArgs g{};
+    unsigned cursor = 0;
+    for (int i = 0; i < n; ++i) {
+        if (pcs[i].a.S <= 1) continue;
+        g.start[g.n] = cursor;
+        g.d[g.n++] = pcs[i].red;
+        cursor += (unsigned)idh_cdiv((long long)pcs[i].red.M * pcs[i].red.Cout, 256);
+    }
+    g.start[g.n] = cursor;
+    return g.n == 0 ? IDH_OK : launch(ctx, splitk_reduce_group_k, dim3(cursor), dim3(256), 0, g);
+}
+
+// One grid for n members laid end to end (start[i] = member i's first workgroup, start[n] = the grid size), then their reduces.  G = LdsGroupArgs | LevelArgs
+template <typename G, typename K>
+int launch_members(G &g, K kernel, const PreparedConv *pcs, int n, RunCtx &ctx) {
+    unsigned cursor = 0;
+    for (int i = 0; i < n; ++i) { g.start[i] = cursor; g.op[i] = pcs[i].la; cursor += pcs[i].blocks; }
+    g.start[g.n = n] = cursor;
+    if (!kernel) return IDH_EUNSUPPORTED;  // (a table hole: impossible after the prefix scans)
+    if (const int rc = launch(ctx, kernel, dim3(cursor), dim3(256), 0, g)) return rc;
+    return launch_reduces(pcs, n, ctx);
+}
+
+// pcs[0..n): convs of one dependency level that map to the 4-row LDS kernel with one channel tile, as one grid
+int launch_group(const PreparedConv *pcs, int n, RunCtx &ctx) {
+    LdsGroupArgs g{};
+    bool any_up = false;
+    for (int i = 0; i < n; ++i) any_up = any_up || pcs[i].up;
+    return launch_members(g, tile_slot(pcs[0].nj) >= 0 ? kGroupKernels[tile_slot(pcs[0].nj)][any_up] : nullptr, pcs, n, ctx);
+}
+
+// pcs[0..n): a heterogeneous level (see level_k), member i of kind pcs[i].level (LV_UP2: only la.c's upsample fields are read)
+int launch_level(const PreparedConv *pcs, int n, RunCtx &ctx) {
+    LevelArgs g{};
+    bool wide = false;
+    for (int i = 0; i < n; ++i) { g.kind[i] = pcs[i].level; wide = wide || pcs[i].level == LV_LDS4; }
+    return launch_members(g, kLevelKernels[wide], pcs, n, ctx);
+}
+
+// pcs[0..n): Winograd F(2x2) convs with the same kind of second source, as one persistent grid
+int launch_wino_group(const PreparedConv *pcs, int n, RunCtx &ctx) {
+    const ConvArgs *as[kMaxGroup];
+    int ns[kMaxGroup];
+    for (int j = 0; j < n; ++j) { as[j] = &pcs[j].a; ns[j] = pcs[j].n_img; }
+    int rc = launch_ext(ctx, [&] { return launch_conv_wino_group(as, ns, n, ctx.st); });
+    if (rc == IDH_EUNSUPPORTED) {  // (a device whose resident grid is not whole XCD octets): one launch per op
+        rc = IDH_OK;
+        for (int j = 0; j < n && rc == IDH_OK; ++j) rc = launch_conv(pcs[j], ctx);
+    }
+    return rc;
+}
+
+// ---- host side: one function per op kind ----------------------------------------------------------------------------------
+// run_<kind>(ops, i, n, ctx) validates ops[i] (and what it can share a grid with), launches, and returns the number of ops consumed or a
+// negative IDH_E* code.  Grid caps, in workgroups of 256 threads (tests/op_kind_ref.py mirrors them):
+constexpr int kNearestMaxBlocks = 8192;
+constexpr int kCopyMaxBlocks = 8192;
+constexpr int kHeadMaxBlocks = 8192;
+constexpr int kUpsampleMaxBlocks = 32768;
+constexpr int kPwNchwMaxBlocks = 256 * 4 * 4;
+constexpr int kPwUpMaxBlocks = 256 * 8;
+constexpr int kInstnormApplyMaxBlocks = 16384;
 // Members of a level launch are small by construction (one frame / low-resolution maps): a member that fills the chip
 // for several rounds on its own gains nothing from sharing a grid and keeps its specialised kernel.
 constexpr unsigned kLevelMaxBlocks = 512;
 constexpr unsigned kLevelUpsampleBlocks = 512;
 constexpr long long kLevelUpsampleNatural = 4096;  // one frame's largest upsample (64 ch, 96x128 -> 192x256) is 3072
+constexpr long long kImportGroupMaxBlocks = 8 * kLevelMaxBlocks;  // a larger import keeps its own 3-D grid
+
+// The shape predicates the kinds share.  Where two kinds differ in what they check, the reason stands at the one that checks less.
+bool map_bad(const idh_op &op) { return !op.src[0].in || op.N <= 0 || op.src[0].H <= 0 || op.src[0].W <= 0; }  // no N x H x W map behind src[0].in
+bool quads_bad(const idh_conv_src &s, int out_cs) { return s.Cin <= 0 || (s.Cin & 3) || (s.cs & 3) || (out_cs & 3); }  // float4 access on either side
+bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }  // (NULL passes: optional pointers)
+
+// A lone IDH_OP_UPSAMPLE2 (validated by prep_upsample)
+int run_upsample2(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    const long long quads = (long long)op.N * s.H * s.W * (s.Cin >> 2);  // one thread per 2x2 output quad x 4 channels
+    const int grid = std::min(idh_cdiv(quads, 256), kUpsampleMaxBlocks);
+    return consumed(launch(ctx, upsample2_k, dim3(grid), dim3(256), 0, s.in, op.out, op.N, s.H, s.W, s.Cin, s.cs, op.out_cs), 1);
+}
+
+// An IDH_OP_UPSAMPLE2 as a member of a run: la.c carries what upsample2_body reads
+int prep_upsample(const idh_op &op, PreparedConv &pc) {
+    const idh_conv_src &s = op.src[0];
+    // no cs >= Cin / out_cs >= Cin, unlike NEAREST and COPY: the rule came with those kinds and was never added here (an oversight, kept)
+    if (map_bad(op) || !op.out || quads_bad(s, op.out_cs)) return IDH_EINVAL;
+    if ((long long)op.N * s.H * s.W * (s.Cin >> 2) >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (upsample2_body: 32-bit quad index)
+    pc = PreparedConv{};
+    ConvArgs &c = pc.la.c;
+    c.s[0].in = s.in; c.s[0].H = s.H; c.s[0].W = s.W; c.s[0].Cin = s.Cin; c.s[0].cs = s.cs;
+    c.out = op.out; c.out_cs = op.out_cs; c.M = op.N; c.S = 1;
+    pc.a = c;
+    const long long tot = (long long)op.N * 4 * s.H * s.W * (s.Cin >> 2);
+    const long long natural = idh_cdiv(tot, 256);  // (output float4s: the measure the thresholds were tuned in)
+    pc.blocks = (unsigned)std::min<long long>(idh_cdiv(tot / 4, 256), kLevelUpsampleBlocks);  // one thread per 2x2 quad
+    // a large upsample (batch >= 2 at the top resolutions) runs at HBM speed on its own grid of thousands
+    // of blocks; squeezed into 512 grid-stride blocks it is slower than the launch it saves
+    pc.level = natural <= kLevelUpsampleNatural ? LV_UP2 : -1;
+    return IDH_OK;
+}
+
+// The run of consecutive CONV / UPSAMPLE2 ops from ops[i] on that share its (non-zero) group id, prepared into pcs[kMaxGroup]: the host scheduler
+// guarantees they are mutually independent (one dependency level).  Returns the run's length (>= 1) or the error of the first bad member.
+int gather_run(const idh_op *ops, int i, int n, PreparedConv *pcs) {
+    int run = 0;
+    for (int j = i; j < n && run < kMaxGroup; ++j, ++run) {
+        const idh_op &o = ops[j];
+        if ((j > i && (ops[i].group == 0 || o.group != ops[i].group)) || (o.kind != IDH_OP_CONV && o.kind != IDH_OP_UPSAMPLE2)) break;
+        const int rc = o.kind == IDH_OP_CONV ? prep_conv(o, pcs[run]) : prep_upsample(o, pcs[run]);
+        if (rc != IDH_OK) return rc;
+    }
+    return run;
+}
+
+// The three prefixes of a run that can share a grid (an upsample member is no Lds / Wino2 conv: it ends the first and the third):
+// 4-row LDS convs with one channel tile (conv3x3_lds_group_k), small members level_k can host, F(2x2) convs with the same kind of second source
+template <typename Pred>
+int prefix(const PreparedConv *p, int run, Pred ok) {
+    int c = 0;
+    while (c < run && ok(p[c])) ++c;
+    return c;
+}
+int lds_group_prefix(const PreparedConv *p, int run) {
+    return prefix(p, run, [&](const PreparedConv &m) { return m.kernel == ConvKernel::Lds && m.rows == 4 && m.nj == p[0].nj && !m.norm && !m.s2; });
+}
+int level_prefix(const PreparedConv *p, int run) {
+    return prefix(p, run, [](const PreparedConv &m) { return m.level >= 0 && m.blocks <= kLevelMaxBlocks; });
+}
+int wino_group_prefix(const PreparedConv *p, int run) {
+    return prefix(p, std::min(run, wino_max_group()), [&](const PreparedConv &m) { return m.kernel == ConvKernel::Wino2 && !m.a.s[1].in == !p[0].a.s[1].in; });
+}
+
+// Launch the longest shareable prefix of the run at ops[i] (or its first op alone); returns the ops consumed
+int launch_run(const idh_op *ops, int i, int n, const PreparedConv *pcs, int run, RunCtx &ctx) {
+    const int wg = wino_group_prefix(pcs, run), mix = level_prefix(pcs, run), cnt = lds_group_prefix(pcs, run);
+    if (wg > 1) return consumed(launch_wino_group(pcs, wg, ctx), wg);
+    if (mix > cnt && mix > 1) return consumed(launch_level(pcs, mix, ctx), mix);
+    if (cnt > 1) return consumed(launch_group(pcs, cnt, ctx), cnt);
+    if (ops[i].kind == IDH_OP_UPSAMPLE2) return run_upsample2(ops, i, n, ctx);
+    const int rc = launch_conv(pcs[0], ctx);
+    return consumed(rc != IDH_OK ? rc : launch_reduces(pcs, 1, ctx), 1);
+}
+
+// IDH_OP_CONV, and an IDH_OP_UPSAMPLE2 (either may start a run)
+int run_conv(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    PreparedConv pcs[kMaxGroup];
+    const int run = gather_run(ops, i, n, pcs);
+    return run < 0 ? run : launch_run(ops, i, n, pcs, run, ctx);
+}
+
+int run_upsample2_nearest(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    if (map_bad(op) || !op.out || quads_bad(s, op.out_cs) || s.cs < s.Cin || op.out_cs < s.Cin) return IDH_EINVAL;
+    const long long tot = (long long)op.N * 4 * s.H * s.W * (s.Cin >> 2);
+    const int grid = std::min(idh_cdiv(tot, 256), kNearestMaxBlocks);
+    return consumed(launch(ctx, upsample2_nearest_k, dim3(grid), dim3(256), 0, s.in, op.out, op.N, s.H, s.W, s.Cin, s.cs, op.out_cs), 1);
+}
+
+int run_copy(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    if (map_bad(op) || !op.out || quads_bad(s, op.out_cs) || s.cs < s.Cin || op.out_cs < s.Cin) return IDH_EINVAL;
+    const long long npix = (long long)op.N * s.H * s.W;
+    const int grid = std::min(idh_cdiv(npix * (s.Cin >> 2), 256), kCopyMaxBlocks);
+    return consumed(launch(ctx, copy_nhwc_k, dim3(grid), dim3(256), 0, s.in, op.out, npix, s.Cin, s.cs, op.out_cs), 1);
+}
+
+// Consecutive imports that share a (non-zero) group id are mutually independent (one dependency level): one grid
+int run_nchw_to_nhwc(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i];
+    ImportGroupArgs g{};
+    unsigned cursor = 0;
+    for (int j = i; j < n && g.n < kMaxImport; ++j) {
+        const idh_op &o = ops[j]; const idh_conv_src &s = o.src[0];
+        if (o.kind != IDH_OP_NCHW_TO_NHWC || (j > i && (op.group == 0 || o.group != op.group))) break;
+        // scalar loads and stores of a dense NCHW source, any channel count: no quad or stride rule; N rides in gridDim.z of the lone launch
+        if (map_bad(o) || s.Cin <= 0 || !o.out || o.N > 65535) return IDH_EINVAL;
+        const int HW = s.H * s.W, nbx = idh_cdiv(HW, 64), nby = idh_cdiv(s.Cin, 32);
+        const long long blocks = (long long)nbx * nby * o.N;
+        if (blocks > kImportGroupMaxBlocks || cursor + blocks >= (1ll << 31)) break;
+        auto &d = g.d[g.n];  // (field by field: the padding of g{} stays zero)
+        d.src = s.in; d.dst = o.out; d.C = s.Cin; d.HW = HW; d.out_cs = o.out_cs; d.nbx = nbx; d.nby = nby;
+        g.start[g.n++] = cursor;
+        cursor += (unsigned)blocks;
+    }
+    g.start[g.n] = cursor;
+    if (g.n > 1) return consumed(launch(ctx, import_nchw_group_k, dim3(cursor), dim3(256), 0, g), g.n);
+    const idh_conv_src &s = op.src[0];  // (validated as the loop's first member)
+    const int HW = s.H * s.W;
+    return consumed(launch(ctx, import_nchw_k, dim3(idh_cdiv(HW, 64), idh_cdiv(s.Cin, 32), op.N), dim3(256), 0, s.in, op.out, s.Cin, HW, op.out_cs), 1);
+}
+
+int run_nhwc_to_nchw(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    // scalar loads, any channel count: no quad rule, but the slice must lie inside its pixel (cs >= Cin); the output is dense
+    if (map_bad(op) || s.Cin <= 0 || !op.out || op.N > 65535 || s.cs < s.Cin) return IDH_EINVAL;
+    const int HW = s.H * s.W;
+    return consumed(launch(ctx, export_nchw_k, dim3(idh_cdiv(HW, 64), idh_cdiv(s.Cin, 32), op.N), dim3(256), 0, s.in, op.out, s.Cin, HW, s.cs), 1);
+}
+
+int run_pointwise_head(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    if (map_bad(op) || !s.w || !op.out || quads_bad(s, 0) || s.cs < s.Cin) return IDH_EINVAL;  // (the output is one dense channel: out_cs plays no part)
+    const long long M = (long long)op.N * s.H * s.W;
+    const int grid = std::min(idh_cdiv(M, 256), kHeadMaxBlocks);
+    return consumed(launch(ctx, pointwise_head_k, dim3(grid), dim3(256), 0, s.in, s.w, op.bias, op.out, op.ws, M, s.Cin, s.cs), 1);
+}
+
+// src[0].in = (N, 64, H, W) dense NCHW, src[0].w = idh_pack_conv_weight(128, 64, 1), out = NHWC slice
+int run_pointwise_nchw(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    // the channel counts are fixed, so a wrong one (zero included) is IDH_EUNSUPPORTED, not a bad map; the input is dense (no cs)
+    if (map_bad(op) || !s.w || !op.out || (op.out_cs & 3) || misaligned(op.out) || misaligned(op.bias)) return IDH_EINVAL;
+    if (s.Cin != kPwCin || op.Cout != kPwCout || op.out_cs < kPwCout || (long long)s.H * s.W * kPwCin * 4 >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    PwNchwArgs pa{};
+    pa.in = s.in; pa.w = s.w; pa.bias = op.bias; pa.out = op.out; pa.HW = s.H * s.W; pa.out_cs = op.out_cs;
+    pa.tiles_per_img = idh_cdiv(pa.HW, kPwTile); pa.tiles = (long long)op.N * pa.tiles_per_img;
+    const int grid = (int)std::min<long long>(pa.tiles, kPwNchwMaxBlocks);
+    return consumed(launch(ctx, pointwise_nchw_k, dim3(grid), dim3(256), 0, pa), 1);
+}
+
+// src[0] = x (N, H, W, Cin) + idh_pack_conv_weight(Cout, Cin, 1); src[1].in = the half-resolution map (N, H/2, W/2, Cout), src[1].cs its stride
+int run_pointwise_up(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0], &lo = op.src[1];
+    // three strided tensors read and written by whole 16-byte lines: every one aligned, every stride checked against its own channel count
+    if (map_bad(op) || !s.w || !lo.in || !op.out || (s.H & 1) || (s.W & 1) || (s.cs & 3) || (lo.cs & 3) || (op.out_cs & 3) || s.cs < s.Cin ||
+        lo.cs < op.Cout || op.out_cs < op.Cout || misaligned(s.in) || misaligned(lo.in) || misaligned(op.out) || misaligned(s.w) ||
+        misaligned(op.bias) || lo.H != s.H / 2 || lo.W != s.W / 2)
+        return IDH_EINVAL;
+    if (s.Cin != op.Cout || (s.Cin != 64 && s.Cin != 128) || (long long)s.H * s.W >= (1ll << 31)) return IDH_EUNSUPPORTED;
+    const int tiles_per_img = idh_cdiv(s.H * s.W, kPwTile);
+    const PwUpArgs pa{s.in, s.w, op.bias, lo.in, op.out, s.H, s.W, s.cs, lo.cs, op.out_cs, tiles_per_img, (long long)op.N * tiles_per_img};
+    const int grid = (int)std::min<long long>(pa.tiles, kPwUpMaxBlocks);
+    const bool c64 = s.Cin == 64;
+    return consumed(launch(ctx, c64 ? pointwise_up_k<4, 4> : pointwise_up_k<8, 8>, dim3(grid), dim3(256), (c64 ? 16 * 64 : 32 * 128) * sizeof(f32x4), pa), 1);
+}
+
+int run_stem(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    return ++ctx.launches, consumed(idh_stem_op(ops[i], ctx.st, !ctx.dry), 1);  // (csrc/stem.hip validates either way)
+}
+
+int run_instnorm(const idh_op *ops, int i, int n, RunCtx &ctx) {
+    const idh_op &op = ops[i]; const idh_conv_src &s = op.src[0];
+    const int C = s.Cin, HW = s.H * s.W;
+    // out == NULL is "statistics only", so out_cs counts only with an output; N rides in gridDim.y; a block sums whole pixels: 256 % (C / 4) == 0.
+    // No cs >= C / out_cs >= C, unlike COPY (an oversight, kept).  (H W = 0 would be a zero-sized statistics grid)
+    if (map_bad(op) || !op.ws || quads_bad(s, op.out ? op.out_cs : 0) || 256 % (C >> 2) || op.N > 65535) return IDH_EINVAL;
+    const int nchunks = idh_cdiv(HW, kInChunk);
+    // C >= 64: the chunk is summed as 1024 / (C/4) rows at either block size (bit-identical statistics at every batch size)
+    const int sthreads = ((long long)nchunks * op.N < 512 && C >= 64) ? 1024 : 256;
+    const bool sub4 = C >= 64 && sthreads == 256;
+    if (const int rc = launch(ctx, sub4 ? instnorm_stats_k<4> : instnorm_stats_k<1>, dim3(nchunks, op.N), dim3(sthreads),
+                              (sub4 ? 1024 : sthreads) * 8 * sizeof(float), s.in, s.cs, C, HW, nchunks, op.ws))
+        return rc;
+    float *stats = op.ws + (size_t)op.N * nchunks * 2 * C;
+    if (const int rc = launch(ctx, instnorm_finalize_k, dim3(op.N), dim3(256), 0, op.ws, s.in, s.cs, C, HW, nchunks, stats)) return rc;
+    if (!op.out) return 1;  // statistics only: the consumer conv normalises on load (idh_conv_src.norm)
+    const long long total = (long long)op.N * HW * (C >> 2);
+    const int gx = std::min(idh_cdiv(total, 256 * 4), kInstnormApplyMaxBlocks);  // ~4 float4 per thread
+    return consumed(launch(ctx, instnorm_apply_k, dim3(gx), dim3(256), 0, s.in, s.cs, op.out, op.out_cs, C, HW, total, stats, op.act, op.slope), 1);
+}
+
+// By IDH_OP_* code.  CONV and UPSAMPLE2 may both start a run; 0 is no kind and 5 (IDH_OP_SPLITK_REDUCE) is reserved: IDH_EINVAL, like any other number
+using RunKind = int (*)(const idh_op *, int, int, RunCtx &);
+const RunKind kRunKind[] = {nullptr, run_conv, run_conv, run_nchw_to_nhwc, run_nhwc_to_nchw, nullptr, run_pointwise_head, run_instnorm, run_upsample2_nearest,
+                            run_copy, run_pointwise_nchw, run_pointwise_up, run_stem};
+static_assert(IDH_OP_CONV == 1 && IDH_OP_UPSAMPLE2 == 2 && IDH_OP_NCHW_TO_NHWC == 3 && IDH_OP_NHWC_TO_NCHW == 4 && IDH_OP_POINTWISE_HEAD == 6 && IDH_OP_INSTNORM == 7 &&
+              IDH_OP_UPSAMPLE2_NEAREST == 8 && IDH_OP_COPY == 9 && IDH_OP_POINTWISE_NCHW == 10 && IDH_OP_POINTWISE_UP == 11 && IDH_OP_STEM == 12, "kRunKind's order");
+
+int run_ops(const idh_op *ops, int n, RunCtx &ctx) {
+    if (n < 0 || (n > 0 && !ops)) return IDH_EINVAL;
+    for (int i = 0, used; i < n; i += used) {
+        const int kind = ops[i].kind;
+        if (kind < 0 || kind >= (int)(sizeof(kRunKind) / sizeof(*kRunKind)) || !kRunKind[kind]) return IDH_EINVAL;
+        if ((used = kRunKind[kind](ops, i, n, ctx)) < 0) return used;
+    }
+    return IDH_OK;
+}
 
 }  // namespace
 
@@ -1630,274 +1871,29 @@ extern "C" int idh_pack_conv_weight(const float *w, float *dst, int Cout, int Ci
 }
 
 extern "C" int idh_run_ops(const idh_op *ops, int n, void *stream) {
-    if (n < 0 || (n > 0 && !ops)) return IDH_EINVAL;
-    hipStream_t st = idh_stream(stream);
-    for (int i = 0; i < n; ++i) {
-        const idh_op &op = ops[i];
-        const idh_conv_src &s = op.src[0];
-        switch (op.kind) {
-            case IDH_OP_CONV:
-            case IDH_OP_UPSAMPLE2: {
-                // gather the run of consecutive ops that share a (non-zero) group id: the host scheduler guarantees they
-                // are mutually independent (same dependency level).  [i, i+cnt) = the homogeneous prefix of 4-row LDS convs
-                // (one conv3x3_lds_group_k grid); [i, i+run) = the mixed run level_k can host when every member is small.
-                PreparedConv pcs[kMaxGroup];
-                int kinds[kMaxGroup];
-                int run = 0;
-                for (int j = i; j < n && run < kMaxGroup; ++j) {
-                    const idh_op &o = ops[j];
-                    if (j > i && (op.group == 0 || o.group != op.group)) break;
-                    PreparedConv &pc = pcs[run];
-                    if (o.kind == IDH_OP_CONV) {
-                        const int rc = prep_conv(o, pc);
-                        if (rc != IDH_OK) return rc;
-                        kinds[run] = level_kind(pc);
-                    } else if (o.kind == IDH_OP_UPSAMPLE2) {
-                        const int rc = check_upsample(o);
-                        if (rc != IDH_OK) return rc;
-                        const idh_conv_src &us = o.src[0];
-                        pc = PreparedConv{};
-                        ConvArgs &c = pc.la.c;
-                        c.s[0].in = us.in; c.s[0].H = us.H; c.s[0].W = us.W; c.s[0].Cin = us.Cin; c.s[0].cs = us.cs;
-                        c.out = o.out; c.out_cs = o.out_cs; c.M = o.N; c.S = 1;
-                        pc.a = c;
-                        const long long tot = (long long)o.N * 4 * us.H * us.W * (us.Cin >> 2);
-                        const long long natural = idh_cdiv(tot, 256);  // (output float4s: the measure the thresholds were tuned in)
-                        pc.blocks = (unsigned)std::min<long long>(idh_cdiv(tot / 4, 256), kLevelUpsampleBlocks);  // one thread per 2x2 quad
-                        // a large upsample (batch >= 2 at the top resolutions) runs at HBM speed on its own grid of thousands
-                        // of blocks; squeezed into 512 grid-stride blocks it is slower than the launch it saves
-                        kinds[run] = natural <= kLevelUpsampleNatural ? LV_UP2 : -1;
-                    } else {
-                        break;
-                    }
-                    ++run;
-                }
-                int cnt = 0;  // homogeneous prefix
-                if (op.kind == IDH_OP_CONV && pcs[0].lds_rows == 4 && !pcs[0].norm && !pcs[0].s2) {
-                    cnt = 1;
-                    while (cnt < run && ops[i + cnt].kind == IDH_OP_CONV && pcs[cnt].lds_rows == 4 && pcs[cnt].nj == pcs[0].nj &&
-                           (!pcs[cnt].up || pcs[0].nj == 4) && !pcs[cnt].norm && !pcs[cnt].s2)
-                        ++cnt;
-                }
-                int mix = 0;  // mixed prefix of small members
-                while (mix < run && kinds[mix] >= 0 && pcs[mix].blocks <= kLevelMaxBlocks) ++mix;
-                int wg = 0;  // prefix of Winograd convs with the same kind of second source: one persistent grid
-                if (op.kind == IDH_OP_CONV && pcs[0].lds_rows == 32) {
-                    wg = 1;
-                    while (wg < run && wg < wino_max_group() && ops[i + wg].kind == IDH_OP_CONV && pcs[wg].lds_rows == 32 &&
-                           (pcs[wg].a.s[1].in != nullptr) == (pcs[0].a.s[1].in != nullptr))
-                        ++wg;
-                }
-                int rc, used;
-                if (wg > 1) {
-                    if (t_dry_run) {
-                        ++t_launches;
-                        rc = IDH_OK;
-                    } else {
-                        const ConvArgs *as[kMaxGroup];
-                        int ns[kMaxGroup];
-                        for (int j = 0; j < wg; ++j) { as[j] = &pcs[j].a; ns[j] = pcs[j].n_img; }
-                        rc = launch_conv_wino_group(as, ns, wg, st);
-                        if (rc == IDH_EUNSUPPORTED) {  // (a device whose resident grid is not whole XCD octets): one launch per op
-                            rc = IDH_OK;
-                            for (int j = 0; j < wg && rc == IDH_OK; ++j) rc = launch_conv(pcs[j], st);
-                        }
-                    }
-                    used = wg;
-                } else if (mix > cnt && mix > 1) {
-                    rc = launch_level(pcs, kinds, mix, st);
-                    used = mix;
-                } else if (cnt > 1) {
-                    rc = launch_group(pcs, cnt, st);
-                    used = cnt;
-                } else if (op.kind == IDH_OP_CONV) {
-                    rc = launch_conv(pcs[0], st);
-                    if (rc == IDH_OK) rc = launch_reduces(pcs, 1, st);
-                    used = 1;
-                } else {
-                    const long long quads = (long long)op.N * s.H * s.W * (s.Cin >> 2);  // one thread per 2x2 output quad x 4 channels
-                    int grid = idh_cdiv(quads, 256);
-                    if (grid > 32768) grid = 32768;
-                    IDH_LAUNCH(upsample2_k, dim3(grid), dim3(256), 0, st, s.in, op.out, op.N, s.H, s.W, s.Cin, s.cs, op.out_cs);
-                    IDH_CHECK_LAUNCH();
-                    rc = IDH_OK;
-                    used = 1;
-                }
-                if (rc != IDH_OK) return rc;
-                i += used - 1;
-                break;
-            }
-            case IDH_OP_UPSAMPLE2_NEAREST: {
-                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 ||
-                    s.cs < s.Cin || op.out_cs < s.Cin)
-                    return IDH_EINVAL;
-                const long long tot = (long long)op.N * 4 * s.H * s.W * (s.Cin >> 2);
-                int grid = idh_cdiv(tot, 256);
-                if (grid > 8192) grid = 8192;
-                IDH_LAUNCH(upsample2_nearest_k, dim3(grid), dim3(256), 0, st, s.in, op.out, op.N, s.H, s.W, s.Cin, s.cs, op.out_cs);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_NCHW_TO_NHWC: {
-                // consecutive imports that share a (non-zero) group id are mutually independent (one dependency level): one grid
-                ImportGroupArgs g{};
-                unsigned cursor = 0;
-                int run = 0;
-                for (int j = i; j < n && run < kMaxImport; ++j) {
-                    const idh_op &o = ops[j];
-                    if (o.kind != IDH_OP_NCHW_TO_NHWC || (j > i && (op.group == 0 || o.group != op.group))) break;
-                    const idh_conv_src &os = o.src[0];
-                    if (!os.in || !o.out || o.N <= 0 || o.N > 65535 || os.H <= 0 || os.W <= 0 || os.Cin <= 0) return IDH_EINVAL;
-                    const int HWj = os.H * os.W;
-                    const long long blocks = (long long)idh_cdiv(HWj, 64) * idh_cdiv(os.Cin, 32) * o.N;
-                    if (blocks > kLevelMaxBlocks * 8ll || cursor + blocks >= (1ll << 31)) break;  // a large import keeps its own 3-D grid
-                    g.d[run].src = os.in; g.d[run].dst = o.out; g.d[run].C = os.Cin; g.d[run].HW = HWj; g.d[run].out_cs = o.out_cs;
-                    g.d[run].nbx = idh_cdiv(HWj, 64); g.d[run].nby = idh_cdiv(os.Cin, 32);
-                    g.start[run] = cursor;
-                    cursor += (unsigned)blocks;
-                    ++run;
-                }
-                if (run > 1) {
-                    g.n = run;
-                    g.start[run] = cursor;
-                    IDH_LAUNCH(import_nchw_group_k, dim3(cursor), dim3(256), 0, st, g);
-                    IDH_CHECK_LAUNCH();
-                    i += run - 1;
-                    break;
-                }
-                if (!s.in || !op.out || op.N <= 0 || op.N > 65535) return IDH_EINVAL;
-                const int HW = s.H * s.W;
-                IDH_LAUNCH(import_nchw_k, dim3(idh_cdiv(HW, 64), idh_cdiv(s.Cin, 32), op.N), dim3(256), 0, st, s.in,
-                                   op.out, s.Cin, HW, op.out_cs);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_NHWC_TO_NCHW: {
-                if (!s.in || !op.out || op.N <= 0 || op.N > 65535 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 || s.cs < s.Cin) return IDH_EINVAL;
-                const int HW = s.H * s.W;
-                IDH_LAUNCH(export_nchw_k, dim3(idh_cdiv(HW, 64), idh_cdiv(s.Cin, 32), op.N), dim3(256), 0, st, s.in,
-                                   op.out, s.Cin, HW, s.cs);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_POINTWISE_HEAD: {
-                if (!s.in || !s.w || !op.out || (s.Cin & 3) || (s.cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 || s.cs < s.Cin)
-                    return IDH_EINVAL;
-                const long long M = (long long)op.N * s.H * s.W;
-                int grid = idh_cdiv(M, 256);
-                if (grid > 8192) grid = 8192;
-                IDH_LAUNCH(pointwise_head_k, dim3(grid), dim3(256), 0, st, s.in, s.w, op.bias, op.out, op.ws, M, s.Cin,
-                                   s.cs);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_POINTWISE_NCHW: {
-                // src[0].in = (N, 64, H, W) dense NCHW, src[0].w = idh_pack_conv_weight(128, 64, 1), out = NHWC slice
-                if (!s.in || !s.w || !op.out || op.N <= 0 || s.H <= 0 || s.W <= 0 || (op.out_cs & 3) || ((uintptr_t)op.out & 15) ||
-                    (op.bias && ((uintptr_t)op.bias & 15)))
-                    return IDH_EINVAL;
-                if (s.Cin != kPwCin || op.Cout != kPwCout || op.out_cs < kPwCout || (long long)s.H * s.W * kPwCin * 4 >= (1ll << 31))
-                    return IDH_EUNSUPPORTED;
-                PwNchwArgs pa{};
-                pa.in = s.in; pa.w = s.w; pa.bias = op.bias; pa.out = op.out;
-                pa.HW = s.H * s.W; pa.out_cs = op.out_cs;
-                pa.tiles_per_img = idh_cdiv(pa.HW, kPwTile);
-                pa.tiles = (long long)op.N * pa.tiles_per_img;
-                const int grid = (int)std::min<long long>(pa.tiles, 256 * 4 * 4);
-                IDH_LAUNCH(pointwise_nchw_k, dim3(grid), dim3(256), 0, st, pa);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_POINTWISE_UP: {
-                // src[0] = x (N, H, W, Cin) + idh_pack_conv_weight(Cout, Cin, 1); src[1].in = the half-resolution map (N, H/2, W/2, Cout), src[1].cs its stride
-                const idh_conv_src &lo = op.src[1];
-                if (!s.in || !s.w || !lo.in || !op.out || op.N <= 0 || s.H <= 0 || s.W <= 0 || (s.H & 1) || (s.W & 1) || (s.cs & 3) || (lo.cs & 3) || (op.out_cs & 3) ||
-                    s.cs < s.Cin || lo.cs < op.Cout || op.out_cs < op.Cout || ((uintptr_t)s.in & 15) || ((uintptr_t)lo.in & 15) || ((uintptr_t)op.out & 15) ||
-                    ((uintptr_t)s.w & 15) || (op.bias && ((uintptr_t)op.bias & 15)) || lo.H != s.H / 2 || lo.W != s.W / 2)
-                    return IDH_EINVAL;
-                if (s.Cin != op.Cout || (s.Cin != 64 && s.Cin != 128) || (long long)s.H * s.W >= (1ll << 31)) return IDH_EUNSUPPORTED;
-                PwUpArgs pa{};
-                pa.in = s.in; pa.w = s.w; pa.bias = op.bias; pa.low = lo.in; pa.out = op.out;
-                pa.H = s.H; pa.W = s.W; pa.in_cs = s.cs; pa.low_cs = lo.cs; pa.out_cs = op.out_cs;
-                pa.tiles_per_img = idh_cdiv(s.H * s.W, kPwTile);
-                pa.tiles = (long long)op.N * pa.tiles_per_img;
-                const int grid = (int)std::min<long long>(pa.tiles, 256 * 8);
-                if (s.Cin == 64) IDH_LAUNCH((pointwise_up_k<4, 4>), dim3(grid), dim3(256), 16 * 64 * sizeof(f32x4), st, pa);
-                else IDH_LAUNCH((pointwise_up_k<8, 8>), dim3(grid), dim3(256), 32 * 128 * sizeof(f32x4), st, pa);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_STEM: {
-                const int rc = idh_stem_op(op, st, !t_dry_run);
-                if (rc != IDH_OK) return rc;
-                if (t_dry_run) ++t_launches;
-                break;
-            }
-            case IDH_OP_COPY: {
-                if (!s.in || !op.out || (s.Cin & 3) || (s.cs & 3) || (op.out_cs & 3) || op.N <= 0 || s.H <= 0 || s.W <= 0 || s.Cin <= 0 ||
-                    s.cs < s.Cin || op.out_cs < s.Cin)
-                    return IDH_EINVAL;
-                const long long npix = (long long)op.N * s.H * s.W;
-                int grid = idh_cdiv(npix * (s.Cin >> 2), 256);
-                if (grid > 8192) grid = 8192;
-                IDH_LAUNCH(copy_nhwc_k, dim3(grid), dim3(256), 0, st, s.in, op.out, npix, s.Cin, s.cs, op.out_cs);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            case IDH_OP_INSTNORM: {
-                const int C = s.Cin, HW = s.H * s.W;
-                if (!s.in || !op.ws || C <= 0 || (C & 3) || 256 % (C >> 2) || (s.cs & 3) || (op.out && (op.out_cs & 3)) ||
-                    op.N <= 0 || op.N > 65535 || s.H <= 0 || s.W <= 0)  // (H W = 0: a zero-sized statistics grid)
-                    return IDH_EINVAL;
-                const int nchunks = idh_cdiv(HW, kInChunk);
-                // C >= 64: the chunk is summed as 1024 / (C/4) rows at either block size (bit-identical statistics at every batch size)
-                const int sthreads = ((long long)nchunks * op.N < 512 && C >= 64) ? 1024 : 256;
-                if (C >= 64 && sthreads == 256)
-                    IDH_LAUNCH(instnorm_stats_k<4>, dim3(nchunks, op.N), dim3(256), 1024 * 8 * sizeof(float), st, s.in, s.cs, C, HW, nchunks, op.ws);
-                else
-                    IDH_LAUNCH(instnorm_stats_k<1>, dim3(nchunks, op.N), dim3(sthreads), sthreads * 8 * sizeof(float), st, s.in, s.cs, C, HW,
-                                       nchunks, op.ws);
-                IDH_CHECK_LAUNCH();
-                float *stats = op.ws + (size_t)op.N * nchunks * 2 * C;
-                IDH_LAUNCH(instnorm_finalize_k, dim3(op.N), dim3(256), 0, st, op.ws, s.in, s.cs, C, HW, nchunks, stats);
-                IDH_CHECK_LAUNCH();
-                if (!op.out) break;  // statistics only: the consumer conv normalises on load (idh_conv_src.norm)
-                const long long total = (long long)op.N * HW * (C >> 2);
-                int gx = idh_cdiv(total, 256 * 4);  // ~4 float4 per thread
-                if (gx > 16384) gx = 16384;
-                IDH_LAUNCH(instnorm_apply_k, dim3(gx), dim3(256), 0, st, s.in, s.cs, op.out, op.out_cs, C, HW, total, stats, op.act,
-                                   op.slope);
-                IDH_CHECK_LAUNCH();
-                break;
-            }
-            default:
-                return IDH_EINVAL;
-        }
-    }
-    return IDH_OK;
+    RunCtx ctx{idh_stream(stream), false, 0};
+    return run_ops(ops, n, ctx);
 }
 
+// Replays idh_run_ops' validation and launch decisions without launching anything
+extern "C" int idh_count_launches(const idh_op *ops, int n) {
+    RunCtx ctx{nullptr, true, 0};
+    const int rc = run_ops(ops, n, ctx);
+    return rc == IDH_OK ? ctx.launches : rc;
+}
+
+// The documented tuple {lds_rows, nj, tm, tn, S, up, norm, s2} (include/idh_ops.h): the only place that knows its numbering
 extern "C" int idh_conv_variant(const idh_op *op, int32_t out[8]) {
     if (!op || !out || op->kind != IDH_OP_CONV) return IDH_EINVAL;
-    PreparedConv pc{};
-    const int rc = prep_conv(*op, pc);
-    if (rc != IDH_OK) return rc;
-    const bool lds = pc.lds_rows == 8 || pc.lds_rows == 4;
-    out[0] = pc.lds_rows;
-    out[1] = lds ? pc.nj : 0;
-    out[2] = lds ? 0 : pc.tm;
-    out[3] = lds ? 0 : pc.tn;
-    out[4] = pc.a.S;
-    out[5] = pc.up;
-    out[6] = pc.norm;
-    out[7] = pc.s2;
+    PreparedConv pc;
+    if (const int rc = prep_conv(*op, pc)) return rc;
+    switch (pc.kernel) {
+        case ConvKernel::Direct: out[0] = 0; out[1] = 0; out[2] = pc.tm; out[3] = pc.tn; break;
+        case ConvKernel::Lds: out[0] = pc.rows; out[1] = pc.nj; out[2] = 0; out[3] = 0; break;
+        case ConvKernel::Split: out[0] = 16; out[1] = 0; out[2] = pc.split_mode; out[3] = pc.rows; break;
+        case ConvKernel::Wino2: out[0] = 32; out[1] = 0; out[2] = IDH_TILE_WINO; out[3] = 0; break;
+        case ConvKernel::Wino4: out[0] = 36; out[1] = 0; out[2] = IDH_TILE_WINO4; out[3] = 0; break;
+    }
+    out[4] = pc.a.S; out[5] = pc.up; out[6] = pc.norm; out[7] = pc.s2;
     return IDH_OK;
-}
-
-extern "C" int idh_count_launches(const idh_op *ops, int n) {
-    t_dry_run = true;
-    t_launches = 0;
-    const int rc = idh_run_ops(ops, n, nullptr);
-    t_dry_run = false;
-    return rc == IDH_OK ? t_launches : rc;
 }

@@ -246,8 +246,9 @@ def _cases():
 
 CASES = _cases()
 
-# Every branch of launch_conv (csrc/conv.hip), written out: (lds_rows, nj, tm, tn, up, norm, s2).
-# A new branch there needs a line here and a case above, or test_conv_op_matrix_cpu.py::test_every_launch_conv_branch_has_a_case fails.
+# Every kernel launch_conv (csrc/conv.hip) can pick, written out in idh_conv_variant's numbering (lds_rows, nj, tm, tn, up, norm, s2): the non-null
+# entries of its tables kLdsRow<rows / 4>[nj][flavour] (14) and kDirectKernels[tm][tn] (9), and the launchers of the other three kernels.
+# A new table entry needs a line here and a case above, or test_conv_op_matrix_cpu.py::test_every_launch_conv_branch_has_a_case fails.
 LAUNCH_CONV_BRANCHES = {
     (16, 0, TILE_SPLIT, 16, 0, 0, 0),  # launch_conv_split: conv3x3_split_k<4, 2, f16x3, SRC2>
     (16, 0, TILE_SPLIT, 8, 0, 0, 0),   # launch_conv_split: conv3x3_split_k<4, 1, f16x3, SRC2>

@@ -2,7 +2,7 @@
 
 ``nhwc.Plan`` reaches the layout imports / exports, the two upsamplings, the concat copy, the 1-channel head, the two fused pointwise kernels
 and InstanceNorm only at the shapes a network produces.  test_op_kinds_cpu.py / test_op_kinds_gpu.py build the descriptors themselves
-(csrc/conv.hip: the case labels of idh_run_ops): the smallest shapes that still have a tail, strided inputs and outputs, the grouped import
+(csrc/conv.hip: one run_<kind> function per op kind): the smallest shapes that still have a tail, strided inputs and outputs, the grouped import
 grid, and one "large" case per kernel whose grid is capped - the only way its grid-stride / persistent loop takes a second trip.
 
 Buffers follow the hostile convention of tests/conv_op_ref.py: an NHWC output is channels [OUT_C0, OUT_C0 + C) of a wider buffer prefilled
@@ -32,16 +32,17 @@ RESERVED = {"SPLITK_REDUCE": 5}     # never accepted (test_conv_op_matrix_cpu.py
 BIT_EXACT = ("import", "export", "copy", "nearest")  # pure data movement
 DENSE_OUT = ("export", "head")                       # the output is a dense (N, C, H, W) tensor
 
-# The grid caps of csrc/conv.hip, in workgroups of 256 threads, and what one workgroup takes (natural_grid below).
-CAP_COPY = 8192      # csrc/conv.hip:1842  `if (grid > 8192) grid = 8192;`  (IDH_OP_COPY, one thread per channel quad of a pixel)
-CAP_NEAREST = 8192   # csrc/conv.hip:1736  `if (grid > 8192) grid = 8192;`  (IDH_OP_UPSAMPLE2_NEAREST, one thread per OUTPUT channel quad)
-CAP_HEAD = 8192      # csrc/conv.hip:1788  `if (grid > 8192) grid = 8192;`  (IDH_OP_POINTWISE_HEAD, one thread per pixel)
-CAP_UP2 = 32768      # csrc/conv.hip:1720  `if (grid > 32768) grid = 32768;`  (lone IDH_OP_UPSAMPLE2, one thread per INPUT channel quad)
-CAP_PW_NCHW = 4096   # csrc/conv.hip:1806  `std::min<long long>(pa.tiles, 256 * 4 * 4)`  (one workgroup per tile of 64 pixels)
-CAP_PW_UP = 2048     # csrc/conv.hip:1824  `std::min<long long>(pa.tiles, 256 * 8)`  (one workgroup per tile of 64 pixels)
+# The grid caps of csrc/conv.hip (named constants there, each used by the run_<kind> function of its op kind), in workgroups of 256 threads,
+# and what one workgroup takes (natural_grid below).  test_op_kinds_cpu.py::test_mirrored_caps_are_the_sources holds them against the source.
+CAP_COPY = 8192      # kCopyMaxBlocks  (IDH_OP_COPY, one thread per channel quad of a pixel)
+CAP_NEAREST = 8192   # kNearestMaxBlocks  (IDH_OP_UPSAMPLE2_NEAREST, one thread per OUTPUT channel quad)
+CAP_HEAD = 8192      # kHeadMaxBlocks  (IDH_OP_POINTWISE_HEAD, one thread per pixel)
+CAP_UP2 = 32768      # kUpsampleMaxBlocks  (lone IDH_OP_UPSAMPLE2, one thread per INPUT channel quad)
+CAP_PW_NCHW = 4096   # kPwNchwMaxBlocks = 256 * 4 * 4  (IDH_OP_POINTWISE_NCHW, one workgroup per tile of 64 pixels)
+CAP_PW_UP = 2048     # kPwUpMaxBlocks = 256 * 8  (IDH_OP_POINTWISE_UP, one workgroup per tile of 64 pixels)
 CAPS = {"copy": CAP_COPY, "nearest": CAP_NEAREST, "head": CAP_HEAD, "up2": CAP_UP2, "pw_nchw": CAP_PW_NCHW, "pw_up": CAP_PW_UP}
-K_MAX_IMPORT = 8               # csrc/conv.hip:972  kMaxImport
-IMPORT_GROUP_MAX_BLOCKS = 4096  # csrc/conv.hip:1753  kLevelMaxBlocks * 8: a larger import keeps its own 3-D grid
+K_MAX_IMPORT = 8               # kMaxImport
+IMPORT_GROUP_MAX_BLOCKS = 4096  # kImportGroupMaxBlocks = 8 * kLevelMaxBlocks: a larger import keeps its own 3-D grid
 PW_TILE = 64                   # kPwTile
 
 

@@ -48,6 +48,39 @@ def test_every_launch_conv_branch_has_a_case():
     assert any(s.split_k > s.S > 1 for s in R.CASES if s.variant[0] == 0) and any(s.split_k > s.S > 1 for s in R.CASES if s.variant[0] != 0)
 
 
+def test_prep_conv_accepts_nothing_outside_the_kernel_tables():
+    """The other direction: whatever prep_conv accepts, launch_conv has a kernel for.  Every direct / LDS case of the table (all its sources,
+    paddings, strides, split counts, fused upsampling and normalise-on-load) is asked onto every tile_m x tile_n x Cout of the sweep; a request
+    idh_conv_variant accepts must name an entry of LAUNCH_CONV_BRANCHES (so the dry count launches it: 1 + the reduce), a refused one leaves
+    the outputs untouched."""
+    import copy
+
+    L, nhwc = _lib_nhwc()
+    bases = [s for s in R.CASES if s.family in ("direct", "lds")]
+    accepted, refused, seen = 0, 0, set()
+    for base in bases:
+        for tm in (0, 1, 2, 4, 8, 9):
+            for tn in (0, 1, 2, 4):
+                for cout in (16, 32, 48, 64):
+                    spec = copy.copy(base)
+                    spec.tile_m, spec.tile_n, spec.cout = tm, tn, cout
+                    op = R.build_op(nhwc, spec, R.fake_ptr)
+                    rc, v = R.variant_of(L, nhwc, op)
+                    what = (base.name, tm, tn, cout, rc, v)
+                    if rc != R.OK:
+                        assert rc in (R.EINVAL, R.EUNSUPPORTED) and v == (-7,) * 8, what
+                        assert _count(L, nhwc, [op]) == rc, what
+                        refused += 1
+                        continue
+                    assert v[:4] + v[5:] in R.LAUNCH_CONV_BRANCHES, what
+                    assert 1 <= v[4] <= max(1, spec.split_k) and _count(L, nhwc, [op]) == 1 + (v[4] > 1), what
+                    accepted += 1
+                    seen.add(v[:4] + v[5:])
+    print(f"{len(bases)} base cases x 96 requests: {accepted} accepted on {len(seen)} table entries, {refused} refused")
+    assert accepted + refused == 6 * 4 * 4 * len(bases) and refused > 0
+    assert seen == {b for b in R.LAUNCH_CONV_BRANCHES if b[0] in (0, 4, 8)}  # the sweep is not vacuous: it reaches all 14 + 9 table entries itself
+
+
 def test_every_hidden_kernel_template_has_a_case():
     """The Winograd and split-precision launchers pick template arguments the variant tuple does not show (a fused second source, F(4x4)'s
     <PROJ, RES>, the split kernel's SRC2 x tile rows, the grouped F(2x2) kernel with / without second sources): the table reaches each, and

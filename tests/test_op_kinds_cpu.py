@@ -162,25 +162,48 @@ def test_large_cases_cross_their_grid_cap_by_a_part(spec):
 
 
 def test_mirrored_caps_are_the_sources():
-    """The constants of op_kind_ref.py against the case labels of idh_run_ops they copy (by label, not by line: the line numbers in the
-    comments there are a reading aid and may drift): a cap that changes fails here, before a large case silently stops crossing it."""
+    """The constants of op_kind_ref.py against the named constants of csrc/conv.hip they copy: each is defined ONCE with the mirrored value, is
+    the bound of the grid clamp (or the grouping test) inside the run_<kind> function of its op kind, and appears in no other one - a cap that
+    changes, or moves to another kind, fails here, before a large case silently stops crossing it."""
     import os
     import re
 
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "implicit-depth_amd", "csrc", "conv.hip")
     with open(path) as f:
-        src = f.read()
-    src = src[src.index('extern "C" int idh_run_ops'):]
-    body = {m.group(1): src[m.end():].split("            case IDH_OP_")[0] for m in re.finditer(r"            case IDH_OP_(\w+): \{", src)}
-    cap = lambda v: f"if (grid > {v}) grid = {v};"
-    assert cap(K.CAP_COPY) in body["COPY"] and cap(K.CAP_NEAREST) in body["UPSAMPLE2_NEAREST"] and cap(K.CAP_HEAD) in body["POINTWISE_HEAD"]
-    assert cap(K.CAP_UP2) in body["UPSAMPLE2"]
-    assert "std::min<long long>(pa.tiles, 256 * 4 * 4)" in body["POINTWISE_NCHW"] and K.CAP_PW_NCHW == 256 * 4 * 4
-    assert "std::min<long long>(pa.tiles, 256 * 8)" in body["POINTWISE_UP"] and K.CAP_PW_UP == 256 * 8
-    assert "blocks > kLevelMaxBlocks * 8ll" in body["NCHW_TO_NHWC"] and "run < kMaxImport" in body["NCHW_TO_NHWC"]
-    whole = open(path).read()
-    assert f"constexpr int kMaxImport = {K.K_MAX_IMPORT};" in whole and "constexpr unsigned kLevelMaxBlocks = 512;" in whole
-    assert K.IMPORT_GROUP_MAX_BLOCKS == 512 * 8 and "constexpr int kPwCin = 64, kPwCout = 128, kPwTile = 64;" in whole and K.PW_TILE == 64
+        whole = f.read()
+    defs = {}
+    for m in re.finditer(r"^constexpr (?:int|unsigned|long long) (k\w+) = ([^;]+);", whole, re.M):
+        assert m.group(1) not in defs, m.group(1)  # defined once
+        defs[m.group(1)] = m.group(2)
+
+    def value(name):  # products of integer literals and other constants of the file, nothing else
+        v = 1
+        for f in defs[name].split("*"):
+            f = f.strip()
+            v *= int(f) if re.fullmatch(r"\d+", f) else value(f)
+        return v
+
+    # each run_<kind> is a function of the anonymous namespace: its body ends at the first closing brace in column 0
+    body = {m.group(1): whole[m.end():].split("\n}\n")[0] for m in re.finditer(r"^int (run_\w+)\(const idh_op \*ops, int i, int n, RunCtx &ctx\) \{$", whole, re.M)}
+    caps = {"kCopyMaxBlocks": (K.CAP_COPY, "run_copy", "std::min(idh_cdiv(npix * (s.Cin >> 2), 256), kCopyMaxBlocks)"),
+            "kNearestMaxBlocks": (K.CAP_NEAREST, "run_upsample2_nearest", "std::min(idh_cdiv(tot, 256), kNearestMaxBlocks)"),
+            "kHeadMaxBlocks": (K.CAP_HEAD, "run_pointwise_head", "std::min(idh_cdiv(M, 256), kHeadMaxBlocks)"),
+            "kUpsampleMaxBlocks": (K.CAP_UP2, "run_upsample2", "std::min(idh_cdiv(quads, 256), kUpsampleMaxBlocks)"),
+            "kPwNchwMaxBlocks": (K.CAP_PW_NCHW, "run_pointwise_nchw", "std::min<long long>(pa.tiles, kPwNchwMaxBlocks)"),
+            "kPwUpMaxBlocks": (K.CAP_PW_UP, "run_pointwise_up", "std::min<long long>(pa.tiles, kPwUpMaxBlocks)"),
+            "kImportGroupMaxBlocks": (K.IMPORT_GROUP_MAX_BLOCKS, "run_nchw_to_nhwc", "blocks > kImportGroupMaxBlocks"),
+            "kMaxImport": (K.K_MAX_IMPORT, "run_nchw_to_nhwc", "g.n < kMaxImport")}
+    assert set(K.CAPS.values()) <= {v[0] for v in caps.values()} and len(body) == 11, sorted(body)
+    for name, (mirrored, fn, use) in caps.items():
+        assert value(name) == mirrored, (name, defs[name], mirrored)
+        assert use in body[fn], (name, fn)
+        assert [f for f in body if name in body[f]] == [fn], name  # ... and is the bound of no other kind
+    # ... and that clamp is the function's only one: no bare literal took a cap's place beside it
+    for name, (mirrored, fn, use) in caps.items():
+        assert body[fn].count("std::min") == use.startswith("std::min") and "if (grid >" not in body[fn], fn
+    assert value("kLevelMaxBlocks") == 512 and defs["kImportGroupMaxBlocks"] == "8 * kLevelMaxBlocks" and K.IMPORT_GROUP_MAX_BLOCKS == 512 * 8
+    assert K.CAP_PW_NCHW == 256 * 4 * 4 and K.CAP_PW_UP == 256 * 8
+    assert "constexpr int kPwCin = 64, kPwCout = 128, kPwTile = 64;" in whole and K.PW_TILE == 64
 
 
 # ------------------------------------------------------------------------------------------------------------------
