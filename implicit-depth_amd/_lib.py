@@ -31,7 +31,8 @@ class VolumeOpts(C.Structure):
 
     _fields_ = [("cur_batch_stride", C.c_int64), ("src_batch_stride", C.c_int64), ("planes", C.c_void_p),
                 ("planes_batch_stride", C.c_int64), ("planes_plane_stride", C.c_int64), ("planes_pixel_stride", C.c_int32),
-                ("kernel", C.c_int32), ("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("struct_size", C.c_int64)]
+                ("kernel", C.c_int32), ("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("struct_size", C.c_int64),
+                ("fv_keep_empty_views", C.c_int32), ("reserved0", C.c_int32)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)

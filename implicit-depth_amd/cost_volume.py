@@ -50,7 +50,7 @@ def _is_device_scalar(v) -> bool:
 
 
 def volume_opts(B, K, C, H, W, D, planes_bdhw: Optional[Tensor] = None, cur_batch_stride: int = 0, src_batch_stride: int = 0, kernel: int = 0,
-                dot_scratch_device=None):
+                dot_scratch_device=None, fv_keep_empty_views: int = 0):
     """``idh_volume_opts`` for one launch -> (ctypes struct or None, keep-alive list).  ``planes_bdhw`` is the
     reference's ``depth_planes_bdhw`` (modules/cost_volume.py:324-347): any (B,D,H,W) fp32 device tensor; views
     that are constant over the image (``expand()``ed (B,D,1,1) / (1,D,1,1), what generate_depth_planes returns)
@@ -58,10 +58,11 @@ def volume_opts(B, K, C, H, W, D, planes_bdhw: Optional[Tensor] = None, cur_batc
     # dot-product volume (``dot_scratch_device`` given): scratch that lets the arg-max pass of a plane-split launch combine per-group
     # results instead of re-reading the volume (idh_volume_opts.scratch); taken from torch's stream-ordered caching allocator
     n_scratch = int(_lib.lib().idh_cost_volume_dot_scratch_floats(B, K, C, H, W, D)) if dot_scratch_device is not None else 0
-    if planes_bdhw is None and not cur_batch_stride and not src_batch_stride and not kernel and not n_scratch:
+    if planes_bdhw is None and not cur_batch_stride and not src_batch_stride and not kernel and not n_scratch and not fv_keep_empty_views:
         return None, []
     o = _lib.VolumeOpts()
     o.cur_batch_stride, o.src_batch_stride, o.kernel = int(cur_batch_stride), int(src_batch_stride), int(kernel)
+    o.fv_keep_empty_views = int(fv_keep_empty_views)  # MLP feature volume: 0 = the launch picks its kernel, 1 = fv_mlp_k (every view processed), 2 = fv_mlp_skip_k
     keep = []
     if n_scratch:
         sc = torch.empty(n_scratch, device=dot_scratch_device, dtype=torch.float32)
@@ -286,6 +287,10 @@ class FeatureVolumeManager(CostVolumeManager):
         self.num_source_views = num_source_views
         self.mlp = MLP(channel_list=mlp_channels, disable_final_activation=True)
         self.mlp_math: Optional[str] = None  # None = DEFAULT_MLP_MATH
+        # True: a launch whose cameras leave enough samples outside the source images runs fv_mlp_skip_k, which drops, per 16-voxel tile and plane,
+        # the source views in which no voxel has a non-zero bilinear weight (same results), any other launch fv_mlp_k.  False: always fv_mlp_k
+        # (every view processed); "always": always fv_mlp_skip_k (A/B timing, tests).  = idh_volume_opts.fv_keep_empty_views 0 / 1 / 2
+        self.skip_empty_views = True
 
     def _math(self) -> str:
         m = DEFAULT_MLP_MATH if self.__dict__.get("mlp_math") is None else self.mlp_math
@@ -361,7 +366,8 @@ class FeatureVolumeManager(CostVolumeManager):
         lowest = torch.empty(B, H, W, device=dev)
         mask = torch.empty(B, H, W, device=dev, dtype=torch.bool) if want_mask else None  # the kernel writes 0/1 bytes
         planes = sc["fv_planes"] if planes_t is None else None
-        opts, keep = volume_opts(B, K, C, H, W, D, planes_t, cur_batch_stride, src_batch_stride)
+        opts, keep = volume_opts(B, K, C, H, W, D, planes_t, cur_batch_stride, src_batch_stride,
+                                 fv_keep_empty_views={True: 0, False: 1, "always": 2}[self.__dict__.get("skip_empty_views", True)])
         mats = [t if t.is_contiguous() else t.contiguous() for t in (src_Ks, src_extrinsics, src_poses, cur_invK)]  # alive until enqueued
         _lib.check(
             L.idh_feature_volume_ex_fwd(cur_ptr, src_ptr, mats[0].data_ptr(), mats[1].data_ptr(), mats[2].data_ptr(), mats[3].data_ptr(),

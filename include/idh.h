@@ -87,6 +87,13 @@ typedef struct idh_volume_opts {
                             against the shorter version-100 struct: for such a caller the field itself lies past the end of its struct.  A
                             binding must therefore compare idh_sizeof_volume_opts() / idh_version() with its own mirror when it loads the
                             library (implicit-depth_amd/_lib.py does, and refuses to bind on a mismatch). */
+    int32_t fv_keep_empty_views; /* MLP feature volume only (C = 16, K <= 8, fp32).  fv_mlp_skip_k drops a source view from a 16-voxel tile's plane when none
+                                    of the voxels has a non-zero bilinear weight in it - no taps, blend or layer-1 MFMAs; the same values for finite
+                                    features (csrc/feature_volume.hip names the Inf / NaN and -0 footnotes) - and is slower than fv_mlp_k where nothing
+                                    can be dropped.  0 (default): each launch runs the faster of the two for its cameras (a device-side estimate, no
+                                    synchronisation); 1: always fv_mlp_k, every view processed; 2: always fv_mlp_skip_k (A/B timing, tests).
+                                    Appended after struct_size: honoured when struct_size reaches past it. */
+    int32_t reserved0;
 } idh_volume_opts;
 
 /* sizeof(idh_volume_opts) as compiled into the library (bindings assert their mirror matches; idh_version() >= 101). */
