@@ -317,6 +317,8 @@ _SIGS = {
     "idh_binary_mlp_f16x3_fwd": (C.c_int, [f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_float, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_feature_volume_workspace_bytes": (C.c_size_t, [C.c_int]),
     "idh_feature_volume_plane_groups": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2),
+    "idh_feature_volume_grid": (C.c_int, [C.c_longlong]),
+    "idh_feature_volume_skip_task": (C.c_longlong, [C.c_longlong] + [C.c_int] * 4),
     "idh_feature_volume_fwd": (
         C.c_int,
         [f32p] * 6 + [C.c_float, C.c_float] + [C.c_int] * 6 + [f32p] * 6 + [f32p, C.c_int, f32p, C.c_void_p, f32p, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -123,6 +123,31 @@ __device__ __forceinline__ bool fv_selected(const FvArgs &a, bool skipping_kerne
     return (s >= kSkipMinOutside * (float)a.B) == skipping_kernel;
 }
 
+// ---- task order of fv_mlp_skip_k.  Tasks are handed out in rounds of gridDim.x * 8: in round r, workgroup `block` owns the eight consecutive tasks
+// from (r * grid + idh_xcd_remap(block)) * 8 on, as in the uniform-cost kernels, but wave w takes sub-slot (w + r) & 7 of them and not always
+// sub-slot w.  Since views are dropped a task costs 352 .. 576 MFMAs per plane, and the static stride is a multiple of 8: where the tiles of an image
+// row are a multiple of 8 too (128 / 16 at the benchmark's shape), wave w met the same x-block of the image in every round, and the share of
+// dropped views is a function of x when the source cameras are translated along it - the SIMD with the two dearest columns ran 8 % longer than the
+// mean (tools/fv_task_balance.py).  The workgroup's task set per round is unchanged, so is the XCD / L2 locality.  Returns the task, or
+// -1 where the slot lies past ntasks (a rotated sub-slot can do so in the last round while a lower one does not: the caller skips that slot and
+// goes on).  One function for the kernel and for idh_feature_volume_skip_task.
+__host__ __device__ __forceinline__ long long fv_skip_task(long long ntasks, int grid, int block, int wave, long long round) {
+#ifdef IDH_ABL_FV_STATIC_ORDER  // (timing experiments: the static stride of the uniform-cost kernels, for A/B runs of the rotation)
+    const int sub = wave;
+#else
+    const int sub = (int)((wave + round) & 7);
+#endif
+    const long long task = (round * grid + (long long)idh_xcd_remap((unsigned)block, (unsigned)grid)) * 8 + sub;
+    return task < ntasks ? task : -1;
+}
+
+#ifdef IDH_FV_WAVE_CLOCKS
+// Developer build only (tools/perf_fv_skip.py --wave-clocks; in no shipped library): per (workgroup, wave) of fv_mlp_skip_k's last launch the 100 MHz
+// wall clock at entry and at exit, and the HW_ID register (SIMD and CU the wave ran on).
+constexpr int kClkWords = 4;
+__device__ unsigned long long fv_wave_clocks[256 * 8 * kClkWords];
+#endif
+
 // ---- setup: homographies, source camera centres, pose-distance bias (one block per b) --------
 // w1_pose: (128, 3K) row-major = W1[:, pose-distance | R-measure | t-measure columns]
 __global__ void fv_setup_k(const float *__restrict__ src_K, const float *__restrict__ src_E,
@@ -572,6 +597,9 @@ __global__ __launch_bounds__(512) void fv_mlp_k(const FvArgs a) {
 template <int KT>
 __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
     if (!fv_selected(a, true)) return;
+#ifdef IDH_FV_WAVE_CLOCKS
+    const unsigned long long clk0 = wall_clock64();
+#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     f32x4 *sW1 = reinterpret_cast<f32x4 *>(smem_raw);            // (K+4)*8*64
     f32x4 *sW2 = sW1 + (a.K + 4) * kNS * 64;                       // 8*8*64
@@ -596,8 +624,11 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
     const long long ntasks = (long long)a.B * a.tiles_per_img * a.G;
 
     // XCD-aware: hardware puts workgroup b on XCD b % 8; after the remap each XCD walks a contiguous run of tasks
-    // (= a band of image rows) per round, so the taps of its 32 workgroups share that XCD's 4 MB L2
-    for (long long task = (long long)idh_xcd_remap(blockIdx.x, gridDim.x) * 8 + wave; task < ntasks; task += (long long)gridDim.x * 8) {
+    // (= a band of image rows) per round, so the taps of its 32 workgroups share that XCD's 4 MB L2.  Within the workgroup's eight tasks of a round
+    // the waves rotate (fv_skip_task): a slot past ntasks in the last round is skipped, the wave's loop does not end there.
+    for (long long round = 0; round * gridDim.x * 8 < ntasks; ++round) {
+        const long long task = fv_skip_task(ntasks, (int)gridDim.x, (int)blockIdx.x, wave, round);
+        if (task < 0) continue;
         // wave-uniform task coordinates: pin to SGPRs so the per-b constants come through the scalar cache
         const int g = __builtin_amdgcn_readfirstlane((int)(task % a.G));
         const int tile = __builtin_amdgcn_readfirstlane((int)((task / a.G) % a.tiles_per_img));
@@ -1060,6 +1091,12 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
             P = Pn; cur = curn; wc = wcn; act = actn;
         }
     }
+#ifdef IDH_FV_WAVE_CLOCKS
+    if (lane == 0 && blockIdx.x < 256) {  // (plain vector stores; HW_ID = hardware register 4: SIMD in bits 4-5, CU in 8-11, SH in 12, SE in 13-15)
+        unsigned long long *o = fv_wave_clocks + ((size_t)blockIdx.x * 8 + wave) * kClkWords;
+        o[0] = clk0; o[1] = wall_clock64(); o[2] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)); o[3] = 1;
+    }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1687,6 +1724,25 @@ extern "C" int idh_feature_volume_plane_groups(int B, int H, int W, int D, int *
     return IDH_OK;
 }
 
+// persistent: one 512-thread workgroup per CU (LDS-resident weights), eight tasks per workgroup and round
+static int fv_grid(long long ntasks) { return ntasks >= 256ll * 8 ? 256 : (int)((ntasks + 7) / 8); }
+
+extern "C" int idh_feature_volume_grid(long long ntasks) { return ntasks <= 0 ? 0 : fv_grid(ntasks); }
+
+extern "C" long long idh_feature_volume_skip_task(long long ntasks, int grid, int block, int wave, int round) {
+    if (ntasks <= 0 || grid <= 0 || block < 0 || block >= grid || wave < 0 || wave >= 8 || round < 0) return -1;
+    return fv_skip_task(ntasks, grid, block, wave, round);
+}
+
+#ifdef IDH_FV_WAVE_CLOCKS
+// developer build only: copies the wave clocks of the last fv_mlp_skip_k launch (4 words per wave, 8 waves per workgroup) after a device synchronise
+extern "C" __attribute__((visibility("default"))) int idh_dev_fv_wave_clocks(unsigned long long *dst, int workgroups) {
+    if (!dst || workgroups < 0 || workgroups > 256) return IDH_EINVAL;
+    if (hipDeviceSynchronize() != hipSuccess) return IDH_ELAUNCH;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(fv_wave_clocks), (size_t)workgroups * 8 * kClkWords * sizeof(unsigned long long)) == hipSuccess ? IDH_OK : IDH_ELAUNCH;
+}
+#endif
+
 static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                                const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
                                float dmin, float dmax, int B, int K, int C, int H, int W, int D,
@@ -1788,8 +1844,7 @@ static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, con
     fv_plane_groups(B, H, W, D, &a.G, &a.DP);  // (shared with idh_feature_volume_plane_groups)
     const long long pix_tasks = (long long)B * a.tiles_per_img;
     const long long ntasks = pix_tasks * a.G;
-    int grid = (int)((ntasks + 7) / 8);
-    if (grid > 256) grid = 256;  // persistent: one 512-thread workgroup per CU (LDS-resident weights)
+    const int grid = fv_grid(ntasks);  // (shared with idh_feature_volume_grid)
     static IdhDeviceOnce attr_set;
     if (attr_set.first()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_k<0>), hipFuncAttributeMaxDynamicSharedMemorySize,

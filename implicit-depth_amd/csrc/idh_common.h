@@ -38,8 +38,8 @@ static inline int idh_cdiv(long long a, long long b) { return (int)((a + b - 1) 
 // XCD-aware block remap (guide T1): hardware places block b on XCD b % 8, so consecutive
 // logical tiles land on different L2s.  Remap so each XCD owns a contiguous run of logical
 // tiles (neighbouring tiles share halo rows / weight panels in its private L2).  Bijective for
-// any grid size.
-__device__ __forceinline__ unsigned idh_xcd_remap(unsigned bid, unsigned nblocks) {
+// any grid size.  (__host__ too: the host-side restatement of a kernel's task order calls the same function.)
+__host__ __device__ __forceinline__ unsigned idh_xcd_remap(unsigned bid, unsigned nblocks) {
     const unsigned NX = 8;
     unsigned full = nblocks / NX, rem = nblocks % NX;
     unsigned xcd = bid % NX, slot = bid / NX;

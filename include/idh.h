@@ -170,6 +170,13 @@ size_t idh_feature_volume_workspace_bytes(int B);
  * last one may be shorter.  The launch calls the same function, so the answer is the partition the kernels run (K, C and the math mode
  * do not enter the choice).  IDH_EINVAL for non-positive sizes, D > 4096 or a NULL output pointer. */
 int idh_feature_volume_plane_groups(int B, int H, int W, int D, int *groups, int *planes_per_group);
+/* Host-only queries (additive: idh_version() stays as it is): the order in which the kernel that drops views (fv_mlp_skip_k) walks its
+ * ntasks = B * ceil(H * W / 16) * groups tasks.  idh_feature_volume_grid: the number of workgroups the launch uses (8 waves each; 0 for
+ * ntasks <= 0).  idh_feature_volume_skip_task: the task that wave `wave` (0..7) of workgroup `block` (0..grid-1, the hardware's block index)
+ * takes in round `round` (0, 1, ...), or -1 when it takes none there - the slot lies past ntasks, or an argument is out of range.  Task t is
+ * plane group t % groups of tile (t / groups) % tiles of frame t / (groups * tiles).  The kernel calls the same function. */
+int idh_feature_volume_grid(long long ntasks);
+long long idh_feature_volume_skip_task(long long ntasks, int grid, int block, int wave, int round);
 int idh_feature_volume_fwd(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                            const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
                            float dmin, float dmax, int B, int K, int C, int H, int W, int D,

@@ -10,7 +10,16 @@ Camera sets, all at the benchmark's shape (B x 7 views, 16 channels, 96 x 128, 6
   golden_g2  cost_volume_inputs with the dims of tests/golden/g2_full_k7d64.npz (the full-size feature-volume golden)
 One JSON line per camera set: "on" = the default (each launch picks fv_mlp_k or fv_mlp_skip_k), "off" = always fv_mlp_k, "always" = always
 fv_mlp_skip_k.  A library without the switch (FeatureVolumeManager.skip_empty_views) is timed once, as "on".
+
+  IDH_LIB=<developer library> python tools/perf_fv_skip.py [B] --wave-clocks [cameras ...]
+
+Load balance of fv_mlp_skip_k's task order (tools/fv_task_balance.py has the model): needs a library whose csrc/feature_volume.hip was
+compiled with -DIDH_FV_WAVE_CLOCKS (every wave stores the 100 MHz wall clock at entry and exit and its HW_ID; in no shipped build), and
+-DIDH_ABL_FV_STATIC_ORDER beside it for the static order the rotation replaced.  One launch of the kernel, forced, after three warm-up launches;
+per camera set (default: bench) one JSON line: the kernel's span, the mean exit time per wave index relative to the mean over all waves, which
+wave indices share a SIMD, and over the SIMDs (exit of a SIMD = exit of its last wave) busiest / mean and the mean idle tail before the kernel ends.
 """
+import ctypes
 import json
 import os
 import sys
@@ -76,7 +85,68 @@ def camera_sets(B):
     return sets
 
 
+def wave_clock_stats(clk):
+    """clk: (workgroups, 8, 4) uint64 = [entry, exit, HW_ID, written] per wave (csrc/feature_volume.hip, IDH_FV_WAVE_CLOCKS); times in 10 ns ticks."""
+    clk = clk[clk[:, :, 3].all(1)]  # workgroups that ran
+    t0 = clk[:, :, 0].min()
+    exit_t = (clk[:, :, 1] - t0).astype(np.float64)  # workgroups, 8
+    hw = clk[:, :, 2].astype(np.int64)
+    simd = (hw >> 4) & 3
+    cu = ((hw >> 13) & 7) * 32 + ((hw >> 12) & 1) * 16 + ((hw >> 8) & 15)  # (SE, SH, CU: the XCD is not in HW_ID, a workgroup stays on one CU anyway)
+    assert (cu == cu[:, :1]).all(), "a workgroup's waves on more than one CU"
+    simd_exit, sharing = [], {}
+    for b in range(clk.shape[0]):
+        for s in range(4):
+            ws = np.nonzero(simd[b] == s)[0]
+            if len(ws):
+                simd_exit.append(exit_t[b, ws].max())
+                sharing["+".join(map(str, ws))] = sharing.get("+".join(map(str, ws)), 0) + 1
+    simd_exit = np.array(simd_exit)
+    end = exit_t.max()
+    cu_exit = exit_t.max(1)
+    in_cu = np.array([exit_t[b].max() - exit_t[b].min() for b in range(clk.shape[0])])
+    return {"workgroups": int(clk.shape[0]), "kernel_span_us": round(end / 100, 1),
+            "wave_index_exit_over_mean": [round(v, 4) for v in (exit_t.mean(0) / exit_t.mean()).tolist()],
+            "wave_exit_first_mean_last_us": [round(exit_t.min() / 100, 1), round(exit_t.mean() / 100, 1), round(end / 100, 1)],
+            "simd_exit_busiest_over_mean": round(simd_exit.max() / simd_exit.mean(), 4),
+            "simd_idle_tail_mean_share": round(float((end - simd_exit).mean() / end), 4),
+            "cu_exit_busiest_over_mean": round(cu_exit.max() / cu_exit.mean(), 4),
+            "first_to_last_wave_within_cu_mean_us": round(in_cu.mean() / 100, 1),
+            "waves_sharing_a_simd": dict(sorted(sharing.items(), key=lambda kv: -kv[1])[:8])}
+
+
+def wave_clocks(B, names):
+    from implicit_depth_amd import _lib
+
+    L = _lib.lib()
+    try:
+        fn = L.idh_dev_fv_wave_clocks
+    except AttributeError:
+        raise SystemExit("--wave-clocks needs a library built with -DIDH_FV_WAVE_CLOCKS (IDH_LIB=...), see the top of this file")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]
+    dev = torch.device("cuda:0")
+    m = cv.FeatureVolumeManager(H, W, D, num_source_views=K).to(dev)
+    syn.fill_state_dict(m.mlp, 99, gain=1.4)
+    m.skip_empty_views = "always"
+    vol = torch.empty(B, H, W, D, device=dev)
+    sets = camera_sets(B)
+    for name in names or ["bench"]:
+        d = {k: v.to(dev) for k, v in sets[name].items()}
+        cur_n, src_n = cv.to_nhwc(d["cur_feats"]), cv.to_nhwc(d["src_feats"])
+        st = {}
+        for _ in range(4):
+            m._run(cur_n.data_ptr(), src_n.data_ptr(), (B, K, C, H, W), d["src_extrinsics"], d["src_poses"], d["src_Ks"], d["cur_invK"], DMIN, DMAX,
+                   vol.data_ptr(), D, False, dev, scratch=st)
+        torch.cuda.synchronize()
+        clk = np.zeros((256, 8, 4), dtype=np.uint64)
+        _lib.check(fn(clk.ctypes.data, 256), "idh_dev_fv_wave_clocks")
+        print(json.dumps({"cameras": name, "B": B, **wave_clock_stats(clk)}), flush=True)
+
+
 def main():
+    if "--wave-clocks" in sys.argv:
+        i = sys.argv.index("--wave-clocks")
+        return wave_clocks(int(sys.argv[1]) if i > 1 else 32, sys.argv[i + 1:])
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
     iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
