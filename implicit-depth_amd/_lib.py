@@ -32,7 +32,7 @@ class VolumeOpts(C.Structure):
     _fields_ = [("cur_batch_stride", C.c_int64), ("src_batch_stride", C.c_int64), ("planes", C.c_void_p),
                 ("planes_batch_stride", C.c_int64), ("planes_plane_stride", C.c_int64), ("planes_pixel_stride", C.c_int32),
                 ("kernel", C.c_int32), ("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("struct_size", C.c_int64),
-                ("fv_keep_empty_views", C.c_int32), ("reserved0", C.c_int32)]
+                ("fv_keep_empty_views", C.c_int32), ("win_units_per_split", C.c_int32)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
@@ -288,6 +288,7 @@ _SIGS = {
     "idh_version": (C.c_int, []),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
     "idh_cost_volume_dot_scratch_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "idh_cost_volume_dot_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "idh_error_string": (C.c_char_p, [C.c_int]),
     "idh_nchw_to_nhwc_f32": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "idh_nhwc_to_nchw_f32": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

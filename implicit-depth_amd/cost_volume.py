@@ -9,6 +9,7 @@ torch is only used to own device memory and the stream.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -50,18 +51,27 @@ def _is_device_scalar(v) -> bool:
 
 
 def volume_opts(B, K, C, H, W, D, planes_bdhw: Optional[Tensor] = None, cur_batch_stride: int = 0, src_batch_stride: int = 0, kernel: int = 0,
-                dot_scratch_device=None, fv_keep_empty_views: int = 0):
+                dot_scratch_device=None, fv_keep_empty_views: int = 0, win_units: int = 0):
     """``idh_volume_opts`` for one launch -> (ctypes struct or None, keep-alive list).  ``planes_bdhw`` is the
     reference's ``depth_planes_bdhw`` (modules/cost_volume.py:324-347): any (B,D,H,W) fp32 device tensor; views
     that are constant over the image (``expand()``ed (B,D,1,1) / (1,D,1,1), what generate_depth_planes returns)
     are passed by stride, anything else as a dense per-pixel map."""
     # dot-product volume (``dot_scratch_device`` given): scratch that lets the arg-max pass of a plane-split launch combine per-group
     # results instead of re-reading the volume (idh_volume_opts.scratch); taken from torch's stream-ordered caching allocator
-    n_scratch = int(_lib.lib().idh_cost_volume_dot_scratch_floats(B, K, C, H, W, D)) if dot_scratch_device is not None else 0
-    if planes_bdhw is None and not cur_batch_stride and not src_batch_stride and not kernel and not n_scratch and not fv_keep_empty_views:
+    n_scratch = 0
+    if dot_scratch_device is not None and (kernel or win_units):
+        # a forced kernel or plane split (``win_units`` = idh_volume_opts.win_units_per_split, tests / profiling): the scratch THAT launch wants;
+        # an invalid combination sizes nothing here and is refused by the launch itself
+        n = ctypes.c_longlong(0)
+        if _lib.lib().idh_cost_volume_dot_plan(B, K, C, H, W, D, int(kernel), int(win_units), None, None, None, None, ctypes.byref(n)) == 0:
+            n_scratch = int(n.value)
+    elif dot_scratch_device is not None:
+        n_scratch = int(_lib.lib().idh_cost_volume_dot_scratch_floats(B, K, C, H, W, D))
+    if planes_bdhw is None and not cur_batch_stride and not src_batch_stride and not kernel and not n_scratch and not fv_keep_empty_views and not win_units:
         return None, []
     o = _lib.VolumeOpts()
     o.cur_batch_stride, o.src_batch_stride, o.kernel = int(cur_batch_stride), int(src_batch_stride), int(kernel)
+    o.win_units_per_split = int(win_units)  # dot-product volume, window kernel: 0 = the launcher's plane split
     o.fv_keep_empty_views = int(fv_keep_empty_views)  # MLP feature volume: 0 = the launch picks its kernel, 1 = fv_mlp_k (every view processed), 2 = fv_mlp_skip_k
     keep = []
     if n_scratch:
@@ -97,6 +107,7 @@ class CostVolumeManager(nn.Module):
         self.backprojector = BackprojectDepth(height=matching_height, width=matching_width)
         self.projector = Project3D()
         self.kernel = 0  # 0 = the launcher's choice; _lib.CV_KERNEL_* forces one of the three dot-volume kernels (tests / profiling)
+        self.win_units = 0  # 0 = the launcher's plane split; else 4-plane units per workgroup of the window kernel (idh_volume_opts.win_units_per_split)
 
     # -- helpers ------------------------------------------------------------------------
     def _check(self, cur_feats, src_feats):
@@ -142,7 +153,8 @@ class CostVolumeManager(nn.Module):
         lowest = torch.empty(B, H, W, device=dev, dtype=torch.float32)
         L = _lib.lib()
         planes_t, dmin, dmax = self._planes_arg(B, min_depth, max_depth, depth_planes_bdhw)
-        opts, keep = volume_opts(B, K, C, H, W, D, planes_t, kernel=self.__dict__.get("kernel", 0), dot_scratch_device=dev)
+        opts, keep = volume_opts(B, K, C, H, W, D, planes_t, kernel=self.__dict__.get("kernel", 0), dot_scratch_device=dev,
+                                 win_units=self.__dict__.get("win_units", 0))
         planes_d = torch.empty(D, device=dev, dtype=torch.float32) if planes_t is None else None
         # keep the contiguous copies alive until the launch is enqueued (a temporary's block may be
         # recycled by the next .contiguous() before the kernel runs)

@@ -13,6 +13,8 @@ extern "C" int idh_version(void) { return 111; }  // 101: idh_volume_opts.scratc
                                                    // 111: idh_conv_select / idh_conv_tuning_defaults / idh_schedule_ops (csrc/plan_select.hip): the one kernel-selection rule and level scheduler of both plan builders
                                                    // (still 111) idh_binary_mlp_rays_fwd / idh_project_points_fwd (csrc/mlp_rays.hip) are additive: no struct, code or packed layout changed, so the
                                                    //      version stays; a binding that needs them finds them missing by name when it loads an older library
+                                                   // (still 111) idh_volume_opts.reserved0 is now win_units_per_split (same offset and size; 0 = what every caller wrote there = automatic) and
+                                                   //      idh_cost_volume_dot_plan (host-only query of the window kernel's plane split and scratch layout) is additive
 extern "C" size_t idh_sizeof_volume_opts(void) { return sizeof(idh_volume_opts); }
 
 extern "C" const char *idh_error_string(int code) {

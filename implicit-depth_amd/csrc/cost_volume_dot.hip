@@ -543,6 +543,7 @@ struct RunEntry {
     int info;  // wneed | hneed << 8 | mode << 16 | j0 << 18 | (L - 1) << 22 | pair << 26
 };
 constexpr int kRunsPerPair = 16;  // worst case: sixteen single planes
+static_assert(kMaxPairs * kRunsPerPair <= 256, "a task's run list has at most 256 entries = one per thread of cv_dot_win_k, which clamps the count it reads from the scratch to this");
 constexpr int kCntOff = 16384;  // prologue scratch inside the window: PlaneBox at 0, per-pair counts here
 
 // The run list of one (frame, tile, plane group) task: pass 1 = per (pair, plane) the tap bounding box of the four tile corners, pass 2 = one
@@ -755,9 +756,10 @@ __global__ __launch_bounds__(256, 4) void cv_dot_win_k(const WinArgs a) {
     // ---- run list of this (tile, plane group): built here, or (a.runs: idh_volume_opts.scratch large enough) read from the list cv_runs_k left ----
     if (a.runs != nullptr) {
         const int *rl = a.runs + (size_t)((((size_t)b * a.tiles_y + ty) * a.tiles_x + tx) * a.psplit + sp) * a.runs_stride;
-        const int cnt = rl[0];
+        // never past the list, whatever the scratch holds (the constant bound lets the compiler see that the loop runs at most once)
+        const int cnt = min(rl[0], min(a.list_bytes / (int)sizeof(RunEntry), kMaxPairs * kRunsPerPair));
         if (tid == 0) s_total = cnt;
-        if (tid < cnt) s_list[tid] = RunEntry{rl[1 + 2 * tid], rl[2 + 2 * tid]};
+        for (int i = tid; i < cnt; i += 256) s_list[i] = RunEntry{rl[1 + 2 * i], rl[2 + 2 * i]};
     } else {
         cv_build_runs(a, s_h, s_planes, reinterpret_cast<PlaneBox *>(s_win), s_cnt, s_list, &s_total, b, px0, py0, sg0, nsg, ua, ub, tid, 256);
     }
@@ -1104,6 +1106,38 @@ static void cv_win_split(int B, int K, int H, int W, int D, int *psplit, int *un
     *psplit = idh_cdiv(nunits, per);
 }
 
+// Everything the host decides about one window-kernel launch: the plane split (cv_win_split, or idh_volume_opts.win_units_per_split) and the
+// layout of the optional scratch.  The one place it is worked out: the launch, idh_cost_volume_dot_plan and idh_cost_volume_dot_scratch_floats call it.
+struct CvWinPlan {
+    int psplit, units_per_split;
+    int list_entries;          // capacity of one task's run list: pairs x kRunsPerPair
+    int runs_stride;           // ints per task in the scratch: count + (xy, info) x list_entries
+    long long partial_floats;  // arg-max partials in front of the run lists (0 when one workgroup owns all planes of a tile)
+    long long tasks;           // (frame, tile, plane group) tasks = workgroups
+    long long scratch_floats;  // partial_floats + tasks * runs_stride
+};
+// `forced_units`: 0 = the automatic rule; otherwise 1, 2 or a multiple of 4 (clamped to the super-groups D has), else IDH_EINVAL
+static int cv_win_plan(int B, int K, int H, int W, int D, int forced_units, CvWinPlan *p) {
+    int psplit = 1, per = 0;
+    const int nunits = (D + 3) / 4;
+    if (forced_units == 0) {
+        cv_win_split(B, K, H, W, D, &psplit, &per);
+    } else {
+        if (forced_units < 0 || (forced_units != 1 && forced_units != 2 && (forced_units & 3) != 0)) return IDH_EINVAL;
+        per = forced_units < 4 * idh_cdiv(nunits, 4) ? forced_units : 4 * idh_cdiv(nunits, 4);
+        if ((long long)(per / 4) * K > kMaxPairs) return IDH_EINVAL;
+        psplit = idh_cdiv(nunits, per);
+    }
+    p->psplit = psplit;
+    p->units_per_split = per;
+    p->list_entries = ((per + 3) / 4) * K * kRunsPerPair;
+    p->runs_stride = 1 + 2 * p->list_entries;
+    p->partial_floats = psplit > 1 ? 2ll * psplit * B * H * W : 0;
+    p->tasks = (long long)B * idh_cdiv(W, kTileW) * idh_cdiv(H, kTileH) * psplit;
+    p->scratch_floats = p->partial_floats + p->tasks * p->runs_stride;
+    return IDH_OK;
+}
+
 // 0 = automatic; otherwise the caller's choice when that kernel covers the shape (else -1)
 static int cv_pick_kernel(int forced, int B, int K, int H, int W, int D, int C = kC) {
     if (C != kC) return (forced == 0 || forced == IDH_CV_KERNEL_LANE) ? IDH_CV_KERNEL_LANE : -1;  // wider texels: the lane kernel only
@@ -1162,18 +1196,20 @@ extern "C" int idh_cost_volume_dot_ex_fwd(const float *cur_nhwc, const float *sr
         a.cost = cost; a.lowest = lowest_bhw; a.planes_out = planes_d; a.dmin = dmin; a.dmax = dmax;
         a.B = B; a.K = K; a.H = H; a.W = W; a.D = D; a.cost_cs = cost_nhwc_cs; a.ext = ext;
         a.tiles_x = idh_cdiv(W, kTileW); a.tiles_y = idh_cdiv(H, kTileH);
-        cv_win_split(B, K, H, W, D, &a.psplit, &a.units_per_split);
+        // the plane split: the automatic rule, or the caller's (idh_volume_opts.win_units_per_split, a test / profiling hook)
+        const int forced_units = (opts && opts->struct_size >= (int64_t)(offsetof(idh_volume_opts, win_units_per_split) + sizeof(int32_t))) ? opts->win_units_per_split : 0;
+        CvWinPlan plan;
+        if (int rc = cv_win_plan(B, K, H, W, D, forced_units, &plan)) return rc;
+        a.psplit = plan.psplit; a.units_per_split = plan.units_per_split;
         // optional scratch for the arg-max over split planes (idh_volume_opts.scratch: >= idh_cost_volume_dot_scratch_floats)
         a.partial = (opts && opts->struct_size >= (int64_t)(offsetof(idh_volume_opts, struct_size) + sizeof(int64_t)) && opts->scratch && lowest_bhw && a.psplit > 1 &&
-                     opts->scratch_floats >= 2ll * a.psplit * B * H * W) ? opts->scratch : nullptr;
-        a.list_bytes = ((a.units_per_split + 3) / 4) * K * kRunsPerPair * (int)sizeof(RunEntry);
+                     opts->scratch_floats >= plan.partial_floats) ? opts->scratch : nullptr;
+        a.list_bytes = plan.list_entries * (int)sizeof(RunEntry);
         // ... and, behind the arg-max partials, for the run lists of every (frame, tile, plane group) task, built by cv_runs_k ahead of the volume kernel
         {
             const bool scratch_ok = opts && opts->struct_size >= (int64_t)(offsetof(idh_volume_opts, struct_size) + sizeof(int64_t)) && opts->scratch;
-            const long long part = a.psplit > 1 ? 2ll * a.psplit * B * H * W : 0;
-            const long long tasks = (long long)B * a.tiles_x * a.tiles_y * a.psplit;
-            a.runs_stride = 1 + 2 * (a.list_bytes / (int)sizeof(RunEntry));
-            a.runs = (scratch_ok && tasks < (1ll << 31) && opts->scratch_floats >= part + tasks * a.runs_stride) ? reinterpret_cast<const int *>(opts->scratch + part) : nullptr;
+            a.runs_stride = plan.runs_stride;
+            a.runs = (scratch_ok && plan.tasks < (1ll << 31) && opts->scratch_floats >= plan.scratch_floats) ? reinterpret_cast<const int *>(opts->scratch + plan.partial_floats) : nullptr;
 #ifdef IDH_DOT_NO_PREPASS
             a.runs = nullptr;
 #endif
@@ -1230,15 +1266,26 @@ extern "C" int idh_cost_volume_dot_ex_fwd(const float *cur_nhwc, const float *sr
     return IDH_OK;
 }
 
+extern "C" int idh_cost_volume_dot_plan(int B, int K, int C, int H, int W, int D, int kernel, int win_units_per_split, int *psplit, int *units_per_split,
+                                        long long *partial_floats, int *runs_stride, long long *scratch_floats) {
+    if (B <= 0 || K < 0 || H <= 0 || W <= 0 || D <= 0 || D > kMaxPlanes || K > IDH_MAX_SOURCE_VIEWS) return IDH_EINVAL;
+    const int which = cv_pick_kernel(kernel, B, K, H, W, D, C);
+    if (which < 0) return IDH_EINVAL;
+    CvWinPlan plan{};  // another kernel takes the launch: no split, no scratch
+    if (which == IDH_CV_KERNEL_WINDOW)
+        if (int rc = cv_win_plan(B, K, H, W, D, win_units_per_split, &plan)) return rc;
+    if (psplit) *psplit = plan.psplit;
+    if (units_per_split) *units_per_split = plan.units_per_split;
+    if (partial_floats) *partial_floats = plan.partial_floats;
+    if (runs_stride) *runs_stride = plan.runs_stride;
+    if (scratch_floats) *scratch_floats = plan.scratch_floats;  // arg-max partials of the split planes + the run lists cv_runs_k builds ahead of the volume
+                                                                // kernel (either part is optional: a shorter scratch only forgoes what does not fit)
+    return IDH_OK;
+}
+
 extern "C" long long idh_cost_volume_dot_scratch_floats(int B, int K, int C, int H, int W, int D) {
-    if (B <= 0 || K < 0 || H <= 0 || W <= 0 || D <= 0 || cv_pick_kernel(0, B, K, H, W, D, C) != IDH_CV_KERNEL_WINDOW) return 0;
-    int psplit = 1, per = 0;
-    cv_win_split(B, K, H, W, D, &psplit, &per);
-    // arg-max partials of the split planes + the run lists cv_runs_k builds ahead of the volume kernel (either part is optional: a shorter scratch
-    // only forgoes what does not fit)
-    const long long tasks = (long long)B * idh_cdiv(W, kTileW) * idh_cdiv(H, kTileH) * psplit;
-    const long long stride = 1 + 2ll * ((per + 3) / 4) * K * kRunsPerPair;
-    return (psplit > 1 ? 2ll * psplit * B * H * W : 0) + tasks * stride;
+    long long n = 0;
+    return idh_cost_volume_dot_plan(B, K, C, H, W, D, 0, 0, nullptr, nullptr, nullptr, nullptr, &n) == IDH_OK ? n : 0;
 }
 
 extern "C" const char *idh_cost_volume_dot_kernel_name(int B, int K, int H, int W, int D) {

@@ -93,7 +93,14 @@ typedef struct idh_volume_opts {
                                     can be dropped.  0 (default): each launch runs the faster of the two for its cameras (a device-side estimate, no
                                     synchronisation); 1: always fv_mlp_k, every view processed; 2: always fv_mlp_skip_k (A/B timing, tests).
                                     Appended after struct_size: honoured when struct_size reaches past it. */
-    int32_t reserved0;
+    int32_t win_units_per_split; /* dot-product volume, window kernel only (was reserved0: same offset, same struct size): 0 = automatic (the launcher's
+                                    rule), otherwise the number of 4-plane units one workgroup of cv_dot_win_k processes - a test / profiling hook so
+                                    that every plane split (4- and 8-plane slices, whole super-groups of 16 planes, several super-groups per
+                                    workgroup) can be checked against the same oracle at a small shape.  Must be 1, 2 or a multiple of 4; values
+                                    beyond the planes there are count as 4 * ceil(ceil(D / 4) / 4), and (units / 4) * K must stay <= 16 (the
+                                    per-workgroup pair table): anything else is IDH_EINVAL before any launch.  Results do not depend on it.  No
+                                    effect when another kernel takes the launch.  Honoured when struct_size reaches past it;
+                                    idh_cost_volume_dot_plan reports the split and the scratch a launch with this value wants. */
 } idh_volume_opts;
 
 /* sizeof(idh_volume_opts) as compiled into the library (bindings assert their mirror matches; idh_version() >= 101). */
@@ -132,6 +139,18 @@ int idh_cost_volume_dot_ex_fwd(const float *cur_nhwc, const float *src_nhwc, con
  * which a small kernel (cv_runs_k) then builds AHEAD of the volume kernel instead of every workgroup in its own prologue (~10 % of its life).  Results
  * are bit-identical with any scratch size: a scratch that only covers the first part just forgoes the second. */
 long long idh_cost_volume_dot_scratch_floats(int B, int K, int C, int H, int W, int D);
+
+/* Host-only query (additive: idh_version() stays as it is; no device access, usable without a GPU): what a launch of these dimensions with
+ * idh_volume_opts.kernel = `kernel` and .win_units_per_split = `win_units_per_split` (0 / 0 = automatic) would do - the function the launch calls.
+ *   psplit            plane groups = workgroups per tile; > 1: a second, small kernel finishes the arg-max
+ *   units_per_split   4-plane units per workgroup (the effective value of the hook)
+ *   partial_floats    floats of arg-max partials at the start of the scratch (0 when psplit == 1); the run lists start behind them
+ *   runs_stride       ints per (frame, tile, plane group) task in the run-list part: {count, (xy, info) x capacity}, task = ((b ty) tx) psplit + group
+ *   scratch_floats    partial_floats + tasks * runs_stride = idh_cost_volume_dot_scratch_floats for kernel = win_units_per_split = 0
+ * All five are 0 when another kernel takes the launch.  Any output pointer may be NULL.  IDH_EINVAL for dimensions, a kernel or a split the launch
+ * refuses too. */
+int idh_cost_volume_dot_plan(int B, int K, int C, int H, int W, int D, int kernel, int win_units_per_split, int *psplit, int *units_per_split,
+                             long long *partial_floats, int *runs_stride, long long *scratch_floats);
 
 /* Name of the kernel idh_cost_volume_dot*_fwd launches for this shape (what rocprofv3 --kernel-trace will show);
  * lets bench.py label its roofline without guessing the launcher's choice. */

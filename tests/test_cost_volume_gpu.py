@@ -242,8 +242,9 @@ def test_every_kernel_matches_reference_golden(name, kernel):
 def test_window_kernel_matches_oracle_fp64(shape):
     """Ragged tiles (maps that are not multiples of 32 x 8), D not a multiple of 16 or 4, K up to 16, views behind the
     camera and strongly rotated views, batch > 1; the smallest map the kernel takes (48 x 12) with many planes (the
-    launch splits the planes over workgroups and runs the separate arg-max kernel) and a batch large enough that it
-    does not; 5 x 5 and 3 x 7 tile grids over many frames with 3 and 5 plane groups (the task order rotates plane groups and
+    launch splits the planes over workgroups and runs the separate arg-max kernel) and the same map with 40 frames (still
+    five plane groups: every shape here runs one 4-plane unit per workgroup; tests/test_cost_volume_split_gpu.py runs the
+    larger splits and the arg-max inside the kernel); 5 x 5 and 3 x 7 tile grids over many frames with 3 and 5 plane groups (the task order rotates plane groups and
     tile columns: every (tile, group) must still be computed exactly once)."""
     B, K, C, H, W, D = shape
     inp = syn.cost_volume_inputs(B, K, C, H, W, seed=B + K, behind_view=K - 1 if K > 2 else -1, big_rotation_view=0 if K > 3 else -1)
