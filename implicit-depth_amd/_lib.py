@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IDH_LIB") or os.path.join(_HERE, "lib", "libidh.so")
 
 _lib = None
-MIN_ABI_VERSION = 111
+MIN_ABI_VERSION = 112
 
 f32p = C.c_void_p  # device pointers travel as integers
 
@@ -284,8 +284,12 @@ class ConvChoice(C.Structure):
                                          "direct_tile_m", "direct_tile_n", "direct_split_k")]
 
 
+# idh_plan_observer of include/idh_net.h: (ops, n, n_first, order, ws, ws_floats, blob, blob_floats, user); ops = n nhwc.Op descriptors
+PlanObserver = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p)
+
 _SIGS = {
     "idh_version": (C.c_int, []),
+    "idh_debug_set_plan_observer": (None, [PlanObserver, C.c_void_p]),
     "idh_sizeof_volume_opts": (C.c_size_t, []),
     "idh_cost_volume_dot_scratch_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "idh_cost_volume_dot_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),

@@ -1,6 +1,6 @@
 #include "idh_common.h"
 
-extern "C" int idh_version(void) { return 111; }  // 101: idh_volume_opts.scratch / scratch_floats / struct_size; 102: Winograd F(4x4) conv (IDH_TILE_WINO4);
+extern "C" int idh_version(void) { return 112; }  // 101: idh_volume_opts.scratch / scratch_floats / struct_size; 102: Winograd F(4x4) conv (IDH_TILE_WINO4);
                                                    // 103: struct_size accepted when >= the fields it guards, hidden visibility (the C ABI is the only export);
                                                    // 104: IDH_OP_POINTWISE_UP, tile_m 8 / 9 for a lone 3x3 stride-2 source, split-K boundaries of the LDS conv in cost units
                                                    // 105: idh_binary_mlp_fwd takes any feature row stride / 4-byte-aligned base; network-level entry points idh_basic_block_fwd,
@@ -15,6 +15,8 @@ extern "C" int idh_version(void) { return 111; }  // 101: idh_volume_opts.scratc
                                                    //      version stays; a binding that needs them finds them missing by name when it loads an older library
                                                    // (still 111) idh_volume_opts.reserved0 is now win_units_per_split (same offset and size; 0 = what every caller wrote there = automatic) and
                                                    //      idh_cost_volume_dot_plan (host-only query of the window kernel's plane split and scratch layout) is additive
+                                                   // 112: idh_debug_set_plan_observer (include/idh_net.h): a host-only hook that shows every scheduled plan of csrc/networks.hip; the made-up addresses
+                                                   //      of the *_sizes plans no longer collide (one range per caller-owned tensor, workspace and blob apart)
 extern "C" size_t idh_sizeof_volume_opts(void) { return sizeof(idh_volume_opts); }
 
 extern "C" const char *idh_error_string(int code) {

@@ -37,6 +37,18 @@ __global__ __launch_bounds__(256) void bias_sum_k(const float *__restrict__ a, c
 
 enum Mode { MODE_SIZES, MODE_PACK, MODE_RUN };
 
+// idh_debug_set_plan_observer (include/idh_net.h): called by Plan::finish with the scheduled op list; host only, off by default
+idh_plan_observer g_observer = nullptr;
+void *g_observer_user = nullptr;
+
+// Addresses of a plan that is never run (MODE_SIZES / MODE_PACK): nothing dereferences them, but a plan audit reads them, so two distinct tensors
+// never share a float - 16 TiB per class, 256 GiB per caller-owned tensor (the largest, B = 32 at 384 x 512, stays under 2 GiB)
+constexpr int kFakeClassShift = 44, kFakeTensorShift = 38;
+enum FakeClass : uintptr_t { FAKE_WS = 1, FAKE_EXTERNAL = 2, FAKE_BLOB = 3, FAKE_PHANTOM = 7 };
+inline float *fake_address(FakeClass c, size_t index = 0) {
+    return reinterpret_cast<float *>(((uintptr_t)c << kFakeClassShift) + ((uintptr_t)index << kFakeTensorShift));
+}
+
 struct Buf {
     float *base;  // device address of channel 0 of pixel 0 (a fake, aligned address in MODE_SIZES / MODE_PACK)
     int N, H, W, cs;
@@ -73,8 +85,8 @@ struct Norm {
 class Plan {
   public:
     Plan(Mode mode, float *ws, size_t ws_cap, float *blob, hipStream_t st) : mode_(mode), ws_(ws), ws_cap_(ws_cap), blob_(blob), st_(st) {
-        if (mode_ != MODE_RUN) ws_ = reinterpret_cast<float *>(uintptr_t(1) << 32);   // fake, aligned: only offsets matter
-        if (mode_ == MODE_SIZES) blob_ = reinterpret_cast<float *>(uintptr_t(1) << 40);
+        if (mode_ != MODE_RUN) ws_ = fake_address(FAKE_WS);   // fake, aligned: only offsets matter
+        if (mode_ == MODE_SIZES) blob_ = fake_address(FAKE_BLOB);
     }
 
     int err = IDH_OK;
@@ -127,15 +139,17 @@ class Plan {
     View phantom(int n, int h, int w, int c, int cs_) {
         Buf b{};
         b.N = n; b.H = h; b.W = w; b.cs = cs_; b.internal = false; b.zero_fill = false;
-        b.base = reinterpret_cast<float *>((uintptr_t(7) << 32) + ((uintptr_t)bufs.size() << 24));
+        b.base = fake_address(FAKE_PHANTOM, bufs.size());
         bufs.push_back(b);
         return View{(int)bufs.size() - 1, 0, c};
     }
+    // A caller-owned tensor of a plan that is never run: each gets an address range of its own
+    float *fake_tensor() { return fake_address(FAKE_EXTERNAL, n_fake_++); }
     // A caller-owned NHWC tensor as a view (read or written in place)
     View external(const idh_tensor &t, int n) {
         Buf b{};
         b.N = n; b.H = t.H; b.W = t.W; b.cs = t.cs; b.internal = false; b.zero_fill = false;
-        b.base = mode_ == MODE_RUN ? t.ptr : reinterpret_cast<float *>((uintptr_t(2) << 32) + ((uintptr_t)bufs.size() << 24));
+        b.base = mode_ == MODE_RUN ? t.ptr : fake_tensor();
         bufs.push_back(b);
         return View{(int)bufs.size() - 1, 0, t.C};
     }
@@ -256,7 +270,7 @@ class Plan {
         idh_op op;
         std::memset(&op, 0, sizeof op);
         op.kind = IDH_OP_NCHW_TO_NHWC; op.N = n;
-        op.src[0].in = mode_ == MODE_RUN ? src : reinterpret_cast<const float *>(uintptr_t(3) << 32);
+        op.src[0].in = mode_ == MODE_RUN ? src : fake_tensor();
         op.src[0].H = H_; op.src[0].W = W_; op.src[0].Cin = C;
         op.out = ptr(out); op.out_cs = cs(out);
         ops.push_back(op);
@@ -269,7 +283,7 @@ class Plan {
         op.kind = IDH_OP_NHWC_TO_NCHW; op.N = N(x);
         idh_conv_src &s = op.src[0];
         s.in = ptr(x); s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
-        op.out = mode_ == MODE_RUN ? dst : reinterpret_cast<float *>(uintptr_t(4) << 32);
+        op.out = mode_ == MODE_RUN ? dst : fake_tensor();
         ops.push_back(op);
         meta.push_back(Meta{{region(x)}, {}});
     }
@@ -288,7 +302,7 @@ class Plan {
         idh_conv_src &s = op.src[0];
         s.in = ptr(x); s.w = w; s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
         op.bias = b;
-        op.out = mode_ == MODE_RUN ? out : reinterpret_cast<float *>(uintptr_t(5) << 32);
+        op.out = mode_ == MODE_RUN ? out : fake_tensor();
         op.ws = mode_ == MODE_RUN ? out_exp : nullptr;
         ops.push_back(op);
         meta.push_back(Meta{{region(x)}, {}});
@@ -332,7 +346,7 @@ class Plan {
         std::memset(&op, 0, sizeof op);
         op.kind = IDH_OP_POINTWISE_NCHW; op.N = n;
         idh_conv_src &s = op.src[0];
-        s.in = mode_ == MODE_RUN ? src : reinterpret_cast<const float *>(uintptr_t(6) << 32);
+        s.in = mode_ == MODE_RUN ? src : fake_tensor();
         s.w = packed(cv, IDH_W_DIRECT); s.H = H_; s.W = W_; s.Cin = C; s.ks = 1; s.stride = 1;
         op.bias = bias_of(cv, nullptr);
         op.out = ptr(out); op.out_cs = cs(out); op.Ho = H_; op.Wo = W_; op.Cout = cv.cout;
@@ -347,7 +361,7 @@ class Plan {
         std::memset(&op, 0, sizeof op);
         op.kind = IDH_OP_STEM; op.N = n;
         idh_conv_src &s = op.src[0];
-        s.in = mode_ == MODE_RUN ? images : reinterpret_cast<const float *>(uintptr_t(3) << 32);
+        s.in = mode_ == MODE_RUN ? images : fake_tensor();
         s.w = blob; s.H = h; s.W = w; s.Cin = 3;
         s.up_C = n; s.up_cs[0] = 3 * h * w; s.up_cs[1] = n * 3 * h * w;  // (Plan.stem: one group of N dense images)
         op.out = ptr(out); op.out_cs = cs(out); op.Ho = H(out); op.Wo = W(out); op.Cout = 64;
@@ -392,7 +406,7 @@ class Plan {
 
     // ---- Plan.schedule_segments: idh_schedule_ops over the regions recorded per op (ops [0, n_first) and the rest are levelled and ordered each
     // on their own - the volume kernel runs between them)
-    int schedule(int n_first = 0) {
+    int schedule(int n_first, std::vector<int32_t> &order) {
         std::vector<Region> flat;
         std::vector<int32_t> offs{0};
         for (const Meta &m : meta)
@@ -401,11 +415,14 @@ class Plan {
                 offs.push_back((int32_t)flat.size());
             }
         flat.push_back(Region{});  // (a non-NULL array for a plan whose ops touch nothing)
-        return idh_schedule_ops(ops.data(), (int)ops.size(), n_first, &flat[0].buf, offs.data(), IDH_SCHED_MERGE_LEVELS | IDH_SCHED_WINO_GROUP, nullptr, nullptr);
+        order.assign(ops.size() + 1, 0);  // (+ 1: non-NULL for an empty plan)
+        return idh_schedule_ops(ops.data(), (int)ops.size(), n_first, &flat[0].buf, offs.data(), IDH_SCHED_MERGE_LEVELS | IDH_SCHED_WINO_GROUP, order.data(), nullptr);
     }
 
     int finish(idh_net_sizes *sizes, int n_first = 0) {
-        if (err || (err = schedule(n_first)) != IDH_OK) return err;
+        std::vector<int32_t> order;
+        if (err || (err = schedule(n_first, order)) != IDH_OK) return err;
+        if (g_observer) g_observer(ops.data(), (int)ops.size(), n_first, order.data(), ws_, ws_off, blob_, blob_off, g_observer_user);
         if (sizes) {
             sizes->workspace_floats = ws_off;
             sizes->weight_floats = blob_off;
@@ -438,6 +455,7 @@ class Plan {
     float *blob_;
     hipStream_t st_;
     bool dry_ = false;  // reserve_block
+    size_t n_fake_ = 0;  // fake_tensor
     std::map<std::tuple<int, int, int, int>, std::vector<int>> free_;
 };
 
@@ -752,6 +770,11 @@ int idh_internal::conv_stage(int mode, ConvStage *s, float *ws, size_t ws_cap, f
         s->layout_hash = layout_hash(p.ops);
     }
     return IDH_OK;
+}
+
+extern "C" void idh_debug_set_plan_observer(idh_plan_observer fn, void *user) {
+    g_observer = fn;
+    g_observer_user = user;
 }
 
 extern "C" int idh_basic_block_sizes(const idh_block_params *blk, int N, const idh_tensor *x, const idh_tensor *out, idh_net_sizes *sizes) {

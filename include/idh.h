@@ -316,7 +316,7 @@ int idh_sample_prior_fwd(const float *rendered_depth_bphw, const float *prior_pr
                          const float *K_44, const float *invK_44, int B, int P, int H, int W,
                          float *out_bphw, void *stream);
 
-/* ---- occlusion queries at sparse rays and 3D points (additive: idh_version() stays 111; csrc/mlp_rays.hip) -------- */
+/* ---- occlusion queries at sparse rays and 3D points (additive: idh_version() stayed 111; csrc/mlp_rays.hip) -------- */
 /* Fused form of BDModel.run_mlp_train's ray path (reference experiment_modules/bd_model.py:313-393): per ray, the feature row is
  * sampled bilinearly from an NHWC map (F.grid_sample, align_corners=False, zero padding, :357-362) and the S depth samples of the ray go
  * through the MLP of idh_binary_mlp_fwd on that one row:

@@ -150,6 +150,20 @@ int idh_matching_stem_pack(const idh_stem_params *params, int N, const idh_tenso
 int idh_matching_stem_fwd(const idh_stem_params *params, const float *weight_blob, int N, const idh_tensor *images, const idh_tensor *out,
                           float *workspace, size_t workspace_floats, void *stream);
 
+/* ---- debugging hook: the op list of every plan the builders above (and idh_model_sizes / _fwd) schedule (ABI >= 112) ------------------------
+ * After idh_schedule_ops and before anything is launched (the *_sizes queries launch nothing), the builder calls fn with the scheduled
+ * descriptors: ops[0 .. n) in launch order, ops [0, n_first) and the rest being the two segments of idh_schedule_ops; order[i] = the build
+ * index of the op at position i; [ws, ws + ws_floats) = the workspace range the plan carved its buffers, split-K partials and InstanceNorm
+ * workspaces from; [blob, blob + blob_floats) = the weight blob range of its packed weights and biases.  A *_sizes query has no memory: its
+ * addresses are made up (aligned, never dereferenced) such that two distinct tensors never share a float, and no caller-owned tensor shares
+ * one with the workspace or the blob.  The arrays belong to the builder and die when fn returns.  Host only: no device access, no effect on
+ * what is launched.  One process-global hook, not thread safe; fn == NULL clears it; off by default.  tests/plan_audit.py checks plans
+ * through it. */
+struct idh_op; /* include/idh_ops.h */
+typedef void (*idh_plan_observer)(const struct idh_op *ops, int n, int n_first, const int32_t *order, const float *ws, size_t ws_floats,
+                                  const float *blob, size_t blob_floats, void *user);
+void idh_debug_set_plan_observer(idh_plan_observer fn, void *user);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

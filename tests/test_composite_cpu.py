@@ -164,7 +164,7 @@ def test_composite_entry_validates_before_launching():
 
     L = _lib.lib()
     EINVAL, EUNSUPPORTED = -1, -2
-    assert L.idh_version() == 111
+    assert L.idh_version() == 112
     assert L.idh_sizeof_composite_args() == C.sizeof(_lib.CompositeArgs) == _lib.CompositeArgs().struct_size
     call = lambda a: L.idh_composite_fwd(C.byref(a), None)
     assert L.idh_composite_fwd(None, None) == EINVAL

@@ -35,8 +35,8 @@ def test_version_and_exports():
     from implicit_depth_amd import _lib
 
     L = _lib.lib()
-    assert L.idh_version() == 111
-    for s in ("idh_model_sizes", "idh_model_pack", "idh_model_fwd"):
+    assert L.idh_version() == 112
+    for s in ("idh_model_sizes", "idh_model_pack", "idh_model_fwd", "idh_debug_set_plan_observer"):
         assert s in _lib.declared_symbols()
 
 
