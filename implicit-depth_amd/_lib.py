@@ -250,6 +250,33 @@ class TsdfMeshColorsArgs(C.Structure):
         self.mesh.struct_size = C.sizeof(TsdfMeshArgs)
 
 
+class TsdfIntegrateWeightedArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_integrate_weighted_args`` (include/idh_fusion.h, per-observation weights)."""
+
+    _fields_ = TsdfIntegrateColorArgs._fields_ + [("weight_m1hw", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfIntegrateWeightedArgs)
+
+
+class MvConsistencyArgs(C.Structure):
+    """ctypes mirror of ``idh_mv_consistency_args`` (include/idh_geometry.h, multi-view depth consistency)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_b1hw", C.c_void_p), ("gate_depth_b1hw", C.c_void_p), ("invK_b44", C.c_void_p),
+                ("world_T_cam_b44", C.c_void_p), ("src_depth_bk1hw", C.c_void_p), ("src_K_bk44", C.c_void_p), ("src_cam_T_world_bk44", C.c_void_p),
+                ("counts_b3hw", C.c_void_p), ("weight_b1hw", C.c_void_p), ("filtered_depth_b1hw", C.c_void_p), ("visible_bkhw", C.c_void_p),
+                ("err_bkhw", C.c_void_p), ("loss", C.c_void_p), ("loss_sum_k", C.c_void_p), ("loss_count_k", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("ratio", C.c_float), ("log_tol", C.c_float), ("min_consistent", C.c_int32),
+                ("max_conflict", C.c_int32), ("B", C.c_int32), ("K", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("src_h", C.c_int32),
+                ("src_w", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(MvConsistencyArgs)
+
+
+MV_MAX_SOURCES, MV_MAX_MAPS = 16, 128  # IDH_MV_MAX_*
 TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
 TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
 
@@ -386,6 +413,11 @@ _SIGS = {
     "idh_tsdf_integrate_color_fwd": (C.c_int, [C.POINTER(TsdfIntegrateColorArgs), C.c_void_p]),
     "idh_tsdf_raycast_color_fwd": (C.c_int, [C.POINTER(TsdfRaycastColorArgs), C.c_void_p]),
     "idh_tsdf_mesh_colors_fwd": (C.c_int, [C.POINTER(TsdfMeshColorsArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_integrate_weighted_args": (C.c_size_t, []),
+    "idh_tsdf_integrate_weighted_fwd": (C.c_int, [C.POINTER(TsdfIntegrateWeightedArgs), C.c_void_p]),
+    "idh_sizeof_mv_consistency_args": (C.c_size_t, []),
+    "idh_mv_consistency_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "idh_mv_consistency_fwd": (C.c_int, [C.POINTER(MvConsistencyArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -484,7 +516,9 @@ def lib():
                                   ("idh_tsdf_mesh_args", h.idh_sizeof_tsdf_mesh_args(), TsdfMeshArgs),
                                   ("idh_tsdf_integrate_color_args", h.idh_sizeof_tsdf_integrate_color_args(), TsdfIntegrateColorArgs),
                                   ("idh_tsdf_raycast_color_args", h.idh_sizeof_tsdf_raycast_color_args(), TsdfRaycastColorArgs),
-                                  ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs)):
+                                  ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs),
+                                  ("idh_tsdf_integrate_weighted_args", h.idh_sizeof_tsdf_integrate_weighted_args(), TsdfIntegrateWeightedArgs),
+                                  ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

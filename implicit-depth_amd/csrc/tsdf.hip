@@ -7,6 +7,7 @@
 //                     registers over the M maps: one 8-byte load at the first map that touches it, one 8-byte store at the end.
 //                     With IntegrateColorArgs the same kernel also averages a camera frame's tap into the voxel's {R, G, B, Wc} quad
 //                     (one 16-byte load and store per coloured voxel, three byte gathers per coloured voxel and map).
+//                     With Weighted<..> on top of either, a weight map tapped where the depth is scales the observation.
 //   tsdf_raycast_k<SKIP, NORMALS, Args>  one lane per pixel, an 8 x 8-pixel tile per wave.  A sample reads its eight corners as four 16-byte
 //                     loads: the x-neighbours {T0, W0, T1, W1} are adjacent in memory (8-byte aligned, which the global loads of gfx950
 //                     take).  SKIP clips the lattice range to the volume's box and jumps blocks whose flag is 0.  With RaycastColorArgs
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(256) void tsdf_flags_k(const Vol V) {
 
 struct IntegrateArgs {
     static constexpr bool kColor = false;
+    static constexpr bool kWeighted = false;
     Vol V;
     const float *depth, *K, *T;
     float max_weight;
@@ -76,9 +78,16 @@ struct IntegrateColorArgs : IntegrateArgs {
     int hc, wc;
 };
 
+// a per-observation weight map on top of either struct (again after the arguments that were there)
+template <class Base>
+struct Weighted : Base {
+    static constexpr bool kWeighted = true;
+    const float *weight;
+};
+
 template <class Args>
 __global__ __launch_bounds__(256) void tsdf_integrate_k(const Args a) {
-    constexpr bool COLOR = Args::kColor;
+    constexpr bool COLOR = Args::kColor, WEIGHTED = Args::kWeighted;
     const Vol &V = a.V;
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
     if (y >= V.Ny) return;  // whole wave
@@ -101,6 +110,11 @@ __global__ __launch_bounds__(256) void tsdf_integrate_k(const Args a) {
         const int j = (int)floorf(u), i = (int)floorf(v);
         const float d = a.depth[((size_t)m * a.h + i) * a.w + j];
         if (!valid_depth(d)) continue;
+        float g = 1.f;
+        if constexpr (WEIGHTED) {
+            g = a.weight[((size_t)m * a.h + i) * a.w + j];
+            if (!valid_depth(g)) continue;  // a weight that is not finite and > 0 makes the tap a hole
+        }
         const float sdf = d - cz;
         if (sdf < -V.trunc) continue;
         const float s = fminf(1.f, sdf / V.trunc);
@@ -109,28 +123,40 @@ __global__ __launch_bounds__(256) void tsdf_integrate_k(const Args a) {
             T = tw.x, W = tw.y;
             touched = true;
         }
-        T = (W * T + s) / (W + 1.f);
-        W = fminf(W + 1.f, a.max_weight);
+        if constexpr (WEIGHTED) {
+            T = (W * T + g * s) / (W + g);
+            W = fminf(W + g, a.max_weight);
+        } else {
+            T = (W * T + s) / (W + 1.f);
+            W = fminf(W + 1.f, a.max_weight);
+        }
         if constexpr (COLOR) {
             if (!(sdf <= V.trunc)) continue;  // free space in front of the band
             const float *Kc = a.Kc + m * 16;
             const float qx = Kc[0] * (cx / cz) + Kc[2], qy = Kc[5] * (cy / cz) + Kc[6];
             if (!(qx >= 0.f && qx < (float)a.wc && qy >= 0.f && qy < (float)a.hc)) continue;
             const uint8_t *tap = a.frames + (((size_t)m * a.hc + (int)floorf(qy)) * a.wc + (int)floorf(qx)) * 3;
-            const float r = (float)tap[0], g = (float)tap[1], b = (float)tap[2];
+            const float r = (float)tap[0], gr = (float)tap[1], b = (float)tap[2];
             float4 *quad = a.colors + (((size_t)z * V.Ny + y) * V.Nx + x);
             if (!coloured) col = *quad, coloured = true;
-            col.x = (col.w * col.x + r) / (col.w + 1.f);
-            col.y = (col.w * col.y + g) / (col.w + 1.f);
-            col.z = (col.w * col.z + b) / (col.w + 1.f);
-            col.w = fminf(col.w + 1.f, a.max_weight);
+            if constexpr (WEIGHTED) {
+                col.x = (col.w * col.x + g * r) / (col.w + g);
+                col.y = (col.w * col.y + g * gr) / (col.w + g);
+                col.z = (col.w * col.z + g * b) / (col.w + g);
+                col.w = fminf(col.w + g, a.max_weight);
+            } else {
+                col.x = (col.w * col.x + r) / (col.w + 1.f);
+                col.y = (col.w * col.y + gr) / (col.w + 1.f);
+                col.z = (col.w * col.z + b) / (col.w + 1.f);
+                col.w = fminf(col.w + 1.f, a.max_weight);
+            }
         }
     }
     if (touched) *cell = make_float2(T, W);
     if constexpr (COLOR) {
         if (coloured) a.colors[((size_t)z * V.Ny + y) * V.Nx + x] = col;
     }
-    mark_blocks(V, touched, x, y, z);  // a touched voxel has W >= 1
+    mark_blocks(V, touched, x, y, z);  // a touched voxel has W > 0
 }
 
 struct RaycastArgs {
@@ -352,6 +378,7 @@ extern "C" size_t idh_sizeof_tsdf_integrate_args(void) { return sizeof(idh_tsdf_
 extern "C" size_t idh_sizeof_tsdf_raycast_args(void) { return sizeof(idh_tsdf_raycast_args); }
 extern "C" size_t idh_sizeof_tsdf_integrate_color_args(void) { return sizeof(idh_tsdf_integrate_color_args); }
 extern "C" size_t idh_sizeof_tsdf_raycast_color_args(void) { return sizeof(idh_tsdf_raycast_color_args); }
+extern "C" size_t idh_sizeof_tsdf_integrate_weighted_args(void) { return sizeof(idh_tsdf_integrate_weighted_args); }
 
 extern "C" size_t idh_tsdf_block_flag_bytes(int Nz, int Ny, int Nx) {
     if (Nz < 2 || Ny < 2 || Nx < 2) return 0;
@@ -406,6 +433,33 @@ extern "C" int idh_tsdf_integrate_color_fwd(const idh_tsdf_integrate_color_args 
     a.max_weight = e.max_weight, a.M = e.M, a.h = e.h, a.w = e.w;
     a.colors = reinterpret_cast<float4 *>(e.colors_zyx4), a.frames = e.color_mhw3, a.Kc = e.color_K_m44, a.hc = e.hc, a.wc = e.wc;
     hipLaunchKernelGGL(tsdf_integrate_k<IntegrateColorArgs>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" int idh_tsdf_integrate_weighted_fwd(const idh_tsdf_integrate_weighted_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_integrate_weighted_args)) return IDH_EINVAL;
+    const idh_tsdf_integrate_weighted_args &e = *args;
+    const bool color = e.colors_zyx4 || e.color_mhw3 || e.color_K_m44;
+    if (e.M <= 0 || e.h <= 0 || e.w <= 0 || (color && (e.hc <= 0 || e.wc <= 0))) return IDH_EINVAL;
+    if (!(e.max_weight >= 1.f && e.max_weight < INFINITY)) return IDH_EINVAL;
+    if (!e.depth_m1hw || !e.K_m44 || !e.cam_T_world_m44 || !e.weight_m1hw) return IDH_EINVAL;
+    if (color && (!e.colors_zyx4 || !e.color_mhw3 || !e.color_K_m44 || ((uintptr_t)e.colors_zyx4 & 15u))) return IDH_EINVAL;
+    Weighted<IntegrateColorArgs> a;
+    if (const int rc = check_volume(e.volume, a.V)) return rc;
+    if (e.M > IDH_TSDF_MAX_MAPS || (long long)e.M * e.h * e.w >= (1ll << 31) || (color && (long long)e.M * e.hc * e.wc >= (1ll << 31))) return IDH_EUNSUPPORTED;
+    a.depth = e.depth_m1hw, a.K = e.K_m44, a.T = e.cam_T_world_m44;
+    a.max_weight = e.max_weight, a.M = e.M, a.h = e.h, a.w = e.w;
+    a.colors = reinterpret_cast<float4 *>(e.colors_zyx4), a.frames = e.color_mhw3, a.Kc = e.color_K_m44, a.hc = e.hc, a.wc = e.wc;
+    a.weight = e.weight_m1hw;
+    if (color) {
+        hipLaunchKernelGGL(tsdf_integrate_k<Weighted<IntegrateColorArgs>>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), a);
+    } else {
+        Weighted<IntegrateArgs> g;
+        static_cast<IntegrateArgs &>(g) = static_cast<const IntegrateArgs &>(a);
+        g.weight = e.weight_m1hw;
+        hipLaunchKernelGGL(tsdf_integrate_k<Weighted<IntegrateArgs>>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), g);
+    }
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }

@@ -94,8 +94,9 @@ class TSDFVolume:
         if self.colors is not None:
             self.colors.zero_()
 
-    def integrate(self, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None, color_K=None) -> None:
-        integrate_depth(self, depth_m1hw, K_m44, cam_T_world_m44, color_u8, color_K)
+    def integrate(self, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None, color_K=None,
+                  weight: Optional[torch.Tensor] = None) -> None:
+        integrate_depth(self, depth_m1hw, K_m44, cam_T_world_m44, color_u8, color_K, weight_m1hw=weight)
 
     def raycast(self, world_T_cam_b44, invK_b44, size: Sequence[int], near: float = 0.25, far: float = 8.0, step_voxels: float = 1.0,
                 empty_depth: float = -1.0, return_normals: bool = False, world_normals: bool = True, skip: bool = False,
@@ -113,7 +114,7 @@ class TSDFVolume:
 
 
 def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None,
-                    color_K=None) -> None:
+                    color_K=None, weight_m1hw: Optional[torch.Tensor] = None) -> None:
     """Average M depth maps (M,1,h,w) into ``volume`` in one launch (idh_tsdf_integrate_fwd): ``K_m44`` their intrinsics at h x w,
     ``cam_T_world_m44`` their poses ((4,4) or (M,4,4), tensors or arrays).  Taps that are not finite and positive are holes.  M is at most
     ``pipeline.MAX_RING_CAPACITY``.  One call with M maps equals M calls with one map each, bit for bit.
@@ -121,8 +122,14 @@ def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_w
     ``color_u8``: the M camera frames of the maps, uint8 (M,hc,wc,3) RGB on the GPU, averaged into ``volume.colors`` in the same launch
     (idh_tsdf_integrate_color_fwd; ``values`` and ``block_flags`` get the same bits as without).  ``color_K`` their intrinsics at
     hc x wc; None is allowed only when (hc, wc) == (h, w) and then means ``K_m44``.  Without ``color_u8`` the colours are left as they
-    are (depth-only maps)."""
-    _lib.require_cuda_f32(depth_m1hw)
+    are (depth-only maps).
+
+    ``weight_m1hw`` (M,1,h,w): a weight per depth sample (idh_tsdf_integrate_weighted_fwd), e.g. the "weight" of
+    ``geometry.depth_consistency``: a sample enters the averages of T and of the colour with that weight and adds it to W and Wc; one
+    whose weight is not finite and positive is skipped like a hole.  Weights of 1 give the bits of the call without weights."""
+    _lib.require_cuda_f32(depth_m1hw, weight_m1hw)
+    if weight_m1hw is not None and weight_m1hw.shape != depth_m1hw.shape:
+        raise _lib.IdhError(f"integrate_depth: weight {tuple(weight_m1hw.shape)} must be {tuple(depth_m1hw.shape)}")
     if depth_m1hw.dim() != 4 or depth_m1hw.shape[1] != 1:
         raise _lib.IdhError(f"integrate_depth: depth {tuple(depth_m1hw.shape)} must be (M,1,h,w)")
     M, _, h, w = depth_m1hw.shape
@@ -147,12 +154,16 @@ def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_w
             if Kc.shape[0] != M:
                 raise _lib.IdhError(f"integrate_depth: {M} frames need ({M},4,4) color_K, got {tuple(Kc.shape)}")
         frames = color_u8.contiguous()
-        a = _lib.TsdfIntegrateColorArgs()
+        a = _lib.TsdfIntegrateColorArgs() if weight_m1hw is None else _lib.TsdfIntegrateWeightedArgs()
         a.colors_zyx4, a.color_mhw3, a.color_K_m44, a.hc, a.wc = volume.colors.data_ptr(), frames.data_ptr(), Kc.data_ptr(), hc, wc
         fn, name = _lib.lib().idh_tsdf_integrate_color_fwd, "idh_tsdf_integrate_color_fwd"
     else:
-        a = _lib.TsdfIntegrateArgs()
+        a = _lib.TsdfIntegrateArgs() if weight_m1hw is None else _lib.TsdfIntegrateWeightedArgs()
         fn, name = _lib.lib().idh_tsdf_integrate_fwd, "idh_tsdf_integrate_fwd"
+    if weight_m1hw is not None:
+        wgt = weight_m1hw.contiguous()
+        a.weight_m1hw = wgt.data_ptr()
+        fn, name = _lib.lib().idh_tsdf_integrate_weighted_fwd, "idh_tsdf_integrate_weighted_fwd"
     a.volume = volume._struct()
     a.depth_m1hw, a.K_m44, a.cam_T_world_m44 = d.data_ptr(), K.data_ptr(), T.data_ptr()
     a.max_weight, a.M, a.h, a.w = volume.max_weight, M, h, w

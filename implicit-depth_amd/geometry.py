@@ -9,6 +9,9 @@ row; reference utils/geometry_utils.py:22-89) and loads reference checkpoints un
 (csrc/normals.hip, include/idh_geometry.h).  ``depth_normals`` is the same kernel with its options (rotation into world
 space, orientation towards the camera, a validity map from per-pixel flags); ``patch_normals`` the sparse form for 3x3 patches of points.
 There is no CPU fallback.
+
+``depth_consistency`` checks a depth map against source depth maps of other cameras in one launch (csrc/mv_consistency.hip, DESIGN.md
+§4.25) with the arithmetic of the reference's ``MVDepthLoss`` (losses.py:143-261); ``MVDepthLoss`` is that module's forward value on it.
 """
 from typing import Optional, Tuple
 
@@ -138,3 +141,98 @@ class NormalGenerator(nn.Module):
         if tuple(depth_b1hw.shape[-2:]) != (self.height, self.width):
             raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} must be (B,1,{self.height},{self.width})")
         return depth_normals(depth_b1hw, invK_b44, kernel_size=self.kernel_size, std=self.std)[0]
+
+
+def _src_mats(name, t, B, K):
+    _lib.require_cuda_f32(t)
+    if tuple(t.shape) != (B, K, 4, 4):
+        raise _lib.IdhError(f"{name} {tuple(t.shape)} must be ({B},{K},4,4)")
+    return t.contiguous()
+
+
+def depth_consistency(depth_b1hw: torch.Tensor, invK_b44: torch.Tensor, world_T_cam_b44: torch.Tensor, src_depth_bk1hw: torch.Tensor,
+                      src_K_bk44: torch.Tensor, src_cam_T_world_bk44: torch.Tensor, *, gate_depth: Optional[torch.Tensor] = None,
+                      ratio: float = 1.05, log_tol: float = 0.05, min_consistent: int = 1, max_conflict: int = 0,
+                      return_per_source: bool = False, return_loss: bool = False) -> dict:
+    """Check a depth map (B,1,h,w) against K source depth maps (B,K,1,h,w) of other cameras, in one launch (idh_mv_consistency_fwd;
+    contract: include/idh_geometry.h).  Every pixel is back-projected with ``invK_b44`` and ``world_T_cam_b44``,
+    projected into each source with ``src_K_bk44 @ src_cam_T_world_bk44`` and compared with the nearest tap of that source's depth - the
+    arithmetic of the reference's ``MVDepthLoss`` (losses.py:143-261).  A source *sees* the point when the point is not behind the
+    source's surface by more than ``ratio``; it is *consistent* when the two depths agree within ``log_tol`` in log space, and in
+    *conflict* when the point lies in front of the source's surface by more than that - in space the source saw through.  Returns
+
+    * ``"counts"`` (B,3,h,w) uint8: the number of sources that see / are consistent with / conflict with the pixel;
+    * ``"weight"`` (B,1,h,w): ``1 + consistent`` where the pixel is kept - its depth finite and positive, ``consistent >= min_consistent``
+      and ``conflict <= max_conflict`` - else 0: what ``fusion.integrate_depth(weight_m1hw=)`` takes;
+    * ``"filtered_depth"`` (B,1,h,w): the depth where kept, 0 (a hole) elsewhere;
+    * with ``return_per_source`` ``"visible"`` (B,K,h,w) uint8 and ``"err"`` (B,K,h,w), ``|log sampled - log projected|``, NaN where
+      not visible;
+    * with ``return_loss`` ``"loss"`` (a 0-d tensor): the forward value of the reference's ``MVDepthLoss`` - NaN when a source sees no
+      pixel - and ``"loss_sum"`` (K,) float64, ``"loss_count"`` (K,) int64 behind it.  Deterministic: two calls return the same bits.
+
+    ``gate_depth`` (B,1,h,w): the map visibility is computed from (the reference's ``cur_depth_b1hw``); None: the tested map itself.
+    Sources must have the tested map's size; 1 <= K <= 16, B <= 128.  There is no CPU fallback and no backward pass."""
+    _lib.require_cuda_f32(depth_b1hw, invK_b44, world_T_cam_b44, src_depth_bk1hw, gate_depth)
+    if depth_b1hw.dim() != 4 or depth_b1hw.shape[1] != 1:
+        raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} must be (B,1,h,w)")
+    B, _, h, w = depth_b1hw.shape
+    if src_depth_bk1hw.dim() != 5 or src_depth_bk1hw.shape[0] != B or src_depth_bk1hw.shape[2] != 1:
+        raise _lib.IdhError(f"src_depth {tuple(src_depth_bk1hw.shape)} must be ({B},K,1,h,w)")
+    K, (sh, sw) = int(src_depth_bk1hw.shape[1]), (int(s) for s in src_depth_bk1hw.shape[3:])
+    if tuple(invK_b44.shape) != (B, 4, 4) or tuple(world_T_cam_b44.shape) != (B, 4, 4):
+        raise _lib.IdhError(f"invK {tuple(invK_b44.shape)} and world_T_cam {tuple(world_T_cam_b44.shape)} must be ({B},4,4)")
+    if gate_depth is not None and gate_depth.shape != depth_b1hw.shape:
+        raise _lib.IdhError(f"gate_depth {tuple(gate_depth.shape)} must be {tuple(depth_b1hw.shape)}")
+    dev = depth_b1hw.device
+    keep = [depth_b1hw.contiguous(), invK_b44.contiguous(), world_T_cam_b44.contiguous(), src_depth_bk1hw.contiguous(),
+            _src_mats("src_K", src_K_bk44, B, K), _src_mats("src_cam_T_world", src_cam_T_world_bk44, B, K)]
+    a = _lib.MvConsistencyArgs()
+    a.depth_b1hw, a.invK_b44, a.world_T_cam_b44, a.src_depth_bk1hw, a.src_K_bk44, a.src_cam_T_world_bk44 = (t.data_ptr() for t in keep)
+    if gate_depth is not None:
+        keep.append(gate_depth.contiguous())
+        a.gate_depth_b1hw = keep[-1].data_ptr()
+    out = {"counts": torch.empty(B, 3, h, w, device=dev, dtype=torch.uint8), "weight": torch.empty(B, 1, h, w, device=dev),
+           "filtered_depth": torch.empty(B, 1, h, w, device=dev)}
+    a.counts_b3hw, a.weight_b1hw, a.filtered_depth_b1hw = out["counts"].data_ptr(), out["weight"].data_ptr(), out["filtered_depth"].data_ptr()
+    if return_per_source:
+        out["visible"] = torch.empty(B, K, h, w, device=dev, dtype=torch.uint8)
+        out["err"] = torch.empty(B, K, h, w, device=dev)
+        a.visible_bkhw, a.err_bkhw = out["visible"].data_ptr(), out["err"].data_ptr()
+    if return_loss:
+        out["loss"] = torch.full((), float("nan"), device=dev)
+        out["loss_sum"] = torch.zeros(K, device=dev, dtype=torch.float64)
+        out["loss_count"] = torch.zeros(K, device=dev, dtype=torch.int64)
+        nbytes = _lib.lib().idh_mv_consistency_workspace_bytes(B, K, h, w)
+        workspace = torch.empty(max(nbytes, 8) // 8, device=dev, dtype=torch.float64)
+        keep.append(workspace)
+        a.loss, a.loss_sum_k, a.loss_count_k = out["loss"].data_ptr(), out["loss_sum"].data_ptr(), out["loss_count"].data_ptr()
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+    a.ratio, a.log_tol, a.min_consistent, a.max_conflict = float(ratio), float(log_tol), int(min_consistent), int(max_conflict)
+    a.B, a.K, a.h, a.w, a.src_h, a.src_w = B, K, h, w, sh, sw
+    if B == 0:
+        return out
+    _lib.check(_lib.lib().idh_mv_consistency_fwd(a, _lib.stream_ptr()), "idh_mv_consistency_fwd")
+    return out
+
+
+class MVDepthLoss(nn.Module):
+    """The forward value of the reference's ``MVDepthLoss`` (losses.py:143-261) - same constructor, same ``forward`` signature - on the
+    fused kernel of ``depth_consistency``: one launch and a small finalise launch instead of K rounds of back-projection, projection,
+    ``grid_sample`` and ``nanmean``.  A score of a predicted depth map against its source views that needs no ground truth.
+    Forward only: there is no backward pass, and an input that requires grad raises ``IdhError`` instead of returning a value that
+    silently carries no gradient."""
+
+    def __init__(self, height: int, width: int):
+        super().__init__()
+        self.height, self.width = int(height), int(width)
+        self.backproject = BackprojectDepth(self.height, self.width)
+        self.project = Project3D()
+
+    def forward(self, depth_pred_b1hw, cur_depth_b1hw, src_depth_bk1hw, cur_invK_b44, src_K_bk44, cur_world_T_cam_b44, src_cam_T_world_bk44):
+        tensors = (depth_pred_b1hw, cur_depth_b1hw, src_depth_bk1hw, cur_invK_b44, src_K_bk44, cur_world_T_cam_b44, src_cam_T_world_bk44)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            raise _lib.IdhError("MVDepthLoss is forward only (no backward pass): detach the inputs or call it under torch.no_grad()")
+        if tuple(cur_depth_b1hw.shape[-2:]) != (self.height, self.width):
+            raise _lib.IdhError(f"depth {tuple(cur_depth_b1hw.shape)} must be (B,1,{self.height},{self.width})")
+        return depth_consistency(depth_pred_b1hw, cur_invK_b44, cur_world_T_cam_b44, src_depth_bk1hw, src_K_bk44, src_cam_T_world_bk44,
+                                 gate_depth=cur_depth_b1hw, return_loss=True)["loss"]

@@ -121,6 +121,9 @@ class StreamingSession:
         self._fusion: Optional[dict] = None  # start_fusion's arguments; the volume is made when the first map arrives
         self._volume = None                  # fusion.TSDFVolume
         self._fused_maps = 0                 # maps integrated since start_fusion / reset
+        # start_fusion(consistency=): per ring map, newest first, its (K (1,4,4), cam_T_world (1,4,4)) on the device - what the check projects with
+        self._ring_cams: list = []
+        self.last_depth_counts: Optional[torch.Tensor] = None  # (1,3,h,w) uint8 of the last check: sources that see / agree with / conflict with a pixel
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -129,6 +132,7 @@ class StreamingSession:
         self.frame_index, self.last_code, self.last_slots, self.last_indices, self.last_matching, self._prior = 0, None, None, None, None, None
         self._key = None
         self._depth_ring = []
+        self._ring_cams, self.last_depth_counts = [], None
         self._fused_maps = 0
         if self._volume is not None:
             self._volume.reset()  # (with origin=None the next first map centres the grid again)
@@ -352,29 +356,76 @@ class StreamingSession:
                 frame_K = frame_K.reshape(-1, 4, 4)
                 if frame_K.shape[0] != 1:
                     raise _lib.IdhError("remember_depth: frame_K must be (4,4) or (1,4,4)")
-        self._depth_ring.insert(0, (depth_11hw.detach().clone(), pose, invK.detach().clone()))
+        checked = None
+        if self._fusion is not None and self._fusion["consistency"] is not None:
+            checked = self._check_depth(depth_11hw.detach(), pose, invK.detach())  # against the maps already in the ring
+        self._depth_ring.insert(0, (depth_11hw.detach().clone(), pose, invK.detach().clone()))  # the raw map: the warp path is unchanged
         del self._depth_ring[self.query_keyframes:]
         if self._fusion is not None:
-            self._fuse(self._depth_ring[0][0], pose, invK, frame_u8, frame_K)
+            if checked is None:
+                self._fuse(self._depth_ring[0][0], pose, invK, frame_u8, frame_K)
+            elif self._fusion["weighted"]:
+                self._fuse(self._depth_ring[0][0], pose, invK, frame_u8, frame_K, weight=checked["weight"])
+            else:
+                self._fuse(checked["filtered_depth"], pose, invK, frame_u8, frame_K)
+
+    def _check_depth(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor) -> Optional[dict]:
+        """``geometry.depth_consistency`` of a new map against the ring's maps (B = 1, K = their number, one launch), before the map is
+        pushed; None for the first map of a sequence, which has nothing to be checked against.  Also keeps the new map's camera for the
+        checks to come."""
+        from .geometry import depth_consistency
+
+        c, dev = self._fusion["consistency"], depth_11hw.device
+        cams = self._ring_cams
+        checked = None
+        if self._depth_ring:
+            K = len(self._depth_ring)
+            checked = depth_consistency(depth_11hw, invK_144, torch.from_numpy(pose.astype(np.float32))[None].to(dev),
+                                        torch.cat([d for d, _, _ in self._depth_ring])[None], torch.cat([k for k, _ in cams])[None],
+                                        torch.cat([t for _, t in cams])[None], ratio=c["ratio"], log_tol=c["log_tol"],
+                                        min_consistent=min(c["min_consistent"], K), max_conflict=c["max_conflict"])
+            self.last_depth_counts = checked["counts"]
+        cams.insert(0, (torch.linalg.inv(invK_144), torch.from_numpy(np.linalg.inv(pose).astype(np.float32))[None].to(dev)))
+        del cams[self.query_keyframes:]
+        return checked
 
     def start_fusion(self, voxel_size: float = 0.04, dims: Sequence[int] = (96, 256, 256), origin=None, trunc_voxels: float = 3.0,
-                     max_weight: float = 64.0, color: bool = False) -> None:
+                     max_weight: float = 64.0, color: bool = False, consistency: Optional[dict] = None, weighted: bool = False) -> None:
         """From now on ``remember_depth`` - which ``step`` calls with a ``DepthModel``'s predictions - also averages the map it pushes
         into a TSDF volume of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres (``fusion.TSDFVolume``), which
         ``fused_depth_for_view`` ray-casts: maps are combined, holes one map left are filled by another, and a map that has left the ring
         is still in the volume.  ``origin``: the world (x, y, z) of voxel (0,0,0)'s centre; None centres the grid on the camera position
         of the first map integrated.  ``reset()`` empties the volume and keeps its storage.  Calling it again starts a new volume.
         ``color=True`` gives the volume colours (16 more bytes per voxel): ``remember_depth`` and ``step`` then take the
-        camera frame of a map, ``fused_depth_for_view(return_color=True)`` and ``fused_mesh(return_colors=True)`` return them."""
+        camera frame of a map, ``fused_depth_for_view(return_color=True)`` and ``fused_mesh(return_colors=True)`` return them.
+        ``consistency``: a dict with any of ``log_tol`` (0.05), ``min_consistent`` (1), ``max_conflict`` (0) and ``ratio``
+        (1.05), the parameters of ``geometry.depth_consistency``.  ``remember_depth`` then checks every new map against the maps already
+        in the ring, in one launch, and fuses only the pixels enough of them agree with and too few contradict - flying pixels at depth
+        discontinuities stay out of the volume; ``min_consistent`` is capped at the number of ring maps, and the first map of a sequence
+        is fused as it is.  ``weighted=True`` fuses the raw map with the check's weight (0 for a rejected pixel, else 1 + the number of
+        agreeing maps) instead of the filtered map with weight 1.  The ring keeps the raw map; ``last_depth_counts`` holds the counts of
+        the last check.  Start fusion before the first map of a sequence: the check knows the cameras of the maps remembered since."""
         dims = tuple(int(d) for d in dims)
+        if weighted and consistency is None:
+            raise _lib.IdhError("start_fusion: weighted=True needs consistency (the weights are the check's)")
+        if consistency is not None:
+            unknown = set(consistency) - {"log_tol", "min_consistent", "max_conflict", "ratio"}
+            if unknown:
+                raise _lib.IdhError(f"start_fusion: consistency has unknown keys {sorted(unknown)}")
+            if self._depth_ring:
+                raise _lib.IdhError("start_fusion(consistency=) must come before the first remembered map of a sequence (reset() first)")
+            consistency = dict(log_tol=float(consistency.get("log_tol", 0.05)), min_consistent=int(consistency.get("min_consistent", 1)),
+                               max_conflict=int(consistency.get("max_conflict", 0)), ratio=float(consistency.get("ratio", 1.05)))
         if len(dims) != 3 or min(dims) < 2 or not float(voxel_size) > 0:
             raise _lib.IdhError(f"start_fusion: dims {dims} must be three sizes >= 2 and voxel_size {voxel_size} positive")
         self._fusion = dict(voxel_size=float(voxel_size), dims=dims, origin=None if origin is None else tuple(float(o) for o in origin),
-                            trunc_voxels=float(trunc_voxels), max_weight=float(max_weight), color=bool(color))
+                            trunc_voxels=float(trunc_voxels), max_weight=float(max_weight), color=bool(color), consistency=consistency,
+                            weighted=bool(weighted))
         self._volume, self._fused_maps = None, 0
+        self._ring_cams, self.last_depth_counts = [], None
 
     def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor, frame_u8: Optional[torch.Tensor] = None,
-              frame_K_144: Optional[torch.Tensor] = None) -> None:
+              frame_K_144: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None) -> None:
         from .fusion import TSDFVolume
 
         f = self._fusion
@@ -392,7 +443,10 @@ class StreamingSession:
             frame_K_144 = K.clone()
             frame_K_144[:, 0] *= frame_u8.shape[2] / depth_11hw.shape[3]
             frame_K_144[:, 1] *= frame_u8.shape[1] / depth_11hw.shape[2]
-        self._volume.integrate(depth_11hw, K, cam_T_world, frame_u8, frame_K_144)
+        if weight is None:
+            self._volume.integrate(depth_11hw, K, cam_T_world, frame_u8, frame_K_144)
+        else:
+            self._volume.integrate(depth_11hw, K, cam_T_world, frame_u8, frame_K_144, weight=weight)
         self._fused_maps += 1
 
     @property

@@ -289,6 +289,37 @@ int idh_tsdf_raycast_color_fwd(const idh_tsdf_raycast_color_args *args, void *st
  * colors_zyx4 not 16-byte aligned. */
 int idh_tsdf_mesh_colors_fwd(const idh_tsdf_mesh_colors_args *args, void *stream);
 
+/* ---- Per-observation weights (csrc/tsdf.hip) -----------------------------------------------------------------------
+ *
+ * idh_tsdf_integrate_color_fwd with a weight per depth sample: weight_m1hw (M,1,h,w) is tapped where the depth is, g = weight[m, i, j].
+ *   skip the observation entirely - like a hole - unless g is finite and > 0
+ *   T <- (W * T + g * s) / (W + g);   W <- min(W + g, max_weight)
+ *   colour, under the conditions stated there, with the same g:   C <- (Wc * C + g * c) / (Wc + g);   Wc <- min(Wc + g, max_weight)
+ * colors_zyx4, color_mhw3 and color_K_m44 may be NULL, all three together: geometry only, hc and wc are not read and `colors` is left
+ * as it is (idh_tsdf_integrate_fwd with weights).
+ * Promises: with every weight 1.0f, `values`, `block_flags` and `colors` equal, bit for bit, what the unweighted calls leave (1 * s == s
+ * and the build does not contract); two calls return the same bits; one call with M maps equals M calls with one map each.
+ * Codes: those of idh_tsdf_integrate_color_fwd in its order (the colour conditions only when a colour pointer is given, where a null
+ * one among the three is IDH_EINVAL), and IDH_EINVAL for a null weight_m1hw. */
+typedef struct idh_tsdf_integrate_weighted_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *depth_m1hw;       /* the fields of idh_tsdf_integrate_color_args, with their meaning */
+    const float *K_m44;
+    const float *cam_T_world_m44;
+    float max_weight;
+    int32_t M, h, w;
+    float *colors_zyx4;            /* or NULL (then all three) */
+    const uint8_t *color_mhw3;
+    const float *color_K_m44;
+    int32_t hc, wc;
+    const float *weight_m1hw;      /* (M,1,h,w) */
+} idh_tsdf_integrate_weighted_args;
+
+size_t idh_sizeof_tsdf_integrate_weighted_args(void);
+
+int idh_tsdf_integrate_weighted_fwd(const idh_tsdf_integrate_weighted_args *args, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -85,6 +85,84 @@ int idh_depth_normals_fwd(const idh_normals_args *args, void *stream);
  * IDH_EUNSUPPORTED: B * N >= 2^31.  B == 0 or N == 0 is IDH_OK without a launch. */
 int idh_patch_normals_fwd(const idh_patch_normals_args *args, void *stream);
 
+/* ---- Multi-view depth consistency (csrc/mv_consistency.hip) -------------------------------------------------------
+ *
+ * A depth map is checked against K source depth maps of other cameras: per pixel and source, is the point visible there, does the
+ * source agree with it, or does the point float in space the source saw through.  The arithmetic is the reference's MVDepthLoss
+ * (losses.py:143-261: BackprojectDepth, Project3D, a nearest grid_sample tap, the 1.05 gate, |log - log|), operation by operation, so
+ * the same launch also returns that loss's forward value - a quality score of a depth map that needs no ground truth.
+ *
+ * One launch, one lane per pixel (i, j) of map b, a loop over the sources k = 0 .. K - 1.  fp32; a row of a matrix product is summed
+ * left to right with every product after the first fused into the running sum (fmaf), as the BLAS kernels under the reference's
+ * matmuls do; nothing else is contracted:
+ *   q = invK[b][:3,:3] (j + 0.5, i + 0.5, 1)        q.x = fma(k01, v, k00 u) + k02 ...                  utils/geometry_utils.py:60
+ *   cam = d q;   X = world_T_cam[b] (cam, 1)         four components, X.x = fma(e03, 1, fma(e02, c.z, fma(e01, c.y, e00 c.x))) ...  :61, losses.py:165
+ *   P = src_K[b,k] src_cam_T_world[b,k]              formed first, each entry fma(k_r3, e_3c, fma(k_r2, e_2c, fma(k_r1, e_1c, k_r0 e_0c)))    :82
+ *   c = P[:3] X;   z = max(c.z, 1e-5), a NaN staying a NaN as torch.maximum keeps it;   px = c.x / z,  py = c.y / z          :84-87
+ *   tap (rint(py - 0.5), rint(px - 0.5)), round-half-even: the nearest tap of grid_sample(align_corners=False); INSIDE when it is a
+ *   pixel of the source; s = src_depth[b,k] there, 0 when not inside (padding zeros)                                 losses.py:179-185
+ * With gate_depth_b1hw the chain is run twice: from the gate map's depth it gives px, py, s and z_gate (the reference's
+ * cur_depth_b1hw), from depth_b1hw only z_test (its depth_pred_b1hw).  With gate_depth_b1hw NULL the tested map gates itself:
+ * one chain, z_gate = z_test.
+ *   visible = z_gate < ratio * s  &&  z_gate > 0  &&  s > 0          the reference's comparison as written: s = +inf passes      :187-189
+ *   l = log(s) - log(z_test);   err = |l|                                                                                      :222-224
+ *   counted = visible, d of depth_b1hw finite and > 0, s finite and > 0, INSIDE
+ *   consistent = counted && err <= log_tol
+ *   conflict   = counted && l > log_tol      the point lies in front of the surface the source saw: it violates the source's free space
+ *   (a point behind the source's surface is occluded there and is neither)
+ * Per pixel: n_visible, n_consistent, n_conflict over the K sources;
+ *   kept = d finite and > 0  &&  n_consistent >= min_consistent  &&  n_conflict <= max_conflict
+ *   weight = kept ? 1 + n_consistent : 0;   filtered_depth = kept ? d : 0      (0 is a hole to every consumer of depth maps here)
+ * loss = (1 / K) sum_k mean(err over the pixels of all B maps that are visible for k and whose err is not NaN): nanmean of :226, so NaN
+ * when a source has no such pixel.  Which pixels count is decided by the fp32 values above; the err that is summed is evaluated once
+ * more in fp64 from the same fp32 inputs (z_test's chain and the two logarithms), so the value returned is the fp64 mean rounded once -
+ * the fp32 chain's rounding has a bias per source that a mean over a map does not remove.  Wave reduction, the workgroup's four waves through LDS, one partial
+ * per workgroup and source in the workspace, and a second small launch that adds the partials in a fixed order.  No atomics: two calls
+ * return the same bits.  Without `loss` neither the reduction nor the second launch happens and no workspace is needed.
+ * Every per-pixel output of map b depends on map b alone: B maps in one call equal B calls, bit for bit. */
+#define IDH_MV_MAX_SOURCES 16 /* K of one call: pipeline.MAX_RING_CAPACITY */
+#define IDH_MV_MAX_MAPS 128   /* B of one call */
+
+/* Host struct, read during the call.  struct_size as above. */
+typedef struct idh_mv_consistency_args {
+    int64_t struct_size;
+    const float *depth_b1hw;            /* (B,1,h,w) the map under test */
+    const float *gate_depth_b1hw;       /* (B,1,h,w) the map the visibility gate is computed from, or NULL: depth_b1hw gates itself */
+    const float *invK_b44;              /* (B,4,4); only [:3,:3] is read */
+    const float *world_T_cam_b44;       /* (B,4,4) */
+    const float *src_depth_bk1hw;       /* (B,K,1,src_h,src_w) */
+    const float *src_K_bk44;            /* (B,K,4,4) intrinsics at src_h x src_w */
+    const float *src_cam_T_world_bk44;  /* (B,K,4,4) */
+    uint8_t *counts_b3hw;               /* out (B,3,h,w): n_visible, n_consistent, n_conflict; or NULL */
+    float *weight_b1hw;                 /* out (B,1,h,w), or NULL */
+    float *filtered_depth_b1hw;         /* out (B,1,h,w), or NULL */
+    uint8_t *visible_bkhw;              /* out (B,K,h,w) 1 / 0, or NULL */
+    float *err_bkhw;                    /* out (B,K,h,w), NaN where not visible, or NULL */
+    float *loss;                        /* out, one float on the device, or NULL */
+    double *loss_sum_k;                 /* out (K) the sums behind loss, or NULL; only with loss */
+    int64_t *loss_count_k;              /* out (K) their pixel counts, or NULL; only with loss */
+    void *workspace;                    /* idh_mv_consistency_workspace_bytes(B, K, h, w) bytes, 8-byte aligned; read only with loss */
+    int64_t workspace_bytes;            /* what the caller allocated */
+    float ratio;                        /* > 0, finite: the reference's 1.05 */
+    float log_tol;                      /* > 0, finite */
+    int32_t min_consistent;             /* >= 0 */
+    int32_t max_conflict;               /* >= 0 */
+    int32_t B, K, h, w;
+    int32_t src_h, src_w;               /* must equal h, w */
+} idh_mv_consistency_args;
+
+size_t idh_sizeof_mv_consistency_args(void);
+
+/* 16 * K * B * ceil(h * w / 256) bytes: a double and an int64 per workgroup and source.  0 if an argument is <= 0. */
+size_t idh_mv_consistency_workspace_bytes(int B, int K, int h, int w);
+
+/* IDH_EINVAL: args NULL, struct_size short, B < 0, K, h, w, src_h or src_w <= 0, ratio or log_tol not finite and > 0, min_consistent or
+ * max_conflict < 0, a null depth / invK / world_T_cam / src_depth / src_K / src_cam_T_world, loss_sum_k or loss_count_k without loss,
+ * workspace not 8-byte aligned (with loss);
+ * IDH_EUNSUPPORTED: K > IDH_MV_MAX_SOURCES, B > IDH_MV_MAX_MAPS, (src_h, src_w) != (h, w), B * K * h * w >= 2^31;
+ * IDH_EWORKSPACE (with loss): workspace NULL or workspace_bytes short.  B == 0 is IDH_OK without a launch. */
+int idh_mv_consistency_fwd(const idh_mv_consistency_args *args, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
