@@ -260,6 +260,17 @@ class TsdfIntegrateWeightedArgs(C.Structure):
         self.struct_size = C.sizeof(TsdfIntegrateWeightedArgs)
 
 
+class TsdfShiftArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_shift_args`` (include/idh_fusion.h, a volume that follows the camera)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("src", TsdfVolume), ("dst", TsdfVolume), ("src_colors_zyx4", C.c_void_p),
+                ("dst_colors_zyx4", C.c_void_p), ("shift", C.c_int32 * 3)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfShiftArgs)
+
+
 class MvConsistencyArgs(C.Structure):
     """ctypes mirror of ``idh_mv_consistency_args`` (include/idh_geometry.h, multi-view depth consistency)."""
 
@@ -415,6 +426,8 @@ _SIGS = {
     "idh_tsdf_mesh_colors_fwd": (C.c_int, [C.POINTER(TsdfMeshColorsArgs), C.c_void_p]),
     "idh_sizeof_tsdf_integrate_weighted_args": (C.c_size_t, []),
     "idh_tsdf_integrate_weighted_fwd": (C.c_int, [C.POINTER(TsdfIntegrateWeightedArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_shift_args": (C.c_size_t, []),
+    "idh_tsdf_shift_fwd": (C.c_int, [C.POINTER(TsdfShiftArgs), C.c_void_p]),
     "idh_sizeof_mv_consistency_args": (C.c_size_t, []),
     "idh_mv_consistency_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "idh_mv_consistency_fwd": (C.c_int, [C.POINTER(MvConsistencyArgs), C.c_void_p]),
@@ -518,6 +531,7 @@ def lib():
                                   ("idh_tsdf_raycast_color_args", h.idh_sizeof_tsdf_raycast_color_args(), TsdfRaycastColorArgs),
                                   ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs),
                                   ("idh_tsdf_integrate_weighted_args", h.idh_sizeof_tsdf_integrate_weighted_args(), TsdfIntegrateWeightedArgs),
+                                  ("idh_tsdf_shift_args", h.idh_sizeof_tsdf_shift_args(), TsdfShiftArgs),
                                   ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")

@@ -8,6 +8,9 @@
 //                     With IntegrateColorArgs the same kernel also averages a camera frame's tap into the voxel's {R, G, B, Wc} quad
 //                     (one 16-byte load and store per coloured voxel, three byte gathers per coloured voxel and map).
 //                     With Weighted<..> on top of either, a weight map tapped where the depth is scales the observation.
+//   tsdf_shift_k<COLOR>  a second volume whose grid lies a whole number of voxels further: one lane per voxel of it, the
+//                     launch shape of tsdf_integrate_k; what stays is copied bit for bit, what comes in - and what was never observed - is
+//                     written in the empty state, and the flags are marked as tsdf_flags_k marks them.
 //   tsdf_raycast_k<SKIP, NORMALS, Args>  one lane per pixel, an 8 x 8-pixel tile per wave.  A sample reads its eight corners as four 16-byte
 //                     loads: the x-neighbours {T0, W0, T1, W1} are adjacent in memory (8-byte aligned, which the global loads of gfx950
 //                     take).  SKIP clips the lattice range to the volume's box and jumps blocks whose flag is 0.  With RaycastColorArgs
@@ -19,6 +22,8 @@
 // Block flags.  A lane's row is 64 consecutive x, so the eight lanes of an aligned group share one block along x: the group's first lane
 // stores for the group (one ballot), and a touched voxel on a block's low face also stores for the block before it (the + 1 apron).
 // Only the value 1 is ever stored between resets, so concurrent stores need no atomic.
+#include <string.h>
+
 #include "tsdf_common.h"
 
 namespace {
@@ -157,6 +162,43 @@ __global__ __launch_bounds__(256) void tsdf_integrate_k(const Args a) {
         if (coloured) a.colors[((size_t)z * V.Ny + y) * V.Nx + x] = col;
     }
     mark_blocks(V, touched, x, y, z);  // a touched voxel has W > 0
+}
+
+struct ShiftArgs {
+    Vol V;  // dst: its dims are src's too
+    const float2 *src;
+    const float4 *src_colors;
+    float4 *dst_colors;
+    int sx, sy, sz;
+};
+
+// dst voxel (x, y, z) <- src voxel (x + sx, y + sy, z + sz) where that is inside and observed, else the empty state.  The lane's source
+// row is a run of consecutive pairs like its destination row, offset by sx pairs: both stay 8-byte (16-byte for the quads) aligned and
+// coalesced for every shift.  y + sy and z + sz are wave-uniform.  The quad is read only where W > 0: most of a room's volume is not.
+template <bool COLOR>
+__global__ __launch_bounds__(256) void tsdf_shift_k(const ShiftArgs a) {
+    const Vol &V = a.V;
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
+    if (y >= V.Ny) return;  // whole wave
+    const bool live = x < V.Nx;
+    const long long ax = (long long)x + a.sx, ay = (long long)y + a.sy, az = (long long)z + a.sz;
+    float2 tw = make_float2(1.f, 0.f);
+    float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool seen = false;
+    if (live && ax >= 0 && ax < V.Nx && ay >= 0 && ay < V.Ny && az >= 0 && az < V.Nz) {
+        const size_t s = ((size_t)az * V.Ny + (size_t)ay) * V.Nx + (size_t)ax;
+        const float2 t = a.src[s];
+        if (t.y > 0.f) {  // false for NaN
+            tw = t, seen = true;
+            if constexpr (COLOR) col = a.src_colors[s];
+        }
+    }
+    if (live) {
+        const size_t d = ((size_t)z * V.Ny + y) * V.Nx + x;
+        reinterpret_cast<float2 *>(V.values)[d] = tw;
+        if constexpr (COLOR) a.dst_colors[d] = col;
+    }
+    mark_blocks(V, seen, x, y, z);
 }
 
 struct RaycastArgs {
@@ -460,6 +502,44 @@ extern "C" int idh_tsdf_integrate_weighted_fwd(const idh_tsdf_integrate_weighted
         g.weight = e.weight_m1hw;
         hipLaunchKernelGGL(tsdf_integrate_k<Weighted<IntegrateArgs>>, voxel_grid(a.V), dim3(64, 4), 0, idh_stream(stream), g);
     }
+    IDH_CHECK_LAUNCH();
+    return IDH_OK;
+}
+
+extern "C" size_t idh_sizeof_tsdf_shift_args(void) { return sizeof(idh_tsdf_shift_args); }
+
+extern "C" int idh_tsdf_shift_fwd(const idh_tsdf_shift_args *args, void *stream) {
+    if (!args || args->struct_size < (int64_t)sizeof(idh_tsdf_shift_args)) return IDH_EINVAL;
+    const idh_tsdf_shift_args &e = *args;
+    if (!e.src_colors_zyx4 != !e.dst_colors_zyx4) return IDH_EINVAL;
+    if (((uintptr_t)e.src_colors_zyx4 & 15u) || ((uintptr_t)e.dst_colors_zyx4 & 15u)) return IDH_EINVAL;
+    Vol S;
+    ShiftArgs a;
+    if (const int rc = check_volume(e.src, S)) return rc;
+    if (const int rc = check_volume(e.dst, a.V)) return rc;
+    const auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    if (e.src.Nz != e.dst.Nz || e.src.Ny != e.dst.Ny || e.src.Nx != e.dst.Nx) return IDH_EINVAL;
+    if (bits(e.src.voxel_size) != bits(e.dst.voxel_size) || bits(e.src.trunc_voxels) != bits(e.dst.trunc_voxels)) return IDH_EINVAL;
+    for (int i = 0; i < 3; ++i) {
+        const float step = e.src.voxel_size * (float)e.shift[i];
+        const float want = e.src.origin[i] + step;
+        if (bits(e.dst.origin[i]) != bits(want)) return IDH_EINVAL;
+    }
+    const size_t n = (size_t)S.Nx * S.Ny * S.Nz, nb = (size_t)S.nbx * S.nby * S.nbz;
+    const bool color = e.src_colors_zyx4 != nullptr;
+    const uintptr_t lo_s[3] = {(uintptr_t)S.values, (uintptr_t)S.flags, (uintptr_t)e.src_colors_zyx4};
+    const uintptr_t lo_d[3] = {(uintptr_t)a.V.values, (uintptr_t)a.V.flags, (uintptr_t)e.dst_colors_zyx4};
+    const size_t len[3] = {8 * n, nb, 16 * n};
+    for (int i = 0; i < (color ? 3 : 2); ++i)
+        for (int j = 0; j < (color ? 3 : 2); ++j)
+            if (lo_s[i] < lo_d[j] + len[j] && lo_d[j] < lo_s[i] + len[i]) return IDH_EINVAL;
+    a.src = reinterpret_cast<const float2 *>(S.values);
+    a.src_colors = reinterpret_cast<const float4 *>(e.src_colors_zyx4), a.dst_colors = reinterpret_cast<float4 *>(e.dst_colors_zyx4);
+    a.sx = e.shift[0], a.sy = e.shift[1], a.sz = e.shift[2];
+    hipStream_t st = idh_stream(stream);
+    if (const int rc = clear_volume(a.V, false, st)) return rc;
+    if (color) hipLaunchKernelGGL(tsdf_shift_k<true>, voxel_grid(a.V), dim3(64, 4), 0, st, a);
+    else hipLaunchKernelGGL(tsdf_shift_k<false>, voxel_grid(a.V), dim3(64, 4), 0, st, a);
     IDH_CHECK_LAUNCH();
     return IDH_OK;
 }

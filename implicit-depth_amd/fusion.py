@@ -9,7 +9,11 @@ HIP kernel.
 
 Colour: a volume made with ``color=True`` also holds ``colors``, (Nz,Ny,Nx,4) float32 {R, G, B, Wc}; ``integrate_depth``
 then takes the camera frames that belong to the depth maps, ``raycast_volume(return_color=True)`` returns the surface's colour in the
-live camera and ``extract_mesh(return_colors=True)`` the colour of every vertex."""
+live camera and ``extract_mesh(return_colors=True)`` the colour of every vertex.
+
+A volume that follows the camera: ``TSDFVolume.shift`` moves the grid under its contents by whole voxels in one
+launch, ``crop`` and ``leaving_boxes`` keep what such a move drops, and ``follow_shift`` is the rule ``StreamingSession.start_fusion(
+follow=)`` moves by."""
 from __future__ import annotations
 
 import ctypes as C
@@ -61,6 +65,7 @@ class TSDFVolume:
             self.values = _values
         self.block_flags = torch.empty(nbytes, device=self.values.device, dtype=torch.uint8)
         self.colors: Optional[torch.Tensor] = None
+        self._spare: Optional[tuple] = None  # shift()'s second set of (values, block_flags, colors), made at its first call
         if _colors is not None:
             _lib.require_cuda_f32(_colors)
             if tuple(_colors.shape) != (*self.dims, 4) or not _colors.is_contiguous() or _colors.device != self.values.device or _colors.data_ptr() % 16:
@@ -111,6 +116,93 @@ class TSDFVolume:
     def extract_mesh(self, min_weight: float = 0.0, return_weights: bool = False, use_block_flags: bool = MESH_USE_BLOCK_FLAGS,
                      return_colors: bool = False) -> Dict[str, torch.Tensor]:
         return extract_mesh(self, min_weight, return_weights, use_block_flags, return_colors)
+
+    def _origin_after(self, voxels_xyz) -> tuple:
+        """``origin + voxel_size * voxels`` per axis in float32 (one multiply, one add): the arithmetic idh_tsdf_shift_fwd checks bit for bit."""
+        v = np.float32(self.voxel_size)
+        return tuple(float(np.float32(o) + v * np.float32(k)) for o, k in zip(self.origin, voxels_xyz))
+
+    def shift(self, shift_xyz: Sequence[int]) -> None:
+        """Move the grid ``shift_xyz`` = (sx, sy, sz) whole voxels along the world's axes under its contents (idh_tsdf_shift_fwd, one
+        launch): ``origin`` becomes ``origin + voxel_size * shift`` (formed in float32), every world lattice point the
+        old and the new grid share keeps its {T, W} pair and its colour bit for bit, what comes in is empty and what leaves is dropped -
+        ``crop`` the ``leaving_boxes`` first to keep it.  Voxels never observed (W == 0) arrive as ``{1, 0}`` with a zero colour
+        whatever they held, and ``block_flags`` are rebuilt.  Any integers are allowed: a zero shift is a normalising copy, a shift of
+        a whole dim or more empties the volume.
+
+        The shift writes into a second set of ``values`` / ``block_flags`` / ``colors`` tensors, allocated at the first call and kept:
+        a volume that has been shifted holds TWICE its memory (8 + 16 bytes more per voxel with colours).  Afterwards the attributes
+        name the tensors just written and the previous ones are the spare: a reference to ``values``, ``block_flags`` or ``colors``
+        taken before the call now names the spare, which the next ``shift`` overwrites."""
+        s = tuple(int(k) for k in shift_xyz)
+        if len(s) != 3 or any(not -2 ** 31 <= k < 2 ** 31 for k in s):
+            raise _lib.IdhError(f"TSDFVolume.shift: shift {shift_xyz} must be three int32 (sx, sy, sz)")
+        if self._spare is None:
+            self._spare = (torch.empty_like(self.values), torch.empty_like(self.block_flags),
+                           None if self.colors is None else torch.empty_like(self.colors))
+        values, flags, colors = self._spare
+        origin = self._origin_after(s)
+        a = _lib.TsdfShiftArgs()
+        a.src = self._struct()
+        a.dst = self._struct()
+        a.dst.values, a.dst.block_flags = values.data_ptr(), flags.data_ptr()
+        a.dst.origin[0], a.dst.origin[1], a.dst.origin[2] = origin
+        a.src_colors_zyx4, a.dst_colors_zyx4 = _lib.ptr(self.colors), _lib.ptr(colors)
+        a.shift[0], a.shift[1], a.shift[2] = s
+        _lib.check(_lib.lib().idh_tsdf_shift_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_shift_fwd")
+        self._spare = (self.values, self.block_flags, self.colors)
+        self.values, self.block_flags, self.colors = values, flags, colors
+        self.origin = origin
+
+    def crop(self, lo_xyz: Sequence[int], hi_xyz: Sequence[int]) -> "TSDFVolume":
+        """A new ``TSDFVolume`` holding a COPY of the voxels ``lo_xyz`` .. ``hi_xyz`` (inclusive, (x, y, z), at least two per axis): their
+        pairs, their colours if the volume has any, ``origin + voxel_size * lo`` (in float32) as its origin and block flags rebuilt from
+        the copy (idh_tsdf_flags_fwd).  What a caller uses to keep - mesh, save - the ``leaving_boxes`` before a ``shift`` drops them."""
+        lo, hi = tuple(int(k) for k in lo_xyz), tuple(int(k) for k in hi_xyz)
+        nz, ny, nx = self.dims
+        if len(lo) != 3 or len(hi) != 3 or any(not 0 <= a < b < n for a, b, n in zip(lo, hi, (nx, ny, nz))):
+            raise _lib.IdhError(f"TSDFVolume.crop: {lo_xyz} .. {hi_xyz} must be an inclusive (x, y, z) box of at least two voxels per axis inside {(nx, ny, nz)}")
+        box = (slice(lo[2], hi[2] + 1), slice(lo[1], hi[1] + 1), slice(lo[0], hi[0] + 1))
+        values = self.values[box].clone(memory_format=torch.contiguous_format)
+        colors = None if self.colors is None else self.colors[box].clone(memory_format=torch.contiguous_format)
+        return TSDFVolume.from_values(values, self.voxel_size, self._origin_after(lo), self.trunc_voxels, self.max_weight, colors=colors)
+
+
+def leaving_boxes(dims: Sequence[int], shift_xyz: Sequence[int]) -> list:
+    """The voxels of a volume of ``dims`` = (Nz, Ny, Nx) that ``TSDFVolume.shift(shift_xyz)`` drops, as at most three disjoint inclusive
+    boxes ``(lo_xyz, hi_xyz)`` of the CURRENT (unshifted) volume whose union is exactly that set: the slab that leaves along x over all
+    y and z, then the slab along y over the x that stay, then the slab along z over the x and y that stay.  Empty for a zero shift; one
+    box, the whole volume, when the shift is a whole dim or more on an axis.  Pure host arithmetic."""
+    n = (int(dims[2]), int(dims[1]), int(dims[0]))
+    s = tuple(int(k) for k in shift_xyz)
+    if len(s) != 3 or len(dims) != 3 or min(n) < 1:
+        raise _lib.IdhError(f"leaving_boxes: dims {dims} must be (Nz, Ny, Nx) and shift {shift_xyz} (sx, sy, sz)")
+    if any(abs(k) >= m for k, m in zip(s, n)):
+        return [((0, 0, 0), (n[0] - 1, n[1] - 1, n[2] - 1))]
+    # voxel a stays when 0 <= a - s < N: per axis the range that stays and the range that leaves (s > 0 drops the low end)
+    stay = [(max(k, 0), m - 1 + min(k, 0)) for k, m in zip(s, n)]
+    leave = [None if k == 0 else (0, k - 1) if k > 0 else (m + k, m - 1) for k, m in zip(s, n)]
+    boxes = []
+    for axis in range(3):
+        if leave[axis] is None:
+            continue
+        r = [stay[i] if i < axis else leave[i] if i == axis else (0, n[i] - 1) for i in range(3)]
+        boxes.append((tuple(a for a, _ in r), tuple(b for _, b in r)))
+    return boxes
+
+
+def follow_shift(cam_xyz: Sequence[float], origin: Sequence[float], dims: Sequence[int], voxel_size: float, slack: float) -> tuple:
+    """The shift (sx, sy, sz) that brings a volume of ``dims`` = (Nz, Ny, Nx) back under a camera at ``cam_xyz``, in float64 on the host.
+    Per axis c = (cam - centre) / voxel_size with centre = origin + voxel_size * (N - 1) / 2.  While no |c| exceeds
+    ``slack / voxel_size`` the answer is (0, 0, 0); otherwise every axis moves by ``8 * floor(c / 8 + 0.5)``: whole 8-voxel blocks, so
+    the block grid of a scrolled volume stays aligned with its contents, and the camera ends within 4 voxels of the centre."""
+    v = float(voxel_size)
+    n = np.array([dims[2], dims[1], dims[0]], dtype=np.float64)
+    centre = np.asarray(origin, dtype=np.float64).reshape(3) + v * (n - 1.0) / 2.0
+    c = (np.asarray(cam_xyz, dtype=np.float64).reshape(3) - centre) / v
+    if not (np.abs(c) > float(slack) / v).any():
+        return (0, 0, 0)
+    return tuple(int(k) for k in 8 * np.floor(c / 8.0 + 0.5))
 
 
 def integrate_depth(volume: TSDFVolume, depth_m1hw: torch.Tensor, K_m44, cam_T_world_m44, color_u8: Optional[torch.Tensor] = None,

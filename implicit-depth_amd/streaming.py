@@ -124,6 +124,9 @@ class StreamingSession:
         # start_fusion(consistency=): per ring map, newest first, its (K (1,4,4), cam_T_world (1,4,4)) on the device - what the check projects with
         self._ring_cams: list = []
         self.last_depth_counts: Optional[torch.Tensor] = None  # (1,3,h,w) uint8 of the last check: sources that see / agree with / conflict with a pixel
+        # start_fusion(follow=): how often the volume was moved after the camera since start_fusion / reset, and the last (sx, sy, sz)
+        self.fusion_scrolls = 0
+        self.last_scroll: Optional[Tuple[int, int, int]] = None
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -134,6 +137,7 @@ class StreamingSession:
         self._depth_ring = []
         self._ring_cams, self.last_depth_counts = [], None
         self._fused_maps = 0
+        self.fusion_scrolls, self.last_scroll = 0, None
         if self._volume is not None:
             self._volume.reset()  # (with origin=None the next first map centres the grid again)
         if self.query_keyframes > 1:
@@ -390,7 +394,8 @@ class StreamingSession:
         return checked
 
     def start_fusion(self, voxel_size: float = 0.04, dims: Sequence[int] = (96, 256, 256), origin=None, trunc_voxels: float = 3.0,
-                     max_weight: float = 64.0, color: bool = False, consistency: Optional[dict] = None, weighted: bool = False) -> None:
+                     max_weight: float = 64.0, color: bool = False, consistency: Optional[dict] = None, weighted: bool = False,
+                     follow: Optional[float] = None, on_scroll=None) -> None:
         """From now on ``remember_depth`` - which ``step`` calls with a ``DepthModel``'s predictions - also averages the map it pushes
         into a TSDF volume of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres (``fusion.TSDFVolume``), which
         ``fused_depth_for_view`` ray-casts: maps are combined, holes one map left are filled by another, and a map that has left the ring
@@ -404,8 +409,18 @@ class StreamingSession:
         discontinuities stay out of the volume; ``min_consistent`` is capped at the number of ring maps, and the first map of a sequence
         is fused as it is.  ``weighted=True`` fuses the raw map with the check's weight (0 for a rejected pixel, else 1 + the number of
         agreeing maps) instead of the filtered map with weight 1.  The ring keeps the raw map; ``last_depth_counts`` holds the counts of
-        the last check.  Start fusion before the first map of a sequence: the check knows the cameras of the maps remembered since."""
+        the last check.  Start fusion before the first map of a sequence: the check knows the cameras of the maps remembered since.
+        ``follow``: None keeps the grid where the first map put it - what leaves it is not fused.  A slack in metres
+        (> 0) lets the volume follow the camera: before a map is integrated, ``fusion.follow_shift`` is asked with the map's camera
+        position, and once that is further than ``follow`` from the grid's centre on an axis the grid is moved back under it by whole
+        8-voxel blocks (``TSDFVolume.shift``: what stays keeps its bits, what leaves is dropped, the volume holds twice its memory from
+        the first move on).  ``on_scroll(volume, shift_xyz)`` is called just before such a move, with the volume still unshifted: the
+        place to ``crop`` or mesh the ``fusion.leaving_boxes``.  ``fusion_scrolls`` counts the moves, ``last_scroll`` is the last one."""
         dims = tuple(int(d) for d in dims)
+        if follow is not None and not float(follow) > 0:
+            raise _lib.IdhError(f"start_fusion: follow = {follow} must be a positive slack in metres (None: a fixed grid)")
+        if on_scroll is not None and (follow is None or not callable(on_scroll)):
+            raise _lib.IdhError("start_fusion: on_scroll must be callable and needs follow")
         if weighted and consistency is None:
             raise _lib.IdhError("start_fusion: weighted=True needs consistency (the weights are the check's)")
         if consistency is not None:
@@ -420,8 +435,9 @@ class StreamingSession:
             raise _lib.IdhError(f"start_fusion: dims {dims} must be three sizes >= 2 and voxel_size {voxel_size} positive")
         self._fusion = dict(voxel_size=float(voxel_size), dims=dims, origin=None if origin is None else tuple(float(o) for o in origin),
                             trunc_voxels=float(trunc_voxels), max_weight=float(max_weight), color=bool(color), consistency=consistency,
-                            weighted=bool(weighted))
+                            weighted=bool(weighted), follow=None if follow is None else float(follow), on_scroll=on_scroll)
         self._volume, self._fused_maps = None, 0
+        self.fusion_scrolls, self.last_scroll = 0, None
         self._ring_cams, self.last_depth_counts = [], None
 
     def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor, frame_u8: Optional[torch.Tensor] = None,
@@ -437,7 +453,16 @@ class StreamingSession:
             if self._volume is None:
                 self._volume = TSDFVolume(f["dims"], f["voxel_size"], origin, f["trunc_voxels"], f["max_weight"], device=depth_11hw.device, color=f["color"])
             self._volume.origin = tuple(float(o) for o in origin)
-        cam_T_world = torch.from_numpy(np.linalg.inv(pose).astype(np.float32))[None]  # inverted in float64 on the host
+        if f["follow"] is not None:  # the grid goes after the camera before the map is integrated
+            from .fusion import follow_shift
+
+            s = follow_shift(pose[:3, 3], self._volume.origin, f["dims"], f["voxel_size"], f["follow"])
+            if any(s):
+                if f["on_scroll"] is not None:
+                    f["on_scroll"](self._volume, s)  # still unshifted: the caller keeps what is about to leave
+                self._volume.shift(s)
+                self.fusion_scrolls, self.last_scroll = self.fusion_scrolls + 1, s
+        cam_T_world =torch.from_numpy(np.linalg.inv(pose).astype(np.float32))[None]  # inverted in float64 on the host
         K = torch.linalg.inv(invK_144)
         if frame_u8 is not None and frame_K_144 is None:
             frame_K_144 = K.clone()

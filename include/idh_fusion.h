@@ -23,7 +23,8 @@
  *   byte is 0 has W == 0 at EVERY voxel any of its cells reads (its 8 x 8 x 8 cells read 9 x 9 x 9 voxels) - no sample inside it is
  *   known.  This is a superset of "some voxel there has W > 0 and T < 1": the ray cast's flag bits 2 and 4 count known samples, and
  *   observed free space (W > 0, T == 1) is known, so only blocks without any observation can be jumped without changing a bit.
- *   Bytes are set by idh_tsdf_integrate_fwd, rebuilt by idh_tsdf_flags_fwd, cleared by idh_tsdf_reset_fwd alone.
+ *   Bytes are set by idh_tsdf_integrate_fwd, rebuilt by idh_tsdf_flags_fwd (and by idh_tsdf_shift_fwd on the volume it writes), cleared
+ *   by idh_tsdf_reset_fwd alone.
  */
 #ifndef IDH_FUSION_H_
 #define IDH_FUSION_H_
@@ -319,6 +320,41 @@ typedef struct idh_tsdf_integrate_weighted_args {
 size_t idh_sizeof_tsdf_integrate_weighted_args(void);
 
 int idh_tsdf_integrate_weighted_fwd(const idh_tsdf_integrate_weighted_args *args, void *stream);
+
+/* ---- A volume that follows the camera: shift by whole voxels (csrc/tsdf.hip) -------------------------------------------
+ *
+ * The grid moves under its contents: `dst` is a second volume of the same dims, voxel_size and trunc_voxels whose origin lies
+ * shift = (sx, sy, sz) voxels further along the world's axes, and every world lattice point both grids hold keeps what was fused there.
+ * What `src` holds outside `dst` is dropped (the caller keeps it first if it wants it); what `dst` holds outside `src` is empty.
+ * One launch after the clear of dst's flags, one lane per voxel of dst.  Per voxel (x, y, z) of dst:
+ *   a = (x + sx, y + sy, z + sz)                                          (in 64-bit: no shift overflows)
+ *   a inside src and W_src(a) > 0:   the pair {T, W} of dst is the pair of src at a, bit for bit, and the quad {R, G, B, Wc} likewise
+ *   otherwise:                       the pair is {1, 0} and the quad sixteen zero bytes
+ * A voxel of src with W == 0 (or NaN) therefore arrives in the EMPTY state whatever its T and its quad were: no consumer reads T or the
+ * colour of such a voxel, and dst is a function of what the consumers can see of src.  shift = (0,0,0) is a normalising copy; |s| >= N on
+ * an axis leaves dst empty.  Every byte of dst's values (and colours) is written, and dst's first idh_tsdf_block_flag_bytes(Nz, Ny, Nx)
+ * flag bytes equal what idh_tsdf_flags_fwd would leave on dst's new values: 1 iff W > 0 at some voxel the block's cells read (cleared,
+ * then plain byte stores of 1).  src is only read.  No allocation, no synchronisation, no host read-back; two calls return the same bits.
+ * The colours are optional, both pointers or neither.
+ * Codes, in this order.
+ * IDH_EINVAL: args NULL, struct_size short; exactly one of src_colors_zyx4 and dst_colors_zyx4 NULL; a colour pointer not 16-byte aligned;
+ * src's volume conditions, then dst's, with their codes;
+ * IDH_EINVAL: Nz, Ny, Nx, voxel_size or trunc_voxels of the two differ (the floats compared as bits);
+ *   dst.origin[i] is not, bit for bit, src.origin[i] + voxel_size * (float)shift[i] (one fp32 multiply, one fp32 add) - the data cannot
+ *   move without the frame;
+ *   one of src's byte ranges - values, the flag bytes named above, colours - overlaps one of dst's (ping-pong, never in place). */
+typedef struct idh_tsdf_shift_args {
+    int64_t struct_size;
+    idh_tsdf_volume src;           /* read */
+    idh_tsdf_volume dst;           /* written: values and block_flags, every byte of both */
+    const float *src_colors_zyx4;  /* (Nz,Ny,Nx,4), 16-byte aligned, or NULL */
+    float *dst_colors_zyx4;        /* (Nz,Ny,Nx,4), 16-byte aligned; NULL iff src_colors_zyx4 is NULL */
+    int32_t shift[3];              /* (sx, sy, sz) voxels, any int32 */
+} idh_tsdf_shift_args;
+
+size_t idh_sizeof_tsdf_shift_args(void);
+
+int idh_tsdf_shift_fwd(const idh_tsdf_shift_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
