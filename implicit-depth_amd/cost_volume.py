@@ -72,7 +72,7 @@ def volume_opts(B, K, C, H, W, D, planes_bdhw: Optional[Tensor] = None, cur_batc
     o = _lib.VolumeOpts()
     o.cur_batch_stride, o.src_batch_stride, o.kernel = int(cur_batch_stride), int(src_batch_stride), int(kernel)
     o.win_units_per_split = int(win_units)  # dot-product volume, window kernel: 0 = the launcher's plane split
-    o.fv_keep_empty_views = int(fv_keep_empty_views)  # MLP feature volume: 0 = the launch picks its kernel, 1 = fv_mlp_k (every view processed), 2 = fv_mlp_skip_k
+    o.fv_keep_empty_views = int(fv_keep_empty_views)  # MLP feature volume: 0 = the launch picks its kernel, 1 = fv_mlp_k<KT, false> (every view), 2 = <KT, true>
     keep = []
     if n_scratch:
         sc = torch.empty(n_scratch, device=dot_scratch_device, dtype=torch.float32)
@@ -299,9 +299,9 @@ class FeatureVolumeManager(CostVolumeManager):
         self.num_source_views = num_source_views
         self.mlp = MLP(channel_list=mlp_channels, disable_final_activation=True)
         self.mlp_math: Optional[str] = None  # None = DEFAULT_MLP_MATH
-        # True: a launch whose cameras leave enough samples outside the source images runs fv_mlp_skip_k, which drops, per 16-voxel tile and plane,
-        # the source views in which no voxel has a non-zero bilinear weight (same results), any other launch fv_mlp_k.  False: always fv_mlp_k
-        # (every view processed); "always": always fv_mlp_skip_k (A/B timing, tests).  = idh_volume_opts.fv_keep_empty_views 0 / 1 / 2
+        # True: a launch whose cameras leave enough samples outside the source images runs fv_mlp_k<KT, true>, which drops, per 16-voxel tile and plane,
+        # the source views in which no voxel has a non-zero bilinear weight (same results), any other launch fv_mlp_k<KT, false>.  False: always <KT, false>
+        # (every view processed); "always": always <KT, true> (A/B timing, tests).  = idh_volume_opts.fv_keep_empty_views 0 / 1 / 2
         self.skip_empty_views = True
 
     def _math(self) -> str:

@@ -21,19 +21,40 @@
 //     registers from the gather to the final dot product; W1 (per-voxel part) and W2 live in LDS in
 //     MFMA fragment order (152 KiB for K = 7, all 160 KiB for K = 8) and are shared by the 8 waves of a persistent
 //     workgroup; per plane a wave issues (K+4+8)*32 MFMAs.
-//   * views that see nothing can be dropped (fv_mlp_skip_k): a sample that projects outside the source image has four bilinear weights of exactly
-//     0.0f, its 16 blended features are zeros and its 32 MFMAs add zero to every accumulator.  A ballot over the owner quarters' weights, one plane
-//     ahead, gives a wave-uniform bit per view ("some voxel of this 16-voxel tile has a non-zero weight in view k"); a view whose bit is clear gets
-//     no ds_bpermute, tap loads, blend or MFMAs in that plane and its `dot` input stays +0.  Same values as fv_mlp_k for finite features, with two
-//     footnotes: a zero weight times an Inf / NaN tap gives NaN in fv_mlp_k where the dropped view gives the reference's zero, and a kept
-//     all-outside view can put -0 into the `dot` input where the dropped one leaves +0 (a zero of either sign adds nothing to a non-zero
-//     accumulator).  It is a kernel of its own: fv_mlp_k keeps its code, and a launch runs whichever of the two is faster for its cameras
-//     (fv_selected; idh_volume_opts.fv_keep_empty_views forces one).  So (K+4+8)*32 is an upper bound of what a wave issues.  DESIGN 4.3.
+//   * views that see nothing can be dropped (fv_mlp_k<KT, true>, "the skipping kernel"): a sample that projects outside the source image has four
+//     bilinear weights of exactly 0.0f, its 16 blended features are zeros and its 32 MFMAs add zero to every accumulator.  A ballot over the owner
+//     quarters' weights, one plane ahead, gives a wave-uniform bit per view ("some voxel of this 16-voxel tile has a non-zero weight in view k"); a
+//     view whose bit is clear gets no ds_bpermute, tap loads, blend or MFMAs in that plane and its `dot` input stays +0.  Same values as the
+//     all-views kernel fv_mlp_k<KT, false> for finite features, with two footnotes: a zero weight times an Inf / NaN tap gives NaN in the all-views
+//     kernel where the dropped view gives the reference's zero, and a kept all-outside view can put -0 into the `dot` input where the dropped one
+//     leaves +0 (a zero of either sign adds nothing to a non-zero accumulator).  They are two kernels per view count: the all-views one keeps the
+//     code it had before views could be dropped, and a launch runs whichever of the two is faster for its cameras (fv_selected;
+//     idh_volume_opts.fv_keep_empty_views forces one).  So (K+4+8)*32 is an upper bound of what a wave issues.  DESIGN 4.3.
+//   * both come from ONE template, fv_mlp_k<KT, kSkip>, and differ only inside `if constexpr (kSkip)`: a discarded branch is never instantiated, so
+//     each instantiation hands the compiler the statements of the former separate kernel in the same order, and all six (KT = 0, 7, 8 x kSkip)
+//     compiled to the same instructions, registers and scratch as the two hand-kept copies did.  Share text between them ONLY in that way and
+//     compare the compiler's output per kernel after every step; what was tried and changes the code (register assignment, schedule, scratch):
+//       - thin __global__ wrappers around a __device__ __forceinline__ body (arguments by reference or by value): fv_mlp_k<7, false> 3489 -> 3434 /
+//         3432 instructions, <8, false> 3798 -> 3861 / 3851;
+//       - the store + last-plane mask tail as a shared __forceinline__ function (also for fv_mlp_gen_k / fv_mlp_f16_k, which is why those keep
+//         their copies of the task decode and the store): all six change, fv_mlp_k<8, true> goes from 52 to 124 B of scratch per lane;
+//       - the all-views kernel on the skipping branch's layer1_tail() / layer2_chunk() / next_plane(): fv_mlp_k<7, false> 256 -> 253 VGPRs with a
+//         different schedule, <8, false> 100 -> 124 B of scratch;
+//       - lambdas shared by the two branches of the plane body that write the accumulators or only carry scheduling hints - the unrolled view
+//         loop, a view's 32 MFMAs, the metadata blocks, the sched_group_barrier pattern: each changes four to six of the kernels (scratch appears
+//         in <7, false> and <7, true>).  The blend of a view (blend(): values in, values out) is the one such piece that could be shared.
 // Roofline: fp32 MFMA (2*D*N*(16K+64+128)*128 + ... ~ 66.6 GFLOP per 96x128x64 frame).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "idh_common.h"
 #include "split_f16.h"
+
+// vector instructions per group of two MFMAs in fv_mlp_k's unrolled view loop (timing experiments override it: tools/abl_fv32.sh)
+#ifndef IDH_ABL_FV_VALU_PER_GROUP
+#define IDH_ABL_FV_VALU_PER_GROUP 3
+#endif
 
 namespace {
 
@@ -95,7 +116,7 @@ struct FvArgs {
     const float *planes;
     long long planes_sb, planes_sd;
     int planes_sp;
-    int select;            // fv_mlp_k / fv_mlp_skip_k: 0 = the one kernel that was launched runs; 1 = both were launched, fv_selected() picks
+    int select;            // fv_mlp_k<KT, false / true>: 0 = the one kernel that was launched runs; 1 = both were launched, fv_selected() picks
 };
 
 __device__ __forceinline__ float fv_plane(const FvArgs &a, int b, int p, int d) {
@@ -103,12 +124,12 @@ __device__ __forceinline__ float fv_plane(const FvArgs &a, int b, int p, int d) 
                     : fv_depth_plane(d, a.D, a.dmin, a.dmax);
 }
 
-// ---- which of the two kernels of a launch does the work (a.select == 1): fv_mlp_skip_k drops the views that see nothing but is ~0.5 ms slower
+// ---- which of the two kernels of a launch does the work (a.select == 1): fv_mlp_k<KT, true> drops the views that see nothing but is ~0.5 ms slower
 // per 32 frames than fv_mlp_k where nothing can be dropped, and breaks even when about 15 % of the (tile, plane, view) groups are (3.2 ms per unit
 // share, profiles/fv_skip/).  fv_setup_k leaves, per batch element, the share of samples without a bilinear weight on a coarse grid (128 pixels x
 // up to 8 planes x all views, the kernels' own projection arithmetic); the skipping kernel runs when the mean over the batch reaches 25 % (on the
 // cameras measured the group share is 4 - 5 points below the sample share).  This only chooses the faster of two kernels that compute the same
-// values: WHAT is dropped is decided inside fv_mlp_skip_k from its own weights.  Both kernels read the same numbers, so exactly one proceeds; the
+// values: WHAT is dropped is decided inside the skipping kernel from its own weights.  Both kernels read the same numbers, so exactly one proceeds; the
 // other returns before it touches LDS.
 constexpr int kWsOutside = 265;  // (a free float between invK and bias1_b)
 constexpr float kSkipMinOutside = 0.25f;
@@ -123,7 +144,8 @@ __device__ __forceinline__ bool fv_selected(const FvArgs &a, bool skipping_kerne
     return (s >= kSkipMinOutside * (float)a.B) == skipping_kernel;
 }
 
-// ---- task order of fv_mlp_skip_k.  Tasks are handed out in rounds of gridDim.x * 8: in round r, workgroup `block` owns the eight consecutive tasks
+// ---- task order of the skipping kernel, fv_mlp_k<KT, true>.
+// Tasks are handed out in rounds of gridDim.x * 8: in round r, workgroup `block` owns the eight consecutive tasks
 // from (r * grid + idh_xcd_remap(block)) * 8 on, as in the uniform-cost kernels, but wave w takes sub-slot (w + r) & 7 of them and not always
 // sub-slot w.  Since views are dropped a task costs 352 .. 576 MFMAs per plane, and the static stride is a multiple of 8: where the tiles of an image
 // row are a multiple of 8 too (128 / 16 at the benchmark's shape), wave w met the same x-block of the image in every round, and the share of
@@ -142,7 +164,7 @@ __host__ __device__ __forceinline__ long long fv_skip_task(long long ntasks, int
 }
 
 #ifdef IDH_FV_WAVE_CLOCKS
-// Developer build only (tools/perf_fv_skip.py --wave-clocks; in no shipped library): per (workgroup, wave) of fv_mlp_skip_k's last launch the 100 MHz
+// Developer build only (tools/perf_fv_skip.py --wave-clocks; in no shipped library): per (workgroup, wave) of the skipping kernel's last launch the 100 MHz
 // wall clock at entry and at exit, and the HW_ID register (SIMD and CU the wave ran on).
 constexpr int kClkWords = 4;
 __device__ unsigned long long fv_wave_clocks[256 * 8 * kClkWords];
@@ -224,381 +246,14 @@ __global__ void fv_setup_k(const float *__restrict__ src_K, const float *__restr
 
 // KT = compile-time view count (7, 8) or 0 = run-time: with KT > 0 the view loop is fully unrolled so the
 // scheduler can slot view k+1's projection / blend VALU work between view k's 32 MFMAs.
-template <int KT>
+// kSkip = views that see nothing are dropped per tile and plane.  The two are separate kernels, so that the all-views one keeps its code
+// and schedule for launches in which nothing can be dropped: with a run-time second body in one kernel, the all-views path cost 0.4 - 0.5 ms more at
+// 32 frames.  What differs between them stands in `if constexpr (kSkip)` and nowhere else (see the file header for why).
+template <int KT, bool kSkip>
 __global__ __launch_bounds__(512) void fv_mlp_k(const FvArgs a) {
-    if (!fv_selected(a, false)) return;  // (the launcher enqueues this kernel and fv_mlp_skip_k: one of them does the work, see fv_selected)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    f32x4 *sW1 = reinterpret_cast<f32x4 *>(smem_raw);            // (K+4)*8*64
-    f32x4 *sW2 = sW1 + (a.K + 4) * kNS * 64;                       // 8*8*64
-    {
-        const f32x4 *g1 = reinterpret_cast<const f32x4 *>(a.w1v);
-        const f32x4 *g2 = reinterpret_cast<const f32x4 *>(a.w2);
-        const int n1 = (a.K + 4) * kNS * 64, n2 = kNS * kNS * 64;
-        for (int i = threadIdx.x; i < n1; i += 512) sW1[i] = g1[i];
-        for (int i = threadIdx.x; i < n2; i += 512) sW2[i] = g2[i];
-    }
-    __syncthreads();
-    // b2 / w3 / b3 (1 KiB) are read through L1: at K = 8 the weights use the whole 160 KiB of LDS
-    const float *s_b2 = a.vecs, *s_w3 = a.vecs + kHid;
-    const float b3 = a.vecs[2 * kHid];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ln = lane & 15, q = lane >> 4;
-    const int N = a.H * a.W;
-    const int K = KT > 0 ? KT : a.K;
-    const float Wf = (float)a.W, Hf = (float)a.H;
-    const long long ntasks = (long long)a.B * a.tiles_per_img * a.G;
-
-    // XCD-aware: hardware puts workgroup b on XCD b % 8; after the remap each XCD walks a contiguous run of tasks
-    // (= a band of image rows) per round, so the taps of its 32 workgroups share that XCD's 4 MB L2
-    for (long long task = (long long)idh_xcd_remap(blockIdx.x, gridDim.x) * 8 + wave; task < ntasks; task += (long long)gridDim.x * 8) {
-        // wave-uniform task coordinates: pin to SGPRs so the per-b constants come through the scalar cache
-        const int g = __builtin_amdgcn_readfirstlane((int)(task % a.G));
-        const int tile = __builtin_amdgcn_readfirstlane((int)((task / a.G) % a.tiles_per_img));
-        const int b = __builtin_amdgcn_readfirstlane((int)(task / ((long long)a.G * a.tiles_per_img)));
-        const int p_raw = tile * 16 + ln;
-        const bool live = p_raw < N;
-        const int p = live ? p_raw : N - 1;
-        const int py = p / a.W, px = p - py * a.W;
-        const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
-        const float *pb = a.ws + (size_t)b * kWsStrideReal;
-
-        const f32x4 cur4 = *reinterpret_cast<const f32x4 *>(a.cur + (size_t)b * a.cur_bs + (size_t)p * kC + 4 * q);
-        // back-projected ray of the pixel (geometry_utils.py:60) and its direction (cost_volume.py:618)
-        const float *iK = pb + kWsInvK;
-        const float rx = fmaf(iK[0], pxf, fmaf(iK[1], pyf, iK[2]));
-        const float ry = fmaf(iK[3], pxf, fmaf(iK[4], pyf, iK[5]));
-        const float rz = fmaf(iK[6], pxf, fmaf(iK[7], pyf, iK[8]));
-
-        // ---- per-pixel pre-activation: bias_b + W1[:,cur].cur + W1[:,cur_ray].ray -------------
-        f32x4 pre[kNS];
-#pragma unroll
-        for (int i = 0; i < kNS; ++i) pre[i] = *reinterpret_cast<const f32x4 *>(pb + kWsBias + 16 * i + 4 * q);
-        const int d0 = g * a.DP, d1 = min(a.D, d0 + a.DP);
-        if (d0 >= d1) continue;
-        // cur ray = normalize(depth * r): plane independent for depth > 0 (F.normalize eps 1e-12)
-        const float rn = fmaxf(sqrtf(rx * rx + ry * ry + rz * rz), 1e-12f);
-        const float crx = rx / rn, cry = ry / rn, crz = rz / rn;
-        {
-            const f32x4 rayB = (q == 0) ? (f32x4){crx, cry, crz, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
-            const f32x4 *w1p = reinterpret_cast<const f32x4 *>(a.w1p);
-#pragma unroll
-            for (int i = 0; i < kNS; ++i) {
-                const f32x4 A0 = w1p[(0 * kNS + i) * 64 + lane];
-                const f32x4 A1 = w1p[(1 * kNS + i) * 64 + lane];
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) pre[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[kk], cur4[kk], pre[i], 0, 0, 0);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) pre[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A1[kk], rayB[kk], pre[i], 0, 0, 0);
-            }
-        }
-
-        // ---- the projection of a source view is computed ONCE per voxel, by the lane quarter that owns the view's metadata (quarter q: views q and
-        // q + 4), and handed to the other three quarters through ds_bpermute_b32: packed tap address + 4 bilinear weights = 5 values per view
-        // instead of ~65 vector instructions repeated by all four lanes of the voxel (the fp32 MFMAs and the vector ALU share the SIMD: every
-        // instruction removed is matrix time).  Plane-independent parts of the own two views' homographies stay in registers.
-        const int ov[2] = {min(q, K - 1), min(q + 4, K - 1)};  // (absent views: a valid stand-in whose results nobody reads)
-        float oq[2][3], oh[2][3];
-#pragma unroll
-        for (int jv = 0; jv < 2; ++jv) {
-            const float *hm = pb + kWsHom + 12 * ov[jv];
-            oq[jv][0] = fmaf(hm[0], pxf, fmaf(hm[1], pyf, hm[2]));
-            oq[jv][1] = fmaf(hm[3], pxf, fmaf(hm[4], pyf, hm[5]));
-            oq[jv][2] = fmaf(hm[6], pxf, fmaf(hm[7], pyf, hm[8]));
-            oh[jv][0] = hm[9]; oh[jv][1] = hm[10]; oh[jv][2] = hm[11];
-        }
-        // taps through a buffer descriptor of this frame's K source maps: 32-bit offsets (view k: scalar offset k * N * 64 bytes)
-        const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.src + (size_t)b * a.src_bs), 0, K * N * kC * 4, 0x00020000);
-        const int bp0 = 4 * ln;  // ds_bpermute address of this voxel's lane in quarter 0 (+ 64 per quarter)
-
-        f32x4 ob = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const bool vec_ok = ((d0 & 3) == 0) && ((a.vol_cs & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.vol) & 15) == 0);
-        // ---- per-plane prologue of a voxel: the own two views' projection (bilinear weights, packed tap address: pixel index of tap 00 | x step << 30 |
-        // y step << 31) and their viewing rays / ray angles (cost_volume.py:630-659).  It runs ONE PLANE AHEAD, inside the previous plane's layer 2
-        // (256 MFMAs to hide under), together with the first view's tap loads: computed at the top of its own plane, the dependent chain
-        // projection -> ds_bpermute -> address -> tap loads (L2 latency) -> blend stood in front of every plane's first MFMA.
-        struct Own { int pk; float w00, w01, w10, w11, z; };
-        struct Pro { Own own[2]; float depth, m3, m4, m5, m6, m10, m11, m12, m13; };
-        struct Tap { f32x4 t00, t01, t10, t11; };
-        struct Wts { float w00, w01, w10, w11; };
-        float oc[2][3];  // source camera centres of the own views (cost_volume.py:630-633)
-#pragma unroll
-        for (int jv = 0; jv < 2; ++jv) {
-            const float *t = pb + kWsT + 4 * ov[jv];
-            oc[jv][0] = t[0]; oc[jv][1] = t[1]; oc[jv][2] = t[2];
-        }
-        auto prologue = [&](int d) {
-            Pro P;
-            const float depth = fv_plane(a, b, p, d);
-            P.depth = depth;
-#pragma unroll
-            for (int jv = 0; jv < 2; ++jv) {
-#ifdef IDH_ABL_FV2_NOPRO
-                P.own[jv].pk = p; P.own[jv].w00 = P.own[jv].w01 = P.own[jv].w10 = P.own[jv].w11 = depth; P.own[jv].z = depth;
-                continue;
-#endif
-                const float cx = fmaf(depth, oq[jv][0], oh[jv][0]);
-                const float cy = fmaf(depth, oq[jv][1], oh[jv][1]);
-                const float cz = fmaf(depth, oq[jv][2], oh[jv][2]);
-                const float z = fmaxf(cz, 1e-5f);
-                float r = __builtin_amdgcn_rcpf(z);
-                r = r * fmaf(-z, r, 2.0f);
-                const float su = cx * r, sv = cy * r;
-                const float sx = fminf(fmaxf(su - 0.5f, -1.0f), Wf);
-                const float sy = fminf(fmaxf(sv - 0.5f, -1.0f), Hf);
-                const float x0f = floorf(sx), y0f = floorf(sy);
-                const float fx = sx - x0f, fy = sy - y0f;
-                const int x0 = (int)x0f, y0 = (int)y0f;
-                const float wx0 = (x0 >= 0 && x0 < a.W) ? 1.0f - fx : 0.f;
-                const float wx1 = (x0 + 1 < a.W) ? fx : 0.f;
-                const float wy0 = (y0 >= 0 && y0 < a.H) ? 1.0f - fy : 0.f;
-                const float wy1 = (y0 + 1 < a.H) ? fy : 0.f;
-                const int xa0 = min(max(x0, 0), a.W - 1), xa1 = min(x0 + 1, a.W - 1);
-                const int ya0 = min(max(y0, 0), a.H - 1), ya1 = min(y0 + 1, a.H - 1);
-                P.own[jv].pk = (ya0 * a.W + xa0) | ((xa1 - xa0) << 30) | ((ya1 - ya0) << 31);
-                P.own[jv].w00 = wx0 * wy0; P.own[jv].w01 = wx1 * wy0; P.own[jv].w10 = wx0 * wy1; P.own[jv].w11 = wx1 * wy1;
-                P.own[jv].z = z;
-            }
-            // unit ray e = (X - c) / |X - c| through v_rsq_f32 + one Newton step (<= 1 ulp), and the ray angle as the plain dot product cr . e: the
-            // reference divides it by max(|cr|, 1e-5) max(|e|, 1e-5) (cosine_similarity), both 1 up to rounding for unit vectors - a 1e-7 relative
-            // difference, three orders below the 1e-4 bar.  (Absent views: computed on the stand-in view, multiplied by zero weight columns.)
-            const float Xx = depth * rx, Xy = depth * ry, Xz = depth * rz;
-            auto ray = [&](int jv, float &ang, float &e0, float &e1, float &e2) {
-                const float ax = Xx - oc[jv][0], ay = Xy - oc[jv][1], az = Xz - oc[jv][2];
-                const float n2 = fmaf(az, az, fmaf(ay, ay, ax * ax));
-                float in = __builtin_amdgcn_rsqf(fmaxf(n2, 1e-24f));
-                in = in * fmaf(-0.5f * n2 * in, in, 1.5f);
-                e0 = ax * in; e1 = ay * in; e2 = az * in;
-                ang = fmaf(crz, e2, fmaf(cry, e1, crx * e0));
-            };
-#ifdef IDH_ABL_FV2_NORAY
-            P.m3 = P.m4 = P.m5 = P.m6 = P.m10 = P.m11 = P.m12 = P.m13 = depth;
-            return P;
-#endif
-            ray(0, P.m3, P.m4, P.m5, P.m6);
-            ray(1, P.m10, P.m11, P.m12, P.m13);
-            return P;
-        };
-        auto issue = [&](const Pro &P, int k) {  // k: compile-time after unrolling (selects own[k >> 2] and the source quarter k & 3)
-            const int pk = __builtin_amdgcn_ds_bpermute(bp0 + 64 * (k & 3), P.own[k >> 2].pk);
-            const int o00 = ((pk & 0x3fffffff) << 6) + 16 * q;
-            const int o01 = o00 + (((pk >> 30) & 1) << 6);
-            const int ystep = (int)((unsigned)pk >> 31) * (a.W * 64);
-            Tap t;
-#ifdef IDH_ABL_FV2_NOTAPS  // (timing experiments, tools/abl_fv32.sh: results are meaningless)
-            t.t00 = t.t01 = t.t10 = t.t11 = (f32x4){1.f + (float)o00, 2.f + (float)o01, 3.f + (float)ystep, 4.f};
-            return t;
-#endif
-            const int so = __builtin_amdgcn_readfirstlane(k * N * (kC * 4));
-            t.t00 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsS, o00, so, 0));
-            t.t01 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsS, o01, so, 0));
-            t.t10 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsS, o00 + ystep, so, 0));
-            t.t11 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsS, o01 + ystep, so, 0));
-            return t;
-        };
-        auto weights = [&](const Pro &P, int k) {
-            const Own &o = P.own[k >> 2];
-            auto bperm = [&](float v) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bp0 + 64 * (k & 3), __builtin_bit_cast(int, v))); };
-            Wts w;
-            w.w00 = bperm(o.w00); w.w01 = bperm(o.w01); w.w10 = bperm(o.w10); w.w11 = bperm(o.w11);
-            return w;
-        };
-        Pro P = prologue(d0);
-        Tap cur = issue(P, 0);
-        Wts wc = weights(P, 0);
-#pragma unroll 1
-        for (int d = d0; d < d1; ++d) {
-            const float depth = P.depth;
-            f32x4 acc1[kNS];
-#pragma unroll
-            for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
-            // metadata registers of this lane: six per view - z, dot, ray angle, ray xyz - [1..6] view q, [8..13] view q+4, and the plane depth.  The
-            // per-view "valid" input of the reference is identically 1 (z is clamped to 1e-5 BEFORE the z > 0 test, geometry_utils.py:86,
-            // cost_volume.py:216; NaN depths included): its weight columns are folded into the layer-1 bias on the host
-            // (implicit-depth_amd/cost_volume.py), which leaves 12 slots per lane quarter = three 16-column blocks, plus the plane depth: in the
-            // (unused) first slot of view 7 in quarter 3 when K < 8, else as the only column of a fourth block.
-            float m2 = 0.f, m9 = 0.f;
-            const float m1 = q < K ? P.own[0].z : 0.f;
-            float m8 = q + 4 < K ? P.own[1].z : 0.f;
-            // Software-pipelined view loop: the tap address of view k+1 is fetched from its owner quarter and its 4 tap loads are issued before
-            // the bilinear blend / 32 MFMAs of view k, so L2 latency hides under matrix work; the weights follow with the address.
-            // Wave priority: layer 1 (taps, blend, metadata, activation: the vector-heavy half of a plane) runs at priority 2, layers 2 / 3 at 0.
-            // The SIMD's two waves drift into opposite halves and the arbiter then gives the vector-heavy wave its issue slots while the other
-            // wave's back-to-back MFMAs fill the matrix pipe: 15.2 -> 14.6 ms at 32 frames; raising layer 3 as well, or only the view loop, or the
-            // next plane's prologue: 14.8 - 15.1 (profiles/r05/experiments.md).
-            __builtin_amdgcn_s_setprio(2);
-            constexpr int KU = KT > 0 ? KT : kMaxK;
-#pragma unroll
-            for (int k = 0; k < KU; ++k) {
-                if (KT == 0 && k >= K) break;
-                const int kn = (KT > 0) ? (k + 1 < KT ? k + 1 : k) : k + 1;  // (KT = 0: the stand-in of an absent view k + 1 < 8 is fetched, never used)
-                Tap nxt = cur;
-                Wts wn = wc;
-                if (kn != k && kn < KU) { nxt = issue(P, kn); wn = weights(P, kn); }
-                f32x4 wv;
-#ifdef IDH_ABL_FV2_NOBLEND
-                wv = cur.t00 + cur.t11;
-                float part = wc.w00 + wc.w11 + cur.t01[0] + cur.t10[0];
-#else
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    wv[e] = fmaf(wc.w11, cur.t11[e], fmaf(wc.w10, cur.t10[e], fmaf(wc.w01, cur.t01[e], wc.w00 * cur.t00[e])));
-                float part = wv[0] * cur4[0];
-                part = fmaf(wv[1], cur4[1], part); part = fmaf(wv[2], cur4[2], part); part = fmaf(wv[3], cur4[3], part);
-                part += __shfl_xor(part, 16, 64);
-                part += __shfl_xor(part, 32, 64);
-#endif
-                const float dotv = part;  // * mask (== 1)
-                const bool s0 = (k == q), s1 = (k == q + 4);
-                m2 = s0 ? dotv : m2;
-                m9 = s1 ? dotv : m9;
-                // layer-1 block k: warped features of view k
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) {
-#ifdef IDH_ABL_FV2_NOLDSA
-                    const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
-#else
-                    const f32x4 A = sW1[(k * kNS + i) * 64 + lane];
-#endif
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], wv[kk], acc1[i], 0, 0, 0);
-                }
-                if constexpr (KT > 0) {
-                    // Scheduling hint (unrolled view loop = one scheduling region): small alternating groups of MFMAs and vector instructions
-                    // instead of a vector block followed by 32 back-to-back matrix ops (history of the pattern: profiles/r02/experiments.md)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#ifndef IDH_ABL_FV_VALU_PER_GROUP
-#define IDH_ABL_FV_VALU_PER_GROUP 3
-#endif
-                        __builtin_amdgcn_sched_group_barrier(0x002, IDH_ABL_FV_VALU_PER_GROUP, 0);
-                    }
-                }
-                cur = nxt;
-                wc = wn;
-            }
-            const float m3 = P.m3, m4 = P.m4, m5 = P.m5, m6 = P.m6, m10 = P.m10, m11 = P.m11, m12 = P.m12, m13 = P.m13;
-            const bool depth_in_q3 = K < 8;
-            if (depth_in_q3 && q == 3) m8 = depth;
-            const f32x4 mb[4] = {(f32x4){m1, m2, m3, m4}, (f32x4){m5, m6, m8, m9}, (f32x4){m10, m11, m12, m13}, (f32x4){depth, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) {
-                    const f32x4 A = sW1[((K + c) * kNS + i) * 64 + lane];
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], mb[c][kk], acc1[i], 0, 0, 0);
-                }
-            }
-            if (!depth_in_q3) {  // K = 8: the plane depth is the only column of block 3 (quarter 0, k-step 0)
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) {
-                    const float A0 = reinterpret_cast<const float *>(&sW1[((K + 3) * kNS + i) * 64 + lane])[0];
-                    acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0, mb[3][0], acc1[i], 0, 0, 0);
-                }
-            }
-            // ---- LeakyReLU(0.01) -> layer 2 (weights from LDS) -> LeakyReLU -> layer 3 ----------
-            f32x4 acc2[kNS];
-            Pro Pn;
-            Tap curn;
-            Wts wcn;
-#pragma unroll
-            for (int i = 0; i < kNS; ++i) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc1[i][r] = lrelu01(acc1[i][r]);
-                acc2[i] = *reinterpret_cast<const f32x4 *>(s_b2 + 16 * i + 4 * q);
-            }
-            __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-            for (int c = 0; c < kNS; ++c) {
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) {
-#ifdef IDH_ABL_FV2_NOLDSA
-                    const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
-#else
-                    const f32x4 A = sW2[(c * kNS + i) * 64 + lane];
-#endif
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], acc1[c][kk], acc2[i], 0, 0, 0);
-                }
-                // The NEXT plane's prologue and first taps ride on layer 2 (the last plane of a task repeats its own: harmless).  Measured placements,
-                // 32 frames (profiles/r05/experiments.md): prologue at the top of its own plane 15.45 ms; here with a sched_barrier per chunk 15.48 (no
-                // gain: the scheduler then runs the chunk's 32 MFMAs first and the whole dependent chain after them); without the per-chunk barriers,
-                // in chunk 0 / 1 / 4: 14.9 / 15.1 / 15.3; before the activation 15.5; before the metadata MFMAs 15.4.
-                // (Run-time view count, KT = 0: chunk 1 and a barrier per chunk - without them that variant spills 400 B per lane.)
-                if (c == (KT > 0 ? 0 : 1)) {
-                    Pn = prologue(min(d + 1, d1 - 1));
-                    curn = issue(Pn, 0);
-                    wcn = weights(Pn, 0);
-                }
-                if constexpr (KT == 0) __builtin_amdgcn_sched_barrier(0);
-            }
-            float s = 0.f;
-#ifdef IDH_ABL_FV2_NOL3
-#pragma unroll
-            for (int i = 0; i < kNS; ++i) s += acc2[i][0];
-#else
-#pragma unroll
-            for (int i = 0; i < kNS; ++i) {
-                const f32x4 w3 = *reinterpret_cast<const f32x4 *>(s_w3 + 16 * i + 4 * q);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s = fmaf(w3[r], lrelu01(acc2[i][r]), s);
-            }
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-#endif
-            const float val = s + b3;
-            if (a.vol_cs > 0) {
-                // NHWC output: collect 4 consecutive planes and write one 16-byte vector (a 4-byte store
-                // per plane into 256-byte pixel rows cost ~10x write amplification in the PMC counters)
-                const int e = (d - d0) & 3;
-                ob[0] = e == 0 ? val : ob[0]; ob[1] = e == 1 ? val : ob[1]; ob[2] = e == 2 ? val : ob[2]; ob[3] = e == 3 ? val : ob[3];
-                if (q == 0 && live && (e == 3 || d == d1 - 1)) {
-                    float *o = a.vol + ((size_t)b * N + p) * a.vol_cs + (d - e);
-                    if (e == 3 && vec_ok) *reinterpret_cast<f32x4 *>(o) = ob;
-                    else { o[0] = ob[0]; if (e >= 1) o[1] = ob[1]; if (e >= 2) o[2] = ob[2]; if (e >= 3) o[3] = ob[3]; }
-                }
-            } else if (q == 0 && live) {
-                a.vol[((size_t)b * a.D + d) * N + p] = val;
-            }
-            // overall mask: the reference overwrites it every plane, the LAST plane survives
-            // (only the last plane's mask is ever visible, so it is not tracked in the view loop — 10 vector instructions per
-            // view and plane — but recomputed here from the same projection expressions, once per pixel tile)
-            if (a.mask != nullptr && d == a.D - 1) {
-                bool any_inb = false, any_front = false;
-                for (int k = 0; k < K; ++k) {
-                    const float *hm = pb + kWsHom + 12 * k;
-                    const float qx = fmaf(hm[0], pxf, fmaf(hm[1], pyf, hm[2]));
-                    const float qy = fmaf(hm[3], pxf, fmaf(hm[4], pyf, hm[5]));
-                    const float qz = fmaf(hm[6], pxf, fmaf(hm[7], pyf, hm[8]));
-                    const float cx = fmaf(depth, qx, hm[9]);
-                    const float cy = fmaf(depth, qy, hm[10]);
-                    const float cz = fmaf(depth, qz, hm[11]);
-                    const float z = fmaxf(cz, 1e-5f);
-                    float r = __builtin_amdgcn_rcpf(z);
-                    r = r * fmaf(-z, r, 2.0f);
-                    const float u = cx * r, v = cy * r;
-                    any_inb |= (u > 2.f) & (u < Wf - 2.f) & (v > 2.f) & (v < Hf - 2.f);
-                    any_front |= z > 0.f;
-                }
-                if (q == 0 && live) a.mask[(size_t)b * N + p] = (any_front && any_inb) ? 1 : 0;
-            }
-            P = Pn; cur = curn; wc = wcn;
-        }
-    }
-}
-
-// ---- fv_mlp_k with views that see nothing dropped per tile and plane.  A kernel of its own, so that fv_mlp_k above keeps its code and
-// schedule for launches in which nothing can be dropped: built into one kernel, the second body cost the all-views path 0.4 - 0.5 ms at 32 frames.
-// KT = compile-time view count (7, 8) or 0 = run-time: with KT > 0 the view loop is fully unrolled so the
-// scheduler can slot view k+1's projection / blend VALU work between view k's 32 MFMAs.
-template <int KT>
-__global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
-    if (!fv_selected(a, true)) return;
+    if (!fv_selected(a, kSkip)) return;  // (the launcher may enqueue both kernels: one of them does the work, see fv_selected)
 #ifdef IDH_FV_WAVE_CLOCKS
-    const unsigned long long clk0 = wall_clock64();
+    [[maybe_unused]] const unsigned long long clk0 = kSkip ? wall_clock64() : 0;
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     f32x4 *sW1 = reinterpret_cast<f32x4 *>(smem_raw);            // (K+4)*8*64
@@ -624,11 +279,16 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
     const long long ntasks = (long long)a.B * a.tiles_per_img * a.G;
 
     // XCD-aware: hardware puts workgroup b on XCD b % 8; after the remap each XCD walks a contiguous run of tasks
-    // (= a band of image rows) per round, so the taps of its 32 workgroups share that XCD's 4 MB L2.  Within the workgroup's eight tasks of a round
-    // the waves rotate (fv_skip_task): a slot past ntasks in the last round is skipped, the wave's loop does not end there.
-    for (long long round = 0; round * gridDim.x * 8 < ntasks; ++round) {
-        const long long task = fv_skip_task(ntasks, (int)gridDim.x, (int)blockIdx.x, wave, round);
-        if (task < 0) continue;
+    // (= a band of image rows) per round, so the taps of its 32 workgroups share that XCD's 4 MB L2.  All views: wave w walks the tasks of sub-slot w
+    // (`it` is the task).  Skipping: `it` counts the rounds, and within the workgroup's eight tasks of a round the waves rotate (fv_skip_task): a slot
+    // past ntasks in the last round is skipped, the wave's loop does not end there.
+    for (long long it = kSkip ? 0 : (long long)idh_xcd_remap(blockIdx.x, gridDim.x) * 8 + wave; (kSkip ? it * gridDim.x * 8 : it) < ntasks;
+         it += kSkip ? 1 : (long long)gridDim.x * 8) {
+        long long task = it;
+        if constexpr (kSkip) {
+            task = fv_skip_task(ntasks, (int)gridDim.x, (int)blockIdx.x, wave, it);
+            if (task < 0) continue;
+        }
         // wave-uniform task coordinates: pin to SGPRs so the per-b constants come through the scalar cache
         const int g = __builtin_amdgcn_readfirstlane((int)(task % a.G));
         const int tile = __builtin_amdgcn_readfirstlane((int)((task / a.G) % a.tiles_per_img));
@@ -658,14 +318,21 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
         const float crx = rx / rn, cry = ry / rn, crz = rz / rn;
         {
             const f32x4 rayB = (q == 0) ? (f32x4){crx, cry, crz, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
-            // (the 16 fragments through a buffer descriptor - one 32-bit lane offset plus a constant each: as 64-bit pointers the compiler hoists the
-            // 16 addresses out of the task loop and holds 32 vector registers for them through the whole kernel, which the second plane body
-            // cannot afford)
-            const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w1p), 0, 2 * kNS * 64 * 16, 0x00020000);
+            // (skipping: the 16 fragments through a buffer descriptor - one 32-bit lane offset plus a constant each: as 64-bit pointers the compiler
+            // hoists the 16 addresses out of the task loop and holds 32 vector registers for them through the whole kernel, which the second plane
+            // body cannot afford)
+            auto w1p_frag = [&](int j) -> f32x4 {
+                if constexpr (kSkip) {
+                    const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w1p), 0, 2 * kNS * 64 * 16, 0x00020000);
+                    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsP, 16 * lane, j * 1024, 0));
+                } else {
+                    return reinterpret_cast<const f32x4 *>(a.w1p)[j * 64 + lane];
+                }
+            };
 #pragma unroll
             for (int i = 0; i < kNS; ++i) {
-                const f32x4 A0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsP, 16 * lane, (0 * kNS + i) * 1024, 0));
-                const f32x4 A1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsP, 16 * lane, (1 * kNS + i) * 1024, 0));
+                const f32x4 A0 = w1p_frag(0 * kNS + i);
+                const f32x4 A1 = w1p_frag(1 * kNS + i);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) pre[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[kk], cur4[kk], pre[i], 0, 0, 0);
 #pragma unroll
@@ -783,7 +450,8 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
             w.w00 = bperm(o.w00); w.w01 = bperm(o.w01); w.w10 = bperm(o.w10); w.w11 = bperm(o.w11);
             return w;
         };
-        // ---- views that contribute to this tile in plane P: bit k is set when some voxel of the tile has a non-zero bilinear weight in view k.  The
+        // ---- (kSkip only, down to first_view(); the all-views kernel calls none of it)
+        // views that contribute to this tile in plane P: bit k is set when some voxel of the tile has a non-zero bilinear weight in view k.  The
         // kernel's OWN weights decide (a ballot over the owner quarters' w00..w11), so a view is dropped exactly when its blend would have given
         // sixteen zeros for all 16 voxels, never on a geometric estimate.  Wave-uniform (SGPR).
         const unsigned all_views = (1u << K) - 1u;
@@ -833,13 +501,25 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
         // first view of a plane's view loop: the lowest active one (view 0 when all are, or - as a placeholder - when none is)
         auto first_view = [&](unsigned act) { return act ? __builtin_ctz(act) : 0; };
         Pro P = prologue(d0);
-        unsigned act = active(P);
-        Tap cur = issue_rt(P, first_view(act), act == 0);
-        Wts wc = weights_rt(P, first_view(act));
+        [[maybe_unused]] unsigned act = 0;
+        Tap cur;
+        Wts wc;
+        if constexpr (kSkip) {
+            act = active(P);
+            cur = issue_rt(P, first_view(act), act == 0);
+            wc = weights_rt(P, first_view(act));
+        } else {
+            cur = issue(P, 0);
+            wc = weights(P, 0);
+        }
 #pragma unroll 1
         for (int d = d0; d < d1; ++d) {
             const float depth = P.depth;
             f32x4 acc1[kNS], acc2[kNS];
+            Pro Pn;
+            Tap curn;
+            Wts wcn;
+            [[maybe_unused]] unsigned actn = 0;
             // metadata registers of this lane: six per view - z, dot, ray angle, ray xyz - [1..6] view q, [8..13] view q+4, and the plane depth.  The
             // per-view "valid" input of the reference is identically 1 (z is clamped to 1e-5 BEFORE the z > 0 test, geometry_utils.py:86,
             // cost_volume.py:216; NaN depths included): its weight columns are folded into the layer-1 bias on the host
@@ -856,21 +536,59 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
             // next plane's prologue: 14.8 - 15.1 (profiles/r05/experiments.md).
             __builtin_amdgcn_s_setprio(2);
             constexpr int KU = KT > 0 ? KT : kMaxK;
-            auto layer2_chunk = [&](int c) {
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) {
-#ifdef IDH_ABL_FV2_NOLDSA
-                    const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
+            // bilinear blend of a view's four taps (this quarter's four channels) into wv; returns the voxel's <warped, cur> over all 16 channels
+            auto blend = [&](const Tap &t, const Wts &w, f32x4 &wv) -> float {
+#ifdef IDH_ABL_FV2_NOBLEND
+                wv = t.t00 + t.t11;
+                float part = w.w00 + w.w11 + t.t01[0] + t.t10[0];
 #else
-                    const f32x4 A = sW2[(c * kNS + i) * 64 + lane];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) wv[e] = fmaf(w.w11, t.t11[e], fmaf(w.w10, t.t10[e], fmaf(w.w01, t.t01[e], w.w00 * t.t00[e])));
+                float part = wv[0] * cur4[0];
+                part = fmaf(wv[1], cur4[1], part); part = fmaf(wv[2], cur4[2], part); part = fmaf(wv[3], cur4[3], part);
+                part += __shfl_xor(part, 16, 64);
+                part += __shfl_xor(part, 32, 64);
+#endif
+                return part;
+            };
+            if constexpr (!kSkip) {
+#pragma unroll
+                for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
+#pragma unroll
+                for (int k = 0; k < KU; ++k) {
+                    if (KT == 0 && k >= K) break;
+                    const int kn = (KT > 0) ? (k + 1 < KT ? k + 1 : k) : k + 1;  // (KT = 0: the stand-in of an absent view k + 1 < 8 is fetched, never used)
+                    Tap nxt = cur;
+                    Wts wn = wc;
+                    if (kn != k && kn < KU) { nxt = issue(P, kn); wn = weights(P, kn); }
+                    f32x4 wv;
+                    const float dotv = blend(cur, wc, wv);  // * mask (== 1)
+                    const bool s0 = (k == q), s1 = (k == q + 4);
+                    m2 = s0 ? dotv : m2;
+                    m9 = s1 ? dotv : m9;
+                    // layer-1 block k: warped features of view k
+#pragma unroll
+                    for (int i = 0; i < kNS; ++i) {
+#ifdef IDH_ABL_FV2_NOLDSA
+                        const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
+#else
+                        const f32x4 A = sW1[(k * kNS + i) * 64 + lane];
 #endif
 #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], acc1[c][kk], acc2[i], 0, 0, 0);
+                        for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], wv[kk], acc1[i], 0, 0, 0);
+                    }
+                    if constexpr (KT > 0) {
+                        // Scheduling hint (unrolled view loop = one scheduling region): small alternating groups of MFMAs and vector instructions
+                        // instead of a vector block followed by 32 back-to-back matrix ops (history of the pattern: profiles/r02/experiments.md)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x002, IDH_ABL_FV_VALU_PER_GROUP, 0);
+                        }
+                    }
+                    cur = nxt;
+                    wc = wn;
                 }
-            };
-            // what follows the view loop up to where the next plane's prologue starts - metadata blocks of layer 1, LeakyReLU, chunk 0 of layer 2 - is
-            // part of BOTH bodies (not placed behind their join), so that the all-views body stays the one scheduling region it always was
-            auto layer1_tail = [&]() {
                 const float m3 = P.m3, m4 = P.m4, m5 = P.m5, m6 = P.m6, m10 = P.m10, m11 = P.m11, m12 = P.m12, m13 = P.m13;
                 const bool depth_in_q3 = K < 8;
                 if (depth_in_q3 && q == 3) m8 = depth;
@@ -892,77 +610,89 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
                     }
                 }
                 // ---- LeakyReLU(0.01) -> layer 2 (weights from LDS) -> LeakyReLU -> layer 3 ----------
-                // (only the rows chunk 0 reads are activated here; the other seven follow behind the join, where the single-body kernel's compiler
-                // had put them as well)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc1[0][r] = lrelu01(acc1[0][r]);
-#pragma unroll
-                for (int i = 0; i < kNS; ++i) acc2[i] = *reinterpret_cast<const f32x4 *>(s_b2 + 16 * i + 4 * q);
-                __builtin_amdgcn_s_setprio(0);
-                layer2_chunk(0);
-            };
-            // a view whose index is a run-time (wave-uniform) value: the loop over the active views
-            auto view_rt = [&](int k, const Tap &cur, const Wts &wc) {
-                f32x4 wv;
-#ifdef IDH_ABL_FV2_NOBLEND
-                wv = cur.t00 + cur.t11;
-                float part = wc.w00 + wc.w11 + cur.t01[0] + cur.t10[0];
-#else
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    wv[e] = fmaf(wc.w11, cur.t11[e], fmaf(wc.w10, cur.t10[e], fmaf(wc.w01, cur.t01[e], wc.w00 * cur.t00[e])));
-                float part = wv[0] * cur4[0];
-                part = fmaf(wv[1], cur4[1], part); part = fmaf(wv[2], cur4[2], part); part = fmaf(wv[3], cur4[3], part);
-                part += __shfl_xor(part, 16, 64);
-                part += __shfl_xor(part, 32, 64);
-#endif
-                m2 = (k == q) ? part : m2;
-                m9 = (k == q + 4) ? part : m9;
 #pragma unroll
                 for (int i = 0; i < kNS; ++i) {
-#ifdef IDH_ABL_FV2_NOLDSA
-                    const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
-#else
-                    const f32x4 A = sW1[(k * kNS + i) * 64 + lane];
-#endif
 #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], wv[kk], acc1[i], 0, 0, 0);
+                    for (int r = 0; r < 4; ++r) acc1[i][r] = lrelu01(acc1[i][r]);
+                    acc2[i] = *reinterpret_cast<const f32x4 *>(s_b2 + 16 * i + 4 * q);
                 }
-            };
-            // Two bodies, selected per tile and plane by the wave-uniform mask.  Every view active: the fully unrolled loop with
-            // compile-time view indices, as the kernel had it before views could be dropped.  Otherwise a loop over the set bits of the mask with the
-            // same software pipeline (the next ACTIVE view's taps are in flight during this view's blend and MFMAs); a dropped view issues no
-            // ds_bpermute, tap load, blend or MFMA, and its `dot` input keeps the +0 it is initialised with.  The last active view stands outside the
-            // loop so that the loop body issues its loads unconditionally: with a branch around them the wait for THIS view's taps would have to
-            // cover the next view's as well.
-            if (act == all_views) {
+                __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-                for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
+                for (int c = 0; c < kNS; ++c) {
 #pragma unroll
-                for (int k = 0; k < KU; ++k) {
-                    if (KT == 0 && k >= K) break;
-                    const int kn = (KT > 0) ? (k + 1 < KT ? k + 1 : k) : k + 1;  // (KT = 0: the stand-in of an absent view k + 1 < 8 is fetched, never used)
-                    Tap nxt = cur;
-                    Wts wn = wc;
-                    if (kn != k && kn < KU) { nxt = issue(P, kn); wn = weights(P, kn); }
-                    f32x4 wv;
-#ifdef IDH_ABL_FV2_NOBLEND
-                    wv = cur.t00 + cur.t11;
-                    float part = wc.w00 + wc.w11 + cur.t01[0] + cur.t10[0];
+                    for (int i = 0; i < kNS; ++i) {
+#ifdef IDH_ABL_FV2_NOLDSA
+                        const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
 #else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        wv[e] = fmaf(wc.w11, cur.t11[e], fmaf(wc.w10, cur.t10[e], fmaf(wc.w01, cur.t01[e], wc.w00 * cur.t00[e])));
-                    float part = wv[0] * cur4[0];
-                    part = fmaf(wv[1], cur4[1], part); part = fmaf(wv[2], cur4[2], part); part = fmaf(wv[3], cur4[3], part);
-                    part += __shfl_xor(part, 16, 64);
-                    part += __shfl_xor(part, 32, 64);
+                        const f32x4 A = sW2[(c * kNS + i) * 64 + lane];
 #endif
-                    const float dotv = part;  // * mask (== 1)
-                    const bool s0 = (k == q), s1 = (k == q + 4);
-                    m2 = s0 ? dotv : m2;
-                    m9 = s1 ? dotv : m9;
-                    // layer-1 block k: warped features of view k
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk) acc2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], acc1[c][kk], acc2[i], 0, 0, 0);
+                    }
+                    // The NEXT plane's prologue and first taps ride on layer 2 (the last plane of a task repeats its own: harmless).  Measured placements,
+                    // 32 frames (profiles/r05/experiments.md): prologue at the top of its own plane 15.45 ms; here with a sched_barrier per chunk 15.48 (no
+                    // gain: the scheduler then runs the chunk's 32 MFMAs first and the whole dependent chain after them); without the per-chunk barriers,
+                    // in chunk 0 / 1 / 4: 14.9 / 15.1 / 15.3; before the activation 15.5; before the metadata MFMAs 15.4.
+                    // (Run-time view count, KT = 0: chunk 1 and a barrier per chunk - without them that variant spills 400 B per lane.)
+                    if (c == (KT > 0 ? 0 : 1)) {
+                        Pn = prologue(min(d + 1, d1 - 1));
+                        curn = issue(Pn, 0);
+                        wcn = weights(Pn, 0);
+                    }
+                    if constexpr (KT == 0) __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+                auto layer2_chunk = [&](int c) {
+#pragma unroll
+                    for (int i = 0; i < kNS; ++i) {
+#ifdef IDH_ABL_FV2_NOLDSA
+                        const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
+#else
+                        const f32x4 A = sW2[(c * kNS + i) * 64 + lane];
+#endif
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk) acc2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], acc1[c][kk], acc2[i], 0, 0, 0);
+                    }
+                };
+                // what follows the view loop up to where the next plane's prologue starts - metadata blocks of layer 1, LeakyReLU, chunk 0 of layer 2 - is
+                // part of BOTH bodies (not placed behind their join), so that the all-views body stays the one scheduling region it always was
+                auto layer1_tail = [&]() {
+                    const float m3 = P.m3, m4 = P.m4, m5 = P.m5, m6 = P.m6, m10 = P.m10, m11 = P.m11, m12 = P.m12, m13 = P.m13;
+                    const bool depth_in_q3 = K < 8;
+                    if (depth_in_q3 && q == 3) m8 = depth;
+                    const f32x4 mb[4] = {(f32x4){m1, m2, m3, m4}, (f32x4){m5, m6, m8, m9}, (f32x4){m10, m11, m12, m13}, (f32x4){depth, 0.f, 0.f, 0.f}};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                        for (int i = 0; i < kNS; ++i) {
+                            const f32x4 A = sW1[((K + c) * kNS + i) * 64 + lane];
+#pragma unroll
+                            for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], mb[c][kk], acc1[i], 0, 0, 0);
+                        }
+                    }
+                    if (!depth_in_q3) {  // K = 8: the plane depth is the only column of block 3 (quarter 0, k-step 0)
+#pragma unroll
+                        for (int i = 0; i < kNS; ++i) {
+                            const float A0 = reinterpret_cast<const float *>(&sW1[((K + 3) * kNS + i) * 64 + lane])[0];
+                            acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0, mb[3][0], acc1[i], 0, 0, 0);
+                        }
+                    }
+                    // ---- LeakyReLU(0.01) -> layer 2 (weights from LDS) -> LeakyReLU -> layer 3 ----------
+                    // (only the rows chunk 0 reads are activated here; the other seven follow behind the join, where the single-body kernel's compiler
+                    // had put them as well)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc1[0][r] = lrelu01(acc1[0][r]);
+#pragma unroll
+                    for (int i = 0; i < kNS; ++i) acc2[i] = *reinterpret_cast<const f32x4 *>(s_b2 + 16 * i + 4 * q);
+                    __builtin_amdgcn_s_setprio(0);
+                    layer2_chunk(0);
+                };
+                // a view whose index is a run-time (wave-uniform) value: the loop over the active views
+                auto view_rt = [&](int k, const Tap &cur, const Wts &wc) {
+                    f32x4 wv;
+                    const float part = blend(cur, wc, wv);
+                    m2 = (k == q) ? part : m2;
+                    m9 = (k == q + 4) ? part : m9;
 #pragma unroll
                     for (int i = 0; i < kNS; ++i) {
 #ifdef IDH_ABL_FV2_NOLDSA
@@ -973,70 +703,93 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
 #pragma unroll
                         for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], wv[kk], acc1[i], 0, 0, 0);
                     }
-                    if constexpr (KT > 0) {
-                        // Scheduling hint (unrolled view loop = one scheduling region): small alternating groups of MFMAs and vector instructions
-                        // instead of a vector block followed by 32 back-to-back matrix ops (history of the pattern: profiles/r02/experiments.md)
+                };
+                // Two bodies, selected per tile and plane by the wave-uniform mask.  Every view active: the fully unrolled loop with
+                // compile-time view indices, as the kernel had it before views could be dropped.  Otherwise a loop over the set bits of the mask with the
+                // same software pipeline (the next ACTIVE view's taps are in flight during this view's blend and MFMAs); a dropped view issues no
+                // ds_bpermute, tap load, blend or MFMA, and its `dot` input keeps the +0 it is initialised with.  The last active view stands outside the
+                // loop so that the loop body issues its loads unconditionally: with a branch around them the wait for THIS view's taps would have to
+                // cover the next view's as well.
+                if (act == all_views) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#ifndef IDH_ABL_FV_VALU_PER_GROUP
-#define IDH_ABL_FV_VALU_PER_GROUP 3
+                    for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
+#pragma unroll
+                    for (int k = 0; k < KU; ++k) {
+                        if (KT == 0 && k >= K) break;
+                        const int kn = (KT > 0) ? (k + 1 < KT ? k + 1 : k) : k + 1;  // (KT = 0: the stand-in of an absent view k + 1 < 8 is fetched, never used)
+                        Tap nxt = cur;
+                        Wts wn = wc;
+                        if (kn != k && kn < KU) { nxt = issue(P, kn); wn = weights(P, kn); }
+                        f32x4 wv;
+                        const float dotv = blend(cur, wc, wv);  // * mask (== 1)
+                        const bool s0 = (k == q), s1 = (k == q + 4);
+                        m2 = s0 ? dotv : m2;
+                        m9 = s1 ? dotv : m9;
+                        // layer-1 block k: warped features of view k
+#pragma unroll
+                        for (int i = 0; i < kNS; ++i) {
+#ifdef IDH_ABL_FV2_NOLDSA
+                            const f32x4 A = (f32x4){1.f, 2.f, 3.f, 4.f} * (float)(i + 1);
+#else
+                            const f32x4 A = sW1[(k * kNS + i) * 64 + lane];
 #endif
-                            __builtin_amdgcn_sched_group_barrier(0x002, IDH_ABL_FV_VALU_PER_GROUP, 0);
-                        }
-                    }
-                    cur = nxt;
-                    wc = wn;
-                }
-                layer1_tail();
-            } else {
 #pragma unroll
-                for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
-                if (act != 0) {
-                    int k = __builtin_ctz(act);
-                    unsigned rem = act & (act - 1u);
-#pragma unroll 1
-                    while (rem != 0) {
-                        const int kn = __builtin_ctz(rem);
-                        rem &= rem - 1u;
-                        const Tap nxt = issue_rt(P, kn, false);
-                        const Wts wn = weights_rt(P, kn);
-                        view_rt(k, cur, wc);
+                            for (int kk = 0; kk < 4; ++kk) acc1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[kk], wv[kk], acc1[i], 0, 0, 0);
+                        }
+                        if constexpr (KT > 0) {
+                            // Scheduling hint (unrolled view loop = one scheduling region): small alternating groups of MFMAs and vector instructions
+                            // instead of a vector block followed by 32 back-to-back matrix ops (history of the pattern: profiles/r02/experiments.md)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x002, IDH_ABL_FV_VALU_PER_GROUP, 0);
+                            }
+                        }
                         cur = nxt;
                         wc = wn;
-                        k = kn;
                     }
-                    view_rt(k, cur, wc);
+                    layer1_tail();
+                } else {
+#pragma unroll
+                    for (int i = 0; i < kNS; ++i) acc1[i] = pre[i];
+                    if (act != 0) {
+                        int k = __builtin_ctz(act);
+                        unsigned rem = act & (act - 1u);
+#pragma unroll 1
+                        while (rem != 0) {
+                            const int kn = __builtin_ctz(rem);
+                            rem &= rem - 1u;
+                            const Tap nxt = issue_rt(P, kn, false);
+                            const Wts wn = weights_rt(P, kn);
+                            view_rt(k, cur, wc);
+                            cur = nxt;
+                            wc = wn;
+                            k = kn;
+                        }
+                        view_rt(k, cur, wc);
+                    }
+                    layer1_tail();
                 }
-                layer1_tail();
-            }
 #pragma unroll
-            for (int i = 1; i < kNS; ++i) {
+                for (int i = 1; i < kNS; ++i) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc1[i][r] = lrelu01(acc1[i][r]);
-            }
-            Pro Pn;
-            Tap curn;
-            Wts wcn;
-            unsigned actn = 0;
-            // The NEXT plane's prologue and first taps ride on layer 2 (the last plane of a task repeats its own: harmless).  Measured placements,
-            // 32 frames (profiles/r05/experiments.md): prologue at the top of its own plane 15.45 ms; here with a sched_barrier per chunk 15.48 (no
-            // gain: the scheduler then runs the chunk's 32 MFMAs first and the whole dependent chain after them); without the per-chunk barriers,
-            // in chunk 0 / 1 / 4: 14.9 / 15.1 / 15.3; before the activation 15.5; before the metadata MFMAs 15.4.
-            // (Run-time view count, KT = 0: chunk 1 and a barrier per chunk - without them that variant spills 400 B per lane.)
-            auto next_plane = [&]() {
-                Pn = prologue(min(d + 1, d1 - 1));
-                actn = active(Pn);
-                curn = issue_rt(Pn, first_view(actn), actn == 0);
-                wcn = weights_rt(Pn, first_view(actn));
-            };
-            if constexpr (KT > 0) next_plane();
-            else __builtin_amdgcn_sched_barrier(0);
+                    for (int r = 0; r < 4; ++r) acc1[i][r] = lrelu01(acc1[i][r]);
+                }
+                // the next plane's prologue, its mask and first taps ride on layer 2, at the place the all-views branch puts them
+                auto next_plane = [&]() {
+                    Pn = prologue(min(d + 1, d1 - 1));
+                    actn = active(Pn);
+                    curn = issue_rt(Pn, first_view(actn), actn == 0);
+                    wcn = weights_rt(Pn, first_view(actn));
+                };
+                if constexpr (KT > 0) next_plane();
+                else __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int c = 1; c < kNS; ++c) {
-                layer2_chunk(c);
-                if (KT == 0 && c == 1) next_plane();
-                if constexpr (KT == 0) __builtin_amdgcn_sched_barrier(0);
+                for (int c = 1; c < kNS; ++c) {
+                    layer2_chunk(c);
+                    if (KT == 0 && c == 1) next_plane();
+                    if constexpr (KT == 0) __builtin_amdgcn_sched_barrier(0);
+                }
             }
             float s = 0.f;
 #ifdef IDH_ABL_FV2_NOL3
@@ -1092,7 +845,7 @@ __global__ __launch_bounds__(512) void fv_mlp_skip_k(const FvArgs a) {
         }
     }
 #ifdef IDH_FV_WAVE_CLOCKS
-    if (lane == 0 && blockIdx.x < 256) {  // (plain vector stores; HW_ID = hardware register 4: SIMD in bits 4-5, CU in 8-11, SH in 12, SE in 13-15)
+    if (kSkip && lane == 0 && blockIdx.x < 256) {  // (plain vector stores; HW_ID = hardware register 4: SIMD in bits 4-5, CU in 8-11, SH in 12, SE in 13-15)
         unsigned long long *o = fv_wave_clocks + ((size_t)blockIdx.x * 8 + wave) * kClkWords;
         o[0] = clk0; o[1] = wall_clock64(); o[2] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)); o[3] = 1;
     }
@@ -1735,13 +1488,21 @@ extern "C" long long idh_feature_volume_skip_task(long long ntasks, int grid, in
 }
 
 #ifdef IDH_FV_WAVE_CLOCKS
-// developer build only: copies the wave clocks of the last fv_mlp_skip_k launch (4 words per wave, 8 waves per workgroup) after a device synchronise
+// developer build only: copies the wave clocks of the skipping kernel's last launch (4 words per wave, 8 waves per workgroup) after a device synchronise
 extern "C" __attribute__((visibility("default"))) int idh_dev_fv_wave_clocks(unsigned long long *dst, int workgroups) {
     if (!dst || workgroups < 0 || workgroups > 256) return IDH_EINVAL;
     if (hipDeviceSynchronize() != hipSuccess) return IDH_ELAUNCH;
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(fv_wave_clocks), (size_t)workgroups * 8 * kClkWords * sizeof(unsigned long long)) == hipSuccess ? IDH_OK : IDH_ELAUNCH;
 }
 #endif
+
+// calls f with the compile-time view count of a launch as a std::integral_constant: K = 7 and K = 8 have kernels of their own, 0 = run-time count
+template <class F>
+static void fv_with_view_count(int K, F &&f) {
+    if (K == 7) f(std::integral_constant<int, 7>{});
+    else if (K == 8) f(std::integral_constant<int, 8>{});  // (BASELINE.json's literal 8 source views)
+    else f(std::integral_constant<int, 0>{});
+}
 
 static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                                const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
@@ -1750,7 +1511,96 @@ static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, con
                                const float *w1_pose_rowmajor, const float *b1, const void *w2_packed,
                                const float *vecs_b2_w3_b3, float *vol, int vol_nhwc_cs, float *lowest_bhw,
                                unsigned char *mask_bhw, float *planes_d, void *workspace,
-                               size_t workspace_bytes, void *stream, bool f16x3, const idh_volume_opts *opts);
+                               size_t workspace_bytes, void *stream, bool f16x3, const idh_volume_opts *opts) {
+    const bool own_planes = opts && opts->planes;
+    if (own_planes) { dmin = dmax = 1.f; planes_d = nullptr; }
+    if (B < 0 || K <= 0 || H <= 0 || W <= 0 || D <= 0 || !(dmin > 0.f) || !(dmax > 0.f)) return IDH_EINVAL;
+    const bool generic = C != kC || K > kMaxK;  // fv_mlp_gen_k: matching_feature_dims 32, up to IDH_MAX_SOURCE_VIEWS views
+    if ((long long)K * H * W * C * 4 >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (taps through a buffer descriptor per frame: 32-bit byte offsets)
+    if ((C != kC && C != 2 * kC) || K > IDH_MAX_SOURCE_VIEWS || D > 4096 || (generic && f16x3)) return IDH_EUNSUPPORTED;
+    if (B == 0) return IDH_OK;
+    if (!cur_nhwc || !src_nhwc || !src_K_44 || !src_E_44 || !src_poses_44 || !cur_invK_44 || !w1_voxel_packed ||
+        !w1_pixel_packed || !w1_pose_rowmajor || !b1 || !w2_packed || !vecs_b2_w3_b3 || !vol)
+        return IDH_EINVAL;
+    if (vol_nhwc_cs != 0 && vol_nhwc_cs < D) return IDH_EINVAL;
+    if (!workspace || workspace_bytes < idh_feature_volume_workspace_bytes(B)) return IDH_EWORKSPACE;
+    hipStream_t st = idh_stream(stream);
+    float *ws = static_cast<float *>(workspace);
+
+    FvArgs a{};
+    int views_mode = 0;  // idh_volume_opts.fv_keep_empty_views: 0 = the launch picks fv_mlp_k<KT, false> or <KT, true>, 1 = <KT, false> (all views), 2 = <KT, true> (skipping)
+    a.cur = cur_nhwc; a.src = src_nhwc; a.ws = ws; a.w1v = static_cast<const float *>(w1_voxel_packed); a.w1p = w1_pixel_packed;
+    a.w2 = static_cast<const float *>(w2_packed);
+    a.vecs = vecs_b2_w3_b3; a.vol = vol; a.mask = mask_bhw; a.vol_cs = vol_nhwc_cs;
+    a.B = B; a.K = K; a.H = H; a.W = W; a.D = D; a.dmin = dmin; a.dmax = dmax;
+    const int N = H * W;
+    a.cur_bs = (long long)N * C; a.src_bs = (long long)K * N * C;
+    a.J = K <= kMaxK ? 2 : (K + 3) / 4;  // views per lane quarter (the packed W1 columns follow the same rule: feature_mlp_column_maps)
+    a.MB = 2 * a.J;  // fv_mlp_gen_k: eight metadata slots per view group (two 16-column blocks)
+    if (opts) {
+        if (opts->cur_batch_stride) a.cur_bs = opts->cur_batch_stride;
+        if (opts->src_batch_stride) a.src_bs = opts->src_batch_stride;
+        if (a.cur_bs < (long long)N * C || a.src_bs < (long long)K * N * C || (a.cur_bs & 3) || (a.src_bs & 3)) return IDH_EINVAL;
+        if (opts->planes) {
+            if (opts->planes_pixel_stride != 0 && opts->planes_pixel_stride != 1) return IDH_EINVAL;
+            a.planes = opts->planes; a.planes_sb = opts->planes_batch_stride; a.planes_sd = opts->planes_plane_stride;
+            a.planes_sp = opts->planes_pixel_stride;
+        }
+        if (opts->struct_size >= (int64_t)(offsetof(idh_volume_opts, fv_keep_empty_views) + sizeof(int32_t))) views_mode = opts->fv_keep_empty_views;
+        if (views_mode < 0 || views_mode > 2) return IDH_EINVAL;
+    }
+    a.tiles_per_img = (N + 15) / 16;
+    a.select = (!generic && !f16x3 && views_mode == 0) ? 1 : 0;
+    hipLaunchKernelGGL(fv_setup_k, dim3(B), dim3(128), 0, st, src_K_44, src_E_44, src_poses_44, cur_invK_44,
+                       w1_pose_rowmajor, b1, K, ws, a);
+    IDH_CHECK_LAUNCH();
+    fv_plane_groups(B, H, W, D, &a.G, &a.DP);  // (shared with idh_feature_volume_plane_groups)
+    const long long pix_tasks = (long long)B * a.tiles_per_img;
+    const long long ntasks = pix_tasks * a.G;
+    const int grid = fv_grid(ntasks);  // (shared with idh_feature_volume_grid)
+    static IdhDeviceOnce attr_set;
+    if (attr_set.first()) {
+        const struct { const void *kernel; int bytes; } dyn_lds[] = {
+            {reinterpret_cast<const void *>(fv_mlp_k<0, false>), 160 * 1024},  {reinterpret_cast<const void *>(fv_mlp_gen_k<1>), 64 * 1024},
+            {reinterpret_cast<const void *>(fv_mlp_gen_k<2>), 64 * 1024},      {reinterpret_cast<const void *>(fv_mlp_k<7, false>), 160 * 1024},
+            {reinterpret_cast<const void *>(fv_mlp_k<0, true>), 160 * 1024},   {reinterpret_cast<const void *>(fv_mlp_k<7, true>), 160 * 1024},
+            {reinterpret_cast<const void *>(fv_mlp_k<8, true>), 160 * 1024},   {reinterpret_cast<const void *>(fv_mlp_k<8, false>), 160 * 1024},
+            {reinterpret_cast<const void *>(fv_mlp_f16_k<0>), 160 * 1024},     {reinterpret_cast<const void *>(fv_mlp_f16_k<7>), 160 * 1024},
+            {reinterpret_cast<const void *>(fv_mlp_f16_k<8>), 160 * 1024}};
+        for (const auto &e : dyn_lds)
+            if (hipFuncSetAttribute(e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e.bytes) != hipSuccess) return IDH_ELAUNCH;
+        attr_set.mark();
+    }
+    if (generic) {
+        const size_t lds = (size_t)kNS * kNS * 64 * sizeof(f32x4);
+        if (C == kC) hipLaunchKernelGGL(fv_mlp_gen_k<1>, dim3(grid), dim3(512), lds, st, a);
+        else hipLaunchKernelGGL(fv_mlp_gen_k<2>, dim3(grid), dim3(512), lds, st, a);
+    } else if (f16x3) {
+        const int nb32 = (K + 5) / 2;
+        const size_t lds = ((size_t)nb32 * kNS * 2 * 64 + 4 * kNS * 2 * 64) * 16;
+        const float *sw1 = reinterpret_cast<const float *>(static_cast<const char *>(w1_voxel_packed) + (size_t)nb32 * kNS * 2 * 64 * 16);
+        const float *sw2 = reinterpret_cast<const float *>(static_cast<const char *>(w2_packed) + (size_t)4 * kNS * 2 * 64 * 16);
+        fv_with_view_count(K, [&](auto kt) { hipLaunchKernelGGL(fv_mlp_f16_k<decltype(kt)::value>, dim3(grid), dim3(512), lds, st, a, sw1, sw2); });
+    } else {
+        const size_t lds = ((size_t)(K + 4) * kNS * 64 + kNS * kNS * 64) * sizeof(f32x4);
+        if (views_mode != 2) {
+            fv_with_view_count(K, [&](auto kt) { hipLaunchKernelGGL((fv_mlp_k<decltype(kt)::value, false>), dim3(grid), dim3(512), lds, st, a); });
+            IDH_CHECK_LAUNCH();
+        }
+        if (views_mode != 1) {  // (views_mode 0: both are enqueued and one of them returns at once, fv_selected)
+            fv_with_view_count(K, [&](auto kt) { hipLaunchKernelGGL((fv_mlp_k<decltype(kt)::value, true>), dim3(grid), dim3(512), lds, st, a); });
+        }
+    }
+    IDH_CHECK_LAUNCH();
+    if (lowest_bhw) {
+        int g2 = idh_cdiv((long long)B * N, vol_nhwc_cs > 0 ? 16 : 256);
+        if (g2 > 8192) g2 = 8192;
+        hipLaunchKernelGGL(argmax_planes_k, dim3(g2), dim3(256), 0, st, vol, vol_nhwc_cs, B, N, D, dmin, dmax, lowest_bhw,
+                           planes_d, a.planes, a.planes_sb, a.planes_sd, a.planes_sp);
+        IDH_CHECK_LAUNCH();
+    }
+    return IDH_OK;
+}
 
 extern "C" int idh_feature_volume_f16x3_fwd(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
                                             const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
@@ -1789,117 +1639,4 @@ extern "C" int idh_feature_volume_ex_fwd(const float *cur_nhwc, const float *src
     return feature_volume_impl(cur_nhwc, src_nhwc, src_K_44, src_E_44, src_poses_44, cur_invK_44, dmin, dmax, B, K, C, H, W, D,
                                w1_voxel, w1_pixel_packed, w1_pose_rowmajor, b1, w2, vecs_b2_w3_b3, vol, vol_nhwc_cs,
                                lowest_bhw, mask_bhw, planes_d, workspace, workspace_bytes, stream, f16x3 != 0, opts);
-}
-
-static int feature_volume_impl(const float *cur_nhwc, const float *src_nhwc, const float *src_K_44,
-                               const float *src_E_44, const float *src_poses_44, const float *cur_invK_44,
-                               float dmin, float dmax, int B, int K, int C, int H, int W, int D,
-                               const void *w1_voxel_packed, const float *w1_pixel_packed,
-                               const float *w1_pose_rowmajor, const float *b1, const void *w2_packed,
-                               const float *vecs_b2_w3_b3, float *vol, int vol_nhwc_cs, float *lowest_bhw,
-                               unsigned char *mask_bhw, float *planes_d, void *workspace,
-                               size_t workspace_bytes, void *stream, bool f16x3, const idh_volume_opts *opts) {
-    const bool own_planes = opts && opts->planes;
-    if (own_planes) { dmin = dmax = 1.f; planes_d = nullptr; }
-    if (B < 0 || K <= 0 || H <= 0 || W <= 0 || D <= 0 || !(dmin > 0.f) || !(dmax > 0.f)) return IDH_EINVAL;
-    const bool generic = C != kC || K > kMaxK;  // fv_mlp_gen_k: matching_feature_dims 32, up to IDH_MAX_SOURCE_VIEWS views
-    if ((long long)K * H * W * C * 4 >= (1ll << 31)) return IDH_EUNSUPPORTED;  // (taps through a buffer descriptor per frame: 32-bit byte offsets)
-    if ((C != kC && C != 2 * kC) || K > IDH_MAX_SOURCE_VIEWS || D > 4096 || (generic && f16x3)) return IDH_EUNSUPPORTED;
-    if (B == 0) return IDH_OK;
-    if (!cur_nhwc || !src_nhwc || !src_K_44 || !src_E_44 || !src_poses_44 || !cur_invK_44 || !w1_voxel_packed ||
-        !w1_pixel_packed || !w1_pose_rowmajor || !b1 || !w2_packed || !vecs_b2_w3_b3 || !vol)
-        return IDH_EINVAL;
-    if (vol_nhwc_cs != 0 && vol_nhwc_cs < D) return IDH_EINVAL;
-    if (!workspace || workspace_bytes < idh_feature_volume_workspace_bytes(B)) return IDH_EWORKSPACE;
-    hipStream_t st = idh_stream(stream);
-    float *ws = static_cast<float *>(workspace);
-
-    FvArgs a{};
-    int views_mode = 0;  // idh_volume_opts.fv_keep_empty_views: 0 = the launch picks fv_mlp_k or fv_mlp_skip_k, 1 = fv_mlp_k, 2 = fv_mlp_skip_k
-    a.cur = cur_nhwc; a.src = src_nhwc; a.ws = ws; a.w1v = static_cast<const float *>(w1_voxel_packed); a.w1p = w1_pixel_packed;
-    a.w2 = static_cast<const float *>(w2_packed);
-    a.vecs = vecs_b2_w3_b3; a.vol = vol; a.mask = mask_bhw; a.vol_cs = vol_nhwc_cs;
-    a.B = B; a.K = K; a.H = H; a.W = W; a.D = D; a.dmin = dmin; a.dmax = dmax;
-    const int N = H * W;
-    a.cur_bs = (long long)N * C; a.src_bs = (long long)K * N * C;
-    a.J = K <= kMaxK ? 2 : (K + 3) / 4;  // views per lane quarter (the packed W1 columns follow the same rule: feature_mlp_column_maps)
-    a.MB = 2 * a.J;  // fv_mlp_gen_k: eight metadata slots per view group (two 16-column blocks)
-    if (opts) {
-        if (opts->cur_batch_stride) a.cur_bs = opts->cur_batch_stride;
-        if (opts->src_batch_stride) a.src_bs = opts->src_batch_stride;
-        if (a.cur_bs < (long long)N * C || a.src_bs < (long long)K * N * C || (a.cur_bs & 3) || (a.src_bs & 3)) return IDH_EINVAL;
-        if (opts->planes) {
-            if (opts->planes_pixel_stride != 0 && opts->planes_pixel_stride != 1) return IDH_EINVAL;
-            a.planes = opts->planes; a.planes_sb = opts->planes_batch_stride; a.planes_sd = opts->planes_plane_stride;
-            a.planes_sp = opts->planes_pixel_stride;
-        }
-        if (opts->struct_size >= (int64_t)(offsetof(idh_volume_opts, fv_keep_empty_views) + sizeof(int32_t))) views_mode = opts->fv_keep_empty_views;
-        if (views_mode < 0 || views_mode > 2) return IDH_EINVAL;
-    }
-    a.tiles_per_img = (N + 15) / 16;
-    a.select = (!generic && !f16x3 && views_mode == 0) ? 1 : 0;
-    hipLaunchKernelGGL(fv_setup_k, dim3(B), dim3(128), 0, st, src_K_44, src_E_44, src_poses_44, cur_invK_44,
-                       w1_pose_rowmajor, b1, K, ws, a);
-    IDH_CHECK_LAUNCH();
-    fv_plane_groups(B, H, W, D, &a.G, &a.DP);  // (shared with idh_feature_volume_plane_groups)
-    const long long pix_tasks = (long long)B * a.tiles_per_img;
-    const long long ntasks = pix_tasks * a.G;
-    const int grid = fv_grid(ntasks);  // (shared with idh_feature_volume_grid)
-    static IdhDeviceOnce attr_set;
-    if (attr_set.first()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_k<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_gen_k<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_gen_k<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_k<7>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_skip_k<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_skip_k<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_skip_k<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_k<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_f16_k<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_f16_k<7>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(fv_mlp_f16_k<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return IDH_ELAUNCH;
-        attr_set.mark();
-    }
-    if (generic) {
-        const size_t lds = (size_t)kNS * kNS * 64 * sizeof(f32x4);
-        if (C == kC) hipLaunchKernelGGL(fv_mlp_gen_k<1>, dim3(grid), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL(fv_mlp_gen_k<2>, dim3(grid), dim3(512), lds, st, a);
-    } else if (f16x3) {
-        const int nb32 = (K + 5) / 2;
-        const size_t lds = ((size_t)nb32 * kNS * 2 * 64 + 4 * kNS * 2 * 64) * 16;
-        const float *sw1 = reinterpret_cast<const float *>(static_cast<const char *>(w1_voxel_packed) + (size_t)nb32 * kNS * 2 * 64 * 16);
-        const float *sw2 = reinterpret_cast<const float *>(static_cast<const char *>(w2_packed) + (size_t)4 * kNS * 2 * 64 * 16);
-        if (K == 7) hipLaunchKernelGGL(fv_mlp_f16_k<7>, dim3(grid), dim3(512), lds, st, a, sw1, sw2);
-        else if (K == 8) hipLaunchKernelGGL(fv_mlp_f16_k<8>, dim3(grid), dim3(512), lds, st, a, sw1, sw2);
-        else hipLaunchKernelGGL(fv_mlp_f16_k<0>, dim3(grid), dim3(512), lds, st, a, sw1, sw2);
-    } else {
-        const size_t lds = ((size_t)(K + 4) * kNS * 64 + kNS * kNS * 64) * sizeof(f32x4);
-        if (views_mode != 2) {
-            if (K == 7) hipLaunchKernelGGL(fv_mlp_k<7>, dim3(grid), dim3(512), lds, st, a);
-            else if (K == 8) hipLaunchKernelGGL(fv_mlp_k<8>, dim3(grid), dim3(512), lds, st, a);  // (BASELINE.json's literal 8 source views)
-            else hipLaunchKernelGGL(fv_mlp_k<0>, dim3(grid), dim3(512), lds, st, a);
-            IDH_CHECK_LAUNCH();
-        }
-        if (views_mode != 1) {  // (views_mode 0: both are enqueued and one of them returns at once, fv_selected)
-            if (K == 7) hipLaunchKernelGGL(fv_mlp_skip_k<7>, dim3(grid), dim3(512), lds, st, a);
-            else if (K == 8) hipLaunchKernelGGL(fv_mlp_skip_k<8>, dim3(grid), dim3(512), lds, st, a);
-            else hipLaunchKernelGGL(fv_mlp_skip_k<0>, dim3(grid), dim3(512), lds, st, a);
-        }
-    }
-    IDH_CHECK_LAUNCH();
-    if (lowest_bhw) {
-        int g2 = idh_cdiv((long long)B * N, vol_nhwc_cs > 0 ? 16 : 256);
-        if (g2 > 8192) g2 = 8192;
-        hipLaunchKernelGGL(argmax_planes_k, dim3(g2), dim3(256), 0, st, vol, vol_nhwc_cs, B, N, D, dmin, dmax, lowest_bhw,
-                           planes_d, a.planes, a.planes_sb, a.planes_sd, a.planes_sp);
-        IDH_CHECK_LAUNCH();
-    }
-    return IDH_OK;
 }

@@ -87,11 +87,13 @@ typedef struct idh_volume_opts {
                             against the shorter version-100 struct: for such a caller the field itself lies past the end of its struct.  A
                             binding must therefore compare idh_sizeof_volume_opts() / idh_version() with its own mirror when it loads the
                             library (implicit-depth_amd/_lib.py does, and refuses to bind on a mismatch). */
-    int32_t fv_keep_empty_views; /* MLP feature volume only (C = 16, K <= 8, fp32).  fv_mlp_skip_k drops a source view from a 16-voxel tile's plane when none
-                                    of the voxels has a non-zero bilinear weight in it - no taps, blend or layer-1 MFMAs; the same values for finite
-                                    features (csrc/feature_volume.hip names the Inf / NaN and -0 footnotes) - and is slower than fv_mlp_k where nothing
-                                    can be dropped.  0 (default): each launch runs the faster of the two for its cameras (a device-side estimate, no
-                                    synchronisation); 1: always fv_mlp_k, every view processed; 2: always fv_mlp_skip_k (A/B timing, tests).
+    int32_t fv_keep_empty_views; /* MLP feature volume only (C = 16, K <= 8, fp32).  There are two kernels per view count, both instances of one
+                                    template (fv_mlp_k<KT, kSkip>).  The skipping one (<KT, true>) drops a source view from a 16-voxel tile's plane
+                                    when none of the voxels has a non-zero bilinear weight in it - no taps, blend or layer-1 MFMAs; the same values
+                                    for finite features (csrc/feature_volume.hip names the Inf / NaN and -0 footnotes) - and is slower than the
+                                    all-views one (<KT, false>) where nothing can be dropped.  0 (default): each launch runs the faster of the two
+                                    for its cameras (a device-side estimate, no synchronisation); 1: always the all-views kernel, every view
+                                    processed; 2: always the skipping kernel (A/B timing, tests).
                                     Appended after struct_size: honoured when struct_size reaches past it. */
     int32_t win_units_per_split; /* dot-product volume, window kernel only (was reserved0: same offset, same struct size): 0 = automatic (the launcher's
                                     rule), otherwise the number of 4-plane units one workgroup of cv_dot_win_k processes - a test / profiling hook so
@@ -189,7 +191,7 @@ size_t idh_feature_volume_workspace_bytes(int B);
  * last one may be shorter.  The launch calls the same function, so the answer is the partition the kernels run (K, C and the math mode
  * do not enter the choice).  IDH_EINVAL for non-positive sizes, D > 4096 or a NULL output pointer. */
 int idh_feature_volume_plane_groups(int B, int H, int W, int D, int *groups, int *planes_per_group);
-/* Host-only queries (additive: idh_version() stays as it is): the order in which the kernel that drops views (fv_mlp_skip_k) walks its
+/* Host-only queries (additive: idh_version() stays as it is): the order in which the kernel that drops views (fv_mlp_k<KT, true>) walks its
  * ntasks = B * ceil(H * W / 16) * groups tasks.  idh_feature_volume_grid: the number of workgroups the launch uses (8 waves each; 0 for
  * ntasks <= 0).  idh_feature_volume_skip_task: the task that wave `wave` (0..7) of workgroup `block` (0..grid-1, the hardware's block index)
  * takes in round `round` (0, 1, ...), or -1 when it takes none there - the slot lies past ntasks, or an argument is out of range.  Task t is

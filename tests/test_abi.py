@@ -192,7 +192,8 @@ def test_hot_kernels_compile_without_scratch():
 
     csrc = os.path.join(root, "implicit-depth_amd", "csrc")
     rows = {r["Name"]: int(r.get("ScratchSize [bytes/lane]", 0)) for src in ("conv_wino4.hip", "feature_volume.hip") for r in kr.resources(os.path.join(csrc, src))}
-    for name in ("conv3x3_wino4_k<true, false>", "conv3x3_wino4_k<false, true>", "conv3x3_wino4_k<false, false>", "fv_mlp_k<7>", "fv_mlp_k<0>"):
+    for name in ("conv3x3_wino4_k<true, false>", "conv3x3_wino4_k<false, true>", "conv3x3_wino4_k<false, false>",
+                 "fv_mlp_k<7, false>", "fv_mlp_k<0, false>", "fv_mlp_k<7, true>", "fv_mlp_k<0, true>"):  # (<KT, kSkip>: all views / views dropped)
         assert name in rows, (name, sorted(rows))
         assert rows[name] == 0, (name, rows[name])
 

@@ -1,6 +1,6 @@
-"""Every feature-volume kernel instantiation (csrc/feature_volume.hip: fv_mlp_k<7|8|0>, fv_mlp_gen_k<1|2>, fv_mlp_f16_k<7|8|0>) against the
-fp64 oracle under general camera geometry: the four families of tests/volume_geometry.py — random rotations, source cameras whose z = 0
-plane cuts the swept volume, camera roll and pitch, and intrinsics that differ for every (b, k) with a current-frame K per batch element.
+"""Every feature-volume kernel family (csrc/feature_volume.hip: fv_mlp_k<7|8|0, *>, fv_mlp_gen_k<1|2>, fv_mlp_f16_k<7|8|0>; `*`: the all-views
+or the view-dropping instantiation, whichever the launch picks for the case's cameras) against the fp64 oracle under general camera geometry: the
+four families of tests/volume_geometry.py — random rotations, source cameras whose z = 0 plane cuts the swept volume, camera roll and pitch, and intrinsics that differ for every (b, k) with a current-frame K per batch element.
 
 The other fv tests take their cameras from synthetic.cost_volume_inputs: rotations about y alone and one K for every view and batch element,
 for which E[0][1] = E[2][1] = 0 and the indexing src_K + (b * K + k) * 16 / cur_invK + b * 16 of fv_setup_k cannot be told from a constant
@@ -10,9 +10,9 @@ the oracle in float64 with no mask and next to no `lowest` disagreement).
 Measured on an MI355X, scale-relative error against the fp64 oracle: worst over this file's cases per kernel instantiation (variant, family,
 seed, shape of the worst case) | the float32 ORACLE against the float64 one on that same case (the admission figure) | the worst of
 test_feature_volume_planes_gpu.py (cameras of synthetic.cost_volume_inputs, 120k to 280k voxels):
-    fv_mlp_k<7>       6.4e-05  k7 zcross 20 (3, 24, 40, 13)       | 4.5e-05 | 8.2e-06
-    fv_mlp_k<8>       1.6e-05  k8 random 1 (2, 13, 19, 5)         | 1.6e-05 | 5.7e-06
-    fv_mlp_k<0>       5.3e-06  k0 zcross 2 (2, 13, 19, 5)         | 3.5e-06 | 5.1e-06
+    fv_mlp_k<7, *>    6.4e-05  k7 zcross 20 (3, 24, 40, 13)       | 4.5e-05 | 8.2e-06
+    fv_mlp_k<8, *>    1.6e-05  k8 random 1 (2, 13, 19, 5)         | 1.6e-05 | 5.7e-06
+    fv_mlp_k<0, *>    5.3e-06  k0 zcross 2 (2, 13, 19, 5)         | 3.5e-06 | 5.1e-06
     fv_mlp_gen_k<1>   2.3e-05  gen1_16 zcross 8 (2, 13, 19, 5)    | 2.2e-05 | 7.3e-06
     fv_mlp_gen_k<2>   5.4e-06  gen2 intrinsics 4 (2, 13, 19, 5)   | 2.8e-06 | 8.4e-06
     fv_mlp_f16_k<7>   2.4e-05  f16_7 zcross 25 (3, 24, 40, 13)    | 1.6e-05 | 5.8e-06
@@ -38,12 +38,12 @@ pytestmark = pytest.mark.gpu
 # kernel variant -> (source views K, matching channels C, MLP math)
 VARIANTS = dict(planes.VARIANTS)
 VARIANTS.update({
-    "k0_5": (5, 16, "fp32"),      # fv_mlp_k<0> with a real view in a quarter's second slot (view 4 = quarter 0, j = 1)
+    "k0_5": (5, 16, "fp32"),      # fv_mlp_k<0, *> with a real view in a quarter's second slot (view 4 = quarter 0, j = 1)
     "gen1_16": (16, 16, "fp32"),  # fv_mlp_gen_k<1>, every slot of four view groups taken
     "f16_8": (8, 16, "f16x3"),    # fv_mlp_f16_k<8>
     "f16_0_5": (5, 16, "f16x3"),  # fv_mlp_f16_k<0>, as k0_5
 })
-KERNEL = {"k7": "fv_mlp_k<7>", "k8": "fv_mlp_k<8>", "k0": "fv_mlp_k<0>", "k0_5": "fv_mlp_k<0>", "gen1": "fv_mlp_gen_k<1>",
+KERNEL = {"k7": "fv_mlp_k<7, *>", "k8": "fv_mlp_k<8, *>", "k0": "fv_mlp_k<0, *>", "k0_5": "fv_mlp_k<0, *>", "gen1": "fv_mlp_gen_k<1>",
           "gen1_16": "fv_mlp_gen_k<1>", "gen2": "fv_mlp_gen_k<2>", "f16_7": "fv_mlp_f16_k<7>", "f16_8": "fv_mlp_f16_k<8>",
           "f16_0": "fv_mlp_f16_k<0>", "f16_0_5": "fv_mlp_f16_k<0>"}
 

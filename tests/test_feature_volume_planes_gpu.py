@@ -9,9 +9,9 @@ whose partition changed are found again with the query (neighbouring B, H, W), n
 Measured on an MI355X, scale-relative error against the fp64 oracle: worst over this file's cases (shape, layout or argument of the worst
 case) | the same kernel in the small-shape oracle cases of test_feature_volume_gpu.py / test_mlp_split_gpu.py (at most four planes per
 task, 351 to 49152 voxels):
-    fv_mlp_k<7>       8.2e-06  (6, 45, 65, 7)                  | 3.5e-06  (1, 24, 32, 64)
-    fv_mlp_k<8>       5.7e-06  (6, 48, 40, 13)                 | 1.8e-06  (1, 12, 20, 5)
-    fv_mlp_k<0>       5.1e-06  (6, 59, 37, 17), K = 3          | 2.4e-06  (2, 17, 23, 6), K = 5
+    fv_mlp_k<7, *>    8.2e-06  (6, 45, 65, 7)                  | 3.5e-06  (1, 24, 32, 64)
+    fv_mlp_k<8, *>    5.7e-06  (6, 48, 40, 13)                 | 1.8e-06  (1, 12, 20, 5)
+    fv_mlp_k<0, *>    5.1e-06  (6, 59, 37, 17), K = 3          | 2.4e-06  (2, 17, 23, 6), K = 5
     fv_mlp_gen_k<1>   7.3e-06  (6, 48, 40, 16), batch strides  | 2.5e-06  (2, 17, 23, 6), K = 12
     fv_mlp_gen_k<2>   8.4e-06  (6, 48, 40, 13)                 | 2.3e-06  (1, 24, 32, 8), K = 7
     fv_mlp_f16_k<7>   5.8e-06  (6, 48, 40, 16), pixel planes   | 3.4e-06  (1, 24, 32, 64)
@@ -39,9 +39,9 @@ pytestmark = pytest.mark.gpu
 
 # kernel variant -> (source views K, matching channels C, MLP math)
 VARIANTS = {
-    "k7": (7, 16, "fp32"),      # fv_mlp_k<7>
-    "k8": (8, 16, "fp32"),      # fv_mlp_k<8>: the plane depth takes the extra MFMA block
-    "k0": (3, 16, "fp32"),      # fv_mlp_k<0>: absent-view stand-ins in quarters 3 and q + 4
+    "k7": (7, 16, "fp32"),      # fv_mlp_k<7, *>
+    "k8": (8, 16, "fp32"),      # fv_mlp_k<8, *>: the plane depth takes the extra MFMA block
+    "k0": (3, 16, "fp32"),      # fv_mlp_k<0, *>: absent-view stand-ins in quarters 3 and q + 4
     "gen1": (9, 16, "fp32"),    # fv_mlp_gen_k<1>
     "gen2": (3, 32, "fp32"),    # fv_mlp_gen_k<2>
     "f16_7": (7, 16, "f16x3"),  # fv_mlp_f16_k<7>
@@ -63,7 +63,7 @@ SHAPES = {
 }
 MISALIGNED = (6, 48, 40, 13)  # several groups, d0 % 4 != 0 after the first
 DEEP = (6, 48, 40, 16)        # >= 8 planes per task
-SUBSET = [MISALIGNED, DEEP, (6, 59, 37, 17)]  # what the variants other than fv_mlp_k<7> run
+SUBSET = [MISALIGNED, DEEP, (6, 59, 37, 17)]  # what the variants other than fv_mlp_k<7, *> run
 
 LAYOUTS = ["bdn", "nhwc_vec", "nhwc_odd_cs", "nhwc_offset_base", "nhwc_wide"]
 

@@ -1,5 +1,5 @@
-"""fv_mlp_skip_k drops, per 16-voxel tile and plane, the source views in which no voxel has a non-zero bilinear weight (csrc/feature_volume.hip,
-DESIGN 4.3): its outputs must be bit-identical to those of fv_mlp_k, which processes every view (FeatureVolumeManager.skip_empty_views = "always" /
+"""fv_mlp_k<KT, true> drops, per 16-voxel tile and plane, the source views in which no voxel has a non-zero bilinear weight (csrc/feature_volume.hip,
+DESIGN 4.3): its outputs must be bit-identical to those of fv_mlp_k<KT, false>, which processes every view (FeatureVolumeManager.skip_empty_views = "always" /
 False -> idh_volume_opts.fv_keep_empty_views 2 / 1), so must those of the default, where each launch picks one of the two kernels, and all must
 agree with the fp64 oracle at the bar of tests/test_feature_volume_gpu.py."""
 import functools
@@ -17,7 +17,7 @@ DMIN, DMAX = 0.25, 5.0
 # three 16-pixel tiles per row; rows of 40: every other row starts in the middle of a tile, so tiles span two rows; 7 x 23 = 161 pixels: a ragged
 # last tile, whose 15 clamped stand-in voxels take part in the ballot
 MAPS = [(8, 48), (12, 40), (7, 23)]
-VIEWS = [7, 8, 3]  # fv_mlp_k<7>, fv_mlp_k<8>, the run-time variant fv_mlp_k<0>
+VIEWS = [7, 8, 3]  # KT = 7, 8 and the run-time variant KT = 0 of fv_mlp_k<KT, false | true>
 CAMERAS = ["identity", "sideways", "turned_away", "all_outside"]
 
 

@@ -1,6 +1,6 @@
-"""fv_mlp_skip_k hands its tasks to the waves in a rotated order (csrc/feature_volume.hip: fv_skip_task; the order itself:
+"""fv_mlp_k<KT, true> hands its tasks to the waves in a rotated order (csrc/feature_volume.hip: fv_skip_task; the order itself:
 tests/test_fv_task_map_cpu.py).  The order must not change a bit of any output: the kernel forced (idh_volume_opts.fv_keep_empty_views = 2)
-against fv_mlp_k forced (= 1), which keeps the static order - volume, lowest_cost and mask bit-identical - on shapes with several rounds, a
+against fv_mlp_k<KT, false> forced (= 1), which keeps the static order - volume, lowest_cost and mask bit-identical - on shapes with several rounds, a
 partial last round, a grid below 256 workgroups, more than one plane group, and NHWC stores.  The cameras are synthetic.cost_volume_inputs':
 their intrinsics scale with the image, so at every size some (tile, plane, view) groups are dropped and others kept (asserted on the CPU)."""
 import ctypes
@@ -18,9 +18,9 @@ from oracle import cost_volume as ocv
 C = 16
 DMIN, DMAX = 0.25, 5.0
 # (B, K, H, W, D)
-RAGGED = (3, 7, 96, 128, 8)     # fv_mlp_skip_k<7>: more than one round of 2048 tasks, the last one partial
-SMALL = (2, 8, 10, 24, 5)       # fv_mlp_skip_k<8>: 15 tiles per image, one partial round on 4 workgroups, the last of them with 6 of 8 tasks
-RUNTIME_K = (12, 4, 48, 64, 16)  # fv_mlp_skip_k<0>: several rounds
+RAGGED = (3, 7, 96, 128, 8)     # fv_mlp_k<7, true>: more than one round of 2048 tasks, the last one partial
+SMALL = (2, 8, 10, 24, 5)       # fv_mlp_k<8, true>: 15 tiles per image, one partial round on 4 workgroups, the last of them with 6 of 8 tasks
+RUNTIME_K = (12, 4, 48, 64, 16)  # fv_mlp_k<0, true>: several rounds
 NHWC = (2, 7, 24, 40, 8)        # NHWC stores (12 channels per pixel for 8 planes), mask on
 
 
@@ -36,7 +36,7 @@ def _tasks(shape):
 
 def _outside_groups(inp, H, W, D):
     """Share of (16 consecutive pixels of the flattened map, plane, view) groups in which every sample has four zero bilinear weights, fp64 on the
-    CPU: x outside (-1, W) or y outside (-1, H) after the -0.5 shift, z clamped to 1e-5 (prologue() of fv_mlp_skip_k)."""
+    CPU: x outside (-1, W) or y outside (-1, H) after the -0.5 shift, z clamped to 1e-5 (prologue() of fv_mlp_k)."""
     Ks, E, iK = inp["src_Ks"].double(), inp["src_extrinsics"].double(), inp["cur_invK"].double()
     ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64) + 0.5, torch.arange(W, dtype=torch.float64) + 0.5, indexing="ij")
     pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=torch.float64)])

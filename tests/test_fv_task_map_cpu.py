@@ -1,4 +1,4 @@
-"""Task order of fv_mlp_skip_k (csrc/feature_volume.hip: fv_skip_task), read through the host-only entry points the kernel shares
+"""Task order of fv_mlp_k<KT, true> (csrc/feature_volume.hip: fv_skip_task), read through the host-only entry points the kernel shares
 its code with: idh_feature_volume_grid (the launcher's grid) and idh_feature_volume_skip_task (ntasks, grid, block, wave, round) -> task or -1.
 Wave w of a workgroup takes sub-slot (w + round) & 7 of the workgroup's eight tasks of a round; every task must be visited exactly once, also
 where the last round is ragged (a rotated sub-slot past ntasks is skipped, lower ones of the same workgroup are not)."""

@@ -1,4 +1,4 @@
-"""Feature volume, load balance of fv_mlp_skip_k's task order: a CPU model, no GPU needed.
+"""Feature volume, load balance of the task order of the skipping kernel fv_mlp_k<KT, true>: a CPU model, no GPU needed.
 
   python tools/fv_task_balance.py [cameras ...] [--B 32]        cameras: bench identity tuple31 golden_g2 (tools/perf_fv_skip.py), default all
 
@@ -7,7 +7,7 @@ prologue()'s bilinear weights in fp64 (a sample has no weight when x falls outsi
 1e-5), prices a task at  sum over its planes of (352 + 32 * active_views(tile, plane))  - matrix instructions only, the constant vector work per
 plane is not in it - and sums what each wave, SIMD and CU of the persistent grid is handed:
   shipped   the static stride of the uniform-cost kernels: wave w of a workgroup takes sub-slot w of the workgroup's eight tasks of every round
-  rotated   fv_mlp_skip_k's order, read through idh_feature_volume_skip_task (the function the kernel calls)
+  rotated   the skipping kernel's order, read through idh_feature_volume_skip_task (the function the kernel calls)
 Printed per camera set: the dropped shares, the mean cost per wave index relative to the mean, and busiest / mean over the SIMDs (waves w and w + 4
 of a workgroup share a SIMD; in brackets: waves 2s and 2s + 1) and over the CUs of the chip, for both orders.  Then, as a record for a later
 decision and NOT built: workgroup-local dynamic fetching - the workgroup's tasks of all rounds in one queue, each split into 1 / 2 / 4 plane

@@ -8,12 +8,12 @@ Camera sets, all at the benchmark's shape (B x 7 views, 16 channels, 96 x 128, 6
   identity   every source camera = the current camera: nothing can be dropped (the worst case of the dropping)
   tuple31    synthetic.frame_tuple(seed 31): the tuple tests/test_bdmodel_gpu.py feeds with the reference's BDModel goldens (g5 / g9)
   golden_g2  cost_volume_inputs with the dims of tests/golden/g2_full_k7d64.npz (the full-size feature-volume golden)
-One JSON line per camera set: "on" = the default (each launch picks fv_mlp_k or fv_mlp_skip_k), "off" = always fv_mlp_k, "always" = always
-fv_mlp_skip_k.  A library without the switch (FeatureVolumeManager.skip_empty_views) is timed once, as "on".
+One JSON line per camera set: "on" = the default (each launch picks fv_mlp_k<KT, false> or <KT, true>), "off" = always <KT, false>, "always" = always
+<KT, true>.  A library without the switch (FeatureVolumeManager.skip_empty_views) is timed once, as "on".
 
   IDH_LIB=<developer library> python tools/perf_fv_skip.py [B] --wave-clocks [cameras ...]
 
-Load balance of fv_mlp_skip_k's task order (tools/fv_task_balance.py has the model): needs a library whose csrc/feature_volume.hip was
+Load balance of the skipping kernel's task order (tools/fv_task_balance.py has the model): needs a library whose csrc/feature_volume.hip was
 compiled with -DIDH_FV_WAVE_CLOCKS (every wave stores the 100 MHz wall clock at entry and exit and its HW_ID; in no shipped build), and
 -DIDH_ABL_FV_STATIC_ORDER beside it for the static order the rotation replaced.  One launch of the kernel, forced, after three warm-up launches;
 per camera set (default: bench) one JSON line: the kernel's span, the mean exit time per wave index relative to the mean over all waves, which
