@@ -145,11 +145,13 @@ class Plan {
     }
     // A caller-owned tensor of a plan that is never run: each gets an address range of its own
     float *fake_tensor() { return fake_address(FAKE_EXTERNAL, n_fake_++); }
+    // A pointer the caller hands in: itself in a plan that runs, else the next made-up tensor (one fake_tensor() per call, in recording order)
+    template <class T> T *caller_ptr(T *p) { return mode_ == MODE_RUN ? p : fake_tensor(); }
     // A caller-owned NHWC tensor as a view (read or written in place)
     View external(const idh_tensor &t, int n) {
         Buf b{};
         b.N = n; b.H = t.H; b.W = t.W; b.cs = t.cs; b.internal = false; b.zero_fill = false;
-        b.base = mode_ == MODE_RUN ? t.ptr : fake_tensor();
+        b.base = caller_ptr(t.ptr);
         bufs.push_back(b);
         return View{(int)bufs.size() - 1, 0, t.C};
     }
@@ -205,14 +207,25 @@ class Plan {
         return dst;
     }
 
+    // ---- recording (Plan._record / _fill_src): every op below is zeroed by new_op and enters the plan through push, with the regions
+    // idh_schedule_ops orders it by
+    static idh_op new_op(int kind, int n) {
+        idh_op op;
+        std::memset(&op, 0, sizeof op);
+        op.kind = kind; op.N = n;
+        return op;
+    }
+    void src_of(idh_conv_src &s, const View &v) const { s.in = ptr(v); s.cs = cs(v); s.H = H(v); s.W = W(v); s.Cin = v.C; }
+    void push(const idh_op &op, Meta m) {
+        ops.push_back(op);
+        meta.push_back(std::move(m));
+    }
+
     // ---- ops (Plan.conv / upsample2 / import_nchw / export_nchw / head) ---------------------------------------------------------------------
     View conv(const View &x, const idh_conv_params &cv, const View &out, int act, float slope, const View *res, const View *x2, const idh_conv_params *cv2,
               int pad_mode = IDH_PAD_ZEROS, const Norm *norm = nullptr, bool wino4_any_size = false) {
         if (err) return out;
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_CONV;
-        op.N = N(x);
+        idh_op op = new_op(IDH_OP_CONV, N(x));
         std::vector<Src> srcs{{x, &cv}};
         if (x2) srcs.push_back({*x2, cv2});
         const int n = N(out), Ho = H(out), Wo = W(out), cout = cv.cout;
@@ -225,8 +238,8 @@ class Plan {
             if (v.C != c.cin || (c.ks != 1 && c.ks != 3) || c.cout != cout) { err = IDH_EINVAL; return out; }
             if (v.C % 16 && (v.c0 != 0 || cs(v) != ceil16(v.C))) { err = IDH_EINVAL; return out; }  // odd channel counts: whole zero-padded buffers only
             idh_conv_src &s = op.src[i];
-            s.in = ptr(v); s.w = packed(c, i == 0 ? ch.w_layout : IDH_W_DIRECT); s.cs = cs(v); s.H = H(v); s.W = W(v); s.Cin = v.C;
-            s.ks = c.ks; s.stride = c.stride; s.pad_mode = pad_mode;
+            src_of(s, v);
+            s.w = packed(c, i == 0 ? ch.w_layout : IDH_W_DIRECT); s.ks = c.ks; s.stride = c.stride; s.pad_mode = pad_mode;
         }
         op.bias = bias_of(cv, cv2);  // (always present in the blob - BasicBlock's convs all have one, layers.py:52-55; a NULL bias packs as zeros)
         if (res) { op.res = ptr(*res); op.res_cs = cs(*res); }
@@ -244,48 +257,35 @@ class Plan {
         }
         if (dry_) return out;  // (reserve_block: the blob slots are taken, in the layout this conv's kernel reads; no op, no workspace)
         if (split > 1) op.ws = ws_alloc((size_t)split * M * ceil16(cout));
-        ops.push_back(op);
-        Meta m;
+        Meta m{{}, {region(out)}};
         if (res) m.reads.push_back(region(*res));
         if (norm) m.reads.push_back(Region{(uint64_t)norm->buf, 0, 1});
         for (const Src &s : srcs) m.reads.push_back(region(s.v, true));
-        m.writes.push_back(region(out));
-        meta.push_back(m);
+        push(op, m);
         return out;
     }
     void upsample2(const View &x, const View &out) {
         if (err) return;
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_UPSAMPLE2; op.N = N(x);
-        idh_conv_src &s = op.src[0];
-        s.in = ptr(x); s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
+        idh_op op = new_op(IDH_OP_UPSAMPLE2, N(x));
+        src_of(op.src[0], x);
         op.out = ptr(out); op.out_cs = cs(out);
-        ops.push_back(op);
-        meta.push_back(Meta{{region(x)}, {region(out)}});
+        push(op, Meta{{region(x)}, {region(out)}});
     }
     void import_nchw(const float *src, int n, int C, int H_, int W_, const View &out) {
         if (err) return;
         if (n != N(out) || H_ != H(out) || W_ != W(out) || C != out.C) { err = IDH_EINVAL; return; }
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_NCHW_TO_NHWC; op.N = n;
-        op.src[0].in = mode_ == MODE_RUN ? src : fake_tensor();
+        idh_op op = new_op(IDH_OP_NCHW_TO_NHWC, n);
+        op.src[0].in = caller_ptr(src);
         op.src[0].H = H_; op.src[0].W = W_; op.src[0].Cin = C;
         op.out = ptr(out); op.out_cs = cs(out);
-        ops.push_back(op);
-        meta.push_back(Meta{{}, {region(out)}});
+        push(op, Meta{{}, {region(out)}});
     }
     void export_nchw(const View &x, float *dst) {
         if (err) return;
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_NHWC_TO_NCHW; op.N = N(x);
-        idh_conv_src &s = op.src[0];
-        s.in = ptr(x); s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
-        op.out = mode_ == MODE_RUN ? dst : fake_tensor();
-        ops.push_back(op);
-        meta.push_back(Meta{{region(x)}, {}});
+        idh_op op = new_op(IDH_OP_NHWC_TO_NCHW, N(x));
+        src_of(op.src[0], x);
+        op.out = caller_ptr(dst);
+        push(op, Meta{{region(x)}, {}});
     }
     void head(const View &x, const idh_conv_params &cv, float *out, float *out_exp) {
         if (err) return;
@@ -296,16 +296,13 @@ class Plan {
             if (hipMemcpyAsync(w, cv.weight, sizeof(float) * cv.cin, hipMemcpyDeviceToDevice, st_) != hipSuccess ||
                 hipMemcpyAsync(b, cv.bias, sizeof(float), hipMemcpyDeviceToDevice, st_) != hipSuccess) err = IDH_ELAUNCH;
         }
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_POINTWISE_HEAD; op.N = N(x);
-        idh_conv_src &s = op.src[0];
-        s.in = ptr(x); s.w = w; s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
+        idh_op op = new_op(IDH_OP_POINTWISE_HEAD, N(x));
+        src_of(op.src[0], x);
+        op.src[0].w = w;
         op.bias = b;
-        op.out = mode_ == MODE_RUN ? out : fake_tensor();
+        op.out = caller_ptr(out);
         op.ws = mode_ == MODE_RUN ? out_exp : nullptr;
-        ops.push_back(op);
-        meta.push_back(Meta{{region(x)}, {}});
+        push(op, Meta{{region(x)}, {}});
     }
 
     // Plan.instance_norm: nn.InstanceNorm2d (no affine, eps 1e-5) [+ LeakyReLU]; out == nullptr: statistics only, for a normalise-on-load conv
@@ -315,15 +312,11 @@ class Plan {
         if (x.C % 4 || 256 % (x.C / 4)) { err = IDH_EINVAL; return nm; }
         const int nchunks = cdiv(H(x) * W(x), 1024);
         float *w = ws_alloc((size_t)N(x) * (nchunks + 1) * 2 * x.C);
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_INSTNORM; op.N = N(x);
-        idh_conv_src &s = op.src[0];
-        s.in = ptr(x); s.cs = cs(x); s.H = H(x); s.W = W(x); s.Cin = x.C;
+        idh_op op = new_op(IDH_OP_INSTNORM, N(x));
+        src_of(op.src[0], x);
         op.act = act; op.slope = slope;
         if (out) { op.out = ptr(*out); op.out_cs = cs(*out); }
         op.ws = w;
-        ops.push_back(op);
         Meta m{{region(x)}, {}};
         if (out) {
             m.writes.push_back(region(*out));
@@ -334,7 +327,7 @@ class Plan {
             nm.stats = b.base; nm.buf = (int)bufs.size() - 1;
             m.writes.push_back(Region{(uint64_t)nm.buf, 0, 1});
         }
-        meta.push_back(m);
+        push(op, m);
         return nm;
     }
     static bool pointwise_nchw_eligible(const idh_conv_params &c) { return c.ks == 1 && c.stride == 1 && c.cin == 64 && c.cout == 128; }
@@ -342,31 +335,25 @@ class Plan {
     void pointwise_nchw(const float *src, int n, int C, int H_, int W_, const idh_conv_params &cv, const View &out) {
         if (err) return;
         if (n != N(out) || H_ != H(out) || W_ != W(out) || C != cv.cin || out.C != cv.cout || !pointwise_nchw_eligible(cv)) { err = IDH_EINVAL; return; }
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_POINTWISE_NCHW; op.N = n;
+        idh_op op = new_op(IDH_OP_POINTWISE_NCHW, n);
         idh_conv_src &s = op.src[0];
-        s.in = mode_ == MODE_RUN ? src : fake_tensor();
+        s.in = caller_ptr(src);
         s.w = packed(cv, IDH_W_DIRECT); s.H = H_; s.W = W_; s.Cin = C; s.ks = 1; s.stride = 1;
         op.bias = bias_of(cv, nullptr);
         op.out = ptr(out); op.out_cs = cs(out); op.Ho = H_; op.Wo = W_; op.Cout = cv.cout;
-        ops.push_back(op);
-        meta.push_back(Meta{{}, {region(out)}});
+        push(op, Meta{{}, {region(out)}});
     }
 
     // ---- the fused ResNet18 stem pass (Plan.stem): N dense NCHW images -> NHWC 64-channel view
     void stem(const float *images, int n, int h, int w, const float *blob, const View &out) {
         if (err) return;
-        idh_op op;
-        std::memset(&op, 0, sizeof op);
-        op.kind = IDH_OP_STEM; op.N = n;
+        idh_op op = new_op(IDH_OP_STEM, n);
         idh_conv_src &s = op.src[0];
-        s.in = mode_ == MODE_RUN ? images : fake_tensor();
+        s.in = caller_ptr(images);
         s.w = blob; s.H = h; s.W = w; s.Cin = 3;
         s.up_C = n; s.up_cs[0] = 3 * h * w; s.up_cs[1] = n * 3 * h * w;  // (Plan.stem: one group of N dense images)
         op.out = ptr(out); op.out_cs = cs(out); op.Ho = H(out); op.Wo = W(out); op.Cout = 64;
-        ops.push_back(op);
-        meta.push_back(Meta{{}, {region(out)}});
+        push(op, Meta{{}, {region(out)}});
     }
 
     // ---- BasicBlock (Plan.basic_block; reference layers.py:78-95) ------------------------------------------------------------------------------
@@ -689,6 +676,20 @@ uint64_t layout_hash(const std::vector<idh_op> &ops) {
     return h;
 }
 
+// Every extern "C" network entry below: the pointer checks of its mode, the Plan, the network's builder, then the schedule and (MODE_RUN) the
+// pass.  sizes: MODE_SIZES only.  null_ws_ok: MODE_RUN accepts ws == NULL when ws_floats == 0 (a BasicBlock may need no workspace).
+// build(p): the builder's return code; whatever it checks comes after every pointer check and before finish.
+template <class Build>
+int net_entry(Mode mode, const float *blob, float *ws, size_t ws_floats, void *stream, idh_net_sizes *sizes, bool null_ws_ok, Build build) {
+    if (mode == MODE_SIZES && !sizes) return IDH_EINVAL;
+    if (mode != MODE_SIZES && (!blob || ((uintptr_t)blob & 255))) return IDH_EINVAL;
+    if (mode == MODE_RUN && !(null_ws_ok && !ws_floats) && (!ws || ((uintptr_t)ws & 255))) return IDH_EINVAL;
+    Plan p(mode, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
+    const int rc = build(p);
+    if (rc != IDH_OK) return rc;
+    return mode == MODE_PACK ? p.err : p.finish(sizes);
+}
+
 }  // namespace
 
 // The conv stage of one HotPath plan (pipeline.py HotPath._plan): the volume buffer, the layout import of pyramid level 0, the CVEncoder
@@ -778,111 +779,77 @@ extern "C" void idh_debug_set_plan_observer(idh_plan_observer fn, void *user) {
 }
 
 extern "C" int idh_basic_block_sizes(const idh_block_params *blk, int N, const idh_tensor *x, const idh_tensor *out, idh_net_sizes *sizes) {
-    if (!sizes) return IDH_EINVAL;
-    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
-    const int rc = build_basic_block(p, blk, N, x, out);
-    return rc != IDH_OK ? rc : p.finish(sizes);
+    return net_entry(MODE_SIZES, nullptr, nullptr, 0, nullptr, sizes, false, [&](Plan &p) { return build_basic_block(p, blk, N, x, out); });
 }
 extern "C" int idh_basic_block_pack(const idh_block_params *blk, int N, const idh_tensor *x, const idh_tensor *out, float *blob, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
-    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
-    const int rc = build_basic_block(p, blk, N, x, out);
-    return rc != IDH_OK ? rc : p.err;
+    return net_entry(MODE_PACK, blob, nullptr, 0, stream, nullptr, false, [&](Plan &p) { return build_basic_block(p, blk, N, x, out); });
 }
 extern "C" int idh_basic_block_fwd(const idh_block_params *blk, const float *blob, int N, const idh_tensor *x, const idh_tensor *out, float *ws,
                                    size_t ws_floats, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255) || (ws_floats && (!ws || ((uintptr_t)ws & 255)))) return IDH_EINVAL;
-    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
-    const int rc = build_basic_block(p, blk, N, x, out);
-    return rc != IDH_OK ? rc : p.finish(nullptr);
+    return net_entry(MODE_RUN, blob, ws, ws_floats, stream, nullptr, true, [&](Plan &p) { return build_basic_block(p, blk, N, x, out); });
 }
 
 extern "C" int idh_cvencoder_sizes(const idh_block_params *blocks, int num_blocks, int N, const idh_tensor *cost, const idh_tensor *img_feats,
                                    const idh_tensor *outs, idh_net_sizes *sizes) {
-    if (!sizes) return IDH_EINVAL;
-    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
-    const int rc = build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs);
-    return rc != IDH_OK ? rc : p.finish(sizes);
+    return net_entry(MODE_SIZES, nullptr, nullptr, 0, nullptr, sizes, false,
+                     [&](Plan &p) { return build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs); });
 }
 extern "C" int idh_cvencoder_pack(const idh_block_params *blocks, int num_blocks, int N, const idh_tensor *cost, const idh_tensor *img_feats,
                                   const idh_tensor *outs, float *blob, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
-    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
-    const int rc = build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs);
-    return rc != IDH_OK ? rc : p.err;
+    return net_entry(MODE_PACK, blob, nullptr, 0, stream, nullptr, false,
+                     [&](Plan &p) { return build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs); });
 }
 extern "C" int idh_cvencoder_fwd(const idh_block_params *blocks, int num_blocks, const float *blob, int N, const idh_tensor *cost,
                                  const idh_tensor *img_feats, const idh_tensor *outs, float *ws, size_t ws_floats, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
-    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
-    const int rc = build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs);
-    return rc != IDH_OK ? rc : p.finish(nullptr);
+    return net_entry(MODE_RUN, blob, ws, ws_floats, stream, nullptr, false,
+                     [&](Plan &p) { return build_cvencoder(p, blocks, num_blocks, N, cost, img_feats, outs); });
 }
 
 extern "C" int idh_unetpp_sizes(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
                                 const idh_tensor *feature_outs, idh_net_sizes *sizes) {
-    if (!sizes) return IDH_EINVAL;
-    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr);
-    return rc != IDH_OK ? rc : p.finish(sizes);
+    return net_entry(MODE_SIZES, nullptr, nullptr, 0, nullptr, sizes, false,
+                     [&](Plan &p) { return build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr); });
 }
 extern "C" int idh_unetpp_pack(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
                                const idh_tensor *feature_outs, float *blob, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
-    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr);
-    return rc != IDH_OK ? rc : p.err;
+    return net_entry(MODE_PACK, blob, nullptr, 0, stream, nullptr, false,
+                     [&](Plan &p) { return build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr); });
 }
 extern "C" int idh_unetpp_fwd(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, const float *blob, int N,
                               const idh_tensor *feats, const idh_tensor *feature_outs, float *const *log_depth_outs, float *const *depth_outs,
                               float *ws, size_t ws_floats, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
-    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs);
-    return rc != IDH_OK ? rc : p.finish(nullptr);
+    return net_entry(MODE_RUN, blob, ws, ws_floats, stream, nullptr, false,
+                     [&](Plan &p) { return build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs); });
 }
 
 extern "C" int idh_unetpp_sizes_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
                                    const idh_tensor *feature_outs, uint32_t scales, idh_net_sizes *sizes) {
-    if (!sizes) return IDH_EINVAL;
-    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales);
-    return rc != IDH_OK ? rc : p.finish(sizes);
+    return net_entry(MODE_SIZES, nullptr, nullptr, 0, nullptr, sizes, false,
+                     [&](Plan &p) { return build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales); });
 }
 extern "C" int idh_unetpp_pack_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, int N, const idh_tensor *feats,
                                   const idh_tensor *feature_outs, uint32_t scales, float *blob, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
-    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales);
-    return rc != IDH_OK ? rc : p.err;
+    return net_entry(MODE_PACK, blob, nullptr, 0, stream, nullptr, false,
+                     [&](Plan &p) { return build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, nullptr, nullptr, scales); });
 }
 extern "C" int idh_unetpp_fwd_ex(const idh_block_params *blocks, int n_blocks, const idh_conv_params *heads, const float *blob, size_t weight_floats,
                                  int N, const idh_tensor *feats, const idh_tensor *feature_outs, uint32_t scales, float *const *log_depth_outs,
                                  float *const *depth_outs, float *ws, size_t ws_floats, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
-    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
-    const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs, scales);
-    if (rc != IDH_OK) return rc;
-    if (weight_floats != p.blob_off) return IDH_EINVAL;  // a blob sized for another (N, shapes, feature_outs): never read
-    return p.finish(nullptr);
+    return net_entry(MODE_RUN, blob, ws, ws_floats, stream, nullptr, false, [&](Plan &p) {
+        const int rc = build_unetpp(p, blocks, n_blocks, heads, N, feats, feature_outs, log_depth_outs, depth_outs, scales);
+        if (rc != IDH_OK) return rc;
+        return weight_floats != p.blob_off ? IDH_EINVAL : IDH_OK;  // a blob sized for another (N, shapes, feature_outs): never read
+    });
 }
 
 extern "C" int idh_matching_stem_sizes(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, idh_net_sizes *sizes) {
-    if (!sizes) return IDH_EINVAL;
-    Plan p(MODE_SIZES, nullptr, 0, nullptr, nullptr);
-    const int rc = build_matching_stem(p, params, N, images, out);
-    return rc != IDH_OK ? rc : p.finish(sizes);
+    return net_entry(MODE_SIZES, nullptr, nullptr, 0, nullptr, sizes, false, [&](Plan &p) { return build_matching_stem(p, params, N, images, out); });
 }
 extern "C" int idh_matching_stem_pack(const idh_stem_params *params, int N, const idh_tensor *images, const idh_tensor *out, float *blob, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255)) return IDH_EINVAL;
-    Plan p(MODE_PACK, nullptr, 0, blob, idh_stream(stream));
-    const int rc = build_matching_stem(p, params, N, images, out);
-    return rc != IDH_OK ? rc : p.err;
+    return net_entry(MODE_PACK, blob, nullptr, 0, stream, nullptr, false, [&](Plan &p) { return build_matching_stem(p, params, N, images, out); });
 }
 extern "C" int idh_matching_stem_fwd(const idh_stem_params *params, const float *blob, int N, const idh_tensor *images, const idh_tensor *out, float *ws,
                                      size_t ws_floats, void *stream) {
-    if (!blob || ((uintptr_t)blob & 255) || !ws || ((uintptr_t)ws & 255)) return IDH_EINVAL;
-    Plan p(MODE_RUN, ws, ws_floats, const_cast<float *>(blob), idh_stream(stream));
-    const int rc = build_matching_stem(p, params, N, images, out);
-    return rc != IDH_OK ? rc : p.finish(nullptr);
+    return net_entry(MODE_RUN, blob, ws, ws_floats, stream, nullptr, false, [&](Plan &p) { return build_matching_stem(p, params, N, images, out); });
 }
+

@@ -437,15 +437,33 @@ class Plan:
             pool.append(t)
             self.recycled_candidates += 1
 
+    # recording -----------------------------------------------------------------------
+    def _record(self, op: Op, reads, writes) -> int:
+        """The one way an op enters the plan: the descriptor, the (buffer id, c0, c1) regions ``idh_schedule_ops`` orders it by, and the
+        cached ctypes array dropped.  Returns the build index (what ``set_in`` / ``set_out`` take, stable across ``schedule()``)."""
+        self.ops.append(op)
+        self.meta.append({"reads": reads, "writes": writes})
+        self._arr = None
+        return len(self.ops) - 1
+
+    @staticmethod
+    def _fill_src(s: ConvSrc, v: View):
+        s.in_, s.cs, s.H, s.W, s.Cin = v.ptr, v.cs, v.H, v.W, v.C
+
+    def _keep_bias(self, op: Op, bias: Optional[torch.Tensor]):
+        """``op.bias`` = a contiguous copy of ``bias`` that lives as long as the plan (None: the op has no bias)."""
+        if bias is not None:
+            bias = bias.detach().contiguous()
+            self.keep.append(bias)
+            op.bias = bias.data_ptr()
+
     # ops -----------------------------------------------------------------------------
     def conv(self, x: View, conv: nn.Conv2d, out: View, act=ACT_NONE, slope=0.2, res: Optional[View] = None,
              x2: Optional[View] = None, conv2: Optional[nn.Conv2d] = None, pad_mode=PAD_ZEROS, norm=None, wino4_any_size: bool = False):
         """``norm`` = (stats, act, slope): read ``x`` through act((x - mean) * rstd) with the (N, 2, C) statistics of
         ``instance_norm(x, None)`` (``norm_on_load_eligible`` layers only).  ``wino4_any_size``: an fp32 layer of the F(4x4) shape family runs on
         conv3x3_wino4_k whatever its tile count (results then do not depend on the batch size)."""
-        op = Op()
-        op.kind = OP_CONV
-        op.N = x.N
+        op = Op(kind=OP_CONV, N=x.N)
         srcs = [(x, conv)] + ([(x2, conv2)] if x2 is not None else [])
         for v, cv in srcs:
             if v.C != cv.in_channels:
@@ -469,21 +487,17 @@ class Plan:
                 w = pack[ch.w_layout if i == 0 else W_DIRECT](cv)
             self.keep.append(w)
             s = op.src[i]
-            cin = cat.C if cat is not None else v.C
-            s.in_, s.w, s.cs, s.H, s.W, s.Cin = v.ptr, w.data_ptr(), v.cs, v.H, v.W, cin
-            s.ks, s.stride, s.pad_mode = ks, st, pad_mode
+            self._fill_src(s, v)
+            s.w, s.ks, s.stride, s.pad_mode = w.data_ptr(), ks, st, pad_mode
             if cat is not None:
-                s.up_c0, s.up_C = cat.direct.C, cat.ups[0].C
+                s.Cin, s.up_c0, s.up_C = cat.C, cat.direct.C, cat.ups[0].C
                 for ui, u in enumerate(cat.ups):
                     s.up_in[ui], s.up_cs[ui] = u.ptr, u.cs
             self.flops += 2 * out.N * out.H * out.W * cv.out_channels * cv.in_channels * ks * ks
         bias = conv.bias
         if conv2 is not None and conv2.bias is not None:
             bias = (conv.bias + conv2.bias).detach() if conv.bias is not None else conv2.bias
-        if bias is not None:
-            bias = bias.detach().contiguous()
-            self.keep.append(bias)
-            op.bias = bias.data_ptr()
+        self._keep_bias(op, bias)
         if res is not None:
             op.res, op.res_cs = res.ptr, res.cs
         op.out, op.out_cs = out.ptr, out.cs
@@ -500,49 +514,35 @@ class Plan:
             ws = torch.empty(split * M * ceil16(conv.out_channels), device=self.device, dtype=torch.float32)
             self.keep.append(ws)
             op.ws = ws.data_ptr()
-        self.ops.append(op)
         reads = ([_region(res)] if res is not None else []) + ([(norm[0].data_ptr(), 0, 1)] if norm is not None else [])
         for v, _ in srcs:
             if isinstance(v, CatView):
                 reads += [_region(v.direct)] + [_region(u) for u in v.ups]
             else:
                 reads.append(_region(v, pad16=True))
-        self.meta.append({"reads": reads, "writes": [_region(out)]})
-        self._arr = None
+        self._record(op, reads, [_region(out)])
         return out
 
     def upsample2(self, x: View, out: View, nearest: bool = False):
-        op = Op()
-        op.kind, op.N = (OP_UPSAMPLE2_NEAREST if nearest else OP_UPSAMPLE2), x.N
-        s = op.src[0]
-        s.in_, s.cs, s.H, s.W, s.Cin = x.ptr, x.cs, x.H, x.W, x.C
-        op.out, op.out_cs = out.ptr, out.cs
-        self.ops.append(op)
-        self.meta.append({"reads": [_region(x)], "writes": [_region(out)]})
-        self._arr = None
+        op = Op(kind=OP_UPSAMPLE2_NEAREST if nearest else OP_UPSAMPLE2, N=x.N, out=out.ptr, out_cs=out.cs)
+        self._fill_src(op.src[0], x)
+        self._record(op, [_region(x)], [_region(out)])
         return out
 
     def pointwise_up(self, x: View, conv: nn.Conv2d, low: View, out: View):
         """out = conv1x1(x) + upsample2(low) (IDH_OP_POINTWISE_UP, csrc/conv.hip pointwise_up_k)."""
         if conv.kernel_size[0] != 1 or conv.in_channels != x.C or conv.out_channels != out.C or low.C != out.C or (2 * low.H, 2 * low.W) != (x.H, x.W):
             raise _lib.IdhError("pointwise_up: a 1x1 conv of x plus the x2 upsampling of a half-resolution map with the output's channels")
-        op = Op()
-        op.kind, op.N = OP_POINTWISE_UP, x.N
+        op = Op(kind=OP_POINTWISE_UP, N=x.N, out=out.ptr, out_cs=out.cs, Ho=out.H, Wo=out.W, Cout=out.C)
         w = packed_weight(conv)
         self.keep.append(w)
         s = op.src[0]
-        s.in_, s.w, s.cs, s.H, s.W, s.Cin, s.ks, s.stride = x.ptr, w.data_ptr(), x.cs, x.H, x.W, x.C, 1, 1
-        l = op.src[1]
-        l.in_, l.cs, l.H, l.W, l.Cin = low.ptr, low.cs, low.H, low.W, low.C
-        if conv.bias is not None:
-            b = conv.bias.detach().contiguous()
-            self.keep.append(b)
-            op.bias = b.data_ptr()
-        op.out, op.out_cs, op.Ho, op.Wo, op.Cout = out.ptr, out.cs, out.H, out.W, out.C
+        self._fill_src(s, x)
+        s.w, s.ks, s.stride = w.data_ptr(), 1, 1
+        self._fill_src(op.src[1], low)
+        self._keep_bias(op, conv.bias)
         self.flops += 2 * x.N * x.H * x.W * conv.out_channels * conv.in_channels
-        self.ops.append(op)
-        self.meta.append({"reads": [_region(x), _region(low)], "writes": [_region(out)]})
-        self._arr = None
+        self._record(op, [_region(x), _region(low)], [_region(out)])
         return out
 
     def instance_norm(self, x: View, out: Optional[View], act=ACT_NONE, slope=0.2):
@@ -550,35 +550,25 @@ class Plan:
         returns the (N, 2, C) mean / rstd tensor for a consumer conv that normalises on load (``conv(..., norm=...)``)."""
         if x.C % 4 or 256 % (x.C // 4):
             raise _lib.IdhError(f"instance-norm kernel needs C/4 to divide 256 (C={x.C})")
-        op = Op()
-        op.kind, op.N = OP_INSTNORM, x.N
-        s = op.src[0]
-        s.in_, s.cs, s.H, s.W, s.Cin = x.ptr, x.cs, x.H, x.W, x.C
-        op.act, op.slope = act, slope
+        op = Op(kind=OP_INSTNORM, N=x.N, act=act, slope=slope)
+        self._fill_src(op.src[0], x)
         if out is not None:
             op.out, op.out_cs = out.ptr, out.cs
         nchunks = -(-(x.H * x.W) // 1024)
         ws = torch.empty(x.N * (nchunks + 1) * 2 * x.C, device=self.device, dtype=torch.float32)
         self.keep.append(ws)
         op.ws = ws.data_ptr()
-        self.ops.append(op)
         stats = ws[x.N * nchunks * 2 * x.C:].view(x.N, 2, x.C)
-        self.meta.append({"reads": [_region(x)], "writes": [_region(out)] if out is not None else [(stats.data_ptr(), 0, 1)]})
-        self._arr = None
+        self._record(op, [_region(x)], [_region(out)] if out is not None else [(stats.data_ptr(), 0, 1)])
         return out if out is not None else stats
 
     def copy(self, x: View, out: View):
         """NHWC view -> NHWC view (e.g. an existing feature map into a slice of a concat buffer)."""
         if (x.N, x.H, x.W, x.C) != (out.N, out.H, out.W, out.C):
             raise _lib.IdhError("copy: shape mismatch")
-        op = Op()
-        op.kind, op.N = OP_COPY, x.N
-        s = op.src[0]
-        s.in_, s.cs, s.H, s.W, s.Cin = x.ptr, x.cs, x.H, x.W, x.C
-        op.out, op.out_cs = out.ptr, out.cs
-        self.ops.append(op)
-        self.meta.append({"reads": [_region(x)], "writes": [_region(out)]})
-        self._arr = None
+        op = Op(kind=OP_COPY, N=x.N, out=out.ptr, out_cs=out.cs)
+        self._fill_src(op.src[0], x)
+        self._record(op, [_region(x)], [_region(out)])
         return out
 
     def import_nchw(self, shape_nchw, out: View) -> int:
@@ -587,15 +577,16 @@ class Plan:
         N, Cc, H, W = [int(v) for v in shape_nchw]
         if (N, H, W, Cc) != (out.N, out.H, out.W, out.C):
             raise _lib.IdhError(f"import of {tuple(shape_nchw)} into a view of {(out.N, out.C, out.H, out.W)}")
-        op = Op()
-        op.kind, op.N = OP_IMPORT, N
+        op = Op(kind=OP_IMPORT, N=N, out=out.ptr, out_cs=out.cs)
         s = op.src[0]
         s.H, s.W, s.Cin = H, W, Cc
-        op.out, op.out_cs = out.ptr, out.cs
-        self.ops.append(op)
-        self.meta.append({"reads": [], "writes": [_region(out)]})
-        self._arr = None
-        return len(self.ops) - 1
+        return self._record(op, [], [_region(out)])
+
+    def input_nchw(self, shape_nchw):
+        """A plan buffer for a dense (N,C,H,W) input and its layout import: (the NHWC view, the import's op index for ``set_in``)."""
+        N, Cc, H, W = [int(v) for v in shape_nchw]
+        v = self.buffer(N, H, W, Cc)
+        return v, self.import_nchw(shape_nchw, v)
 
     @staticmethod
     def pointwise_nchw_eligible(conv: nn.Conv2d) -> bool:
@@ -609,22 +600,14 @@ class Plan:
         N, Cc, H, W = [int(v) for v in shape_nchw]
         if (N, H, W) != (out.N, out.H, out.W) or Cc != conv.in_channels or out.C != conv.out_channels or not self.pointwise_nchw_eligible(conv):
             raise _lib.IdhError(f"pointwise_nchw: {tuple(shape_nchw)} with {conv} into a view of {(out.N, out.C, out.H, out.W)}")
-        op = Op()
-        op.kind, op.N = OP_POINTWISE_NCHW, N
+        op = Op(kind=OP_POINTWISE_NCHW, N=N, out=out.ptr, out_cs=out.cs, Ho=H, Wo=W, Cout=conv.out_channels)
         s = op.src[0]
         w = packed_weight(conv)
         self.keep.append(w)
         s.w, s.H, s.W, s.Cin, s.ks, s.stride = w.data_ptr(), H, W, Cc, 1, 1
-        if conv.bias is not None:
-            bias = conv.bias.detach().contiguous()
-            self.keep.append(bias)
-            op.bias = bias.data_ptr()
-        op.out, op.out_cs, op.Ho, op.Wo, op.Cout = out.ptr, out.cs, H, W, conv.out_channels
+        self._keep_bias(op, conv.bias)
         self.flops += 2 * N * H * W * conv.out_channels * conv.in_channels
-        self.ops.append(op)
-        self.meta.append({"reads": [], "writes": [_region(out)]})
-        self._arr = None
-        return len(self.ops) - 1
+        return self._record(op, [], [_region(out)])
 
     def stem(self, shape, strides, blob: torch.Tensor, out: View) -> int:
         """conv1 + folded BatchNorm + ReLU + MaxPool2d(2, 1) + BlurPool of the ResNet18 stem (IDH_OP_STEM, csrc/stem.hip) from N fp32 NCHW
@@ -638,47 +621,32 @@ class Plan:
         group, img_stride, grp_stride = [int(v) for v in strides]
         if max(img_stride, grp_stride) >= 1 << 31 or N % group:
             raise _lib.IdhError("stem: image strides must fit in 32 bits and the groups divide the batch")
-        op = Op()
-        op.kind, op.N = OP_STEM, N
+        op = Op(kind=OP_STEM, N=N, out=out.ptr, out_cs=out.cs, Ho=Ho, Wo=Wo, Cout=64)
         s = op.src[0]
         s.w, s.H, s.W, s.Cin = blob.data_ptr(), H, W, 3
         s.up_C, s.up_cs[0], s.up_cs[1] = group, img_stride, grp_stride
         self.keep.append(blob)
-        op.out, op.out_cs, op.Ho, op.Wo, op.Cout = out.ptr, out.cs, Ho, Wo, 64
         self.flops += 2 * N * ((H + 1) // 2) * ((W + 1) // 2) * 64 * 147
-        self.ops.append(op)
-        self.meta.append({"reads": [], "writes": [_region(out)]})
-        self._arr = None
-        return len(self.ops) - 1
+        return self._record(op, [], [_region(out)])
 
     def export_nchw(self, x: View, out_nchw: Optional[torch.Tensor] = None) -> int:
-        op = Op()
-        op.kind, op.N = OP_EXPORT, x.N
-        s = op.src[0]
-        s.in_, s.cs, s.H, s.W, s.Cin = x.ptr, x.cs, x.H, x.W, x.C
+        op = Op(kind=OP_EXPORT, N=x.N)
+        self._fill_src(op.src[0], x)
         if out_nchw is not None:
             op.out = out_nchw.data_ptr()
-        self.ops.append(op)
-        self.meta.append({"reads": [_region(x)], "writes": []})
-        self._arr = None
-        return len(self.ops) - 1
+        return self._record(op, [_region(x)], [])
 
     def head(self, x: View, conv: nn.Conv2d, out: torch.Tensor):
         """1x1 conv to one channel (DepthDecoderPP heads, reference networks.py:158-161)."""
         if conv.out_channels != 1 or conv.kernel_size != (1, 1):
             raise _lib.IdhError("pointwise head kernel covers Conv2d(C,1,1) only")
-        op = Op()
-        op.kind, op.N = OP_HEAD, x.N
+        op = Op(kind=OP_HEAD, N=x.N, out=out.data_ptr())
         w = conv.weight.detach().reshape(-1).contiguous()
         b = conv.bias.detach().contiguous()
         self.keep += [w, b]
-        s = op.src[0]
-        s.in_, s.w, s.cs, s.H, s.W, s.Cin = x.ptr, w.data_ptr(), x.cs, x.H, x.W, x.C
-        op.bias, op.out = b.data_ptr(), out.data_ptr()
-        self.ops.append(op)
-        self.meta.append({"reads": [_region(x)], "writes": []})
-        self._arr = None
-        return len(self.ops) - 1
+        self._fill_src(op.src[0], x)
+        op.src[0].w, op.bias = w.data_ptr(), b.data_ptr()
+        return self._record(op, [_region(x)], [])
 
     # composite: BasicBlock (reference layers.py:78-95) ---------------------------------
     def basic_block(self, x: View, blk, out: Optional[View] = None) -> View:
@@ -829,6 +797,14 @@ class Plan:
         if exp_out is not None:
             op.ws = exp_out.data_ptr()
 
+    def run_with(self, ins=(), outs=()):
+        """``run()`` on this call's tensors: (build index, tensor) pairs patched in with ``set_in`` / ``set_out`` first."""
+        for i, t in ins:
+            self.set_in(i, t)
+        for i, t in outs:
+            self.set_out(i, t)
+        self.run()
+
 
 def math_of(module: nn.Module) -> str:
     """Conv arithmetic of a drop-in module: its ``conv_math`` attribute (set by ``dropin.convert(model,
@@ -910,6 +886,19 @@ def _param_key(module: nn.Module):
     return ParamKey((math_of(module), build_flags()) + tuple((p.data_ptr(), _lib.param_version(p)) for p in module.parameters()))
 
 
+def cached_plan(module: nn.Module, key, device, build) -> tuple:
+    """The drop-ins' cached replay: ``module``'s plan-cache entry (plan, *payload) under ``key``.  On a miss ``build(p)`` records the ops on
+    a fresh ``Plan(device, math=math_of(module))`` and returns the payload (op indices, output views); the plan is scheduled, the entry kept."""
+    cache = _plan_cache(module)
+    ent = cache.get(key)
+    if ent is None:
+        p = Plan(device, math=math_of(module))
+        payload = build(p)
+        p.schedule()
+        ent = cache.put(key, (p, *payload))
+    return ent
+
+
 def _check_in(*ts):
     for t in ts:
         _lib.require_cuda_f32(t)
@@ -921,24 +910,15 @@ def _check_in(*ts):
 def block_forward_nchw(blk, x: torch.Tensor) -> torch.Tensor:
     _check_in(x)
     x = x.contiguous()
-    key = ("bb", tuple(x.shape), str(x.device), _param_key(blk))
-    cache = _plan_cache(blk)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(x.device, math=math_of(blk))
-        N, Cc, H, W = x.shape
-        xin = p.buffer(N, H, W, Cc)
-        i_in = p.import_nchw(x.shape, xin)
+
+    def build(p: Plan):
+        xin, i_in = p.input_nchw(x.shape)
         y = p.basic_block(xin, blk)
-        i_out = p.export_nchw(y)
-        p.schedule()
-        ent = (p, i_in, i_out, y)
-        cache.put(key, ent)
-    p, i_in, i_out, y = ent
+        return i_in, p.export_nchw(y), y
+
+    p, i_in, i_out, y = cached_plan(blk, ("bb", tuple(x.shape), str(x.device), _param_key(blk)), x.device, build)
     out = torch.empty(y.N, y.C, y.H, y.W, device=x.device, dtype=torch.float32)
-    p.set_in(i_in, x)
-    p.set_out(i_out, out)
-    p.run()
+    p.run_with([(i_in, x)], [(i_out, out)])
     return out
 
 
@@ -972,26 +952,15 @@ def cv_encoder_forward_nchw(enc, x: torch.Tensor, img_feats: List[torch.Tensor])
     x = x.contiguous()
     img_feats = [f.contiguous() for f in img_feats]
     key = ("cve", tuple(x.shape), tuple(tuple(f.shape) for f in img_feats), str(x.device), _param_key(enc))
-    cache = _plan_cache(enc)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(x.device, math=math_of(enc))
-        N, D, H, W = x.shape
-        xin = p.buffer(N, H, W, D)
-        i_x = p.import_nchw(x.shape, xin)
+
+    def build(p: Plan):
+        xin, i_x = p.input_nchw(x.shape)
         outs, i_img = build_cv_encoder(p, enc, xin, [f.shape for f in img_feats])
-        i_out = [p.export_nchw(o) for o in outs]
-        p.schedule()
-        ent = (p, i_x, i_img, i_out, outs)
-        cache.put(key, ent)
-    p, i_x, i_img, i_out, outs = ent
+        return [i_x] + i_img, [p.export_nchw(o) for o in outs], outs
+
+    p, i_in, i_out, outs = cached_plan(enc, key, x.device, build)
     res = [torch.empty(o.N, o.C, o.H, o.W, device=x.device, dtype=torch.float32) for o in outs]
-    p.set_in(i_x, x)
-    for i, f in zip(i_img, img_feats):
-        p.set_in(i, f)
-    for i, r in zip(i_out, res):
-        p.set_out(i, r)
-    p.run()
+    p.run_with(zip(i_in, [x] + img_feats), zip(i_out, res))
     return res
 
 
@@ -1072,37 +1041,22 @@ def build_decoder(p: Plan, dec, feats: List[View], scales: int = ALL_SCALES):
 def decoder_forward_nchw(dec, input_features: List[torch.Tensor]) -> Dict[str, torch.Tensor]:
     _check_in(*input_features)
     feats = [f.contiguous() for f in input_features]
-    key = ("dec", tuple(tuple(f.shape) for f in feats), str(feats[0].device), _param_key(dec))
-    cache = _plan_cache(dec)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(feats[0].device, math=math_of(dec))
-        views, i_in = [], []
-        for f in feats:
-            v = p.buffer(f.shape[0], f.shape[2], f.shape[3], f.shape[1])
-            i_in.append(p.import_nchw(f.shape, v))
-            views.append(v)
-        final = build_any_decoder(p, dec, views)
-        i_out = {}
-        for i, v in final.items():
-            if getattr(dec, "depth_head", False):
-                i_out[i] = p.head(v, dec.convs[f"output_{i}"][1], torch.empty(1, device=feats[0].device))
-            else:
-                i_out[i] = p.export_nchw(v)
-        p.schedule()
-        ent = (p, i_in, i_out, final)
-        cache.put(key, ent)
-    p, i_in, i_out, final = ent
-    for i, f in zip(i_in, feats):
-        p.set_in(i, f)
-    res = {}
-    for i, v in final.items():
-        ch = 1 if getattr(dec, "depth_head", False) else v.C
-        t = torch.empty(v.N, ch, v.H, v.W, device=feats[0].device, dtype=torch.float32)
-        p.set_out(i_out[i], t)
-        res[dec.out_key.format(i)] = t
-    p.run()
-    return res
+    dev, depth_head = feats[0].device, getattr(dec, "depth_head", False)
+
+    def build(p: Plan):
+        views, i_in = zip(*[p.input_nchw(f.shape) for f in feats])
+        final = build_any_decoder(p, dec, list(views))
+        if depth_head:
+            i_out = {i: p.head(v, dec.convs[f"output_{i}"][1], torch.empty(1, device=dev)) for i, v in final.items()}
+        else:
+            i_out = {i: p.export_nchw(v) for i, v in final.items()}
+        return i_in, i_out, final
+
+    key = ("dec", tuple(tuple(f.shape) for f in feats), str(dev), _param_key(dec))
+    p, i_in, i_out, final = cached_plan(dec, key, dev, build)
+    res = {i: torch.empty(v.N, 1 if depth_head else v.C, v.H, v.W, device=dev, dtype=torch.float32) for i, v in final.items()}
+    p.run_with(zip(i_in, feats), [(i_out[i], t) for i, t in res.items()])
+    return {dec.out_key.format(i): t for i, t in res.items()}
 
 
 def binary_mlp_forward(net, inputs, max_scale_only):
@@ -1151,29 +1105,26 @@ def matching_head_forward(enc, feat_nchw: torch.Tensor, channels_last: bool = Fa
     _check_in(feat_nchw)
     x = feat_nchw.contiguous()
     key = ("mh", tuple(x.shape), str(x.device), channels_last, _param_key(enc.net[5]) + _param_key(enc.net[8]))
-    cache = _plan_cache(enc)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(x.device, math=math_of(enc))
-        N, Cc, H, W = x.shape
+
+    def build(p: Plan):
         if FUSE_HEAD_IMPORT and Plan.pointwise_nchw_eligible(enc.net[5]):
             y, i_in = build_matching_head(p, enc, None, nchw_shape=x.shape)
         else:
-            xin = p.buffer(N, H, W, Cc)
-            i_in = p.import_nchw(x.shape, xin)
+            xin, i_in = p.input_nchw(x.shape)
             y = build_matching_head(p, enc, xin)
-        i_out = None if channels_last else p.export_nchw(y)
-        p.schedule()
-        ent = (p, i_in, i_out, y)
-        cache.put(key, ent)
+        return i_in, None if channels_last else p.export_nchw(y), y
+
+    return _run_encoder_plan(cached_plan(enc, key, x.device, build), x, channels_last)
+
+
+def _run_encoder_plan(ent, x: torch.Tensor, channels_last: bool) -> torch.Tensor:
+    """Replay a matching-encoder entry (plan, input op, export op or None, output view) on ``x``: NCHW, or a copy of the NHWC map."""
     p, i_in, i_out, y = ent
-    p.set_in(i_in, x)
     if channels_last:
-        p.run()
+        p.run_with([(i_in, x)])
         return y.dense().clone()
     out = torch.empty(y.N, y.C, y.H, y.W, device=x.device, dtype=torch.float32)
-    p.set_out(i_out, out)
-    p.run()
+    p.run_with([(i_in, x)], [(i_out, out)])
     return out
 
 
@@ -1295,26 +1246,14 @@ def matching_encoder_forward(enc, images: torch.Tensor, channels_last: bool = Fa
     images, shape, strides = image_strides(images)
     pk = stem_param_key(enc.net[:5]) + ((_param_key(enc.net[5]) + _param_key(enc.net[8])) if head else ParamKey())
     key = ("stem", tuple(shape), strides, str(images.device), channels_last, head, pk)
-    cache = _plan_cache(enc)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(images.device, math=math_of(enc))
+
+    def build(p: Plan):
         y, i_in = build_matching_stem(p, enc, images)
         if head:
             y = build_matching_head(p, enc, y)
-        i_out = None if channels_last else p.export_nchw(y)
-        p.schedule()
-        ent = (p, i_in, i_out, y)
-        cache.put(key, ent)
-    p, i_in, i_out, y = ent
-    p.set_in(i_in, images)
-    if channels_last:
-        p.run()
-        return y.dense().clone()
-    out = torch.empty(y.N, y.C, y.H, y.W, device=images.device, dtype=torch.float32)
-    p.set_out(i_out, out)
-    p.run()
-    return out
+        return i_in, None if channels_last else p.export_nchw(y), y
+
+    return _run_encoder_plan(cached_plan(enc, key, images.device, build), images, channels_last)
 
 
 # --- SkipDecoder / SkipDecoderRegression (reference modules/networks_fast.py:10-145) ------------
@@ -1374,34 +1313,22 @@ def skip_regression_forward_nchw(dec, input_features: List[torch.Tensor]) -> Dic
     """SkipDecoderRegression.forward (networks_fast.py:137-145): feature maps + log-depth heads."""
     _check_in(*input_features)
     feats = [f.contiguous() for f in input_features]
-    key = ("skipreg", tuple(tuple(f.shape) for f in feats), str(feats[0].device), _param_key(dec))
-    cache = _plan_cache(dec)
-    ent = cache.get(key)
-    if ent is None:
-        p = Plan(feats[0].device, math=math_of(dec))
-        views, i_in = [], []
-        for f in feats:
-            v = p.buffer(f.shape[0], f.shape[2], f.shape[3], f.shape[1])
-            i_in.append(p.import_nchw(f.shape, v))
-            views.append(v)
-        final = build_skip_decoder(p, dec, views)
+    dev = feats[0].device
+
+    def build(p: Plan):
+        views, i_in = zip(*[p.input_nchw(f.shape) for f in feats])
+        final = build_skip_decoder(p, dec, list(views))
         heads = build_regression_heads(p, dec, final)
         i_feat = {i: p.export_nchw(v) for i, v in final.items()}
-        i_head = {i: p.head(hv, last, torch.empty(1, device=feats[0].device)) for i, (hv, last) in heads.items()}
-        p.schedule()
-        ent = (p, i_in, i_feat, i_head, final)
-        cache.put(key, ent)
-    p, i_in, i_feat, i_head, final = ent
-    for i, f in zip(i_in, feats):
-        p.set_in(i, f)
-    res = {}
-    dev = feats[0].device
+        i_head = {i: p.head(hv, last, torch.empty(1, device=dev)) for i, (hv, last) in heads.items()}
+        return i_in, i_feat, i_head, final
+
+    key = ("skipreg", tuple(tuple(f.shape) for f in feats), str(dev), _param_key(dec))
+    p, i_in, i_feat, i_head, final = cached_plan(dec, key, dev, build)
+    res, outs = {}, []
     for i, v in final.items():
-        t = torch.empty(v.N, v.C, v.H, v.W, device=dev)
-        p.set_out(i_feat[i], t)
-        res[f"feature_s{i}_b1hw"] = t
-        d = torch.empty(v.N, 1, v.H, v.W, device=dev)
-        p.set_out(i_head[i], d)
-        res[f"log_depth_pred_s{i}_b1hw"] = d
-    p.run()
+        res[f"feature_s{i}_b1hw"] = t = torch.empty(v.N, v.C, v.H, v.W, device=dev)
+        res[f"log_depth_pred_s{i}_b1hw"] = d = torch.empty(v.N, 1, v.H, v.W, device=dev)
+        outs += [(i_feat[i], t), (i_head[i], d)]
+    p.run_with(zip(i_in, feats), outs)
     return res

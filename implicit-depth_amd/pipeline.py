@@ -399,9 +399,8 @@ class HotPath(nn.Module):
                 # the first 1x1 conv reads the backbone's NCHW map in place: no layout-import pass
                 y, ent["i_l1"] = nhwc.build_matching_head(p, self.matching_model, None, nchw_shape=(M, head_ch, H, W))
             elif head == "nchw":
-                x = p.buffer(M, H, W, head_ch)
-                ent["i_l1"] = p.import_nchw((M, head_ch, H, W), x)
-                y = nhwc.build_matching_head(p, self.matching_model, x)
+                x, ent["i_l1"] = p.input_nchw((M, head_ch, H, W))
+                y =nhwc.build_matching_head(p, self.matching_model, x)
             else:  # channels-last producer: the first conv reads the caller's tensor in place (pointer patched per call)
                 x = nhwc.View(torch.empty(1, device=device).expand(M, H, W, head_ch), 0, head_ch)
                 y = nhwc.build_matching_head(p, self.matching_model, x)
@@ -413,10 +412,9 @@ class HotPath(nn.Module):
             ent["match_view"] = y
         n_pre = len(p.ops)
         cv_in = p.buffer(B, H, W, D)
-        v0 = p.buffer(B, enc_shapes[0][2], enc_shapes[0][3], enc_shapes[0][1])
-        i_enc = [p.import_nchw(enc_shapes[0], v0)]
+        v0, i_v0 = p.input_nchw(enc_shapes[0])
         outs, i_img = nhwc.build_cv_encoder(p, self.cost_volume_net, cv_in, enc_shapes[1:])
-        i_enc += i_img
+        i_enc = [i_v0] + i_img
         final = nhwc.build_any_decoder(p, self.depth_decoder, [v0] + outs, scales)
         ent.update(cv_in=cv_in, i_enc=i_enc, final=final)
         if getattr(self.depth_decoder, "depth_head", False):
