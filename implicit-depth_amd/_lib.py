@@ -287,6 +287,31 @@ class MvConsistencyArgs(C.Structure):
         self.struct_size = C.sizeof(MvConsistencyArgs)
 
 
+class EdgeMaskArgs(C.Structure):
+    """ctypes mirror of ``idh_edge_mask_args`` (include/idh_geometry.h, edge mask of a depth map)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_b1hw", C.c_void_p), ("mask_b1hw", C.c_void_p), ("sobel_b1hw", C.c_void_p),
+                ("threshold_b", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("q", C.c_float), ("dilate", C.c_int32),
+                ("mask_u8", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(EdgeMaskArgs)
+
+
+class BdValLossesArgs(C.Structure):
+    """ctypes mirror of ``idh_bd_val_losses_args`` (include/idh_geometry.h, BDModel's validation losses)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("pred_bdhw", C.c_void_p), ("rendered_bdhw", C.c_void_p), ("depth_b1hw", C.c_void_p),
+                ("edge_mask_b1hw", C.c_void_p), ("out5", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("bd_regularisation_weight", C.c_float), ("positive_weight", C.c_float), ("max_workgroups", C.c_int32), ("B", C.c_int32),
+                ("D", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(BdValLossesArgs)
+
+
 MV_MAX_SOURCES, MV_MAX_MAPS = 16, 128  # IDH_MV_MAX_*
 TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
 TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
@@ -431,6 +456,12 @@ _SIGS = {
     "idh_sizeof_mv_consistency_args": (C.c_size_t, []),
     "idh_mv_consistency_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "idh_mv_consistency_fwd": (C.c_int, [C.POINTER(MvConsistencyArgs), C.c_void_p]),
+    "idh_sizeof_edge_mask_args": (C.c_size_t, []),
+    "idh_edge_mask_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "idh_edge_mask_fwd": (C.c_int, [C.POINTER(EdgeMaskArgs), C.c_void_p]),
+    "idh_sizeof_bd_val_losses_args": (C.c_size_t, []),
+    "idh_bd_val_losses_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "idh_bd_val_losses_fwd": (C.c_int, [C.POINTER(BdValLossesArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -532,7 +563,9 @@ def lib():
                                   ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs),
                                   ("idh_tsdf_integrate_weighted_args", h.idh_sizeof_tsdf_integrate_weighted_args(), TsdfIntegrateWeightedArgs),
                                   ("idh_tsdf_shift_args", h.idh_sizeof_tsdf_shift_args(), TsdfShiftArgs),
-                                  ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs)):
+                                  ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs),
+                                  ("idh_edge_mask_args", h.idh_sizeof_edge_mask_args(), EdgeMaskArgs),
+                                  ("idh_bd_val_losses_args", h.idh_sizeof_bd_val_losses_args(), BdValLossesArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

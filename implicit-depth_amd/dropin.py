@@ -156,7 +156,20 @@ def hot_path_of(model: nn.Module, min_depth: float = 0.25, max_depth: float = 5.
     return hot
 
 
-def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool = False):
+def _reference_get_edge_mask():
+    """The reference's ``utils.generic_utils.get_edge_mask``, or an ``IdhError`` that says what to do without it."""
+    from . import _lib
+
+    try:
+        from utils.generic_utils import get_edge_mask
+    except ImportError as e:
+        raise _lib.IdhError("run_opts.bd_edge_regularision needs the reference's utils.generic_utils.get_edge_mask (kornia) on the "
+                            "import path to fill inputs['edge_mask']; pass fused_forward(..., native_edge_mask=True) for the "
+                            "native mask (geometry.edge_mask), or unset the option for pure inference") from e
+    return get_edge_mask
+
+
+def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool = False, native_edge_mask: bool = False):
     """A replacement for ``BDModel.forward`` / ``DepthModel.forward`` at inference time (bd_model.py:175-311,
     depth_model.py:280-440): same arguments, same output dictionary, but everything between the third-party backbones
     and the outputs runs as ONE fused pass of ``HotPath`` (matching-encoder head, volume, CVEncoder, decoder, occlusion
@@ -167,7 +180,8 @@ def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool
     If ``cur_data`` carries ``sampled_rays`` (B,N,2) and ``sampled_depths`` (B,N,S), the outputs gain ``ray_pred_0..3``: the occlusion
     logits of ``BDModel.run_mlp_train`` (bd_model.py:313-387) at those rays (``HotPath.query_rays``); ``phase == "train"`` keeps raising.
     Side effects on the input dicts are the reference's: ``cur_data["prior_mask"]`` and, with ``bd_edge_regularision``,
-    ``cur_data["edge_mask"]`` (computed by the reference's own ``get_edge_mask``, which must then be importable)."""
+    ``cur_data["edge_mask"]``: with ``native_edge_mask`` from ``geometry.edge_mask`` (the gfx950 kernels, no kornia, the reference never
+    imported), without it from the reference's own ``get_edge_mask``, which must then be importable."""
     from . import _lib
 
     hot = hot_path_of(model, math=math, native_matching_stem=native_matching_stem)
@@ -225,12 +239,11 @@ def fused_forward(model: nn.Module, math: str = None, native_matching_stem: bool
             cur_data["prior_mask"] = out.pop("prior_mask")  # run_mlp_val stores it on the inputs (bd_model.py:431)
         if is_bd and getattr(opts, "bd_edge_regularision", False) and "depth_b1hw" in cur_data:
             # run_mlp_val's other side effect (bd_model.py:444-447): the edge mask compute_binary_losses reads.  It is the
-            # reference's own loss-side helper (utils/generic_utils.py:286, needs kornia) — not part of this path
-            try:
-                from utils.generic_utils import get_edge_mask
-            except ImportError as e:
-                raise _lib.IdhError("run_opts.bd_edge_regularision needs the reference's utils.generic_utils.get_edge_mask (kornia) on the "
-                                    "import path to fill inputs['edge_mask']; unset the option for pure inference") from e
+            # reference's own loss-side helper (utils/generic_utils.py:286, needs kornia) unless the native one is asked for
+            if native_edge_mask:
+                from .geometry import edge_mask as get_edge_mask
+            else:
+                get_edge_mask = _reference_get_edge_mask()
             cur_data["edge_mask"] = get_edge_mask(cur_data["depth_b1hw"])
         return out
 

@@ -235,3 +235,50 @@ def temporal_final_metrics(total_diffs, eval_length, warmup, eval_frame_multipli
     """The two entries test_bd.py:451-459 adds to the final metrics."""
     return {f"total_diffs_d_{temporal_d:.1f}": total_diffs,
             f"temporal_score_d_{temporal_d:.1f}": total_diffs / ((eval_length - warmup) * eval_frame_multiplier * n_scans)}
+
+
+def bd_val_losses(outputs, cur_data, bd_regularisation_weight, edge_regularision=True, binary_loss_weighting=1.0, *, positive_weight=1.0,
+                  return_counts=False, max_workgroups=0) -> Dict[str, torch.Tensor]:
+    """The validation losses of a ``BDModel``: ``compute_losses("val" / "test", cur_data, outputs)`` of the reference
+    (experiment_modules/bd_model.py:451-503, the ``phase != "train"`` branch), forward value only, in two launches
+    (idh_bd_val_losses_fwd; contract: include/idh_geometry.h).  Reads ``outputs["pred_0"]`` (B,D,h,w),
+    ``cur_data["rendered_depth"]`` (B,D,h,w), ``cur_data["depth_b1hw"]`` and - with ``edge_regularision``, the reference's
+    ``run_opts.bd_edge_regularision`` - ``cur_data["edge_mask"]`` (``geometry.edge_mask``; ``fused_forward(native_edge_mask=True)`` fills
+    it).  ``positive_weight`` is ``run_opts.binary_loss_positive_weight``.  Returns the reference's dictionary: ``binary_loss/0``,
+    ``reg_loss/0``, ``binary_loss`` (their weighted sum) and ``loss`` (``binary_loss * binary_loss_weighting``), 0-d fp32 tensors on the
+    device; nothing is synchronised.  Because of that the per-scale entries are always present: where the reference has none - no pixel
+    with ``depth > 0`` and ``rendered > 0`` - they are NaN and ``binary_loss`` is 0, its edge case; an empty ``reg_mask`` gives a NaN
+    ``reg_loss/0`` as the reference's mean of nothing does.  ``return_counts`` adds ``"counts"``: int64 (2,), the sizes of the two masks.
+    Deterministic, and the same for every ``max_workgroups`` (0: the default grid).  There is no CPU fallback and no backward pass."""
+    pred, rendered, depth = outputs["pred_0"], cur_data["rendered_depth"], cur_data["depth_b1hw"]
+    edge = cur_data["edge_mask"] if edge_regularision else None
+    _lib.require_cuda_f32(pred, rendered, depth, edge)
+    if pred.dim() != 4 or rendered.shape != pred.shape:
+        raise _lib.IdhError(f"pred_0 {tuple(pred.shape)} and rendered_depth {tuple(rendered.shape)} must both be (B,D,h,w)")
+    B, D, h, w = pred.shape
+    for name, t in (("depth_b1hw", depth), ("edge_mask", edge)):
+        if t is not None and tuple(t.shape) != (B, 1, h, w):
+            raise _lib.IdhError(f"{name} {tuple(t.shape)} must be ({B},1,{h},{w})")
+    if min(B, D, h, w) < 1:
+        raise _lib.IdhError(f"pred_0 {tuple(pred.shape)} is empty")
+    if torch.is_grad_enabled() and pred.requires_grad:
+        raise _lib.IdhError("bd_val_losses is forward only (no backward pass): detach pred_0 or call it under torch.no_grad()")
+    keep = [pred.contiguous(), rendered.contiguous(), depth.contiguous()]
+    a = _lib.BdValLossesArgs()
+    a.pred_bdhw, a.rendered_bdhw, a.depth_b1hw = (t.data_ptr() for t in keep)
+    if edge is not None:
+        keep.append(edge.contiguous())
+        a.edge_mask_b1hw = keep[-1].data_ptr()
+    out = torch.empty(5, device=pred.device, dtype=torch.float64)
+    nbytes = _lib.lib().idh_bd_val_losses_workspace_bytes(B, D, h, w)
+    workspace = torch.empty(nbytes // 8, device=pred.device, dtype=torch.float64)
+    a.out5, a.workspace, a.workspace_bytes = out.data_ptr(), workspace.data_ptr(), nbytes
+    a.bd_regularisation_weight, a.positive_weight, a.max_workgroups = float(bd_regularisation_weight), float(positive_weight), int(max_workgroups)
+    a.B, a.D, a.h, a.w = B, D, h, w
+    _lib.check(_lib.lib().idh_bd_val_losses_fwd(a, _lib.stream_ptr()), "idh_bd_val_losses_fwd")
+    f = out.float()
+    losses = {"binary_loss/0": f[2], "reg_loss/0": f[3], "binary_loss": f[4]}
+    losses["loss"] = f[4] if binary_loss_weighting == 1.0 else f[4] * binary_loss_weighting
+    if return_counts:
+        losses["counts"] = out[:2].long()
+    return losses

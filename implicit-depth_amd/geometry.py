@@ -12,6 +12,9 @@ There is no CPU fallback.
 
 ``depth_consistency`` checks a depth map against source depth maps of other cameras in one launch (csrc/mv_consistency.hip, DESIGN.md
 §4.25) with the arithmetic of the reference's ``MVDepthLoss`` (losses.py:143-261); ``MVDepthLoss`` is that module's forward value on it.
+
+``edge_mask`` is the reference's ``get_edge_mask`` (utils/generic_utils.py:286-292, and the dataset's variant,
+datasets/generic_mvs_dataset.py:650-658) without kornia and without a sort (csrc/edge_mask.hip).
 """
 from typing import Optional, Tuple
 
@@ -236,3 +239,44 @@ class MVDepthLoss(nn.Module):
             raise _lib.IdhError(f"depth {tuple(cur_depth_b1hw.shape)} must be (B,1,{self.height},{self.width})")
         return depth_consistency(depth_pred_b1hw, cur_invK_b44, cur_world_T_cam_b44, src_depth_bk1hw, src_K_bk44, src_cam_T_world_bk44,
                                  gate_depth=cur_depth_b1hw, return_loss=True)["loss"]
+
+
+def edge_mask(depth_b1hw: torch.Tensor, threshold: float = 0.95, dilate: bool = True, *, as_bool: bool = False, return_sobel: bool = False,
+              return_threshold: bool = False):
+    """The reference's ``get_edge_mask(depth_b1hw, threshold=0.95, dilate=True)`` (utils/generic_utils.py:286-292) on the gfx950 kernels
+    (idh_edge_mask_fwd; contract: include/idh_geometry.h): the Sobel magnitude ``S`` of the disparity ``1 / depth``, per
+    image the exact ``torch.nanquantile(S, threshold)`` by a radix select, ``S > quantile`` and - with ``dilate`` - the 5x5 max-pool.
+    Returns the mask (B,1,H,W) as float 0 / 1, or as bool with ``as_bool``.  ``edge_mask(depth_1hw, 0.975, False, as_bool=True)`` on a
+    (1,H,W) map is the dataset's variant (datasets/generic_mvs_dataset.py:650-658); a 3-D input returns a 3-D mask.
+    ``return_sobel`` / ``return_threshold`` append ``S`` (the input's shape) / the per-image thresholds (B,) to the result, which is then
+    a tuple.  Deterministic: two calls return the same bits.  There is no CPU fallback, no backward pass, and nothing is synchronised."""
+    _lib.require_cuda_f32(depth_b1hw)
+    squeeze = depth_b1hw.dim() == 3
+    d = depth_b1hw.unsqueeze(0) if squeeze else depth_b1hw
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} must be (B,1,H,W) or (1,H,W)")
+    q = float(threshold)
+    if not 0.0 <= q <= 1.0:
+        raise _lib.IdhError(f"threshold must be a quantile in [0, 1], got {threshold}")
+    B, _, H, W = d.shape
+    if H < 1 or W < 1:
+        raise _lib.IdhError(f"depth {tuple(depth_b1hw.shape)} has no pixels")
+    d = d.contiguous()
+    dev = d.device
+    mask = torch.empty(B, 1, H, W, device=dev, dtype=torch.uint8 if as_bool else torch.float32)
+    sobel = torch.empty(B, 1, H, W, device=dev) if return_sobel else None
+    thr = torch.empty(B, device=dev) if return_threshold else None
+    if B > 0:
+        nbytes = _lib.lib().idh_edge_mask_workspace_bytes(B, H, W)
+        workspace = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+        a = _lib.EdgeMaskArgs()
+        a.depth_b1hw, a.mask_b1hw, a.sobel_b1hw, a.threshold_b = d.data_ptr(), mask.data_ptr(), _lib.ptr(sobel), _lib.ptr(thr)
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+        a.q, a.dilate, a.mask_u8, a.B, a.H, a.W = q, int(bool(dilate)), int(bool(as_bool)), B, H, W
+        _lib.check(_lib.lib().idh_edge_mask_fwd(a, _lib.stream_ptr()), "idh_edge_mask_fwd")
+    if as_bool:
+        mask = mask.view(torch.bool)
+    if squeeze:
+        mask, sobel = mask[0], None if sobel is None else sobel[0]
+    extra = tuple(t for t in (sobel, thr) if t is not None)
+    return (mask, *extra) if extra else mask

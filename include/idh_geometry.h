@@ -163,6 +163,83 @@ size_t idh_mv_consistency_workspace_bytes(int B, int K, int h, int w);
  * IDH_EWORKSPACE (with loss): workspace NULL or workspace_bytes short.  B == 0 is IDH_OK without a launch. */
 int idh_mv_consistency_fwd(const idh_mv_consistency_args *args, void *stream);
 
+/* ---- Edge mask of a depth map and the validation losses that read it (csrc/edge_mask.hip) --------------------------
+ *
+ * The reference's get_edge_mask (utils/generic_utils.py:286-292; with q = 0.975, no dilation and a bool result the dataset's variant,
+ * datasets/generic_mvs_dataset.py:650-658) without kornia and without a sort:
+ *   S    = kornia.filters.sobel(1 / depth) of kornia 0.6.7 (normalized=True, eps=1e-6), restated from its documented definition:
+ *          x = 1 / depth as an IEEE fp32 division (depth 0 gives +inf); gx, gy the 3x3 Sobel taps / 8 as a cross-correlation with
+ *          `replicate` padding, all nine products formed and added in row-major order, the zero taps included (0 * inf = NaN);
+ *          S = sqrt((gx gx + gy gy) + 1e-6).  fp32, nothing contracted.  The NaN set and the inf set of S are the composition's.
+ *   thr  = torch.nanquantile(S.flatten(1), q, dim=1), linear interpolation, per image: n = the number of non-NaN values (+inf counts
+ *          and sorts last); rank = max(q * (n - 1), 0) in fp32; the order statistics floor(rank) and ceil(rank) combined by at::lerp
+ *          with the weight rank - floor(rank): a + w (b - a) for w < 0.5, b - (b - a) (1 - w) otherwise, so that a non-finite threshold
+ *          has the class torch's has; n == 0 gives NaN.  The selection is exact (a radix select over order-preserving keys, integer
+ *          histograms): the two order statistics are the ones a sort finds.
+ *   mask = S > thr (a NaN on either side: 0); with `dilate` F.max_pool2d(mask, 5, 1, 2): 1 where any in-image pixel of the 5x5 window is 1.
+ * Three launches (S; one workgroup per image for thr; mask), no floating-point atomics, no workgroup waits on another: two calls return
+ * the same bits. */
+
+/* Host struct, read during the call.  struct_size as above. */
+typedef struct idh_edge_mask_args {
+    int64_t struct_size;
+    const float *depth_b1hw; /* (B,1,H,W) */
+    void *mask_b1hw;         /* out (B,1,H,W): float 1 / 0, or uint8 1 / 0 with mask_u8 */
+    float *sobel_b1hw;       /* out (B,1,H,W) the map S, or NULL */
+    float *threshold_b;      /* out (B) the per-image threshold, or NULL */
+    void *workspace;         /* idh_edge_mask_workspace_bytes(B, H, W) bytes, 4-byte aligned */
+    int64_t workspace_bytes; /* what the caller allocated */
+    float q;                 /* in [0, 1]: the reference's 0.95 (the dataset's 0.975) */
+    int32_t dilate;          /* 1: the 5x5 max-pool */
+    int32_t mask_u8;         /* 1: mask_b1hw is uint8 */
+    int32_t B, H, W;
+} idh_edge_mask_args;
+
+size_t idh_sizeof_edge_mask_args(void);
+
+/* Room for S and the thresholds (each rounded up to 256 bytes); 0 if an argument is <= 0. */
+size_t idh_edge_mask_workspace_bytes(int B, int H, int W);
+
+/* IDH_EINVAL: args NULL, struct_size short, depth or mask NULL, B < 0, H or W < 1, q outside [0, 1] (or NaN), workspace not 4-byte
+ * aligned; IDH_EUNSUPPORTED: H * W > 2^24 (the rank is formed in fp32) or the number of tiles of a launch >= 2^31;
+ * IDH_EWORKSPACE: workspace NULL or workspace_bytes short.  B == 0 is IDH_OK without a launch. */
+int idh_edge_mask_fwd(const idh_edge_mask_args *args, void *stream);
+
+/* The phase != "train" branch of BDModel.compute_binary_losses (experiment_modules/bd_model.py:451-495), forward value only:
+ *   target = rendered < depth;  mask = depth > 0 && rendered > 0 (depth broadcast over the D planes);
+ *   reg_mask = mask && edge_mask != 0 (edge_mask broadcast; NULL: reg_mask = mask, the reference without bd_edge_regularision);
+ *   binary_loss/0 = mean over mask of BCEWithLogits(pred, target; pos_weight):  (1 - t) x + (1 + (pos_weight - 1) t) (log1p(exp(-|x|)) + max(-x, 0));
+ *   reg_loss/0    = mean over reg_mask of 2 (0.5 - |sigmoid(pred) - 0.5|);
+ *   total         = binary_loss/0 + (bd_regularisation_weight > 0 ? reg_loss/0 * bd_regularisation_weight : 0), in fp32 on the two fp32 means.
+ * An empty mask gives total = 0 (the reference's edge case) with both means NaN; an empty reg_mask gives reg_loss/0 = NaN, the mean of
+ * nothing.  Which elements count is decided on the fp32 inputs; the terms are evaluated in fp64 from the fp32 logits and each mean is
+ * rounded to fp32 once.  One partial per chunk of 2048 elements in the workspace and a second launch that adds them in a fixed order: the
+ * result does not depend on the grid (max_workgroups) and two calls return the same bits.  No atomics.
+ * out5 (device, five doubles): count(mask), count(reg_mask), binary_loss/0, reg_loss/0, total. */
+typedef struct idh_bd_val_losses_args {
+    int64_t struct_size;
+    const float *pred_bdhw;         /* (B,D,h,w) logits: outputs["pred_0"] */
+    const float *rendered_bdhw;     /* (B,D,h,w) */
+    const float *depth_b1hw;        /* (B,1,h,w) */
+    const float *edge_mask_b1hw;    /* (B,1,h,w) float, or NULL */
+    double *out5;                   /* out, 8-byte aligned */
+    void *workspace;                /* idh_bd_val_losses_workspace_bytes(B, D, h, w) bytes, 8-byte aligned */
+    int64_t workspace_bytes;        /* what the caller allocated */
+    float bd_regularisation_weight; /* not NaN */
+    float positive_weight;          /* run_opts.binary_loss_positive_weight (1.0 in every shipped configuration); not NaN */
+    int32_t max_workgroups;         /* 0: the default grid; > 0: at most that many workgroups (the result is the same) */
+    int32_t B, D, h, w;
+} idh_bd_val_losses_args;
+
+size_t idh_sizeof_bd_val_losses_args(void);
+
+/* 32 bytes per chunk of 2048 elements of B * D * h * w; 0 if an argument is <= 0. */
+size_t idh_bd_val_losses_workspace_bytes(int B, int D, int h, int w);
+
+/* IDH_EINVAL: args NULL, struct_size short, pred / rendered / depth / out5 NULL, B, D, h or w < 1, max_workgroups < 0, a NaN weight,
+ * out5 or workspace not 8-byte aligned; IDH_EUNSUPPORTED: B * D * h * w >= 2^31; IDH_EWORKSPACE: workspace NULL or workspace_bytes short. */
+int idh_bd_val_losses_fwd(const idh_bd_val_losses_args *args, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
