@@ -312,6 +312,21 @@ class BdValLossesArgs(C.Structure):
         self.struct_size = C.sizeof(BdValLossesArgs)
 
 
+class RegValLossesArgs(C.Structure):
+    """ctypes mirror of ``idh_reg_val_losses_args`` (include/idh_geometry.h, DepthModel's validation losses)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("depth_gt_b1hw", C.c_void_p), ("depth_pred_b1hw", C.c_void_p), ("mask_b_b1hw", C.c_void_p),
+                ("log_depth_pred_s", C.c_void_p * 4), ("normals_gt_b3hw", C.c_void_p), ("normals_pred_b3hw", C.c_void_p), ("mv_loss", C.c_void_p),
+                ("out16", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("si_lambda", C.c_float),
+                ("hypersim", C.c_int32), ("num_scales", C.c_int32), ("terms", C.c_int32), ("max_workgroups", C.c_int32), ("B", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("scale_h", C.c_int32 * 4), ("scale_w", C.c_int32 * 4)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(RegValLossesArgs)
+
+
+REG_TERM_GRAD, REG_TERM_POINT, REG_TERM_NORMALS = 1, 2, 4  # IDH_REG_TERM_*
 MV_MAX_SOURCES, MV_MAX_MAPS = 16, 128  # IDH_MV_MAX_*
 TSDF_MAX_MAPS, TSDF_MAX_CAMERAS, TSDF_MAX_STEPS = 16, 128, 65536  # IDH_TSDF_MAX_*
 TSDF_HIT, TSDF_NONE_KNOWN, TSDF_SOME_KNOWN, TSDF_NO_NORMAL = 1, 2, 4, 8  # IDH_TSDF_* flag bits
@@ -462,6 +477,9 @@ _SIGS = {
     "idh_sizeof_bd_val_losses_args": (C.c_size_t, []),
     "idh_bd_val_losses_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "idh_bd_val_losses_fwd": (C.c_int, [C.POINTER(BdValLossesArgs), C.c_void_p]),
+    "idh_sizeof_reg_val_losses_args": (C.c_size_t, []),
+    "idh_reg_val_losses_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "idh_reg_val_losses_fwd": (C.c_int, [C.POINTER(RegValLossesArgs), C.c_void_p]),
     "idh_sizeof_composite_args": (C.c_size_t, []),
     "idh_prep_rendered_depth_fwd": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "idh_composite_fwd": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
@@ -565,7 +583,8 @@ def lib():
                                   ("idh_tsdf_shift_args", h.idh_sizeof_tsdf_shift_args(), TsdfShiftArgs),
                                   ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs),
                                   ("idh_edge_mask_args", h.idh_sizeof_edge_mask_args(), EdgeMaskArgs),
-                                  ("idh_bd_val_losses_args", h.idh_sizeof_bd_val_losses_args(), BdValLossesArgs)):
+                                  ("idh_bd_val_losses_args", h.idh_sizeof_bd_val_losses_args(), BdValLossesArgs),
+                                  ("idh_reg_val_losses_args", h.idh_sizeof_reg_val_losses_args(), RegValLossesArgs)):
             if got != C.sizeof(mirror):
                 raise IdhError(f"{LIB_PATH}: sizeof({what}) = {got} in the library, {C.sizeof(mirror)} in this binding")
         sizes = (C.c_size_t * 3)()

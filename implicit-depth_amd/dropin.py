@@ -103,14 +103,33 @@ def convert_normal_generator(ref: nn.Module) -> nn.Module:
     return NormalGenerator(ref.height, ref.width, ref.kernel_size, ref.std).to(_device(ref))
 
 
-def convert(model: nn.Module, math: str = None, native_matching_stem: bool = False, native_normals: bool = False) -> nn.Module:
+def _convert_losses(model: nn.Module) -> None:
+    """``grad_loss``, ``normals_loss`` and ``mv_depth_loss`` of a DepthModel (depth_model.py:177-182) -> the modules of ``losses``."""
+    from . import losses
+
+    if all(hasattr(model, n) for n in ("grad_loss", "normals_loss", "mv_depth_loss")):
+        if not isinstance(model.grad_loss, losses.MSGradientLoss):
+            model.grad_loss = losses.MSGradientLoss(getattr(model.grad_loss, "num_scales", 4))
+        if not isinstance(model.normals_loss, losses.NormalsLoss):
+            model.normals_loss = losses.NormalsLoss()
+        if not isinstance(model.mv_depth_loss, losses.MVDepthLoss):
+            model.mv_depth_loss = losses.MVDepthLoss(model.mv_depth_loss.height, model.mv_depth_loss.width).to(_device(model.mv_depth_loss))
+
+
+def convert(model: nn.Module, math: str = None, native_matching_stem: bool = False, native_normals: bool = False,
+            native_losses: bool = False) -> nn.Module:
     """In-place: replace ``cost_volume``, ``cost_volume_net``, ``depth_decoder`` and (BDModel)
     ``binary_mlp`` of a reference model.  Idempotent.  ``math``: None keeps the default (fp32 MFMA); "f16x3" selects the split-precision
     kernels for this model's convs (and, for "f16x3", its MLP feature volume and BinaryMLP).  ``native_matching_stem``: additionally check
     that the matching encoder's ResNet18 stem can run on the native kernels (``IdhError`` if not); its modules and state dict are left
     as they are.  ``native_normals``: additionally replace ``compute_normals`` (DepthModel's ``NormalGenerator``, depth_model.py:191) by
     ``geometry.NormalGenerator`` of the same height, width, kernel size and std, so that the reference's own ``step`` produces
-    ``normals_pred_b3hw`` / ``normals_b3hw`` on the fused kernel, without kornia; a model without that attribute is left as it is."""
+    ``normals_pred_b3hw`` / ``normals_b3hw`` on the fused kernel, without kornia; a model without that attribute is left as it is.
+    ``native_losses``: additionally replace ``grad_loss``, ``normals_loss`` and ``mv_depth_loss`` (DepthModel, depth_model.py:177-182)
+    by ``losses.MSGradientLoss`` / ``NormalsLoss`` / ``MVDepthLoss``, forward value only, so that the reference's own ``compute_losses``
+    runs without kornia under ``torch.no_grad()``; a model without the three attributes is left as it is."""
+    if native_losses:
+        _convert_losses(model)
     if native_matching_stem:
         _check_native_stem(model)
     if native_normals and hasattr(model, "compute_normals"):

@@ -282,3 +282,121 @@ def bd_val_losses(outputs, cur_data, bd_regularisation_weight, edge_regularision
     if return_counts:
         losses["counts"] = out[:2].long()
     return losses
+
+
+REG_LOSS_KEYS = ("loss", "si_loss", "grad_loss", "abs_loss", "normals_loss", "ms_loss", "inv_abs_loss", "log_l1_loss", "mv_loss")  # out16[:9]
+REG_COUNT_KEYS = ("grad_s0", "grad_s1", "grad_s2", "grad_s3", "mask_b", "mask_b_limit", "normals")  # out16[9:]
+
+
+def _forward_only(what, named):
+    if torch.is_grad_enabled():
+        for name, t in named:
+            if t is not None and t.requires_grad:
+                raise _lib.IdhError(f"{what} is forward only (no backward pass): detach {name} or call it under torch.no_grad()")
+
+
+def _map(name, t, B, C, h, w):
+    if t.dim() != 4 or tuple(t.shape) != (B, C, h, w):
+        raise _lib.IdhError(f"{name} {tuple(t.shape)} must be ({B},{C},{h},{w})")
+    return t.contiguous()
+
+
+def reg_losses_call(depth_gt=None, depth_pred=None, mask_b=None, log_preds=(), normals_gt=None, normals_pred=None, mv_loss=None, *, terms=0,
+                    hypersim=False, si_lambda=0.85, num_scales=4, max_workgroups=0):
+    """One idh_reg_val_losses_fwd: the float64 (16,) device tensor of include/idh_geometry.h's ``out16``.  The shape checks of
+    ``reg_val_losses``, ``losses.MSGradientLoss`` and ``losses.NormalsLoss``; ``log_preds``: up to four tensors or None, by scale."""
+    first = depth_gt if depth_gt is not None else normals_gt
+    _lib.require_cuda_f32(depth_gt, depth_pred, normals_gt, normals_pred, mv_loss, *log_preds)
+    if first.dim() != 4:
+        raise _lib.IdhError(f"{'depth_b1hw' if depth_gt is not None else 'normals_b3hw'} {tuple(first.shape)} must have four dimensions")
+    B, _, h, w = first.shape
+    keep = []
+    a = _lib.RegValLossesArgs()
+    if depth_gt is not None:
+        keep += [_map("depth_b1hw", depth_gt, B, 1, h, w), _map("depth_pred_s0_b1hw", depth_pred, B, 1, h, w)]
+        a.depth_gt_b1hw, a.depth_pred_b1hw = keep[-2].data_ptr(), keep[-1].data_ptr()
+    if mask_b is not None:
+        if not mask_b.is_cuda or mask_b.dtype != torch.bool:
+            raise _lib.IdhError(f"mask_b_b1hw must be a bool tensor on the MI355X, got {mask_b.dtype} on {mask_b.device}")
+        keep.append(_map("mask_b_b1hw", mask_b, B, 1, h, w))
+        a.mask_b_b1hw = keep[-1].data_ptr()
+    for i, t in enumerate(log_preds):
+        if t is None:
+            continue
+        name = f"log_depth_pred_s{i}_b1hw"
+        if t.dim() != 4 or tuple(t.shape[:2]) != (B, 1) or min(t.shape[2:]) < 1 or h % t.shape[2] or w % t.shape[3]:
+            raise _lib.IdhError(f"{name} {tuple(t.shape)} must be ({B},1,h_i,w_i) with h_i dividing {h} and w_i dividing {w} (an integer "
+                                "ratio: nearest-neighbour resizing by another ratio is not covered)")
+        keep.append(t.contiguous())
+        a.log_depth_pred_s[i], a.scale_h[i], a.scale_w[i] = keep[-1].data_ptr(), t.shape[2], t.shape[3]
+    if normals_gt is not None:
+        keep += [_map("normals_b3hw", normals_gt, B, 3, h, w), _map("normals_pred_b3hw", normals_pred, B, 3, h, w)]
+        a.normals_gt_b3hw, a.normals_pred_b3hw = keep[-2].data_ptr(), keep[-1].data_ptr()
+    if mv_loss is not None:
+        if mv_loss.numel() != 1:
+            raise _lib.IdhError(f"mv_loss {tuple(mv_loss.shape)} must hold one value")
+        keep.append(mv_loss.contiguous())
+        a.mv_loss = keep[-1].data_ptr()
+    dev = first.device
+    out = torch.empty(16, device=dev, dtype=torch.float64)
+    if min(B, h, w) < 1:
+        raise _lib.IdhError(f"the maps {tuple(first.shape)} are empty")
+    nbytes = _lib.lib().idh_reg_val_losses_workspace_bytes(B, h, w)
+    workspace = torch.empty(max(nbytes, 8) // 8, device=dev, dtype=torch.float64)
+    a.out16, a.workspace, a.workspace_bytes = out.data_ptr(), workspace.data_ptr(), nbytes
+    a.si_lambda, a.hypersim, a.num_scales, a.terms, a.max_workgroups = float(si_lambda), int(bool(hypersim)), int(num_scales), int(terms), int(max_workgroups)
+    a.B, a.h, a.w = B, h, w
+    _lib.check(_lib.lib().idh_reg_val_losses_fwd(a, _lib.stream_ptr()), "idh_reg_val_losses_fwd")
+    return out
+
+
+def reg_val_losses(outputs, cur_data, src_data=None, *, hypersim=False, si_lambda=0.85, compute_normals=False, return_counts=False,
+                   max_workgroups=0) -> Dict[str, torch.Tensor]:
+    """The validation losses of a ``DepthModel``: ``compute_losses(cur_data, src_data, outputs)`` of the reference
+    (experiment_modules/depth_model.py:442-540), forward value only, in at most five launches - one per level of the gradient pyramid,
+    the first of which also evaluates every point-wise term and the normals, and a finalise (idh_reg_val_losses_fwd; contract:
+    include/idh_geometry.h) - plus ``geometry.depth_consistency(return_loss=True)`` for the multi-view term, whose
+    device scalar the finalise reads in stream order.  No kornia, nothing is synchronised.
+
+    Reads ``outputs["depth_pred_s0_b1hw"]``, the ``outputs["log_depth_pred_s{i}_b1hw"]`` that are present (scale 0 must be; sizes that
+    divide the depth map's), ``outputs["normals_pred_b3hw"]``; ``cur_data["depth_b1hw"]``, ``["mask_b_b1hw"]`` (bool), ``["normals_b3hw"]``,
+    ``["invK_s0_b44"]``, ``["world_T_cam_b44"]``; ``src_data["depth_b1hw"]`` (B,K,1,h,w), ``["K_s0_b44"]``, ``["cam_T_world_b44"]``.
+    ``hypersim`` is ``run_opts.dataset == "hypersim"``: ``grad_loss``, ``normals_loss`` and ``mv_loss`` are 0 and neither normals nor
+    ``src_data`` are read.  ``compute_normals`` fills a missing ``normals_b3hw`` / ``normals_pred_b3hw`` with ``geometry.depth_normals`` of
+    the depth (what ``DepthModel.step`` does, :565-570); neither dictionary is modified.  Returns the reference's nine entries as 0-d fp32
+    device tensors; ``return_counts`` adds ``"counts"``: a dict of 0-d int64 tensors, the number of elements behind every mean
+    (``REG_COUNT_KEYS``).  A mean over nothing is NaN, as in the reference.  Deterministic, and the same for every ``max_workgroups``
+    (0: the default grid).  There is no CPU fallback and no backward pass."""
+    present = [outputs.get(f"log_depth_pred_s{i}_b1hw") for i in range(4)]
+    if all(t is None for t in present):
+        raise _lib.IdhError("Could not find a valid scale to compute si loss!")  # (depth_model.py:496)
+    for key in ("depth_pred_s0_b1hw", "log_depth_pred_s0_b1hw"):
+        if outputs.get(key) is None:
+            raise _lib.IdhError(f"reg_val_losses needs outputs['{key}']")
+    depth_gt, depth_pred, mask_b = cur_data["depth_b1hw"], outputs["depth_pred_s0_b1hw"], cur_data["mask_b_b1hw"]
+    _forward_only("reg_val_losses", [("depth_pred_s0_b1hw", depth_pred)] + [(f"log_depth_pred_s{i}_b1hw", t) for i, t in enumerate(present)] +
+                  [("normals_pred_b3hw", outputs.get("normals_pred_b3hw"))])
+    normals_gt = normals_pred = mv = None
+    if not hypersim:
+        if src_data is None:
+            raise _lib.IdhError("reg_val_losses needs src_data (depth_b1hw, K_s0_b44, cam_T_world_b44) for mv_loss; only hypersim=True does without")
+        from . import geometry
+
+        normals_gt, normals_pred = cur_data.get("normals_b3hw"), outputs.get("normals_pred_b3hw")
+        for name, t, depth in (("cur_data['normals_b3hw']", normals_gt, depth_gt), ("outputs['normals_pred_b3hw']", normals_pred, depth_pred)):
+            if t is None and not compute_normals:
+                raise _lib.IdhError(f"reg_val_losses needs {name}; compute_normals=True fills it with geometry.depth_normals")
+        if normals_gt is None:
+            normals_gt = geometry.depth_normals(depth_gt, cur_data["invK_s0_b44"])[0]
+        if normals_pred is None:
+            normals_pred = geometry.depth_normals(depth_pred, cur_data["invK_s0_b44"])[0]
+        mv = geometry.depth_consistency(depth_pred, cur_data["invK_s0_b44"], cur_data["world_T_cam_b44"], src_data["depth_b1hw"],
+                                        src_data["K_s0_b44"], src_data["cam_T_world_b44"], gate_depth=depth_gt, return_loss=True)["loss"]
+    out = reg_losses_call(depth_gt, depth_pred, mask_b, present, normals_gt, normals_pred, mv, hypersim=hypersim, si_lambda=si_lambda,
+                          max_workgroups=max_workgroups)
+    f = out[:9].float()
+    losses = {k: f[i] for i, k in enumerate(REG_LOSS_KEYS)}
+    if return_counts:
+        c = out[9:].long()
+        losses["counts"] = {k: c[i] for i, k in enumerate(REG_COUNT_KEYS)}
+    return losses

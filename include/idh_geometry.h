@@ -240,6 +240,82 @@ size_t idh_bd_val_losses_workspace_bytes(int B, int D, int h, int w);
  * out5 or workspace not 8-byte aligned; IDH_EUNSUPPORTED: B * D * h * w >= 2^31; IDH_EWORKSPACE: workspace NULL or workspace_bytes short. */
 int idh_bd_val_losses_fwd(const idh_bd_val_losses_args *args, void *stream);
 
+/* ---- DepthModel's validation losses (csrc/reg_losses.hip) -----------------------------------------------------------
+ *
+ * DepthModel.compute_losses (experiment_modules/depth_model.py:442-540), forward value only: MSGradientLoss (losses.py:77-101 with
+ * pyrdown, utils/generic_utils.py:85-91), NormalsLoss (losses.py:119-140), the masked point-wise terms (:480-508) and the cocktail
+ * (:527).  The multi-view term (:517-525) is idh_mv_consistency_fwd's `loss`; its device scalar is read here through `mv_loss`.
+ *
+ * kornia's two functions are restated from the documented definition of kornia 0.6.7; kornia is not installed where this project is
+ * built and tested, so this part of the contract is not machine-checked against the library (as for §4.18 and §4.27):
+ *   blur_pool2d(x, 3)    the kernel outer([1,2,1],[1,2,1]) / 16 as a cross-correlation with zero padding 1 and stride 2: an output of
+ *                        ceil(H/2) x ceil(W/2); out[Y][X] = sum_ij k[i][j] x[2Y-1+i][2X-1+j] over the taps inside the image, row-major.
+ *                        All nine weights are non-zero: a NaN or inf input makes every output that touches it non-finite.
+ *   spatial_gradient(x)  (sobel, order 1, normalised) the pair [[-1,0,1],[-2,0,2],[-1,0,1]] / 8 and its transpose as a cross-correlation
+ *                        with `replicate` padding of 1; all nine taps are multiplied and summed in row-major order, the zero taps
+ *                        included (0 * NaN = 0 * inf = NaN): which gradients are finite is part of the contract.
+ * Terms (every mean is sum / count, so the mean of nothing is 0 / 0 = NaN, as nn.L1Loss and torch.mean give on empty input):
+ *   grad_loss    = sum over levels l < num_scales of mean |g_pred - g_gt|, level 0 the two depth maps, level l + 1 = blur_pool2d of level
+ *                  l; the mean of a level runs over the gx and the gy entries, separately, at which that component of g_gt is finite
+ *                  (C = 1: isfinite().all(dim=1) is per component).  A non-finite g_pred there makes the loss non-finite.   losses.py:83-101
+ *   ms_loss      = sum over the present scales i of mean |log gt - nearest(log_pred_s[i])| / 2^i over mask_b; scale i has size
+ *                  (scale_h[i], scale_w[i]) dividing (h, w), and the nearest tap of pixel (y, x) is (y / (h / scale_h), x / (w / scale_w)),
+ *                  which is F.interpolate(mode="nearest") for integer ratios.  Scale 0 is required (the reference reads it at :477).  :480-492
+ *   abs_loss     = mean |gt - pred| over mask_b;   log_l1_loss = mean |d| with d = log gt - log_pred_s[0] over mask_b         :502, :508
+ *   si_loss      = sqrt(mean(d^2) - si_lambda * mean(d)^2) over mask_b                                              losses.py:111-116
+ *   inv_abs_loss = mean |1 / gt - 1 / pred| over mask_b && pred > 0.1f                                                        :505-506
+ *   normals_loss = mean 0.5 (1 - n_gt . n_pred) over the pixels whose six components are all finite                  losses.py:119-140
+ *   loss         = ((ms_loss + grad_loss) + normals_loss) + 0.2f * mv_loss in fp32 on the fp32 values, as :527 forms it.
+ * With `hypersim` grad_loss, normals_loss and mv_loss are the reference's literal 0 (:498-515): their inputs may be NULL and the launches
+ * of pyramid levels 1 .. 3 are skipped.
+ * Which elements count is decided as above; every value is then evaluated in fp64 from the fp32 inputs - the pyramid levels are kept as
+ * doubles in the workspace - and rounded to fp32 once, so the finite / non-finite pattern is the fp32 composition's as long as that does
+ * not overflow.  One launch per pyramid level: a workgroup owns 32 x 32 tiles of a level of one image, stages them with a one-pixel halo
+ * in LDS (a lane's four pixels are one 16-byte load per map where the rows are 16-byte aligned: w a multiple of 4 and aligned bases;
+ * anything else takes scalar loads), and writes one record of fp64 partial sums per tile - not per workgroup - plus its 16 x 16 tile of the next level; level 0's
+ * launch also evaluates the point-wise terms and the normals.  A last launch of one workgroup adds the records in tile order.  At most five
+ * launches, no floating-point atomics: the result is the same for every grid (max_workgroups) and two calls return the same bits.
+ * out16 (device, sixteen doubles): loss, si_loss, grad_loss, abs_loss, normals_loss, ms_loss, inv_abs_loss, log_l1_loss, mv_loss - each
+ * an fp32 value - then the element counts behind the means: gradient levels 0 .. 3, mask_b, mask_b && pred > 0.1, the normals mask.
+ * A term that `terms` leaves out is NaN with a count of 0 (under `hypersim` the three terms above are 0). */
+#define IDH_REG_TERM_GRAD 1    /* the gradient pyramid */
+#define IDH_REG_TERM_POINT 2   /* ms, abs, log_l1, si, inv_abs */
+#define IDH_REG_TERM_NORMALS 4 /* normals_loss */
+#define IDH_REG_TERM_ALL 7
+
+typedef struct idh_reg_val_losses_args {
+    int64_t struct_size;
+    const float *depth_gt_b1hw;        /* (B,1,h,w) cur_data["depth_b1hw"]; with GRAD or POINT */
+    const float *depth_pred_b1hw;      /* (B,1,h,w) outputs["depth_pred_s0_b1hw"]; with GRAD or POINT */
+    const uint8_t *mask_b_b1hw;        /* (B,1,h,w) bool bytes, cur_data["mask_b_b1hw"]; with POINT */
+    const float *log_depth_pred_s[4];  /* (B,1,scale_h[i],scale_w[i]) outputs["log_depth_pred_s{i}_b1hw"], NULL: absent; [0] required with POINT */
+    const float *normals_gt_b3hw;      /* (B,3,h,w); with NORMALS unless hypersim */
+    const float *normals_pred_b3hw;    /* (B,3,h,w); with NORMALS unless hypersim */
+    const float *mv_loss;              /* one float on the device, read by the last launch in stream order; NULL: 0 */
+    double *out16;                     /* out, 8-byte aligned */
+    void *workspace;                   /* idh_reg_val_losses_workspace_bytes(B, h, w) bytes, 8-byte aligned */
+    int64_t workspace_bytes;           /* what the caller allocated */
+    float si_lambda;                   /* not NaN: the reference's 0.85 */
+    int32_t hypersim;                  /* != 0: run_opts.dataset == "hypersim" */
+    int32_t num_scales;                /* pyramid levels of grad_loss, 1 .. 4; 0: 4 */
+    int32_t terms;                     /* a combination of IDH_REG_TERM_*; 0: all */
+    int32_t max_workgroups;            /* 0: the default grid; > 0: at most that many workgroups per launch (the result is the same) */
+    int32_t B, h, w;
+    int32_t scale_h[4], scale_w[4];    /* read for the present scales: each must divide h, w */
+} idh_reg_val_losses_args;
+
+size_t idh_sizeof_reg_val_losses_args(void);
+
+/* Levels 1 .. 3 of both pyramids as doubles (each map rounded up to 256 bytes) and the tile records: 128 bytes per 32 x 32 tile of level 0,
+ * 16 bytes per tile of levels 1 .. 3.  0 if an argument is <= 0. */
+size_t idh_reg_val_losses_workspace_bytes(int B, int h, int w);
+
+/* IDH_EINVAL: args NULL, struct_size short, out16 NULL, B < 0, h or w < 1, max_workgroups < 0, num_scales outside 0 .. 4, unknown bits in
+ * terms, a NaN si_lambda, a pointer NULL that the terms need (above), no scale present / scale 0 absent with POINT, a present scale whose size
+ * is < 1 or does not divide (h, w), out16 or workspace not 8-byte aligned; IDH_EUNSUPPORTED: B * h * w >= 2^31;
+ * IDH_EWORKSPACE: workspace NULL or workspace_bytes short.  B == 0 is IDH_OK without a launch. */
+int idh_reg_val_losses_fwd(const idh_reg_val_losses_args *args, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
