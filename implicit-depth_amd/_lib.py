@@ -271,6 +271,21 @@ class TsdfShiftArgs(C.Structure):
         self.struct_size = C.sizeof(TsdfShiftArgs)
 
 
+class TsdfAlignArgs(C.Structure):
+    """ctypes mirror of ``idh_tsdf_align_args`` (include/idh_fusion.h, pose alignment against the volume)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("volume", TsdfVolume), ("depth_11hw", C.c_void_p), ("invK_44", C.c_void_p),
+                ("weight_11hw", C.c_void_p), ("world_T_cam_in_44", C.c_void_p), ("world_T_cam_out_44", C.c_void_p), ("records_i40", C.c_void_p),
+                ("rows_hw8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("damping", C.c_double),
+                ("min_step", C.c_double), ("min_pivot_ratio", C.c_double), ("huber", C.c_float), ("h", C.c_int32), ("w", C.c_int32),
+                ("iters", C.c_int32), ("stride", C.c_int32), ("min_count", C.c_int32), ("max_workgroups", C.c_int32)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TsdfAlignArgs)
+        self.volume.struct_size = C.sizeof(TsdfVolume)
+
+
 class MvConsistencyArgs(C.Structure):
     """ctypes mirror of ``idh_mv_consistency_args`` (include/idh_geometry.h, multi-view depth consistency)."""
 
@@ -468,6 +483,9 @@ _SIGS = {
     "idh_tsdf_integrate_weighted_fwd": (C.c_int, [C.POINTER(TsdfIntegrateWeightedArgs), C.c_void_p]),
     "idh_sizeof_tsdf_shift_args": (C.c_size_t, []),
     "idh_tsdf_shift_fwd": (C.c_int, [C.POINTER(TsdfShiftArgs), C.c_void_p]),
+    "idh_sizeof_tsdf_align_args": (C.c_size_t, []),
+    "idh_tsdf_align_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "idh_tsdf_align_fwd": (C.c_int, [C.POINTER(TsdfAlignArgs), C.c_void_p]),
     "idh_sizeof_mv_consistency_args": (C.c_size_t, []),
     "idh_mv_consistency_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "idh_mv_consistency_fwd": (C.c_int, [C.POINTER(MvConsistencyArgs), C.c_void_p]),
@@ -581,6 +599,7 @@ def lib():
                                   ("idh_tsdf_mesh_colors_args", h.idh_sizeof_tsdf_mesh_colors_args(), TsdfMeshColorsArgs),
                                   ("idh_tsdf_integrate_weighted_args", h.idh_sizeof_tsdf_integrate_weighted_args(), TsdfIntegrateWeightedArgs),
                                   ("idh_tsdf_shift_args", h.idh_sizeof_tsdf_shift_args(), TsdfShiftArgs),
+                                  ("idh_tsdf_align_args", h.idh_sizeof_tsdf_align_args(), TsdfAlignArgs),
                                   ("idh_mv_consistency_args", h.idh_sizeof_mv_consistency_args(), MvConsistencyArgs),
                                   ("idh_edge_mask_args", h.idh_sizeof_edge_mask_args(), EdgeMaskArgs),
                                   ("idh_bd_val_losses_args", h.idh_sizeof_bd_val_losses_args(), BdValLossesArgs),

@@ -28,10 +28,6 @@
 
 namespace {
 
-typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));  // two neighbouring {T, W} pairs: 8-byte aligned, one 16-byte load
-
-__device__ __forceinline__ bool valid_depth(float d) { return d > 0.f && d < INFINITY; }  // false for NaN
-
 __global__ __launch_bounds__(256) void tsdf_reset_k(float2 *__restrict__ values, long long n, uint8_t *__restrict__ flags, long long nb) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;
     if (i < n) values[i] = make_float2(1.f, 0.f);
@@ -219,36 +215,6 @@ struct RaycastColorArgs : RaycastArgs {  // as IntegrateColorArgs: the plain arg
 
 __device__ __forceinline__ unsigned channel_byte(float c) { return (unsigned)(int)(fminf(fmaxf(c, 0.f), 255.f) + 0.5f); }
 
-// the eight corners of the cell at floor(g): false when the cell is outside the volume or a corner has W == 0
-struct Corners {
-    f4a8 a, b, c, d;  // rows (y, z) = (0,0), (1,0), (0,1), (1,1); each {T_x0, W_x0, T_x1, W_x1}
-    float rx, ry, rz;
-};
-
-__device__ __forceinline__ bool cell_of(const Vol &V, float gx, float gy, float gz, float &fx, float &fy, float &fz) {
-    fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-    return fx >= 0.f && fx <= (float)(V.Nx - 2) && fy >= 0.f && fy <= (float)(V.Ny - 2) && fz >= 0.f && fz <= (float)(V.Nz - 2);  // false for NaN
-}
-
-__device__ __forceinline__ bool load_corners(const Vol &V, float gx, float gy, float gz, float fx, float fy, float fz, Corners &c) {
-    const int x = (int)fx, y = (int)fy, z = (int)fz;
-    const size_t row = (size_t)V.Nx * 2, slice = row * V.Ny;
-    const float *p = V.values + ((size_t)z * V.Ny + y) * row + (size_t)x * 2;
-    c.a = *reinterpret_cast<const f4a8 *>(p);
-    c.b = *reinterpret_cast<const f4a8 *>(p + row);
-    c.c = *reinterpret_cast<const f4a8 *>(p + slice);
-    c.d = *reinterpret_cast<const f4a8 *>(p + slice + row);
-    c.rx = gx - fx, c.ry = gy - fy, c.rz = gz - fz;
-    return c.a.y > 0.f && c.a.w > 0.f && c.b.y > 0.f && c.b.w > 0.f && c.c.y > 0.f && c.c.w > 0.f && c.d.y > 0.f && c.d.w > 0.f;
-}
-
-__device__ __forceinline__ float lerp(float a, float b, float r) { return a + r * (b - a); }
-
-__device__ __forceinline__ float trilinear(const Corners &c) {
-    const float a00 = lerp(c.a.x, c.a.z, c.rx), a10 = lerp(c.b.x, c.b.z, c.rx), a01 = lerp(c.c.x, c.c.z, c.rx), a11 = lerp(c.d.x, c.d.z, c.rx);
-    return lerp(lerp(a00, a10, c.ry), lerp(a01, a11, c.ry), c.rz);
-}
-
 template <bool SKIP, bool NORMALS, class Args>
 __global__ __launch_bounds__(256) void tsdf_raycast_k(const Args a) {
     constexpr bool COLOR = Args::kColor;
@@ -354,10 +320,8 @@ __global__ __launch_bounds__(256) void tsdf_raycast_k(const Args a) {
             bool ok = cell_of(V, gx, gy, gz, fx, fy, fz);
             if (ok) ok = load_corners(V, gx, gy, gz, fx, fy, fz, c);
             if (ok) {
-                // rows: a = (y0,z0), b = (y1,z0), c = (y0,z1), d = (y1,z1); .x / .z are T at x0 / x1
-                const float Gx = lerp(lerp(c.a.z - c.a.x, c.b.z - c.b.x, c.ry), lerp(c.c.z - c.c.x, c.d.z - c.d.x, c.ry), c.rz);
-                const float Gy = lerp(lerp(c.b.x - c.a.x, c.b.z - c.a.z, c.rx), lerp(c.d.x - c.c.x, c.d.z - c.c.z, c.rx), c.rz);
-                const float Gz = lerp(lerp(c.c.x - c.a.x, c.c.z - c.a.z, c.rx), lerp(c.d.x - c.b.x, c.d.z - c.b.z, c.rx), c.ry);
+                float Gx, Gy, Gz;
+                gradient(c, Gx, Gy, Gz);
                 const float len = sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz);
                 ok = len > 0.f;
                 if (ok) {

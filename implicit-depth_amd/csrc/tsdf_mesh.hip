@@ -33,7 +33,6 @@ namespace {
 #define IDH_MC_TABLE_ATTR __device__ const
 #include "mc_table.h"
 
-typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));  // two neighbouring {T, W} pairs: 8-byte aligned, one 16-byte load
 typedef unsigned long long u64;  // a pair of counts: vertices in the low 32 bits, triangles in the high 32 (neither sum reaches 2^31)
 
 constexpr int kThreads = 256, kItems = 4, kChunk = kThreads * kItems;

@@ -13,7 +13,10 @@ live camera and ``extract_mesh(return_colors=True)`` the colour of every vertex.
 
 A volume that follows the camera: ``TSDFVolume.shift`` moves the grid under its contents by whole voxels in one
 launch, ``crop`` and ``leaving_boxes`` keep what such a move drops, and ``follow_shift`` is the rule ``StreamingSession.start_fusion(
-follow=)`` moves by."""
+follow=)`` moves by.
+
+Pose alignment: ``align_depth`` fits the camera of one depth map to what the volume already holds - Gauss-Newton on
+the signed distance field itself, two launches per iteration and no host synchronisation - and ``alignment_summary`` reads its records."""
 from __future__ import annotations
 
 import ctypes as C
@@ -116,6 +119,10 @@ class TSDFVolume:
     def extract_mesh(self, min_weight: float = 0.0, return_weights: bool = False, use_block_flags: bool = MESH_USE_BLOCK_FLAGS,
                      return_colors: bool = False) -> Dict[str, torch.Tensor]:
         return extract_mesh(self, min_weight, return_weights, use_block_flags, return_colors)
+
+    def align(self, depth_11hw: torch.Tensor, invK, world_T_cam, **kw) -> Dict[str, torch.Tensor]:
+        """``align_depth`` of this volume."""
+        return align_depth(self, depth_11hw, invK, world_T_cam, **kw)
 
     def _origin_after(self, voxels_xyz) -> tuple:
         """``origin + voxel_size * voxels`` per axis in float32 (one multiply, one add): the arithmetic idh_tsdf_shift_fwd checks bit for bit."""
@@ -396,3 +403,91 @@ def extract_mesh(volume: TSDFVolume, min_weight: float = 0.0, return_weights: bo
         if V:
             mesh_colors(volume, workspace, out["colors"], min_weight)
     return out
+
+
+ALIGN_RECORD = 40  # doubles per iteration: A (21, row-major upper triangle), b (6), cost, count, status, |v|, |w|, xi (6), two zeros
+ALIGN_OK, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_STOPPED = 0, 1, 2, 3  # a record's status
+
+
+def align_depth(volume: TSDFVolume, depth_11hw: torch.Tensor, invK, world_T_cam, *, iters: int = 8, stride: int = 1, huber: float = 0.0,
+                damping: float = 0.0, min_step: float = 0.0, min_count: int = 64, weight_11hw: Optional[torch.Tensor] = None,
+                return_rows: bool = False, schedule: Optional[Sequence[Sequence[int]]] = None, min_pivot_ratio: float = 1e-6,
+                max_workgroups: int = 0) -> Dict[str, torch.Tensor]:
+    """Fit the camera of one depth map (1,1,h,w) to the surface ``volume`` holds (idh_tsdf_align_fwd; include/idh_fusion.h states the
+    arithmetic): Gauss-Newton on the sum of ``f(T p)^2`` over the map's back-projected points, starting from ``world_T_cam`` ((4,4) or
+    (1,4,4)), with ``invK`` the inverse intrinsics at h x w.  The increment translates the camera and rotates it about its own centre.
+    It converges from about a truncation distance (``trunc_voxels * voxel_size``) away, not further.
+
+    ``iters`` (1..64) iterations of two launches each over the pixels with ``i % stride == 0 and j % stride == 0``; ``huber`` (metres,
+    <= 0: none) down-weights residuals beyond it; ``damping`` adds that share of the diagonal to the normal matrix; once a step is shorter
+    than ``min_step`` (metres and radians) the remaining iterations do nothing; fewer than ``min_count`` usable pixels, or a normal
+    matrix with a pivot below ``min_pivot_ratio`` of its diagonal entry (a plane, say), end the fit with the pose as it is.
+    ``weight_11hw``: a weight per depth sample, e.g. the "weight" of ``geometry.depth_consistency``; one that is not finite and positive
+    makes the pixel a hole.  ``schedule=((stride, iters), ...)`` chains calls coarse to fine on the device instead of ``stride`` / ``iters``.
+
+    Returns ``"world_T_cam"`` (1,4,4) float32 and ``"records"`` (iterations, 40) float64 on the device (``ALIGN_RECORD``; status 0 a step
+    taken, 1 too few pixels, 2 degenerate, 3 an iteration skipped after the fit had ended) and with ``return_rows`` ``"rows"`` (h,w,8):
+    ``(J[6], r, weight)`` per pixel at the input pose - ``r`` the signed distance of the pixel's point in metres, all zero where the pixel
+    was not used.  Nothing is read back and nothing synchronises: ``alignment_summary`` does."""
+    if schedule is None:
+        schedule = ((stride, iters),)
+    schedule = tuple((int(s), int(n)) for s, n in schedule)
+    if not schedule or any(s < 1 or not 1 <= n <= 64 for s, n in schedule):
+        raise _lib.IdhError(f"align_depth: schedule {schedule} must be (stride >= 1, iters in 1..64) pairs")
+    for name, t in (("depth", depth_11hw), ("weight", weight_11hw), ("invK", invK), ("world_T_cam", world_T_cam)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise _lib.IdhError(f"align_depth: {name} requires grad; the alignment is not differentiable")
+    if depth_11hw.dim() != 4 or depth_11hw.shape[0] != 1 or depth_11hw.shape[1] != 1:
+        raise _lib.IdhError(f"align_depth: depth {tuple(depth_11hw.shape)} must be (1,1,h,w)")
+    if weight_11hw is not None and weight_11hw.shape != depth_11hw.shape:
+        raise _lib.IdhError(f"align_depth: weight {tuple(weight_11hw.shape)} must be {tuple(depth_11hw.shape)}")
+    _lib.require_cuda_f32(depth_11hw, weight_11hw)
+    dev = volume.values.device
+    h, w = int(depth_11hw.shape[2]), int(depth_11hw.shape[3])
+    iK, T = _mats("invK", invK, dev), _mats("world_T_cam", world_T_cam, dev)
+    if iK.shape[0] != 1 or T.shape[0] != 1:
+        raise _lib.IdhError(f"align_depth: one map needs one invK and one pose, got {tuple(iK.shape)} and {tuple(T.shape)}")
+    d = depth_11hw.contiguous()
+    wgt = None if weight_11hw is None else weight_11hw.contiguous()
+    records = torch.empty(sum(n for _, n in schedule), ALIGN_RECORD, device=dev, dtype=torch.float64)
+    out = {"records": records}
+    if return_rows:
+        out["rows"] = torch.empty(h, w, 8, device=dev)
+    pose, done = T, 0
+    for k, (s, n) in enumerate(schedule):
+        nbytes = _lib.lib().idh_tsdf_align_workspace_bytes(h, w, s, n)
+        if nbytes == 0:
+            raise _lib.IdhError(f"align_depth: a map of {(h, w)} has 2^31 pixels or more")
+        workspace = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+        nxt = torch.empty(1, 4, 4, device=dev)
+        a = _lib.TsdfAlignArgs()
+        a.volume = volume._struct()
+        a.depth_11hw, a.invK_44, a.weight_11hw = d.data_ptr(), iK.data_ptr(), _lib.ptr(wgt)
+        a.world_T_cam_in_44, a.world_T_cam_out_44 = pose.data_ptr(), nxt.data_ptr()
+        a.records_i40 = records[done:].data_ptr()
+        a.rows_hw8 = out["rows"].data_ptr() if return_rows and k == 0 else None
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+        a.damping, a.min_step, a.min_pivot_ratio, a.huber = float(damping), float(min_step), float(min_pivot_ratio), float(huber)
+        a.h, a.w, a.iters, a.stride, a.min_count, a.max_workgroups = h, w, n, s, int(min_count), int(max_workgroups)
+        _lib.check(_lib.lib().idh_tsdf_align_fwd(C.byref(a), _lib.stream_ptr()), "idh_tsdf_align_fwd")
+        pose, done = nxt, done + n
+    out["world_T_cam"] = pose
+    return out
+
+
+def alignment_summary(records) -> Dict[str, float]:
+    """What an ``align_depth`` call came to, from its ``"records"``.  A HOST helper: a device tensor is copied to the host, which
+    SYNCHRONISES with the stream.  Returns ``"status"`` - that of the last iteration that ran (0 a step taken, 1 too few pixels,
+    2 degenerate) -, its ``"count"`` of pixels and ``"rms"`` = sqrt(cost / count) in metres, the weighted cost per counted pixel (with
+    unit weights the root mean square distance of the map's points from the surface, BEFORE that iteration's step), ``"iterations"``,
+    how many ran, ``"stopped"``, whether later ones were skipped, and ``"translation"`` / ``"rotation"``: the sums of the steps' |v|
+    (metres) and |w| (radians), an upper bound of the total correction."""
+    r = records.detach().cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records, dtype=np.float64)
+    r = r.reshape(-1, ALIGN_RECORD)
+    ran = r[r[:, 29] != ALIGN_STOPPED]
+    if len(ran) == 0:
+        raise _lib.IdhError("alignment_summary: no iteration ran")
+    last = ran[-1]
+    count = float(last[28])
+    return {"status": int(last[29]), "count": int(count), "rms": float(np.sqrt(last[27] / count)) if count > 0 else float("nan"),
+            "iterations": int(len(ran)), "stopped": bool(len(ran) < len(r)), "translation": float(ran[:, 30].sum()), "rotation": float(ran[:, 31].sum())}

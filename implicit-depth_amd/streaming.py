@@ -127,6 +127,8 @@ class StreamingSession:
         # start_fusion(follow=): how often the volume was moved after the camera since start_fusion / reset, and the last (sx, sy, sz)
         self.fusion_scrolls = 0
         self.last_scroll: Optional[Tuple[int, int, int]] = None
+        # start_fusion(track=): what the last alignment of a remembered map came to (None: none yet, or the first map of a sequence)
+        self.last_alignment: Optional[dict] = None
 
     def reset(self) -> None:
         """Start a new sequence: empty buffer, no prior.  The bank's storage is kept."""
@@ -138,6 +140,7 @@ class StreamingSession:
         self._ring_cams, self.last_depth_counts = [], None
         self._fused_maps = 0
         self.fusion_scrolls, self.last_scroll = 0, None
+        self.last_alignment = None
         if self._volume is not None:
             self._volume.reset()  # (with origin=None the next first map centres the grid again)
         if self.query_keyframes > 1:
@@ -336,7 +339,11 @@ class StreamingSession:
         are not finite and positive are holes.  The map is copied; all maps of the ring have one size.  ``reset()`` empties the ring.
         ``frame_u8`` (1,Hf,Wf,3) uint8: the camera frame that belongs to the map, fused into the colours of the volume of
         ``start_fusion(color=True)`` (it is not kept); ``frame_K`` its intrinsics ((4,4) or (1,4,4)) at Hf x Wf, None: the inverse of
-        ``invK`` with rows 0 and 1 scaled by Wf / w and Hf / h (``intrinsics_pyramid``'s rule)."""
+        ``invK`` with rows 0 and 1 scaled by Wf / w and Hf / h (``intrinsics_pyramid``'s rule).
+        After ``start_fusion(track=...)``, and once a map has been fused, the map is first aligned against the volume starting from
+        ``world_T_cam`` (``fusion.align_depth``) and, if the fit is accepted, the refined pose is the one the consistency
+        check, the ring, the volume's follow-shift and the integration use; ``last_alignment`` says what happened.  This reads 16 floats
+        and the fit's records back from the device (the session keeps poses in float64 on the host): one synchronisation per map."""
         from .raster import _pose_f64
 
         _lib.require_cuda_f32(depth_11hw, invK)
@@ -360,6 +367,8 @@ class StreamingSession:
                 frame_K = frame_K.reshape(-1, 4, 4)
                 if frame_K.shape[0] != 1:
                     raise _lib.IdhError("remember_depth: frame_K must be (4,4) or (1,4,4)")
+        if self._fusion is not None and self._fusion["track"] is not None and self._fused_maps > 0:
+            pose = self._track(depth_11hw.detach(), pose, invK.detach())  # before the check, the ring, the follow-shift and the integrate
         checked = None
         if self._fusion is not None and self._fusion["consistency"] is not None:
             checked = self._check_depth(depth_11hw.detach(), pose, invK.detach())  # against the maps already in the ring
@@ -372,6 +381,51 @@ class StreamingSession:
                 self._fuse(self._depth_ring[0][0], pose, invK, frame_u8, frame_K, weight=checked["weight"])
             else:
                 self._fuse(checked["filtered_depth"], pose, invK, frame_u8, frame_K)
+
+    def _fit_pose(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor, kw: dict) -> Tuple[np.ndarray, dict]:
+        """``fusion.align_depth`` of a map against the session's volume from ``pose``: the fitted pose in float64 on the host (the float32
+        result widened) and ``fusion.alignment_summary`` of its records.  One device-to-host read of each."""
+        from .fusion import align_depth, alignment_summary
+
+        start = torch.from_numpy(pose.astype(np.float32)).to(depth_11hw.device)
+        out = align_depth(self._volume, depth_11hw, invK_144, start, **kw)
+        return out["world_T_cam"][0].cpu().numpy().astype(np.float64), alignment_summary(out["records"])
+
+    def _track(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor) -> np.ndarray:
+        """The pose ``remember_depth`` goes on with: the fit's if it ended on a step (status 0, also when later iterations were skipped),
+        counted at least ``min_count`` pixels and moved the camera by no more than ``max_correction``; else the caller's, bit for bit."""
+        from .raster import _pose_f64
+
+        kw = dict(self._fusion["track"])
+        max_t, max_r = kw.pop("max_correction")
+        fitted, summary = self._fit_pose(depth_11hw, pose, invK_144, kw)
+        dt = float(np.linalg.norm(fitted[:3, 3] - pose[:3, 3]))
+        M = fitted[:3, :3] @ pose[:3, :3].T
+        dr = float(np.arctan2(0.5 * np.linalg.norm([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]]), (np.trace(M) - 1.0) / 2.0))
+        ok = summary["status"] == 0 and summary["count"] >= kw.get("min_count", 64) and dt <= max_t and dr <= max_r and bool(np.isfinite(fitted).all())
+        used = _pose_f64("world_T_cam", fitted) if ok else pose
+        self.last_alignment = dict(summary=summary, given=pose.copy(), used=used.copy(), accepted=ok, translation=dt, rotation=dr)
+        return used
+
+    def align_pose(self, depth_11hw: torch.Tensor, world_T_cam, invK: torch.Tensor, **kw) -> Tuple[np.ndarray, dict]:
+        """The fit of ``remember_depth``'s tracking for a map that is NOT remembered - the live camera between keyframes: ``(pose,
+        summary)``, the fitted world_T_cam as a float64 (4,4) host array and ``fusion.alignment_summary`` of the fit, for the caller to
+        judge.  ``kw``: the keywords of ``fusion.align_depth`` (default: those of ``start_fusion(track=)``, if given).  The ring, the
+        volume and ``last_alignment`` are left as they are.  Needs ``start_fusion`` and a fused map; synchronises (two host reads)."""
+        from .raster import _pose_f64
+
+        if self._fusion is None or self._volume is None or self._fused_maps == 0:
+            raise _lib.IdhError("align_pose needs start_fusion() and at least one fused map")
+        _lib.require_cuda_f32(depth_11hw, invK)
+        if depth_11hw.requires_grad or invK.requires_grad:
+            raise _lib.IdhError("align_pose: inputs that require grad (the alignment is not differentiable)")
+        invK = invK.reshape(-1, 4, 4)
+        if invK.shape[0] != 1:
+            raise _lib.IdhError("align_pose: invK must be (4,4) or (1,4,4)")
+        base = dict(self._fusion["track"] or {})
+        base.pop("max_correction", None)
+        base.update(kw)
+        return self._fit_pose(depth_11hw, _pose_f64("world_T_cam", world_T_cam), invK, base)
 
     def _check_depth(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor) -> Optional[dict]:
         """``geometry.depth_consistency`` of a new map against the ring's maps (B = 1, K = their number, one launch), before the map is
@@ -395,7 +449,7 @@ class StreamingSession:
 
     def start_fusion(self, voxel_size: float = 0.04, dims: Sequence[int] = (96, 256, 256), origin=None, trunc_voxels: float = 3.0,
                      max_weight: float = 64.0, color: bool = False, consistency: Optional[dict] = None, weighted: bool = False,
-                     follow: Optional[float] = None, on_scroll=None) -> None:
+                     follow: Optional[float] = None, on_scroll=None, track: Optional[dict] = None) -> None:
         """From now on ``remember_depth`` - which ``step`` calls with a ``DepthModel``'s predictions - also averages the map it pushes
         into a TSDF volume of ``dims`` = (Nz, Ny, Nx) voxels of ``voxel_size`` metres (``fusion.TSDFVolume``), which
         ``fused_depth_for_view`` ray-casts: maps are combined, holes one map left are filled by another, and a map that has left the ring
@@ -415,7 +469,15 @@ class StreamingSession:
         position, and once that is further than ``follow`` from the grid's centre on an axis the grid is moved back under it by whole
         8-voxel blocks (``TSDFVolume.shift``: what stays keeps its bits, what leaves is dropped, the volume holds twice its memory from
         the first move on).  ``on_scroll(volume, shift_xyz)`` is called just before such a move, with the volume still unshifted: the
-        place to ``crop`` or mesh the ``fusion.leaving_boxes``.  ``fusion_scrolls`` counts the moves, ``last_scroll`` is the last one."""
+        place to ``crop`` or mesh the ``fusion.leaving_boxes``.  ``fusion_scrolls`` counts the moves, ``last_scroll`` is the last one.
+        ``track``: None trusts every pose as given.  A dict with any of the keywords of ``fusion.align_depth`` (``iters``,
+        ``stride``, ``huber``, ``damping``, ``min_step``, ``min_count``, ``schedule``, ``min_pivot_ratio``) and ``max_correction`` =
+        (metres, radians), default (0.1, 0.1): from the second map of a sequence on, ``remember_depth`` fits the new map's camera to the
+        volume, starting from the caller's pose, before anything else is done with the map, and uses the fitted pose for the consistency
+        check, the ring, the follow-shift and the integration - if the fit ended on a step, counted ``min_count`` pixels and stayed
+        within ``max_correction``; otherwise the caller's pose is used as it is.  ``last_alignment`` holds "summary", "given", "used",
+        "accepted" and the correction's "translation" / "rotation".  The fit converges from about a truncation distance away, not
+        further.  The keyframe bank of ``step`` keeps the caller's pose: only the depth memory is corrected."""
         dims = tuple(int(d) for d in dims)
         if follow is not None and not float(follow) > 0:
             raise _lib.IdhError(f"start_fusion: follow = {follow} must be a positive slack in metres (None: a fixed grid)")
@@ -431,14 +493,24 @@ class StreamingSession:
                 raise _lib.IdhError("start_fusion(consistency=) must come before the first remembered map of a sequence (reset() first)")
             consistency = dict(log_tol=float(consistency.get("log_tol", 0.05)), min_consistent=int(consistency.get("min_consistent", 1)),
                                max_conflict=int(consistency.get("max_conflict", 0)), ratio=float(consistency.get("ratio", 1.05)))
+        if track is not None:
+            unknown = set(track) - {"iters", "stride", "huber", "damping", "min_step", "min_count", "schedule", "min_pivot_ratio", "max_correction"}
+            if unknown:
+                raise _lib.IdhError(f"start_fusion: track has unknown keys {sorted(unknown)}")
+            track = dict(track)
+            mc = tuple(float(x) for x in track.get("max_correction", (0.1, 0.1)))
+            if len(mc) != 2 or not (mc[0] >= 0 and mc[1] >= 0):
+                raise _lib.IdhError(f"start_fusion: track max_correction {mc} must be (metres, radians), both >= 0")
+            track["max_correction"] = mc
         if len(dims) != 3 or min(dims) < 2 or not float(voxel_size) > 0:
             raise _lib.IdhError(f"start_fusion: dims {dims} must be three sizes >= 2 and voxel_size {voxel_size} positive")
         self._fusion = dict(voxel_size=float(voxel_size), dims=dims, origin=None if origin is None else tuple(float(o) for o in origin),
                             trunc_voxels=float(trunc_voxels), max_weight=float(max_weight), color=bool(color), consistency=consistency,
-                            weighted=bool(weighted), follow=None if follow is None else float(follow), on_scroll=on_scroll)
+                            weighted=bool(weighted), follow=None if follow is None else float(follow), on_scroll=on_scroll, track=track)
         self._volume, self._fused_maps = None, 0
         self.fusion_scrolls, self.last_scroll = 0, None
         self._ring_cams, self.last_depth_counts = [], None
+        self.last_alignment = None
 
     def _fuse(self, depth_11hw: torch.Tensor, pose: np.ndarray, invK_144: torch.Tensor, frame_u8: Optional[torch.Tensor] = None,
               frame_K_144: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None) -> None:

@@ -1,7 +1,7 @@
 /*
- * idh_fusion.h — TSDF fusion of depth maps, the ray cast of the fused surface into live cameras and its extraction as a triangle mesh
- * (additive: idh_version() stays as it is; every struct is versioned through its struct_size; csrc/tsdf.hip, csrc/tsdf_mesh.hip,
- * DESIGN.md §4.21, §4.22, §4.23).
+ * idh_fusion.h — TSDF fusion of depth maps, the ray cast of the fused surface into live cameras, its extraction as a triangle mesh and
+ * the alignment of a depth map's camera against it (additive: idh_version() stays as it is; every struct is versioned through its
+ * struct_size; csrc/tsdf.hip, csrc/tsdf_mesh.hip, csrc/tsdf_align.hip).
  *
  * The depth warp of idh_raster.h draws remembered maps as separate sheets under one z-buffer: maps are not combined, holes stay holes
  * and the memory is as long as the ring.  Here every map is averaged into a truncated signed distance volume (Curless and Levoy) - the
@@ -355,6 +355,77 @@ typedef struct idh_tsdf_shift_args {
 size_t idh_sizeof_tsdf_shift_args(void);
 
 int idh_tsdf_shift_fwd(const idh_tsdf_shift_args *args, void *stream);
+
+/* ---- Pose alignment: fit a depth map's camera to the fused volume (csrc/tsdf_align.hip) ---------------------------------
+ *
+ * Frame-to-model alignment on the signed distance field itself (Bylow et al. 2013): Gauss-Newton on the sum of f(T p)^2 over the map's
+ * back-projected points, with the interpolant f and its gradient G of the ray cast above.  No data association, no rendered map.
+ * The pose is kept in fp64 (R, t) in the workspace, initialised from world_T_cam_in_44; every iteration is two launches - a per-pixel
+ * pass with a chunked fp64 reduction and a one-workgroup solve - and the call enqueues 2 * iters launches without any host
+ * synchronisation or read-back.
+ *
+ * Per pixel (i, j) with i % stride == 0 and j % stride == 0, against the iteration's pose ROUNDED TO fp32 (R, t below are those floats):
+ *   d = depth[i, j]: skip unless finite and > 0;  wm = weight[i, j]: skip unless finite and > 0 (wm = 1 without a weight map)
+ *   q = invK[:3,:3] (j + 0.5, i + 0.5, 1) as in the ray cast, not normalised;   pc = q * d (per component)
+ *   pw = R pc + t in the order of the integrate's c: pw.x = ((r00 pc.x + r01 pc.y) + r02 pc.z) + t.x, ...
+ *   g = (pw - origin) / voxel_size (per component);  cell = floor(g);  skip unless the cell is KNOWN (the ray cast's rule)
+ *   f and G by the ray cast's expressions with r = g - cell;   skip when (G.x G.x + G.y G.y) + G.z G.z == 0 (a saturated cell)
+ *   r = f * trunc (metres);   n = G * trunc_voxels (per component);   a = pw - t (per component)
+ *   J = (n.x, n.y, n.z, a.y n.z - a.z n.y, a.z n.x - a.x n.z, a.x n.y - a.y n.x): the derivative of r under
+ *       pw' = t + v + exp(w^)(pw - t) at (v, w) = 0 - the increment translates the camera and rotates it about its own centre
+ *   wgt = wm * (huber <= 0 || |r| <= huber ? 1 : huber / |r|)
+ * The system, in fp64 from the eight floats widened: A_ab += (wgt J_a) J_b for a <= b (21 entries, row-major upper triangle),
+ *   b_a += (wgt J_a) r,  cost += (wgt r) r,  count += 1.
+ * Reduction: the selected pixels (ceil(h / stride) x ceil(w / stride) of them) are cut into 16 x 16 chunks, whatever the grid; a lane
+ * holds one pixel, a wave an 8 x 8 quarter, summed by shuffles (offsets 32 .. 1) and then over the four waves in order; one record of
+ * 29 doubles per chunk; the solve adds record c into slot c % 8 in ascending c and then the slots in ascending order.  No atomics:
+ * the same bits for every max_workgroups and every call.
+ * The solve, fp64:  status 1 if count < min_count.  Else A' = A + damping * diag(A), Cholesky A' = L L^T with pivots
+ *   p_k = A'_kk - sum_{j<k} L_kj^2; status 2 unless every p_k > min_pivot_ratio * A'_kk (an exactly planar volume has p_0 == 0).
+ *   Else xi = -(A')^-1 b = (v, w);  R <- E R with E = I + (sin th / th) w^ + ((1 - cos th) / th^2) w^ w^, th = |w| (E = I + w^ below
+ *   th = 1e-12);  t <- t + v;  status 0.
+ *   After a non-zero status, or a status-0 step with |v| < min_step and |w| < min_step, the remaining iterations return at once (a flag
+ *   in the workspace); their records are zero but for status 3.
+ * Outputs.  world_T_cam_out_44: the fp64 pose rounded once, bottom row 0 0 0 1 (the input's bits after status 1 or 2 at iteration 0).
+ *   records (iters, 40) doubles: [0..20] A, [21..26] b, [27] cost, [28] count, [29] status, [30] |v|, [31] |w|, [32..37] xi, [38..39] 0.
+ *   rows_hw8 (optional): (h, w, 8) fp32 (J[6], r, wgt) of iteration 0 - the input pose; all zero for a pixel skipped or not selected.
+ * IDH_EINVAL: args NULL, struct_size short, h or w <= 0, iters outside 1 .. IDH_TSDF_ALIGN_MAX_ITERS, stride < 1, min_count < 6,
+ *   max_workgroups < 0, huber NaN or infinite, damping or min_step negative or not finite, min_pivot_ratio outside [0, 1), a null
+ *   depth / invK / pose in / pose out / records, workspace not 8-byte or rows_hw8 not 16-byte aligned; the volume's conditions;
+ * IDH_EUNSUPPORTED: h * w >= 2^31;   IDH_EWORKSPACE: workspace NULL or workspace_bytes < idh_tsdf_align_workspace_bytes(h, w, stride, iters). */
+#define IDH_TSDF_ALIGN_MAX_ITERS 64
+#define IDH_TSDF_ALIGN_RECORD 40  /* doubles per iteration's record */
+
+typedef struct idh_tsdf_align_args {
+    int64_t struct_size;
+    idh_tsdf_volume volume;
+    const float *depth_11hw;          /* (1,1,h,w) */
+    const float *invK_44;             /* inverse intrinsics at h x w */
+    const float *weight_11hw;         /* (1,1,h,w), or NULL */
+    const float *world_T_cam_in_44;   /* the pose to start from */
+    float *world_T_cam_out_44;        /* out (4,4); may be the input's address */
+    double *records_i40;              /* out (iters, 40) */
+    float *rows_hw8;                  /* out (h,w,8), 16-byte aligned, or NULL */
+    void *workspace;                  /* idh_tsdf_align_workspace_bytes(h, w, stride, iters) bytes, 8-byte aligned */
+    int64_t workspace_bytes;          /* what the caller allocated */
+    double damping;                   /* >= 0, finite */
+    double min_step;                  /* >= 0, finite; metres and radians */
+    double min_pivot_ratio;           /* in [0, 1); 1e-6 is the bindings' default */
+    float huber;                      /* metres; <= 0: none */
+    int32_t h, w;
+    int32_t iters;                    /* 1 .. IDH_TSDF_ALIGN_MAX_ITERS */
+    int32_t stride;                   /* >= 1 */
+    int32_t min_count;                /* >= 6 */
+    int32_t max_workgroups;           /* of the per-pixel pass; 0: one per chunk */
+} idh_tsdf_align_args;
+
+size_t idh_sizeof_tsdf_align_args(void);
+
+/* 8 * (16 + 32 * chunks) bytes with chunks = ceil(ceil(h / stride) / 16) * ceil(ceil(w / stride) / 16): the pose state and one record per
+ * chunk (reused by every iteration).  0 if h, w or stride < 1, iters outside 1 .. IDH_TSDF_ALIGN_MAX_ITERS or h * w >= 2^31. */
+size_t idh_tsdf_align_workspace_bytes(int h, int w, int stride, int iters);
+
+int idh_tsdf_align_fwd(const idh_tsdf_align_args *args, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
